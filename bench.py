@@ -16,10 +16,17 @@ Workload (config.workload): BASELINE.json configs[1], the fixed 7q TDNN-F (14 td
 sequences per GPU (--scaling weak, the default: per-GPU work is fixed as N grows) or per node (--scaling strong:
 every rank takes minibatch / N sequences of one global minibatch).
 
-At N = 1 the line also carries: "roofline" (live HIP-event timing of the dominant GEMM class + algorithmic bytes),
-"parity" (the HIP step against the CPU oracle on a bounded sample of the same workload, asserted), "cpu_baseline"
-(the oracle timed on this box's host cores), "alt" (split-bf16 GEMM arithmetic) and "also" (the reference's own egs
-shape and SWBD-scale denominator graphs as further line items).
+The line carries "roofline" (live HIP-event timing of the dominant GEMM class + algorithmic bytes, recorded during
+the timed steps themselves).  A plain run measures nothing else.  With --full it also carries, at N = 1: "parity" (the
+HIP step against the CPU oracle on a bounded sample of the same workload, asserted), "cpu_baseline" (the oracle timed
+on the host cores), "alt" (the f32-equivalent f16x3 GEMM arithmetic) and "also" (the reference's own egs shape and SWBD-scale
+denominator graphs as further line items); at N > 1 with --scaling weak, "strong" (the same node on one sharded
+minibatch).
+
+--dump-outputs DIR writes what the last timed step left to its caller as DIR/<name>.npy (results.npy: the step's
+results vector; params.npy / params_delta.npy: the parameters after it and their change over the timed steps, at a
+fixed seeded sample of positions when the model is larger than 4 Mi parameters; stats.npy: the BatchNorm / ReLU
+statistics).  Every input is seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -258,6 +265,25 @@ def workload_text(args):
             "minibatch), otherwise as configs[1]; " + tail)
 
 
+DUMP_SAMPLE = 1 << 22  # parameters written by --dump-outputs: all of them up to 4 Mi, else this many at seeded positions (16 MB per array)
+
+
+def dump_outputs(out_dir, job):
+    """--dump-outputs: what the last timed step of `job` left to its caller, as float32 / float64 .npy files (< 64 MB in all)."""
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    params = job.net.params.cpu().numpy()
+    n = params.size
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    arrays = {"results": job.net.results.cpu().numpy().astype(np.float64),
+              "params": params[idx].astype(np.float32),
+              "params_delta": (params[idx] - job.params_before[idx]).astype(np.float32),
+              "stats": job.net.get_stats().astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class Job:
     """One replica of the trainer on this rank's GPU with its own synthetic egs resident in HBM."""
 
@@ -359,10 +385,12 @@ class Job:
         self.net.update(self.lr, l2_regularize_scale=self.l2_scale, step=self.i)
         self.i += 1
 
-    def run(self, burn, warmup, steps, sync, profile=False):
+    def run(self, burn, warmup, steps, sync, profile=False, snapshot=False):
         for _ in range(burn + warmup):
             self.step()
         sync()
+        if snapshot:  # --dump-outputs: the parameters the timed steps start from (host copy, before the clock starts)
+            self.params_before = self.net.params.cpu().numpy()
         lib = self.pkg.hipabi.load()
         # Live roofline: HIP events around every GEMM launch of the first `event_steps` timed steps (on the launch streams).  Each
         # event is a marker packet between two launches -- about 1 000 per step, ~3 ms of a 130 ms step -- so the remaining timed
@@ -486,7 +514,14 @@ def main():
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="a tuning option of the library (tdnnf_set_option: ng_grouped, ng_fuse, ng_early_in, wgrad_stream, gemm_ring, planes); "
                          "repeatable -- same-box A/B runs of two code paths")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: parity against the CPU oracle, cpu_baseline, alt, also "
+                         "(N = 1) and strong (N > 1); the --no-* options above trim it.  Off: only the headline steps run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (results, parameters, statistics) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -560,12 +595,14 @@ def main():
         pj.close()
     job = Job(pkg, args, args.chunk, seqs, args.den_states, rank, world, stats=stats0)
     cfg = job.cfg
-    dt = job.run(burn, args.warmup, args.steps, sync, profile=True)
+    dt = job.run(burn, args.warmup, args.steps, sync, profile=True, snapshot=bool(args.dump_outputs) and rank == 0)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     res = job.net.results.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, job)
     den_arcs = int(len(job.den["src"]))
     sync_bn_main = job.sync_bn
     rccl_path_main = job.rccl_path
@@ -573,7 +610,7 @@ def main():
     # N > 1, weak scaling (what the driver runs): the same node also timed on ONE minibatch of --minibatch sequences sharded over the
     # ranks (strong scaling, synchronised BatchNorm) -- the regime north_star's ">= 6x at 8 GPUs" is the harder question in
     strong = None
-    if world > 1 and args.scaling == "weak" and not args.no_strong and args.minibatch % world == 0:
+    if args.full and world > 1 and args.scaling == "weak" and not args.no_strong and args.minibatch % world == 0:
         sj = Job(pkg, args, args.chunk, args.minibatch // world, args.den_states, rank, world, scaling="strong")
         sdt = sj.run(burn, args.warmup, args.steps, sync)
         t = torch.tensor([sdt], dtype=torch.float64, device="cuda")
@@ -702,7 +739,7 @@ def main():
             torch.cuda.empty_cache()
             return it
 
-        if world == 1 and args.gemm == "f32" and not args.no_alt:
+        if args.full and world == 1 and args.gemm == "f32" and not args.no_alt:
             # the same step with the f32-equivalent arithmetic on the 16-bit matrix cores (gemm_precision 3, "f16x3": every GEMM operand pre-split
             # into two scaled f16 planes in HBM, three f16 MFMA products, f32 accumulation): same workload, same steps.  Not the
             # headline -- the reference computes in f32 (BaseFloat) and the headline stays the exact-f32 MFMA -- but held to the same parity bars
@@ -734,7 +771,7 @@ def main():
                                           "note": "event classes as in the headline's roofline (the class names are the f32 kernels'): forward / backward-data GEMMs by "
                                                   "output width, weight gradients; the plane splits (HBM passes, class planes_split) are not in these times but in ms_per_step"}
                 out["alt"]["roofline_hbm"] = hbm_entries(it.get("_hbm_classes", []), max(it.get("_event_steps") or 1, 1), args.chunk, tj16, TRAFFIC_FILE_F16X3)
-        if world == 1 and not args.no_also:
+        if args.full and world == 1 and not args.no_also:
             # further line items, same net and step: the reference's own egs shape (chunk 150 x 64, ...pretrain.sh:46,197) and
             # SWBD-scale denominator graphs (10 000 and 30 000 states)
             recipe = line_item("the recipes' egs shape (--chunk 150 --minibatch 64)", 150, 64, args.den_states, steps=40)
@@ -784,7 +821,7 @@ def main():
                 it["vs_resident_inputs"] = round(resident / it["ms_per_step"], 3)
                 out["also"].append(it)
         ok = True
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             parity, base = parity_and_cpu_baseline(pkg, args, want_baseline=not args.no_cpu_baseline)
             out["parity"] = parity
             ok = parity["ok"]
