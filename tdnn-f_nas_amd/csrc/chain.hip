@@ -703,6 +703,160 @@ __global__ __launch_bounds__(kGammaThreads) void den_gamma_kernel(DenDev g, MatV
     }
   }
 }
+
+// sell_row_sum for N sums over the same arcs, the term of arc a in sum n being pa(a, n) * pb(a, n): every arc is loaded once, and each sum gets
+// den_gamma_kernel's bits.  That is sell_row_sum's order AND the instructions the compiler made of it there: rounded products and adds (its
+// products come packed in pairs, v_pk_mul_f32, which leaves no add to fuse with) except the first term of the last batch, which it fuses into the
+// sum (v_fmac_f32).  Contraction is off here and in the caller's factors (two sums side by side would otherwise become v_pk_fma_f32), and that one
+// fused term is an explicit fmaf.
+template <int N, class Fa, class Fb>
+__device__ __forceinline__ void sell_row_sums(const uint2 *ap, int w, float (&acc)[N], Fa pa, Fb pb) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int n = 0; n < N; n++) acc[n] = 0.f;
+  int j = 0;
+  for (; j + 8 <= w; j += 8) {
+    uint2 a[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) a[u] = ap[(j + u) * 64];
+#pragma unroll
+    for (int u = 0; u < 8; u++)
+#pragma unroll
+      for (int n = 0; n < N; n++) acc[n] += pa(a[u], n) * pb(a[u], n);
+  }
+  if (j + 4 <= w) {
+    uint2 a[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) a[u] = ap[(j + u) * 64];
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+      for (int n = 0; n < N; n++) acc[n] += pa(a[u], n) * pb(a[u], n);
+    j += 4;
+  }
+  if (j < w) {
+    uint2 a[3];
+#pragma unroll
+    for (int u = 0; u < 3; u++) a[u] = ap[min(j + u, w - 1) * 64];
+#pragma unroll
+    for (int n = 0; n < N; n++) acc[n] = __builtin_fmaf(pa(a[0], n), pb(a[0], n), acc[n]);
+#pragma unroll
+    for (int u = 1; u < 3; u++)
+#pragma unroll
+      for (int n = 0; n < N; n++) acc[n] += (j + u < w) ? pa(a[u], n) * pb(a[u], n) : 0.f;
+  }
+}
+
+// The occupancies of TWO consecutive frames of one sequence per 1024-thread workgroup (where both frames' vectors and output rows fit the LDS;
+// option den_gamma_pairs = 1: den_gamma_kernel).  den_gamma_kernel streams the whole by-pdf arc table from L2 for every (frame, sequence) --
+// 384 KB at 48 000 arcs, 3.5 ms of the pass alone at 4 000 states / 128 x 500 -- to use each arc once; here every arc loaded serves both
+// frames.  A frame's output row is formed in LDS (scale * sum, in place of x = exp(y)) and written in one coalesced pass that reads y in the
+// same order, instead of a scattered 4-byte store per row.  Same bits as den_gamma_kernel: each 512-thread half forms its frame's Zd with
+// den_gamma_kernel's lanes and order, a row adds its arcs in SELL order as (prob * ad) * bn, and deriv = (scale * sum) * x.
+constexpr int kGamma2Threads = 2 * kGammaThreads;
+constexpr size_t kLdsBytes = 160 * 1024;  // per CU (gfx950)
+__global__ __launch_bounds__(kGamma2Threads) void den_gamma2_kernel(DenDev g, MatView y, int B, int T, float leaky, const float *alpha_all, const float *b_all,
+                                                                    const float *S_all, int Hs, float deriv_weight, MatView deriv) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ float red[kGamma2Threads / 64];
+  const int t0 = 2 * blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+  const int H = g.H, P = g.P, P4 = (P + 3) & ~3, H4 = (H + 3) & ~3, L = 2 * H4 + P4;  // per frame: ad, bn, the output row
+  const int nf = min(2, T - t0);  // (odd T: the last workgroup's second half forms frame t0 again and writes nothing)
+  {
+    const int f = tid / kGammaThreads, ht = tid % kGammaThreads, t = min(t0 + f, T - 1);
+    float *ad = smem + f * L, *bn = ad + H4;
+    const float *alpha = alpha_all + ((size_t)s * (T + 1) + t) * Hs;  // alpha_dash(t, .)
+    const float *bt = b_all + ((size_t)s * (T + 1) + t) * Hs, *bt1 = bt + Hs;
+    const float inv = 1.0f / S_all[(size_t)s * (T + 1) + t + 1];
+    // (a thread's states in batches of eight, every load of a batch in flight at once: one at a time they were eight trips to HBM in a row; the
+    // two fmaf are what den_gamma_kernel's compiled loop does, and states past H add exact zeros to a sum of non-negative terms)
+    constexpr int kBatch = 8;
+    float local = 0.f;
+    for (int h0 = ht; h0 < H; h0 += kBatch * kGammaThreads) {
+      float av[kBatch], bv[kBatch], b1v[kBatch];
+#pragma unroll
+      for (int i = 0; i < kBatch; i++) {
+        const int h = h0 + i * kGammaThreads;
+        av[i] = h < H ? alpha[h] : 0.f;
+        bv[i] = h < H ? bt[h] : 0.f;
+        b1v[i] = h < H ? bt1[h] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < kBatch; i++) {
+        const int h = h0 + i * kGammaThreads;
+        if (h < H) {
+          ad[h] = av[i];
+          bn[h] = __builtin_fmaf(b1v[i], inv, leaky);
+        }
+        local = __builtin_fmaf(av[i], bv[i], local);
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, 64);  // (block_sum over this half's 8 waves)
+    if ((tid & 63) == 0) red[tid >> 6] = local;
+  }
+  __syncthreads();
+  float scale[2];
+#pragma unroll
+  for (int f = 0; f < 2; f++) {
+    float Zd = 0.f;
+    for (int w = 0; w < kGammaThreads / 64; w++) Zd += red[f * (kGammaThreads / 64) + w];
+    scale[f] = deriv_weight / Zd;
+  }
+  constexpr int kRows = 8;
+  const int nslot = g.by_pdf.nslices * 64, ln = tid & 63;
+  auto pa = [&](const uint2 a, int f) {  // prob * ad(src); the term is (prob * ad) * bn(dst), as in den_gamma_kernel
+#pragma clang fp contract(off)
+    return __uint_as_float(a.y) * smem[f * L + (a.x & 0xffffu)];
+  };
+  auto pb = [&](const uint2 a, int f) { return smem[f * L + H4 + (a.x >> 16)]; };
+  for (int s0 = tid; s0 < nslot; s0 += kRows * kGamma2Threads) {
+    int b0[kRows], w[kRows];
+    unsigned row[kRows];
+#pragma unroll
+    for (int k = 0; k < kRows; k++) {
+      const int slot = s0 + k * kGamma2Threads;
+      b0[k] = 0;
+      w[k] = 0;
+      row[k] = 0xffffffffu;
+      if (slot < nslot) {
+        b0[k] = g.by_pdf.base[slot >> 6];
+        w[k] = (g.by_pdf.base[(slot >> 6) + 1] - b0[k]) >> 6;
+        row[k] = g.by_pdf.row[slot];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kRows; k++) {
+      if (row[k] == 0xffffffffu) continue;
+      float acc[2];
+      sell_row_sums<2>(g.by_pdf.arc + b0[k] + ln, w[k], acc, pa, pb);
+#pragma unroll
+      for (int f = 0; f < 2; f++) smem[f * L + 2 * H4 + row[k]] = scale[f] * acc[f];
+    }
+  }
+  __syncthreads();
+  constexpr int kOut = 6;  // (both frames' y loads of a batch in flight at once)
+  for (int p0 = tid; p0 < P; p0 += kOut * kGamma2Threads) {
+    float yv[2][kOut];
+#pragma unroll
+    for (int f = 0; f < 2; f++)
+#pragma unroll
+      for (int i = 0; i < kOut; i++) {
+        const int p = p0 + i * kGamma2Threads;
+        yv[f][i] = f < nf && p < P ? y.data[(size_t)((t0 + f) * B + s) * y.stride + p] : 0.f;
+      }
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+      if (f >= nf) break;
+      const float *o = smem + f * L + 2 * H4;
+      float *dr = deriv.data + (size_t)((t0 + f) * B + s) * deriv.stride;
+#pragma unroll
+      for (int i = 0; i < kOut; i++) {
+        const int p = p0 + i * kGamma2Threads;
+        if (p < P) dr[p] = o[p] * exp_limited(yv[f][i]);
+      }
+    }
+  }
+}
 // ---------------------------------------------------------------------------------------------- denominator, wide form
 // The persistent kernels above give a sequence one workgroup and keep its state vectors in LDS: right while they fit (up to
 // ~10 000 states), a crawl beyond (30 000 states / 360 000 arcs: every arc is a 4-byte gather from L2, 580 ms per
@@ -1675,7 +1829,6 @@ int chain_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
     if (rc) return rc;
     TDNNF_HIP(hipFuncSetAttribute((const void *)den_forward_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.p.lds_fwd));
     TDNNF_HIP(hipFuncSetAttribute((const void *)den_beta_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_beta));
-    TDNNF_HIP(hipFuncSetAttribute((const void *)den_gamma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gamma));
     TDNNF_HIP(hipEventRecord(ev_fork, s));
     TDNNF_HIP(hipStreamWaitEvent(aux, ev_fork, 0));
     int G = mw_groups(g, B, T);
@@ -1765,7 +1918,13 @@ int chain_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
       TDNNF_HIP(hipEventRecord(ev_recursions, s));
       if (ev_recorded) *ev_recorded = true;
     }
-    hipLaunchKernelGGL(den_gamma_kernel, dim3(T, B), dim3(kGammaThreads), lds_gamma, s, gd, yv, B, T, leaky, b.alpha, b_all, S_all, b.p.Hs, -sp->weight, dv);
+    if (options().den_gamma_pairs != 1 && 2 * lds_gamma + sizeof(float) * kGamma2Threads / 64 <= kLdsBytes) {  // two frames per workgroup
+      TDNNF_HIP(hipFuncSetAttribute((const void *)den_gamma2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds_gamma)));
+      hipLaunchKernelGGL(den_gamma2_kernel, dim3((T + 1) / 2, B), dim3(kGamma2Threads), 2 * lds_gamma, s, gd, yv, B, T, leaky, b.alpha, b_all, S_all, b.p.Hs, -sp->weight, dv);
+    } else {
+      TDNNF_HIP(hipFuncSetAttribute((const void *)den_gamma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gamma));
+      hipLaunchKernelGGL(den_gamma_kernel, dim3(T, B), dim3(kGammaThreads), lds_gamma, s, gd, yv, B, T, leaky, b.alpha, b_all, S_all, b.p.Hs, -sp->weight, dv);
+    }
   } else if (b.p.lds_state) {
     TDNNF_HIP(hipFuncSetAttribute((const void *)den_backward_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.p.lds_bwd));
     if (g->by_dst.nslices * 64 <= kDenFastSlots * kDenThreads && g->H <= kDenFastStates * kDenThreads) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Stand-alone timing of chain::ComputeChainObjfAndDeriv (denominator + numerator) on synthetic graphs.
-usage (GPU box): [DEN_MODE=0|1|2] python tools/den_bench.py [states] [degree] [B] [T_out]   (1 persistent, 2 wide, 0 automatic)"""
+usage (GPU box): [DEN_MODE=0|1|2] [DEN_GAMMA_PAIRS=0|1] python tools/den_bench.py [states] [degree] [B] [T_out]   (1 persistent, 2 wide, 0 automatic)"""
 import ctypes as C
 import os
 import sys
@@ -14,6 +14,7 @@ pkg = ge.load_package()
 abi = pkg.hipabi
 lib = abi.load()
 abi.check(lib.tdnnf_chain_set_denominator_mode(int(os.environ.get("DEN_MODE", "0"))))
+abi.check(lib.tdnnf_set_option(b"den_gamma_pairs", int(os.environ.get("DEN_GAMMA_PAIRS", "0"))))  # (the split form's occupancy pass)
 H = int(sys.argv[1]) if len(sys.argv) > 1 else 4000
 deg = float(sys.argv[2]) if len(sys.argv) > 2 else 12.0
 B = int(sys.argv[3]) if len(sys.argv) > 3 else 128
