@@ -644,6 +644,49 @@ int tdnnf_net_set_capture(tdnnf_net *, int on);
 int tdnnf_net_get_activation(const tdnnf_net *, const char *name, tdnnf_mat *out, tdnnf_stream);
 int tdnnf_net_activation_dims(const tdnnf_net *, const char *name, int *rows, int *cols);
 
+/* ======================================================================== inference (forward only, whole utterances)
+ * The model's output for decoding: nnet3's DecodableNnetSimple (UPSTREAM, not shipped) restated -- what steps/nnet3/decode.sh
+ * hands to latgen-faster-mapped (run_tdnn_fbk_40_iv_sp_7q.sh:254-258).  Utterances u = 0..U-1 of T_u input frames:
+ *  - feats: sum T_u x feat_dim, the utterances stacked row-wise.  ivectors: R_u rows per utterance, stacked, one every
+ *    ivector_period input frames; ivector_period <= 0: one per utterance (R_u = 1; ivector_rows_host may be NULL).
+ *  - out: O_u = (T_u + fsf - 1) / fsf rows per utterance, stacked (fsf = frame_subsampling); row j of utterance u is the
+ *    output at input frame j * fsf.  which_output 0: "output" (the chain head, raw, no log-softmax: what
+ *    latgen-faster-mapped --acoustic-scale 1.0 reads); 1: "output-xent" (log-softmax of the xent head).
+ *  - Chunks of F = frames_per_chunk input frames (a multiple of fsf): chunk k of utterance u covers input frames
+ *    [k F, k F + F) widened by the model's left / right context at this chunk width (tdnnf_net_input_frames of a net with
+ *    frames_per_chunk F); frames outside [0, T_u) are clamped to the first / last frame (nnet3's edge padding).  The last
+ *    chunk is computed at full width, its rows past O_u are dropped.  With a constant i-vector the output does not depend on F.
+ *  - I-vector of chunk k: n_k = its output rows inside O_u; row min(((k F / fsf) + n_k / 2) * fsf / ivector_period, R_u - 1)
+ *    (integer arithmetic; the middle of the chunk, as DecodableNnetSimple::GetCurrentIvector does -- restated, not checked
+ *    against Kaldi).
+ *  - BatchNorm in test mode from the model's stored statistics (BatchNormTestComponent: epsilon 1e-3, target rms 1),
+ *    dropout off, no ReLU statistics; nothing in the model is written.
+ *  - Models: the 7q graph and derived children (layer offsets, per-layer bottleneck, strided affine rows), gemm_precision 0.
+ *    The offset supernet (darts_num_offsets >= 2), the bottleneck supernet (bn_num_choices > 0) and any other gemm_precision
+ *    fail with TDNNF_EINVAL. */
+typedef struct tdnnf_infer tdnnf_infer;
+/* binds the model net's parameter buffer and statistics by reference (read at every compute: an update or set_stats on the
+   model is seen by the next call); max_chunks bounds the chunks of one batch (the arena is sized for it) */
+int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, tdnnf_infer **out);
+void tdnnf_infer_destroy(tdnnf_infer *);
+/* host only, no device call: the chunk plan above -- per chunk 4 ints (utterance, first input frame k F, i-vector row within
+   the utterance, valid output rows n_k); *num_chunks = the number of chunks.  More than `capacity` chunks: the first
+   `capacity` are written and the call fails (TDNNF_EINVAL) with *num_chunks still set. */
+int tdnnf_infer_plan(const tdnnf_infer *, int num_utts, const int *frames_host, const int *ivector_rows_host, int ivector_period,
+                     int *chunks_out, int capacity, int *num_chunks);
+/* the same plan for a chunk width and frame_subsampling alone (no model, no device): what tdnnf_infer_plan returns for a
+   model with that frame_subsampling and frames_per_chunk; frames_per_chunk not a positive multiple of it: TDNNF_EINVAL */
+int tdnnf_chunk_plan(int frames_per_chunk, int frame_subsampling, int num_utts, const int *frames_host, const int *ivector_rows_host,
+                     int ivector_period, int *chunks_out, int capacity, int *num_chunks);
+/* feats / ivectors / out: stacked as above (device); any number of chunks (batches of max_chunks inside).  Does not
+   synchronise the stream. */
+int tdnnf_infer_compute(tdnnf_infer *, int num_utts, const int *frames_host, const tdnnf_mat *feats, const int *ivector_rows_host,
+                        const tdnnf_mat *ivectors, int ivector_period, tdnnf_mat *out, tdnnf_stream);
+/* of the last compute: BatchNorm stages (tdnn1, every tdnnf layer, the head's two: num_layers + 3) applied in a GEMM epilogue
+   -- with the layer's bypass --, and those applied by a separate elementwise pass (tdnnf layers whose bypass rows are strided
+   against their output rows) */
+int tdnnf_infer_counts(const tdnnf_infer *, int *fused_layers, int *fallback_passes);
+
 /* ======================================================================== profiling
  * Optional per-launch timing of the MFMA GEMM kernels with HIP events recorded on the launch stream
  * (bench.py's live roofline measurement).  Classes: 0 = rows_gemm 128x128 tile, 1 = rows_gemm 128x160 tile,

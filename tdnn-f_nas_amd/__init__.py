@@ -12,3 +12,4 @@ from . import derive  # noqa: F401
 from . import configs  # noqa: F401
 from . import outer_loop  # noqa: F401
 from . import egs  # noqa: F401
+from . import infer  # noqa: F401

@@ -61,7 +61,17 @@ struct RowsGemmArgs {
   int alt_seg_order;    // set by rows_gemm(): odd row tiles visit the K segments in reverse order (taps = row shifts of one matrix, gemm_f32.hip)
   int nseg;
   GemmSeg seg[kMaxSeg];
+  // Inference epilogue (all off by default; any of them set: exact f32, no K split, no statistics).  After the ReLU:
+  //   C = col_scale[n] * relu?(init + acc) + col_offset[n] + add_scale * add[row]
+  // -- a test-mode BatchNorm and the TDNN-F bypass while the tile is stored.  post_add moves the addend behind the ReLU and the
+  // column affine (without it, `add` keeps its place in front of the ReLU).  row_map (device, M ints): C row m goes to row
+  // row_map[m] of C; a negative entry drops the row.
+  const float *col_scale;   // N floats or null (= 1)
+  const float *col_offset;  // N floats or null (= 0)
+  int post_add;
+  const int *row_map;
 };
+inline bool rows_gemm_has_post(const RowsGemmArgs &a) { return a.col_scale || a.col_offset || a.post_add || a.row_map; }
 
 // Event-timing class of the launches made while one of these is alive (tdnnf_profile_*: 0 rows_gemm 128x128,
 // 1 rows_gemm 128x160, 2 wgrad, 3 natural-gradient skinny GEMMs).

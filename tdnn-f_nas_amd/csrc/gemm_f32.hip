@@ -161,7 +161,35 @@ __device__ __forceinline__ float4 ld4(const float *p, bool v0, bool v1, bool v2,
 // TAG only gives the launches of the natural-gradient statistics (ProfClassOverride(3)) their own kernel symbol, so
 // that per-kernel profiler summaries keep them apart from the TDNN-F GEMMs; the code is identical.
 // (the body of a block: block `bx` of the `gx` blocks that work on `p` -- the whole grid of a plain launch, one task's share of a grouped one)
-template <int WM, int WN, int TM, int TN, int BK, bool B_KC, int VEC>
+// The inference epilogue of RowsGemmArgs (col_scale / col_offset / post_add / row_map) for a float4 of row m: pre = bias (or
+// zero), addv = the addend.  Only rows_gemm_post_kernel instantiates rows_gemm_block with POST: every other kernel compiles the
+// code it had before this stage existed.
+__device__ __forceinline__ void post_store4(const RowsGemmArgs &p, int m, int n, float4 v, float4 pre, float4 addv) {
+  v.x += pre.x; v.y += pre.y; v.z += pre.z; v.w += pre.w;
+  if (!p.post_add) { v.x += p.add_scale * addv.x; v.y += p.add_scale * addv.y; v.z += p.add_scale * addv.z; v.w += p.add_scale * addv.w; }
+  if (p.relu) { v.x = floor_keep_nan(v.x, 0.f); v.y = floor_keep_nan(v.y, 0.f); v.z = floor_keep_nan(v.z, 0.f); v.w = floor_keep_nan(v.w, 0.f); }
+  const float4 sc = p.col_scale ? *reinterpret_cast<const float4 *>(p.col_scale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+  const float4 of = p.col_offset ? *reinterpret_cast<const float4 *>(p.col_offset + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float as = p.post_add ? p.add_scale : 0.f;
+  v.x = sc.x * v.x + of.x + as * addv.x;
+  v.y = sc.y * v.y + of.y + as * addv.y;
+  v.z = sc.z * v.z + of.z + as * addv.z;
+  v.w = sc.w * v.w + of.w + as * addv.w;
+  const int mo = p.row_map ? p.row_map[m] : m;
+  if (mo >= 0) *reinterpret_cast<float4 *>(p.C + (long long)mo * p.ldc + n) = v;
+}
+// the same for one element (tile edges, C rows without 16-byte alignment)
+__device__ __forceinline__ void post_store1(const RowsGemmArgs &p, int m, int n, float x) {
+  if (p.init_mode == 1) x += p.bias[n];
+  const float a = (p.add && m >= p.add_lo && m < p.add_hi) ? p.add[(long long)(m - p.add_lo) * p.ldadd + n] : 0.f;
+  if (!p.post_add) x += p.add_scale * a;
+  if (p.relu) x = floor_keep_nan(x, 0.f);
+  x = (p.col_scale ? p.col_scale[n] : 1.f) * x + (p.col_offset ? p.col_offset[n] : 0.f) + (p.post_add ? p.add_scale * a : 0.f);
+  const int mo = p.row_map ? p.row_map[m] : m;
+  if (mo >= 0) p.C[(long long)mo * p.ldc + n] = x;
+}
+
+template <int WM, int WN, int TM, int TN, int BK, bool B_KC, int VEC, bool POST = false>
 __device__ __forceinline__ void rows_gemm_block(const RowsGemmArgs &p, int ntm, int ntn, int bx, int gx) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int LDAS = BK + 4;
@@ -474,6 +502,10 @@ __device__ __forceinline__ void rows_gemm_block(const RowsGemmArgs &p, int ntm, 
           const int idx = t + 256 * (g + u), row = idx / (BN / 4), c4 = (idx % (BN / 4)) * 4;
           const int m = m0 + pass * HALF + row, n = n0 + c4;
           float4 v = *reinterpret_cast<const float4 *>(Cs + row * LDCS + c4);
+          if constexpr (POST) {
+            post_store4(p, m, n, v, pre[u], addv[u]);
+            continue;
+          }
           v.x += pre[u].x + p.add_scale * addv[u].x;
           v.y += pre[u].y + p.add_scale * addv[u].y;
           v.z += pre[u].z + p.add_scale * addv[u].z;
@@ -498,6 +530,20 @@ __device__ __forceinline__ void rows_gemm_block(const RowsGemmArgs &p, int ntm, 
       if (p.ksplit > 1) {  // raw partial tile; the reduce kernel applies the epilogue
         const int ldp = (p.N + 3) & ~3;
         *reinterpret_cast<float4 *>(p.partial + ((long long)sp * p.M + m) * ldp + n) = v;
+        continue;
+      }
+      if constexpr (POST) {  // (init_mode 1 or 2: rows_gemm() refuses an accumulating launch with this stage)
+        if (cvec && n + 3 < p.N) {
+          const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+          const float4 b = p.init_mode == 1 ? *reinterpret_cast<const float4 *>(p.bias + n) : z;
+          const float4 o = (p.add && m >= p.add_lo && m < p.add_hi) ? *reinterpret_cast<const float4 *>(p.add + (long long)(m - p.add_lo) * p.ldadd + n) : z;
+          post_store4(p, m, n, v, b, o);
+        } else {
+          const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+            if (n + e < p.N) post_store1(p, m, n + e, vv[e]);
+        }
         continue;
       }
       float *c = p.C + (long long)m * p.ldc + n;
@@ -565,6 +611,11 @@ __device__ __forceinline__ void rows_gemm_block(const RowsGemmArgs &p, int ntm, 
 template <int WM, int WN, int TM, int TN, int BK, bool B_KC, int VEC, int TAG = 0>
 __global__ __launch_bounds__(256) void rows_gemm_kernel(const RowsGemmArgs p, int ntm, int ntn) {
   rows_gemm_block<WM, WN, TM, TN, BK, B_KC, VEC>(p, ntm, ntn, (int)blockIdx.x, (int)gridDim.x);
+}
+// the same GEMM with the inference epilogue (RowsGemmArgs::col_scale ...): plain launches, k-contiguous B
+template <int WM, int WN, int TM, int TN, int BK, int VEC>
+__global__ __launch_bounds__(256) void rows_gemm_post_kernel(const RowsGemmArgs p, int ntm, int ntn) {
+  rows_gemm_block<WM, WN, TM, TN, BK, true, VEC, true>(p, ntm, ntn, (int)blockIdx.x, (int)gridDim.x);
 }
 // Grouped launch: task i owns the blocks [first[i], first[i + 1]) and runs them exactly as a launch of its own would (one column tile,
 // no K split: its arguments say so).  The natural-gradient input-side statistics of a whole net at the recipes' minibatch: 33 launches
@@ -1314,6 +1365,27 @@ hipError_t launch_rows_sumsq(const RowsGemmArgs &a, bool b_kc, bool vec, hipStre
 
 }  // namespace
 
+namespace {
+// A launch with the inference epilogue (RowsGemmArgs::col_scale ...): one plain launch of rows_gemm_post_kernel -- no K split (its
+// partial tiles would need the stage in the reduce kernel as well), no LDS-DMA ring, exact f32.
+template <int WM, int WN, int TM, int TN, int BK>
+hipError_t launch_rows_post(const RowsGemmArgs &a, bool vec, int cls, double flops, hipStream_t s) {
+  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
+  const size_t lds = sizeof(float) * 2 * (BM * (BK + 4) + BN * (BK + 4));
+  static bool attr_done = false;  // (> 64 KiB of dynamic LDS must be opted into)
+  if (!attr_done) {
+    hipFuncSetAttribute((const void *)rows_gemm_post_kernel<WM, WN, TM, TN, BK, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipFuncSetAttribute((const void *)rows_gemm_post_kernel<WM, WN, TM, TN, BK, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_done = true;
+  }
+  ProfScope ps(cls, flops, s);
+  if (vec) hipLaunchKernelGGL((rows_gemm_post_kernel<WM, WN, TM, TN, BK, 4>), dim3(ntm * ntn), dim3(256), lds, s, a, ntm, ntn);
+  else hipLaunchKernelGGL((rows_gemm_post_kernel<WM, WN, TM, TN, BK, 1>), dim3(ntm * ntn), dim3(256), lds, s, a, ntm, ntn);
+  return hipGetLastError();
+}
+}  // namespace
+
 // floor division / modulus for element offsets that may be negative (row shifts of the backward-data gather)
 static inline long long floordiv(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
@@ -1527,6 +1599,21 @@ hipError_t rows_gemm(const RowsGemmArgs &a_in, bool b_kc, hipStream_t s) {
     g_prof_next_flops = flops;
   }
   a.serial_epilogue = 0;
+  if (rows_gemm_has_post(a)) {  // the inference epilogue: the tile choice below, its own kernels
+    if (!b_kc || a.init_mode == 0 || a.sumsq || a.ksplit > 1 || (a.init_mode == 1 && !a.bias)) return hipErrorInvalidValue;
+    a.prec = 0;
+    a.colstats = nullptr;
+    if (a.colstats_rows) *a.colstats_rows = 0;
+    a.alt_seg_order = options().gemm_alt_taps && a.nseg == 2 && a.seg[0].klen == a.seg[1].klen && a.lda > 0 && a.seg[0].a_off != a.seg[1].a_off &&
+                      (a.seg[1].a_off - a.seg[0].a_off) % a.lda == 0;
+    a.c_vec = a.c_vec && (!a.col_scale || aligned16(a.col_scale)) && (!a.col_offset || aligned16(a.col_offset));
+    if (waste160 < waste128) return launch_rows_post<4, 1, 1, 5, 16>(a, vec, 1, flops, s);
+    long long kt = 0;
+    for (int i = 0; i < a.nseg; i++) kt += a.seg[i].klen;
+    if ((long long)((a.M + 127) / 128) * ((a.N + 127) / 128) < 768) return launch_rows_post<2, 2, 1, 2, 16>(a, vec, 0, flops, s);
+    if (kt <= 512) return launch_rows_post<2, 2, 2, 2, 16>(a, vec, 0, flops, s);
+    return launch_rows_post<2, 2, 2, 2, 32>(a, vec, 0, flops, s);
+  }
   // two taps of one matrix (same reduction length, A offsets whole rows apart): alternate the order row tile by row tile (rows_gemm_kernel)
   a.alt_seg_order = options().gemm_alt_taps && a.nseg == 2 && a.seg[0].klen == a.seg[1].klen && a.lda > 0 && a.seg[0].a_off != a.seg[1].a_off &&
                     (a.seg[1].a_off - a.seg[0].a_off) % a.lda == 0;

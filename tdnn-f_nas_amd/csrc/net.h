@@ -226,6 +226,10 @@ struct tdnnf_net {
 };
 
 namespace tdnnf {
+// net.hip: the grids of every tdnnf layer for Tout output frames (stride, taps, bottleneck, gout / glin / gin, perm) and the first
+// layer's input grid; the indexes of one TdnnComponent between two grids for B sequences (t-major rows)
+int net_layer_grids(const tdnnf_net_config &c, int Tout, std::vector<TdnnfLayer> &layers, Grid *g_lda);
+void net_make_tdnn(Tdnn *t, int comp, int Di, int Do, const std::vector<int> &offs, const Grid &in, const Grid &out, int B);
 // parameter / gradient views of component `comp` inside the flat buffers
 inline float *net_W(const tdnnf_net *n, int comp) { return n->params + n->comps[comp].begin; }
 inline float *net_alpha(const tdnnf_net *n, int comp) {

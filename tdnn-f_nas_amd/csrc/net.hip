@@ -655,6 +655,71 @@ int bn_stats(tdnnf_net *n, float *x, int rows, int cols, float *memo, double *st
 
 }  // namespace
 
+namespace tdnnf {
+// the grids of every tdnnf layer for Tout output frames (stride, taps, bottleneck, gout / glin / gin, perm), derived backwards from the
+// output grid; *g_lda = the first layer's input grid
+int net_layer_grids(const tdnnf_net_config &c, int Tout, std::vector<TdnnfLayer> &layers, Grid *g_lda) {
+  layers.resize(c.num_layers);
+  Grid g{0, c.frame_subsampling, Tout};
+  for (int l = c.num_layers - 1; l >= 0; l--) {
+    TdnnfLayer &L = layers[l];
+    L.stride = c.time_stride[l];
+    L.left = c.use_layer_offsets ? c.offset_left[l] : L.stride;
+    L.right = c.use_layer_offsets ? c.offset_right[l] : L.stride;
+    L.bn = c.bottleneck_dim[l];
+    TDNNF_REQUIRE(L.bn > 0 && L.bn <= 512 && L.left >= 0 && L.right >= 0 && L.left <= 64 && L.right <= 64,
+                  "net_create: layer %d: bottleneck-dim must be in 1..512, time-stride / layer offsets in 0..64", l);
+    L.gout = g;
+    L.perm = false;
+    Grid lin = g, in = g;
+    const int Kd = c.darts_num_offsets;
+    if (Kd >= 2) {
+      // offset supernet: taps -(K-1)..0 / 0..K-1 at the input frame rate on every layer
+      if (g.step == 1) {
+        lin = Grid{g.t0, 1, g.n + Kd - 1};
+      } else {
+        const int rho = g.step;
+        const int cnt = rho * (g.n - 1) + Kd;
+        lin = Grid{g.t0, 1, ((cnt + rho - 1) / rho) * rho};  // padded to a multiple of rho (:841-843)
+        L.perm = true;
+      }
+      in = Grid{lin.t0 - (Kd - 1), 1, lin.n + Kd - 1};
+    } else if (L.left > 0 || L.right > 0) {
+      // X.linear taps {-a, 0}, X.affine taps {0, b} (time-stride s: a = b = s; a derived child: any a, b >= 0).  The
+      // linear runs on the coarsest regular grid that holds every frame the affine needs and whose own taps stay on the
+      // input grid: step gcd(output step, a, b).  When that is finer than the output grid the affine has row_stride
+      // rho > 1 and the grid is padded to a multiple of rho (nnet-tdnn-component.cc:841-843).
+      const int a = L.left, b = L.right;
+      auto gcd = [](int x, int y) {
+        while (y) {
+          const int t = x % y;
+          x = y;
+          y = t;
+        }
+        return x;
+      };
+      const int ls = gcd(gcd(g.step, a), b);
+      if (ls == g.step) {
+        lin = Grid{g.t0, g.step, g.n + b / g.step};
+      } else {
+        const int rho = g.step / ls, cnt = ((g.n - 1) * g.step + b) / ls + 1;
+        lin = Grid{g.t0, ls, ((cnt + rho - 1) / rho) * rho};
+        L.perm = true;
+      }
+      in = Grid{lin.t0 - a, ls, lin.n + a / ls};
+    }
+    L.glin = lin;
+    L.gin = in;
+    g = in;
+  }
+  *g_lda = g;
+  return TDNNF_OK;
+}
+void net_make_tdnn(Tdnn *t, int comp, int Di, int Do, const std::vector<int> &offs, const Grid &in, const Grid &out, int B) {
+  make_tdnn(t, comp, Di, Do, offs, in, out, B);
+}
+}  // namespace tdnnf
+
 extern "C" {
 
 int tdnnf_splice_input(const tdnnf_mat *feats, const tdnnf_mat *iv, int B, int S, tdnnf_mat *out, tdnnf_stream stream) {
@@ -725,60 +790,8 @@ static int net_create_impl(const tdnnf_net_config *cfg, const tdnnf_net *share, 
   n->Tout = c.frames_per_chunk / c.frame_subsampling;
   const int B = n->B, Hd = c.hidden_dim, S = c.prefinal_small_dim, P = c.num_pdfs, lda_dim = 3 * c.feat_dim + c.ivector_dim;
   // ---- grids, derived backwards from the output grid
-  n->layers.resize(c.num_layers);
-  Grid g{0, c.frame_subsampling, n->Tout};
-  for (int l = c.num_layers - 1; l >= 0; l--) {
-    TdnnfLayer &L = n->layers[l];
-    L.stride = c.time_stride[l];
-    L.left = c.use_layer_offsets ? c.offset_left[l] : L.stride;
-    L.right = c.use_layer_offsets ? c.offset_right[l] : L.stride;
-    L.bn = c.bottleneck_dim[l];
-    TDNNF_REQUIRE(L.bn > 0 && L.bn <= 512 && L.left >= 0 && L.right >= 0 && L.left <= 64 && L.right <= 64,
-                  "net_create: layer %d: bottleneck-dim must be in 1..512, time-stride / layer offsets in 0..64", l);
-    L.gout = g;
-    L.perm = false;
-    Grid lin = g, in = g;
-    const int Kd = c.darts_num_offsets;
-    if (Kd >= 2) {
-      // offset supernet: taps -(K-1)..0 / 0..K-1 at the input frame rate on every layer
-      if (g.step == 1) {
-        lin = Grid{g.t0, 1, g.n + Kd - 1};
-      } else {
-        const int rho = g.step;
-        const int cnt = rho * (g.n - 1) + Kd;
-        lin = Grid{g.t0, 1, ((cnt + rho - 1) / rho) * rho};  // padded to a multiple of rho (:841-843)
-        L.perm = true;
-      }
-      in = Grid{lin.t0 - (Kd - 1), 1, lin.n + Kd - 1};
-    } else if (L.left > 0 || L.right > 0) {
-      // X.linear taps {-a, 0}, X.affine taps {0, b} (time-stride s: a = b = s; a derived child: any a, b >= 0).  The
-      // linear runs on the coarsest regular grid that holds every frame the affine needs and whose own taps stay on the
-      // input grid: step gcd(output step, a, b).  When that is finer than the output grid the affine has row_stride
-      // rho > 1 and the grid is padded to a multiple of rho (nnet-tdnn-component.cc:841-843).
-      const int a = L.left, b = L.right;
-      auto gcd = [](int x, int y) {
-        while (y) {
-          const int t = x % y;
-          x = y;
-          y = t;
-        }
-        return x;
-      };
-      const int ls = gcd(gcd(g.step, a), b);
-      if (ls == g.step) {
-        lin = Grid{g.t0, g.step, g.n + b / g.step};
-      } else {
-        const int rho = g.step / ls, cnt = ((g.n - 1) * g.step + b) / ls + 1;
-        lin = Grid{g.t0, ls, ((cnt + rho - 1) / rho) * rho};
-        L.perm = true;
-      }
-      in = Grid{lin.t0 - a, ls, lin.n + a / ls};
-    }
-    L.glin = lin;
-    L.gin = in;
-    g = in;
-  }
-  n->g_lda = g;
+  CK(net_layer_grids(c, n->Tout, n->layers, &n->g_lda));
+  const Grid g = n->g_lda;
   n->g_feat = Grid{g.t0 - 1, 1, g.n * g.step + 2};
   TDNNF_REQUIRE(g.step == 1, "net_create: the first tdnnf layers must run at the input frame rate");
   // ---- components, in nnet3 config order

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Forward-only inference over whole utterances (tdnnf_infer_compute) of the 7q model at full width: 1536 hidden, 6034 pdfs,
+200 synthetic utterances of 300-1500 frames, frames_per_chunk 51 (decode.sh's 50 rounded to frame_subsampling) and 150.
+Prints one JSON line: input frames/s and ms per call, the GEMM rate against the 157.3 TFLOP/s exact-f32 MFMA peak (GEMM FLOPs
+from the library's own launch accounting, tdnnf_profile_*, in a separate call), the chunk-context overhead (F + context) / F
+and the fused / fallback counts.
+usage (GPU box): python tools/infer_bench.py [--calls K] [--utts N] [--max-chunks M]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import __graft_entry__ as ge  # noqa: E402
+
+PEAK_TFLOPS = 157.3
+
+
+def model_stats(cfg):
+    """BatchNorm statistics of mean 0.3, variance 1 (and ReLU statistics) in tdnnf_net_get_stats order."""
+    Hd, S, out = cfg.hidden_dim, cfg.prefinal_small_dim, []
+    bn = lambda D: out.append(np.concatenate([[64.0], np.full(D, 64 * 0.3), np.full(D, 64 * 1.09)]))
+    relu = lambda D: out.append(np.concatenate([[64.0], np.full(D, 10.0), np.full(D, 32.0), [0.0], np.zeros(D)]))
+    for _ in range(cfg.num_layers + 1):
+        bn(Hd), relu(Hd)
+    for _ in range(2):
+        bn(Hd), relu(Hd), bn(S)
+    return np.concatenate(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=3)
+    ap.add_argument("--utts", type=int, default=200)
+    ap.add_argument("--max-chunks", type=int, default=256)
+    ap.add_argument("--widths", default="51,150")
+    args = ap.parse_args()
+    pkg = ge.load_package()
+    lib = pkg.hipabi.load()
+    cfg = pkg.trainer.make_config(frames_per_chunk=150, num_sequences=1, cv_update=1)  # 7q graph, 1536 / 6034
+    net = pkg.trainer.ChainNet(cfg)
+    net.set_params(net.init_params_numpy(seed=0, output_stddev=0.05))
+    net.set_stats(model_stats(cfg))
+    rng = np.random.default_rng(1)
+    lengths = rng.integers(300, 1501, size=args.utts)
+    utts = [(rng.standard_normal((int(T), 40)).astype(np.float32), rng.standard_normal((-(-int(T) // 10), 100)).astype(np.float32)) for T in lengths]
+    frames = int(lengths.sum())
+    res = dict(metric="infer_7q_full_width", utterances=args.utts, input_frames=frames, max_chunks=args.max_chunks, peak_tflops=PEAK_TFLOPS)
+    for F in [int(w) for w in args.widths.split(",")]:
+        am = pkg.infer.AcousticModel(net, frames_per_chunk=F, max_chunks=args.max_chunks)
+        probe = pkg.trainer.ChainNet(pkg.trainer.make_config(frames_per_chunk=F, num_sequences=1, cv_update=1), share=net)
+        context = probe.num_t_in - F
+        probe.close()
+        am.compute(utts)  # warm-up (uploads, first launches)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.calls):
+            am.compute(utts)
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / args.calls
+        pkg.hipabi.check(lib.tdnnf_profile_enable(1))
+        am.compute(utts)
+        torch.cuda.synchronize()
+        flops = 0.0
+        for k in range(4):
+            n, t, fl = C.c_double(), C.c_double(), C.c_double()
+            pkg.hipabi.check(lib.tdnnf_profile_read(k, C.byref(n), C.byref(t), C.byref(fl)))
+            flops += fl.value
+        pkg.hipabi.check(lib.tdnnf_profile_enable(0))
+        fused, fallback = am.counts()
+        res[f"F{F}"] = dict(frames_per_s=round(frames / (ms / 1e3)), ms_per_call=round(ms, 2), gemm_tflop=round(flops / 1e12, 3),
+                           gemm_tflops_per_s=round(flops / (ms / 1e3) / 1e12, 1), of_peak=round(flops / (ms / 1e3) / 1e12 / PEAK_TFLOPS, 3),
+                           context_overhead=round((F + context) / F, 3), fused_layers=fused, fallback_passes=fallback)
+        am.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
