@@ -9,7 +9,7 @@
 //
 // These follow the reference's LITERAL order -- splice [c_i X_i ..., 1] into a temporary, copy out_deriv, precondition
 // both copies in place, multiply by the product of the two scales -- because a caller that owns its own preconditioner
-// objects and accumulators (a Kaldi component) expects exactly that state evolution.  The chain trainer (net.hip) uses
+// objects and accumulators (a Kaldi component) expects exactly that state evolution.  The chain trainer (net_step.hip) uses
 // the algebraically equal projection form of ng.h, which never materialises the N x D temporaries.
 #include <string.h>
 

@@ -1,4 +1,4 @@
-// fused.hip -- fused HBM-bound passes used by the chain trainer (net.hip) between the MFMA GEMMs.
+// fused.hip -- fused HBM-bound passes used by the chain trainer (net_step.hip) between the MFMA GEMMs.
 //
 // The reference runs ReLU, BatchNorm, (dropout) and the bypass Sum() of a tdnnf-layer
 // (/root/reference/steps/libs/nnet3/xconfig/composite_layers.py:177-213) as separate components, each a

@@ -2,7 +2,7 @@
 //
 // nnet3's DecodableNnetSimple (UPSTREAM, not shipped) restated for the TDNN-F graphs of net.hip: utterances are cut into chunks of
 // F input frames, a batch of up to max_chunks chunks runs the network once, and the output rows that lie inside their utterance
-// go straight to the caller's stacked output.  The schedule is the trainer's forward pass in test mode (cv_update) without the
+// go straight to the caller's stacked output.  The schedule is the trainer's forward pass (net_step.hip) in test mode (cv_update) without the
 // separate elementwise passes: every BatchNorm -- and a TDNN-F layer's bypass -- is applied while the GEMM stores its tile
 // (RowsGemmArgs::col_scale / col_offset / post_add, gemm_f32.h).  Memory: two ping-pong activation buffers (a layer's input
 // dies once its bypass is consumed), the linear and head temporaries and the chunk table; no gradients, natural-gradient
@@ -22,9 +22,6 @@ using namespace tdnnf;
 namespace {
 
 constexpr int kTab = 6;  // device chunk table: [first feature row of the utterance, T_u, k F, stacked i-vector row, first output row, n_k]
-
-inline int ldpad(int cols) { return (cols + 31) & ~31; }  // (the trainer's row stride: rows start on 128-byte lines)
-tdnnf_mat M(float *p, int rows, int cols) { return tdnnf_mat{p, rows, cols, ldpad(cols)}; }
 
 // Spliced LDA input of a batch of B chunks, t-major (row k B + b, k < nk): [feats(t_k), feats(t_k + 1), feats(t_k + 2) ; i-vector]
 // with t_k = kF + first_t + k clamped to the utterance -- the layout tdnnf_splice_input produces, read through the chunk table.
@@ -116,13 +113,6 @@ struct tdnnf_infer {
 };
 
 namespace {
-
-tdnnf_mat sub_grid_view(float *data, const Grid &g, const Grid &sub, int B, int cols) {  // (as net.hip's)
-  const int stride = ldpad(cols);
-  const int tau0 = (sub.t0 - g.t0) / g.step, ratio = sub.step / g.step;
-  if (ratio == 1) return tdnnf_mat{data + (size_t)tau0 * B * stride, sub.n * B, cols, stride};
-  return tdnnf_mat{data + (size_t)tau0 * B * stride, sub.n, B * stride - (stride - cols), ratio * B * stride};
-}
 
 struct Arena {
   size_t off = 0;
@@ -228,12 +218,6 @@ int gemm_post(const tdnnf_tdnn_indexes &ix, const tdnnf_mat &in, const float *W,
   TDNNF_HIP(rows_gemm(a, true, s));
   return TDNNF_OK;
 }
-
-#define CK(expr)             \
-  do {                       \
-    int rc__ = (expr);       \
-    if (rc__) return rc__;   \
-  } while (0)
 
 // one batch of B chunks (their table entries at tab)
 int forward_batch(tdnnf_infer *q, const tdnnf_mat *feats, const tdnnf_mat *iv, const int *tab, int B, tdnnf_mat *out, hipStream_t s, bool count) {

@@ -1,4 +1,5 @@
-// net.h -- data structures of the chain trainer (net.hip), shared with the model reader / writer (model_io.hip).
+// net.h -- data structures of the chain trainer (net.hip: layout, creation, update; net_step.hip: one minibatch), shared with the model
+// reader / writer (model_io.hip) and the forward-only inference (infer.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,7 +123,7 @@ struct tdnnf_net {
   // caller's stream (or the weight-gradient stream) into buffers the component keeps for the step; everything latency-bound that
   // follows (L, traces, the rank-R projections of T, commit; K and the host hand-off on a refresh) runs ONCE PER GRADIENT BUCKET
   // as grouped launches on stream s3 (ng.h, ng_group.hip).  The per-object form of that chain remains for the first minibatch
-  // (the preconditioners initialise themselves from it) and for TDNNF_NG_GROUPED=0.
+  // (the preconditioners initialise themselves from it) and for option ng_grouped = 0.
   struct NgComp {
     float *H_in = nullptr, *H_out = nullptr, *T = nullptr, *bsum = nullptr;
     double *part_in = nullptr, *part_out = nullptr;
@@ -153,12 +154,12 @@ struct tdnnf_net {
   // independent of the backward-data GEMM that follows it.  At the recipes' minibatch (3 200 rows) neither fills the chip, so
   // they run side by side: param_grad() goes to s4 with a workspace of its own, the caller's stream waits for the one before
   // the last (the buffers a gradient reads are rewritten two components later at the earliest).  Off for minibatches whose
-  // GEMMs fill the chip by themselves (TDNNF_WGRAD_STREAM=0|1 forces it).
+  // GEMMs fill the chip by themselves (option wgrad_stream = 0 | 1 forces it).
   bool wg_on;
   hipStream_t s4;
   hipEvent_t ev_pg[4], ev_pg_in;
   int wg_lag = 3;        // the caller's stream waits for the weight gradient of the component wg_lag back (option wgrad_lag: 1 or 3)
-  float *dC2 = nullptr, *dS[2] = {nullptr, nullptr};  // wg_lag 3: second buffers for the derivative matrices weight gradients read (net.hip)
+  float *dC2 = nullptr, *dS[2] = {nullptr, nullptr};  // wg_lag 3: second buffers for the derivative matrices weight gradients read (net_step.hip)
   unsigned pg_count;
   void *ws4;
   void *ws2;           // the same for components whose weight gradients go to the denominator's stream (wg_two)
@@ -240,4 +241,39 @@ inline float *net_bias(const tdnnf_net *n, int comp) {
   const CompDesc &c = n->comps[comp];
   return c.has_bias ? n->params + c.begin + (long long)c.rows * c.cols + c.num_alpha : nullptr;
 }
+// the same places in this minibatch's gradient (gtmp); net_Ag: the architecture logits' (whatever num_alpha is)
+inline float *net_Wg(const tdnnf_net *n, int comp) { return n->gtmp + n->comps[comp].begin; }
+inline float *net_Ag(const tdnnf_net *n, int comp) { return n->gtmp + n->comps[comp].begin + (long long)n->comps[comp].rows * n->comps[comp].cols; }
+inline float *net_Bg(const tdnnf_net *n, int comp) {
+  const CompDesc &c = n->comps[comp];
+  return c.has_bias ? n->gtmp + c.begin + (long long)c.rows * c.cols + c.num_alpha : nullptr;
+}
+// Row stride of every activation matrix of the trainer: a multiple of 32 floats, so that rows start on 128-byte lines.
+// (With the 16-byte minimum, the 6034-wide output matrices ran their GEMMs at 80 instead of 120 TFLOP/s: every 128-byte
+// row segment a tile load fetches straddled two cache lines.)
+inline int ldpad(int cols) { return (cols + 31) & ~31; }
+inline tdnnf_mat M(float *p, int rows, int cols) { return tdnnf_mat{p, rows, cols, ldpad(cols)}; }
+inline int N_of(const Grid &g, int B) { return g.n * B; }
+// view of the rows of a t-major matrix (grid g, B sequences, `cols` wide) that lie on a coarser grid `sub`
+inline tdnnf_mat sub_grid_view(float *data, const Grid &g, const Grid &sub, int B, int cols) {
+  const int stride = ldpad(cols);
+  const int tau0 = (sub.t0 - g.t0) / g.step, ratio = sub.step / g.step;
+  if (ratio == 1) return tdnnf_mat{data + (size_t)tau0 * B * stride, sub.n * B, cols, stride};
+  // every ratio-th block of B rows: n "super rows" of B*stride elements
+  return tdnnf_mat{data + (size_t)tau0 * B * stride, sub.n, B * stride - (stride - cols), ratio * B * stride};
+}
+// diagnostics: phase boundary k of the step (option phase_events)
+inline int phase_mark(tdnnf_net *n, int k, hipStream_t s) {
+  if (!options().phase_events) return TDNNF_OK;
+  if (!n->ev_phase[k]) TDNNF_HIP(hipEventCreate(&n->ev_phase[k]));
+  TDNNF_HIP(hipEventRecord(n->ev_phase[k], s));
+  n->phase_rec[k] = true;
+  return TDNNF_OK;
+}
 }  // namespace tdnnf
+
+#define CK(expr)             \
+  do {                       \
+    int rc__ = (expr);       \
+    if (rc__) return rc__;   \
+  } while (0)

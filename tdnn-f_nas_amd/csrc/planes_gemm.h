@@ -127,7 +127,7 @@ void planes_split_group_destroy(PlanesSplitGroup *g);
 hipError_t planes_pad(int np, void *P, long long k_blocks, long long R, int lead, long long rows, hipStream_t s);
 // tile shape the GEMM uses for an N-column output: the A buffer needs tail >= tile rows beyond the last row read, the B buffer rows padded to the tile's columns
 // ---- routing of the f32 GEMM entry points (rows_gemm / wgrad, gemm_f32.h) onto the plane kernels.
-// The caller that owns the matrices (net.hip) splits an operand, describes the result in a PlanesOperand and installs it as a hint
+// The caller that owns the matrices (net_step.hip) splits an operand, describes the result in a PlanesOperand and installs it as a hint
 // around the call; rows_gemm() / wgrad() check that the hinted planes really are those of their operands (base pointer, leading
 // dimension, row range, zero rows around the views) and run the plane kernels, else their own.
 struct PlanesOperand {

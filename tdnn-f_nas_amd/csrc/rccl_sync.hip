@@ -4,7 +4,7 @@
 // parameter-gradient buffer per minibatch, bucketed and overlapped with the backward pass, and (2) for exact single-GPU equivalence the
 // column sums of every train-mode BatchNorm (/root/reference/src/nnet3/nnet-normalize-component.cc:433-445 takes its statistics over all
 // rows of the minibatch).  Both are enqueued here with ncclAllReduce -- the gradient buckets on a communication stream behind the event
-// net.hip records when a bucket is final, the BatchNorm sums on the compute stream between the two finalize launches -- so that no
+// net_step.hip records when a bucket is final, the BatchNorm sums on the compute stream between the two finalize launches -- so that no
 // host language sits in the step's critical path (round 3 called back into Python 56 times per step for the BatchNorm sums).
 //
 // librccl.so is resolved with dlopen on first use: the library has no link-time dependency on RCCL, a single-GPU user never loads it.
