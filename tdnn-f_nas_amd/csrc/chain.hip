@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "device.h"
 #include "gemm_f32.h"
 
 struct tdnnf_den_graph {
@@ -1448,19 +1449,13 @@ int g_den_mode = 0;  // tdnnf_chain_set_denominator_mode: 0 automatic, 1 persist
 struct MwDev {
   unsigned *fallbacks = nullptr;  // pinned host memory, written by den_mw_check_kernel
   bool off = false;               // a multi-workgroup launch gave up once on this device: not used again there
-  int cus = 0;                    // compute units (0 = not asked yet, -1 = unknown)
 };
 constexpr int kMaxDev = 64;
 MwDev g_mw[kMaxDev];
 MwDev *mw_dev() {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return nullptr;
-  MwDev &d = g_mw[dev];
-  if (d.cus == 0) {
-    hipDeviceProp_t prop;
-    d.cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : -1;
-  }
-  return &d;
+  return &g_mw[dev];
 }
 // exchange buffers and counters of the multi-workgroup recursions (den_mw_kernel), behind b_all / S_all in the split region
 size_t mw_slots(const tdnnf_den_graph *g) { return (size_t)std::max(g->by_dst.nslices, g->by_src.nslices) * 64; }
@@ -1473,7 +1468,7 @@ int mw_groups(const tdnnf_den_graph *g, int B, int T) {
   MwDev *md = mw_dev();
   if (g_den_mode == 3 || !md || md->off || T < 8) return 0;
   (void)hipGetLastError();
-  const int cus = md->cus, G = 4;
+  const int cus = device_cus_known(), G = 4;  // (-1: unknown, the one-workgroup kernels)
   if (cus <= 0 || 2 * B * G > cus) return 0;
   const int ns = std::min(g->by_dst.nslices, g->by_src.nslices), nsmax = std::max(g->by_dst.nslices, g->by_src.nslices);
   if (ns < G || (nsmax + G - 1) / G > 64) return 0;
@@ -1833,6 +1828,7 @@ int chain_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
     TDNNF_HIP(hipStreamWaitEvent(aux, ev_fork, 0));
     int G = mw_groups(g, B, T);
     MwDev *md = mw_dev();
+    const int cus = device_cus_known();  // (-1: unknown)
     if (!md) G = 0;
     if (G > 0 && !md->fallbacks) {  // (first use on this device: the host-visible fallback counter)
       if (hipHostMalloc((void **)&md->fallbacks, sizeof(unsigned), hipHostMallocMapped) != hipSuccess) {
@@ -1860,7 +1856,7 @@ int chain_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
       int occ_f = 0, occ_b = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_f, den_mw_kernel<0>, kDenThreads, lds_f) != hipSuccess ||
           hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_b, den_mw_kernel<1>, kDenThreads, lds_b) != hipSuccess || occ_f < 1 || occ_b < 1 ||
-          md->cus <= 0 || 2 * B * G > md->cus) {
+          cus <= 0 || 2 * B * G > cus) {
         (void)hipGetLastError();
         G = 0;
       }
@@ -1891,7 +1887,7 @@ int chain_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
       const bool fast = g->by_dst.nslices * 64 <= kDenFastSlots * kDenThreads && g->by_src.nslices * 64 <= kDenFastSlots * kDenThreads && g->H <= kDenFastStates * kDenThreads;
       const size_t lf = b.p.lds_fwd + (fast ? sizeof(float) * b.p.Hs : 0), lb = lds_beta + (fast ? sizeof(float) * H4 : 0);
       int res_f = 0, res_b = 0;
-      if (md && md->cus > 0 && 2 * B >= md->cus) {
+      if (md && cus > 0 && 2 * B >= cus) {
         const size_t budget = 150 * 1024;
         if (lf < budget) res_f = (int)std::min<long long>(g->by_dst.entries, (long long)((budget - lf) / 8)) & ~63;
         if (lb < budget) res_b = (int)std::min<long long>(g->by_src.entries, (long long)((budget - lb) / 8)) & ~63;

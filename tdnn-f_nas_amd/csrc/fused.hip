@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "device.h"
 #include "fused.h"
 #include "gemm_f32.h"
 #include "planes_gemm.h"
@@ -500,13 +501,7 @@ bool bn_relu_bwd_ng_ok(MatView x, MatView dz, MatView d_aff, int Rp) {
 // (514 blocks on 256 CUs: 0.50 ms against 0.32 ms for 512), and a launch of few blocks (a 9 600-row minibatch: 75) leaves most
 // CUs idle while each block walks all its columns; in both cases the separate passes are faster.
 bool bn_relu_bwd_ng_pays(int rows) {
-  static int slots = 0;
-  if (!slots) {
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    slots = 2 * cus;
-  }
+  const int slots = 2 * device_cus();
   const int blocks = (rows + 127) / 128, rounds = (blocks + slots - 1) / slots;
   return 4 * blocks >= 3 * rounds * slots;  // the rounds at least 3/4 used: fewer blocks walk their 1536 columns on idle CUs' time
 }

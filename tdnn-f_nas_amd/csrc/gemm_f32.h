@@ -1,9 +1,12 @@
-// gemm_f32.h -- host-side interface of the exact-f32 MFMA GEMM kernels (gfx950).
+// gemm_f32.h -- host-side interface of the MFMA GEMMs (gfx950): the rows GEMM (rows_gemm.hip) and the weight gradient (wgrad.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #include <vector>
+
+#include "prof.h"
 
 namespace tdnnf {
 
@@ -58,7 +61,7 @@ struct RowsGemmArgs {
   // to ~2^-16 relative, f32 accumulation); needs a k-contiguous B and 16-byte alignment, otherwise the f32 kernel runs.
   int prec;
   int serial_epilogue;  // 1: the one-segment-at-a-time epilogue for every tile (rows_gemm() sets 0)
-  int alt_seg_order;    // set by rows_gemm(): odd row tiles visit the K segments in reverse order (taps = row shifts of one matrix, gemm_f32.hip)
+  int alt_seg_order;    // set by rows_gemm(): odd row tiles visit the K segments in reverse order (taps = row shifts of one matrix, rows_gemm_kernels.h)
   int nseg;
   GemmSeg seg[kMaxSeg];
   // Inference epilogue (all off by default; any of them set: exact f32, no K split, no statistics).  After the ReLU:
@@ -72,39 +75,6 @@ struct RowsGemmArgs {
   const int *row_map;
 };
 inline bool rows_gemm_has_post(const RowsGemmArgs &a) { return a.col_scale || a.col_offset || a.post_add || a.row_map; }
-
-// Event-timing class of the launches made while one of these is alive (tdnnf_profile_*: 0 rows_gemm 128x128,
-// 1 rows_gemm 128x160, 2 wgrad, 3 natural-gradient skinny GEMMs).
-struct ProfClassOverride {
-  int prev;
-  explicit ProfClassOverride(int cls);
-  ~ProfClassOverride();
-};
-
-// Event timing of an HBM-bound pass while tdnnf_profile_enable is on: class 4 bn_apply_bypass, 5 bn_relu_bwd (both stages),
-// 6 denominator (forward + backward recursions), 7 planes_split; `bytes` = the pass's algorithmic HBM bytes (every element once).
-struct ProfHbmRange {
-  void *c;
-  hipStream_t s;
-  ProfHbmRange(int cls, double bytes, hipStream_t stream);
-  ~ProfHbmRange();
-};
-
-// Event pair + algorithmic work of ONE launch made outside gemm_f32.hip that belongs to a GEMM class (0 .. 3; ng_valu.hip: class 3).
-struct ProfGemmRange {
-  void *c;
-  hipStream_t s;
-  ProfGemmRange(int cls, double flops, double bytes, hipStream_t stream);
-  ~ProfGemmRange();
-};
-
-// Scales the algorithmic FLOPs recorded for the launches made while alive: the host cannot see device-side tap
-// coefficients, so a caller that knows only `active` of K taps are non-zero (DARTS uniform-sample mode) says so.
-struct ProfFlopsScale {
-  double prev;
-  explicit ProfFlopsScale(double f);
-  ~ProfFlopsScale();
-};
 
 // rows_gemm() keeps one process-wide scratch buffer for its split-K partial tiles, which is only safe for launches that
 // are ordered on one stream.  Launches made on another stream while one of these is alive use `buf` instead.
@@ -123,6 +93,7 @@ struct GemmPrecisionScope {
   explicit GemmPrecisionScope(int prec);
   ~GemmPrecisionScope();
 };
+int gemm_precision_default();  // what the innermost GemmPrecisionScope alive asked for, 0 without one
 // Transposed copies of weight matrices for the split-bf16 backward-data GEMMs (their B operand must be k-contiguous):
 // while alive, a weight pointer W inside [w_base, w_base + n) has its transpose (cols x rows, dense) at wt_base + (W - w_base).
 struct TransposedWeightsScope {
@@ -132,6 +103,8 @@ struct TransposedWeightsScope {
   ~TransposedWeightsScope();
 };
 const float *transposed_weights(const float *W);  // null when there is none (or split-bf16 is not the default)
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // capacity of the p.sumsq array for M rows: one entry per 128-row block, or per (block, K-slice) when rows_gemm() splits K
 // over idle CUs for a launch of few blocks (then blocks x slices <= the chip's resident blocks <= 1024); the kernel zeroes

@@ -4,7 +4,7 @@
 
 namespace tdnnf {
 
-bool rows_gemm_ring_enabled();  // TDNNF_GEMM_RING != 0
+bool rows_gemm_ring_enabled();  // option gemm_ring != 0
 int rows_gemm_ring_mode();      // 1: the 128 x 128 tile only (default); 2: the 128 x 160 tile as well
 // k-contiguous B, whole-K-step segments, exact f32, 16-byte aligned operands (vec), no tap coefficients / sumsq / split-K
 bool rows_gemm_ring_ok(const RowsGemmArgs &a, bool b_kcontig, bool vec);

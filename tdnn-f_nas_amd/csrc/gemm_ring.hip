@@ -1,6 +1,6 @@
 // gemm_ring.hip -- the exact-f32 rows GEMM as a PERSISTENT kernel fed by an LDS-DMA ring (gfx950).
 //
-// Same arithmetic and arguments as rows_gemm_kernel (gemm_f32.hip): C[m][n] (+)= sum over K-segments (the taps of
+// Same arithmetic and arguments as rows_gemm_kernel (rows_gemm_kernels.h): C[m][n] (+)= sum over K-segments (the taps of
 // TdnnComponent::Propagate / Backprop, /root/reference/src/nnet3/nnet-tdnn-component.cc:302-324, :378-411) of A_s[m][k] B_s[k][n] with
 // v_mfma_f32_32x32x2_f32, bias / old C / fused addend / ReLU / column statistics in the epilogue.  What differs is how a tile is fed
 // and what happens between tiles -- the two things the K = 320 shapes of a TDNN-F layer (20 K steps per tile) spent their time on
@@ -18,10 +18,11 @@
 //     fragment reads of 16 consecutive rows fall on 16 different 16-byte columns of the 256-byte bank row.
 //
 // Taken by rows_gemm() for exact-f32 launches whose segments are whole K steps, without tap coefficients / sumsq / split-K; everything
-// else stays on rows_gemm_kernel.  TDNNF_GEMM_RING=0 turns it off (A/B runs).
+// else stays on rows_gemm_kernel.  Option gemm_ring = 0 turns it off (A/B runs).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "device.h"
 #include "gemm_f32.h"
 #include "gemm_ring.h"
 
@@ -349,18 +350,6 @@ __global__ __launch_bounds__(256, TN == 5 ? 2 : 3) void rows_gemm_ring_kernel(co
   }
 }
 
-int g_ring_cus = 0;
-int ring_cus() {
-  if (g_ring_cus == 0) {
-    int dev = 0;
-    g_ring_cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_ring_cus = prop.multiProcessorCount;
-    (void)hipGetLastError();
-  }
-  return g_ring_cus;
-}
-
 template <int WM, int WN, int TM, int TN>
 hipError_t launch_ring(const RowsGemmArgs &a, int blocks, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -395,7 +384,7 @@ bool rows_gemm_ring_ok(const RowsGemmArgs &a, bool b_kc, bool vec) {
   return true;
 }
 
-int rows_gemm_ring_slots(int tile_cols) { return (tile_cols == 160 ? 2 : 3) * ring_cus(); }
+int rows_gemm_ring_slots(int tile_cols) { return (tile_cols == 160 ? 2 : 3) * device_cus(); }
 
 hipError_t rows_gemm_ring(const RowsGemmArgs &a, bool b_kc, int tile_cols, hipStream_t s) {
   const int blocks = rows_gemm_ring_slots(tile_cols);

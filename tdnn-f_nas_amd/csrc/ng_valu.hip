@@ -312,7 +312,7 @@ hipError_t ng_rowdot(const NgRowdotArgs &a, hipStream_t s) {
   const int cap = a.part ? a.part_cap : 1024;
   const int grid = std::max(1, std::min(ntiles, std::min(cap, 1024)));
   // algorithmic work of the pass for the event-timed class (bench.py roofline_secondary): 2 N D R FLOPs; X once, H once
-  // (taps = row shifts of one matrix share its rows, as gemm_f32.hip counts them)
+  // (taps = row shifts of one matrix share its rows, as rows_gemm.hip counts them)
   const double D = (double)a.nseg * a.Di;
   long long lo = a.seg_off[0], hi = a.seg_off[0];
   for (int i = 1; i < a.nseg; i++) {

@@ -9,7 +9,7 @@
 //     the exact-f32 kernel's own summation error (tests/test_gpu_planes_gemm.py, against float64): an element that is small against
 //     its matrix's rms loses relative precision (its low plane becomes subnormal: absolute error <= 2^-25 of the scaled value 1), which a
 //     product that sums thousands of typical elements does not see.
-// The round-2 kernels (gemm_f32.hip, rows_gemm_x3_kernel) split f32 operands when a staged tile goes to LDS and wait for exactly that
+// The round-2 kernels (rows_gemm_kernels.h, rows_gemm_x3_kernel) split f32 operands when a staged tile goes to LDS and wait for exactly that
 // path.  Here the split happens ONCE per operand, in a pass of its own (planes_split_kernel), into a layout made for the consumer:
 //
 //   P16 planes of an R x C matrix:  e16 P[kb][plane][row][16],  kb = c / 16 (K blocks of 16), row 0..R-1
@@ -1046,7 +1046,7 @@ hipError_t planes_gemm(const PlanesGemmArgs &a, hipStream_t s) {
   if (a.np != 2 && a.np != 3) return hipErrorInvalidValue;
   if (a.ntap > 1 && a.nseg != 1) return hipErrorInvalidValue;
   // 160-wide tiles for the TDNN-F bottleneck, 256- / 128-wide otherwise; 8 waves (two per SIMD)
-  // Measured on MI355X for np = 3 (tools/planes_bench.py, f32-equivalent TFLOP/s; exact-f32 kernel of gemm_f32.hip in brackets):
+  // Measured on MI355X for np = 3 (tools/planes_bench.py, f32-equivalent TFLOP/s; exact-f32 kernel of rows_gemm_kernels.h in brackets):
   //   256 x 256 tile, 8 waves of 64 x 128:  N = 1536, K = 2 x 1536: 227 [130];  K = 2 x 160 (.affine forward): 162 [116]
   //   256 x 160 tile, 8 waves of 32 x 160:  N = 160, K = 2 x 1536 (.linear forward): 151 [117]
   //   256 x 128 tile, 4 x 2 waves of 64 x 64: 201 / 150.  Four waves of 64 rows x the tile's width: 194 / 121 (one wave per SIMD
