@@ -1,0 +1,227 @@
+// chain_num.hip -- the numerator of the chain objective (one wave per sequence, log domain), the kernels that finish the objective
+// (sum, l2 term, failure path) and the entry point that runs all three parts.  Denominator: chain_den.hip.
+#include <math.h>
+
+#include "chain_plan.h"
+
+namespace tdnnf {
+namespace {
+
+// The numerator recursion runs in the log domain, where the values grow with the frame index (log alpha ~ -8 t): at 500
+// frames a float's 24 bits leave an absolute error of ~2e-4 in the exponent of a posterior, 2e-3 in the posteriors of a
+// 1500-frame chunk (measured: frame sums of gamma_num off by up to 2.2e-3, derivative 6.8e-4 from a float64 evaluation).  Doubles:
+// one wave per sequence walks a few states per frame, the arithmetic is free.
+__device__ __forceinline__ double log_add(double a, double b) {
+  if (a == -INFINITY) return b;
+  if (b == -INFINITY) return a;
+  const double m = fmax(a, b), d = fmin(a, b) - m;
+  return m + log1p(exp(d));
+}
+
+// one wave per sequence.  la/lb: global scratch indexed by global state id.
+__global__ __launch_bounds__(64) void numerator_kernel(SupDev sp, MatView y, MatView xent_out, double *la, double *lb,
+                                                       double *num_logprob, double *xent_objf, MatView deriv,
+                                                       MatView xent_deriv, float xent_scale, int phases) {
+  // phases bit 0: forward-backward recursion (la, lb, total -> num_logprob): needs the chain output y only;
+  //        bit 2: xent posteriors / objective; bit 1: deriv += weight * gamma_num  (both need the recursion's la / lb / total,
+  //        possibly from an earlier launch)
+  const int s = blockIdx.x, lane = threadIdx.x, B = sp.B, T = sp.T;
+  const int *fsb = sp.frame_state_begin + (size_t)s * (T + 2);
+  const int s0 = sp.seq_state_begin[s], s1 = sp.seq_state_begin[s + 1];
+  double tot = -INFINITY;
+  if (phases & 1) {
+  for (int i = s0 + lane; i < s1; i += 64) la[i] = (i == s0) ? 0.0 : -INFINITY;
+  __syncthreads();
+  for (int t = 1; t <= T; t++) {  // states entered at time t
+    for (int st = fsb[t] + lane; st < fsb[t + 1]; st += 64) {
+      double v = -INFINITY;
+      for (int a = sp.in_begin[st]; a < sp.in_begin[st + 1]; a++)
+        v = log_add(v, la[sp.in_src[a]] + ((double)sp.in_lp[a] + (double)y.data[(size_t)((t - 1) * B + s) * y.stride + sp.in_pdf[a]]));
+      la[st] = v;
+    }
+    __syncthreads();
+  }
+  for (int st = fsb[T] + lane; st < fsb[T + 1]; st += 64) {
+    const float f = sp.final_logprob[st];
+    lb[st] = (double)f;
+    if (f != -INFINITY) tot = log_add(tot, la[st] + (double)f);
+  }
+  for (int o = 32; o > 0; o >>= 1) tot = log_add(tot, __shfl_xor(tot, o, 64));
+  __syncthreads();
+  for (int t = T - 1; t >= 0; t--) {
+    for (int st = fsb[t] + lane; st < fsb[t + 1]; st += 64) {
+      double v = -INFINITY;
+      for (int a = sp.out_begin[st]; a < sp.out_begin[st + 1]; a++)
+        v = log_add(v, ((double)sp.out_lp[a] + (double)y.data[(size_t)(t * B + s) * y.stride + sp.out_pdf[a]]) + lb[sp.out_dst[a]]);
+      lb[st] = v;
+    }
+    __syncthreads();
+  }
+  } else {
+    tot = num_logprob[s];
+  }
+  const bool do_xent = (phases & 4) != 0, do_deriv = (phases & 2) != 0;
+  if ((phases & 1) && lane == 0) num_logprob[s] = tot;
+  // posteriors: lane = frame (distinct output rows per lane, fixed arc order -> deterministic)
+  double xo = 0.0;
+  for (int t = lane; t < T; t += 64) {
+    const size_t row = (size_t)(t * B + s);
+    for (int st = fsb[t]; st < fsb[t + 1]; st++)
+      for (int a = sp.out_begin[st]; a < sp.out_begin[st + 1]; a++) {
+        const int pdf = sp.out_pdf[a];
+        const double ll = (double)sp.out_lp[a] + (double)y.data[row * y.stride + pdf];
+        const float gam = sp.weight * (float)exp(la[st] + ll + lb[sp.out_dst[a]] - tot);
+        if (do_deriv && deriv.data) deriv.data[row * deriv.stride + pdf] += gam;
+        if (do_xent && xent_deriv.data) xent_deriv.data[row * xent_deriv.stride + pdf] += xent_scale * gam;
+        if (do_xent && xent_out.data) xo += (double)gam * (double)xent_out.data[row * xent_out.stride + pdf];
+      }
+  }
+  if (do_xent) {
+    for (int o = 32; o > 0; o >>= 1) xo += __shfl_xor(xo, o, 64);
+    if (lane == 0) xent_objf[s] = xo;
+  }
+}
+
+// results: [0] objf [1] l2_term [2] weight [3] num [4] den [5] ok [6] xent objf
+__global__ void chain_finalize_kernel(const double *num_lp, const double *den_lp, const double *xent, const double *l2sum,
+                                      int B, int T, float weight, float l2_regularize, double *results) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double num = 0, den = 0, xo = 0;
+  for (int s = 0; s < B; s++) {
+    num += num_lp[s];
+    den += den_lp[s];
+    xo += xent[s];
+  }
+  num *= weight;
+  den *= weight;
+  double objf = num - den;
+  const double w = (double)weight * B * T;
+  const bool ok = (objf - objf == 0.0);
+  if (!ok) objf = -10.0 * w;
+  results[0] = objf;
+  results[1] = (l2_regularize == 0.f || !l2sum) ? 0.0 : -0.5 * (double)weight * l2_regularize * l2sum[0];
+  results[2] = w;
+  results[3] = num;
+  results[4] = den;
+  results[5] = ok ? 1.0 : 0.0;
+  results[6] = ok ? xo : 0.0;
+}
+
+// failure path (objf not finite): zero the derivatives; otherwise add the l2 term's derivative.
+__global__ void chain_guard_kernel(const double *results, MatView y, float l2_scale, MatView d, MatView xd) {
+  const bool ok = results[5] != 0.0;
+  if (ok && l2_scale == 0.f) return;
+  const long long total = (long long)d.rows * d.cols;
+  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += gridDim.x * 256LL) {
+    const int r = (int)(e / d.cols), c = (int)(e % d.cols);
+    if (!ok) {
+      d.data[(size_t)r * d.stride + c] = 0.f;
+      if (xd.data) xd.data[(size_t)r * xd.stride + c] = 0.f;
+    } else {
+      d.data[(size_t)r * d.stride + c] += -l2_scale * y.data[(size_t)r * y.stride + c];
+    }
+  }
+}
+__global__ __launch_bounds__(256) void sumsq_kernel(MatView y, double *out) {
+  __shared__ double red[4];
+  double s = 0;
+  const long long total = (long long)y.rows * y.cols;
+  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += gridDim.x * 256LL) {
+    const double v = y.data[(size_t)(e / y.cols) * y.stride + e % y.cols];
+    s += v * v;
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
+}
+__global__ void zero_rows_kernel(MatView m) {
+  const long long total = (long long)m.rows * m.cols;
+  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += gridDim.x * 256LL)
+    m.data[(size_t)(e / m.cols) * m.stride + e % m.cols] = 0.f;
+}
+
+}  // namespace
+}  // namespace tdnnf
+
+namespace tdnnf {
+float chain_supervision_weight(const tdnnf_supervision *sp) { return sp->weight; }
+// (2) numerator recursion; xent_deriv = xent_regularize * gamma_num, xent objective -> workspace.  Does not touch deriv.
+// In two launchable halves: the recursion needs the chain output only (the trainer starts it beside the denominator, under the
+// xent head's forward pass: 1.35 ms of one wave per sequence walking 2 x 500 dependent frames that the step otherwise waited for),
+// the xent posteriors need the recursion and the xent head's log-softmax.
+int chain_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph *g, const tdnnf_mat *y, void *ws, hipStream_t s) {
+  const int B = sp->B, T = sp->T;
+  ChainBufs b = chain_bufs(g, B, T, ws);
+  const MatView none{nullptr, 0, 0, 0};
+  hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), view(y), none, b.la, b.lb, b.num_lp, b.xent, none, none, 0.f, 1);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+int chain_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, float xent_regularize,
+                   tdnnf_mat *xent_deriv, void *ws, hipStream_t s, bool xent_deriv_initialised) {
+  const int B = sp->B, T = sp->T;
+  ChainBufs b = chain_bufs(g, B, T, ws);
+  MatView yv = view(y);
+  MatView xdv = xent_deriv ? view(xent_deriv) : MatView{nullptr, 0, 0, 0};
+  MatView xov = xent_output ? view(xent_output) : MatView{nullptr, 0, 0, 0};
+  if (xent_deriv && !xent_deriv_initialised) {  // (initialised: the posteriors are added onto what the caller put there)
+    if (xdv.stride == xdv.cols) TDNNF_HIP(hipMemsetAsync(xdv.data, 0, sizeof(float) * (size_t)xdv.rows * xdv.cols, s));  // one contiguous fill
+    else hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for((long long)xdv.rows * xdv.cols, 256)), dim3(256), 0, s, xdv);
+  }
+  hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, xov, b.la, b.lb, b.num_lp, b.xent, MatView{nullptr, 0, 0, 0},
+                     xdv, xent_regularize, 4);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+int chain_num(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output,
+              float xent_regularize, tdnnf_mat *xent_deriv, void *ws, hipStream_t s, bool xent_deriv_initialised) {
+  int rc = chain_num_recursion(sp, g, y, ws, s);
+  if (rc) return rc;
+  return chain_num_xent(g, sp, y, xent_output, xent_regularize, xent_deriv, ws, s, xent_deriv_initialised);
+}
+// (3) after (1) and (2): deriv += weight * gamma_num; objective, l2 term, failure handling
+int chain_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, float l2_regularize, double *results,
+                 tdnnf_mat *deriv, tdnnf_mat *xent_deriv, void *ws, hipStream_t s) {
+  const int B = sp->B, T = sp->T;
+  ChainBufs b = chain_bufs(g, B, T, ws);
+  MatView yv = view(y), dv = view(deriv);
+  MatView xdv = xent_deriv ? view(xent_deriv) : MatView{nullptr, 0, 0, 0};
+  hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, MatView{nullptr, 0, 0, 0}, b.la, b.lb, b.num_lp, b.xent, dv,
+                     MatView{nullptr, 0, 0, 0}, 0.f, 2);
+  if (l2_regularize != 0.f) {
+    TDNNF_HIP(hipMemsetAsync(b.l2sum, 0, sizeof(double), s));
+    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for((long long)yv.rows * yv.cols, 256, 1024)), dim3(256), 0, s, yv, b.l2sum);
+  }
+  hipLaunchKernelGGL(chain_finalize_kernel, dim3(1), dim3(64), 0, s, b.num_lp, b.den_lp, b.xent, l2_regularize != 0.f ? b.l2sum : nullptr,
+                     B, T, sp->weight, l2_regularize, results);
+  hipLaunchKernelGGL(chain_guard_kernel, dim3(grid_for((long long)dv.rows * dv.cols, 256)), dim3(256), 0, s, results, yv,
+                     sp->weight * l2_regularize, dv, xdv);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+}  // namespace tdnnf
+
+using namespace tdnnf;
+
+extern "C" {
+
+int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y,
+                               const tdnnf_mat *xent_output, float leaky, float l2_regularize, float xent_regularize,
+                               double *results, tdnnf_mat *deriv, tdnnf_mat *xent_deriv, void *ws, size_t ws_bytes,
+                               tdnnf_stream stream) {
+  TDNNF_REQUIRE(g && sp && mat_ok(y) && mat_ok(deriv) && results, "chain_objf_and_deriv: bad arguments");
+  const int B = sp->B, T = sp->T;
+  TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P && same_dim(y, deriv), "chain_objf_and_deriv: nnet_output must be (B*T) x num_pdfs, t-major");
+  TDNNF_REQUIRE(!xent_deriv || (mat_ok(xent_deriv) && same_dim(y, xent_deriv)), "chain_objf_and_deriv: bad xent_deriv");
+  TDNNF_REQUIRE(!xent_output || (mat_ok(xent_output) && same_dim(y, xent_output)), "chain_objf_and_deriv: bad xent_output");
+  TDNNF_REQUIRE(sp->num_states <= B * 4 * (T + 1), "chain_objf_and_deriv: supervision has more than 4*(T+1) states per sequence on average");
+  TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_workspace_bytes(g, B, T), "chain_objf_and_deriv: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = chain_den(g, sp, y, leaky, deriv, ws, s))) return rc;
+  if ((rc = chain_num(g, sp, y, xent_output, xent_regularize, xent_deriv, ws, s))) return rc;
+  return chain_finish(g, sp, y, l2_regularize, results, deriv, xent_deriv, ws, s);
+}
+
+}  // extern "C"

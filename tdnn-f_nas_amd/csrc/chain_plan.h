@@ -1,0 +1,36 @@
+// chain_plan.h -- which form of the denominator a (graph, minibatch) gets and where the chain objective's arrays lie in the caller's
+// workspace.  One definition (chain_den.hip) for the denominator and for the numerator (chain_num.hip), which share the workspace.
+#pragma once
+#include "chain_types.h"
+
+namespace tdnnf {
+
+constexpr size_t kLdsBytes = 160 * 1024;  // per CU (gfx950)
+// What the planner lets one workgroup's dynamic LDS grow to.  Nobody wrote down what the 10 KiB below kLdsBytes are for; the kernels' static
+// arrays (block_sum's sums, den_mw_kernel's slice offsets) take under 1 KiB of them.
+constexpr size_t kLdsBudget = 150 * 1024;
+
+// a row of P or H floats, padded to whole float4 (what the kernels compute as P4 / H4 and get as Hs)
+inline int pad4(int n) { return (n + 3) & ~3; }
+
+struct ChainPlan {
+  int Hs;
+  bool lds_state;
+  bool split;         // persistent form with the backward recursion beside the forward one (den_beta_kernel + den_gamma_kernel)
+  bool wide;          // den_wide_*: one launch per frame over all sequences, sequence-minor arrays
+  int wide_blocks;    // partial rows of the widest launch
+  int SG, NG;         // wide: sequences per group, groups
+  size_t alpha_floats, asum_floats, gstate_floats, la_floats;
+  size_t lds_fwd, lds_bwd;
+};
+
+struct ChainBufs {
+  ChainPlan p;
+  double *den_lp, *num_lp, *xent, *l2sum;
+  float *alpha, *asum, *gstate;
+  double *la, *lb;  // numerator log alpha / log beta
+};
+// (not part of the library's symbol table: chain_den.hip and chain_num.hip only)
+__attribute__((visibility("hidden"))) ChainBufs chain_bufs(const tdnnf_den_graph *g, int B, int T, void *ws);
+
+}  // namespace tdnnf

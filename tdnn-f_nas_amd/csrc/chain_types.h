@@ -1,0 +1,84 @@
+// chain_types.h -- what the chain objective's files share: the two opaque handle types of the C ABI and the views of them that the
+// kernels take by value.  Built by chain_graph.hip, walked by the denominator (chain_den.hip) and the numerator (chain_num.hip).
+//
+// LF-MMI objective and derivative on gfx950: chain::ComputeChainObjfAndDeriv,
+// DenominatorComputation and NumeratorComputation (UPSTREAM Kaldi, not shipped in the reference;
+// reached via /root/reference/steps/nnet3/chain/train.py:515; options pinned by
+// local/chain_NAS/run_TDNN_DARTSV3_fbk_stride_pretrain.sh:185-195).  SURVEY.md 8(a) row A7.
+//
+// MI355X design (vs. upstream's 2*T kernel launches with atomics):
+//  * ONE persistent workgroup per sequence walks all T frames inside a single launch; the HMM state
+//    vectors (alpha/beta) and the exponentiated output row live in LDS, the per-frame renormaliser
+//    is a workgroup reduction.  Sequences are independent, so there is no inter-workgroup traffic.
+//  * the denominator graph is stored three times in sliced-ELL (SELL-64) form -- by destination
+//    (forward), by source (beta) and by pdf (occupancies) -- so every arc gather is a coalesced
+//    stream and every sum is a fixed-order per-thread loop: no float atomics, results are bitwise
+//    reproducible.  An arc is 8 bytes: (state | pdf << 16, prob).
+//  * the numerator (tiny time-synchronous graphs) runs one wave per sequence in the log domain.
+#pragma once
+#include "common.h"
+
+struct tdnnf_den_graph {
+  int H, A, P;
+  // SELL-64 over rows sorted by descending degree (so a slice's rows have near-equal degree and padding is
+  // negligible): slot s = 64*k + lane holds original row row[s] (0xffffffff = padding slot); its j-th arc is
+  // arc[base[k] + j*64 + lane] = (packed key, prob bits), j < (base[k+1]-base[k])/64.
+  struct Sell {
+    int nrows, nslices;
+    int *base;       // nslices + 1 (device)
+    unsigned *row;   // nslices * 64
+    uint2 *arc;      // key: (other-state-or-src | pdf << 16), or (src | dst << 16) for the by-pdf table
+    uint4 *arc4;     // the same arcs as (key, prob, prob * init[key & 0xffff] or 0, 0): what the wide form loads
+    long long entries;
+    int mw_max_arcs[9];  // [G]: most arc entries any of G workgroups owns when slice k belongs to workgroup k % G (den_*_mw_kernel); G = 2, 4, 8
+  } by_dst, by_src, by_pdf;
+  float *init;  // H
+  float init_sum;
+};
+
+struct tdnnf_supervision {
+  int B, T;
+  int num_states, num_arcs;
+  float weight;
+  int *seq_state_begin;  // B+1
+  int *state_time;
+  float *final_logprob;
+  // arcs grouped by destination state (forward) and by source state (backward), CSR over global state ids
+  int *in_begin, *in_src, *in_pdf;
+  float *in_lp;
+  int *out_begin, *out_dst, *out_pdf;
+  float *out_lp;
+  // states of a sequence are sorted by time; frame_state_begin[s*(T+2) + t] = first state with time t
+  int *frame_state_begin;
+  int max_states_per_seq;
+};
+
+namespace tdnnf {
+namespace {
+
+// what the kernels get of a graph / a supervision, by value
+struct DenDev {
+  int H, P;
+  tdnnf_den_graph::Sell by_dst, by_src, by_pdf;
+  const float *init;
+  float init_sum;
+};
+inline DenDev den_dev(const tdnnf_den_graph *g) { return DenDev{g->H, g->P, g->by_dst, g->by_src, g->by_pdf, g->init, g->init_sum}; }
+
+struct SupDev {
+  int B, T;
+  float weight;
+  const int *seq_state_begin, *frame_state_begin;
+  const float *final_logprob;
+  const int *in_begin, *in_src, *in_pdf;
+  const float *in_lp;
+  const int *out_begin, *out_dst, *out_pdf;
+  const float *out_lp;
+};
+inline SupDev sup_dev(const tdnnf_supervision *sp) {
+  return SupDev{sp->B, sp->T, sp->weight, sp->seq_state_begin, sp->frame_state_begin, sp->final_logprob, sp->in_begin, sp->in_src,
+                sp->in_pdf, sp->in_lp, sp->out_begin, sp->out_dst, sp->out_pdf, sp->out_lp};
+}
+
+}  // namespace
+}  // namespace tdnnf

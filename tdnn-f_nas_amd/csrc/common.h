@@ -214,7 +214,7 @@ hipError_t batchnorm_stats_from_partials(const float *partial, int chunks, int r
 hipError_t batchnorm_stats(MatView a, float epsilon, float target_rms, float *memo, void *ws, hipStream_t s, double *store_stats = nullptr);
 hipError_t colsum_add(MatView a, float scale, float *acc, void *ws, hipStream_t s);  // ws: colreduce_bytes(rows, cols)
 
-// the three separately launchable parts of the chain objective (chain.hip)
+// the three separately launchable parts of the chain objective (chain_den.hip, chain_num.hip)
 bool log_softmax_propagate_with_aux(const tdnnf_mat *in, tdnnf_mat *out, tdnnf_mat *aux, float aux_scale, hipStream_t s);  // elementwise.hip
 float chain_supervision_weight(const tdnnf_supervision *sp);
 // beside_other_work: the caller runs other kernels next to the denominator (the trainer: the xent head), so the persistent form keeps

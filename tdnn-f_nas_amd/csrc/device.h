@@ -4,11 +4,13 @@
 
 namespace tdnnf {
 
+constexpr int kMaxDevices = 64;  // per-device state (the cache below, chain_den.hip's) is an array of this many
+
 // Compute units of the current device, asked once per device (a process may drive several); -1 when the device does not say.
 inline int device_cus_known() {
-  static int cus_of[64];  // 0: not asked yet
+  static int cus_of[kMaxDevices];  // 0: not asked yet
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -1;
   if (cus_of[dev] == 0) {
     hipDeviceProp_t prop;
     cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : -1;

@@ -397,7 +397,7 @@ def test_chain_objective_at_500_frames_matches_oracle(pkg, ora, mode):
     """chain::ComputeChainObjfAndDeriv at the length of a 1500-frame chunk (500 output frames), 6034 pdfs, the bench's
     4 000-state graph, supervision paths drawn from the denominator graph: errors of a log-domain recursion grow with the
     frame index (a float numerator was 6.8e-4 off here and its frame posteriors summed to 1 +- 2.2e-3: it runs in double now).
-    Eight sequences: the persistent form takes four workgroups per sequence (chain.hip, den_mw_kernel) unless the mode is 3."""
+    Eight sequences: the persistent form takes four workgroups per sequence (den_mw_kernels.h, den_mw_kernel) unless the mode is 3."""
     hip = Hip(pkg)
     L = ora.lib()
     H, P, B, T = 4000, 6034, 8, 500

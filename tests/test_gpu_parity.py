@@ -538,7 +538,7 @@ def test_natural_gradient(hip, ora):
     L.oracle_ng_destroy(ng_ref)
 
 
-# the recursions with several workgroups per sequence (few sequences: chain.hip, den_mw_kernel), against the oracle like the other forms
+# the recursions with several workgroups per sequence (few sequences: den_mw_kernels.h, den_mw_kernel), against the oracle like the other forms
 # and against the one-workgroup kernels; four workgroups per sequence (B = 16 / 8: a sequence's workgroups on one XCD; B = 12: the plain block order)
 @pytest.mark.parametrize("H,P,B,T,leaky", [(4000, 6034, 16, 40, 0.1), (1500, 700, 8, 60, 1e-5), (900, 400, 12, 30, 0.05), (2100, 900, 24, 25, 0.1)])
 def test_chain_denominator_several_workgroups_per_sequence(hip, ora, pkg, H, P, B, T, leaky):
