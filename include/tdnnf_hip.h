@@ -59,7 +59,11 @@ int tdnnf_abi_version(void);
      "planes"        1 (default) gemm_precision 2 runs the pre-split bf16-plane GEMMs where they apply, 0 the in-kernel split
      "den_mw_test_abort", "planes_check_bound": test hooks (0 = off), see tests/test_gpu_parity.py, tests/test_gpu_net.py
      "den_split"     -1 (default) the trainer runs the denominator's two recursions side by side for <= 96 sequences, 0 never, 1 always
-                     (set before the first tdnnf_net_forward_backward of a net: it sizes the chain workspace) */
+                     (set before the first tdnnf_net_forward_backward of a net: it sizes the chain workspace)
+     "num_form"      0 (default) the numerator by the supervision's width: one wave per sequence for at most 4 states per frame on average,
+                     one workgroup per sequence with the frontier in LDS for wider ones; 1 / 2 force one (A/B runs, tests).  A narrow
+                     supervision can take form 2 only if it was created while the option was 2 (tdnnf_supervision_create builds the tables then)
+     "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory */
 int tdnnf_set_option(const char *name, int value);
 int tdnnf_get_option(const char *name, int *value_out);
 
@@ -269,6 +273,13 @@ int tdnnf_supervision_create(int num_sequences, int frames_per_sequence, const i
                              const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
                              float weight, tdnnf_supervision **out);
 void tdnnf_supervision_destroy(tdnnf_supervision *);
+/* What a supervision may be: per sequence ANY time-synchronous acceptor over frames 0 .. frames_per_sequence -- every arc goes from a state
+   of time t to one of time t + 1, the states of a sequence are sorted by time and its first state is its only state of time 0.  There is no
+   bound on the number of states or arcs per frame (alignments, lattices with a frame tolerance, several alternative transcripts).  A
+   supervision of more than 4 * (frames_per_sequence + 1) states per sequence on average holds its own numerator scratch on the device
+   (16 bytes per state) and a second copy of its arcs (20 bytes per arc); the chain workspace does not depend on the supervision.
+   Any of the out-pointers may be NULL; *wide: 1 if the supervision is over that mark. */
+int tdnnf_supervision_info(const tdnnf_supervision *, int *num_states, int *num_arcs, int *max_states_per_frame, int *wide);
 
 /* The denominator recursion has two forms: one persistent workgroup per sequence with the state vectors in LDS (graphs up
    to ~10 000 states), and one launch per frame over all sequences on sequence-minor arrays (larger graphs).  0 = chosen by
@@ -291,6 +302,11 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *, const tdnnf_supervision 
                                float l2_regularize, float xent_regularize, double *results_dev,
                                tdnnf_mat *nnet_output_deriv, tdnnf_mat *xent_deriv, void *workspace_dev,
                                size_t workspace_bytes, tdnnf_stream);
+/* diagnostics (tools/num_bench.py): ONE part of the numerator's work as tdnnf_chain_objf_and_deriv enqueues it -- part 1 the forward-backward
+   recursion, 4 the posterior pass behind the xent head (xent_deriv, xent objective), 2 the pass that adds the posteriors to nnet_output_deriv
+   (with the kernels that finish the objective).  Parts 4 and 2 read what part 1 left in the workspace / the supervision. */
+int tdnnf_chain_numerator_part(const tdnnf_den_graph *, const tdnnf_supervision *, const tdnnf_mat *nnet_output, int part, double *results_dev,
+                               tdnnf_mat *nnet_output_deriv, tdnnf_mat *xent_deriv, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
 
 /* ========================================================================== A8
  * OnlineNaturalGradient::PreconditionDirections (UPSTREAM; call sites

@@ -78,7 +78,7 @@ ChainPlan chain_plan(const tdnnf_den_graph *g, int B, int T, int num_states_sup)
 }  // namespace
 
 // workspace layout: [doubles: den_lp[B], num_lp[B], xent[B], l2sum[1]] [alpha] [asum] [la, lb] [gstate]
-// (the numerator scratch is sized for up to 4*(T+1) states per sequence; larger graphs are rejected)
+// (the numerator scratch is sized for up to 4*(T+1) states per sequence on average; a wider supervision brings its own, chain_types.h)
 ChainBufs chain_bufs(const tdnnf_den_graph *g, int B, int T, void *ws) {
   ChainBufs b;
   b.p = chain_plan(g, B, T, B * 4 * (T + 1));

@@ -1,5 +1,5 @@
 // chain_graph.hip -- host only: builds the denominator graph's three SELL-64 tables and the supervision's per-state arc lists
-// (chain_types.h) and copies them to the device.
+// (chain_types.h), for a wide supervision also its numerator scratch and its per-frame arcs ordered by pdf, and copies them to the device.
 #include <string.h>
 
 #include <algorithm>
@@ -220,6 +220,44 @@ int tdnnf_supervision_create(int B, int T, const int *seq_state_begin, const int
   sp->num_arcs = NA;
   sp->weight = weight;
   sp->max_states_per_seq = max_states;
+  // A supervision wider than the workspace's numerator scratch (chain_den.hip chain_bufs) owns its log alpha / log beta, and carries what
+  // num_wide_kernels.h walks: the arcs that leave each frame ordered by pdf.  A narrow one gets the latter only when option num_form asks
+  // for the wide form at creation (A/B runs, tests).
+  sp->wide = (long long)NS > (long long)B * 4 * (T + 1);
+  std::vector<int> pf_src, pf_dst, pf_pdf, pf_t;
+  std::vector<float> pf_lp;
+  const bool tables = sp->wide || options().num_form == 2;
+  for (int s = 0; s < B; s++)
+    for (int t = 0; t <= T; t++) {
+      const int f0 = fsb[(size_t)s * (T + 2) + t], f1 = fsb[(size_t)s * (T + 2) + t + 1];
+      sp->max_states_per_frame = std::max(sp->max_states_per_frame, f1 - f0);
+      sp->max_arcs_per_frame = std::max(sp->max_arcs_per_frame, out_begin[f1] - out_begin[f0]);
+    }
+  if (tables) {
+    pf_src.resize(NA);
+    pf_dst.resize(NA);
+    pf_pdf.resize(NA);
+    pf_t.resize(NA);
+    pf_lp.resize(NA);
+    std::vector<int> src_of(NA), order;
+    for (int st = 0; st < NS; st++)
+      for (int o = out_begin[st]; o < out_begin[st + 1]; o++) src_of[o] = st;
+    for (int s = 0; s < B; s++)
+      for (int t = 0; t < T; t++) {
+        const int a0 = out_begin[fsb[(size_t)s * (T + 2) + t]], a1 = out_begin[fsb[(size_t)s * (T + 2) + t + 1]];
+        order.resize(a1 - a0);
+        for (int o = a0; o < a1; o++) order[o - a0] = o;
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return out_pdf[x] < out_pdf[y]; });
+        for (int o = a0; o < a1; o++) {
+          const int from = order[o - a0];
+          pf_src[o] = src_of[from];
+          pf_dst[o] = out_dst[from];
+          pf_pdf[o] = out_pdf[from];
+          pf_t[o] = t;
+          pf_lp[o] = out_lp[from];
+        }
+      }
+  }
   std::vector<int> ssb(seq_state_begin, seq_state_begin + B + 1), stime(state_time, state_time + NS);
   std::vector<float> fin(final_logprob, final_logprob + NS);
   int rc;
@@ -232,14 +270,36 @@ int tdnnf_supervision_create(int B, int T, const int *seq_state_begin, const int
     tdnnf_supervision_destroy(sp);
     return rc;
   }
+  if (tables) {
+    const size_t parts = (size_t)B * ((T + kNumWideFrames - 1) / kNumWideFrames);
+    hipError_t e = hipSuccess;
+    if ((rc = to_device(pf_src, &sp->pf_src)) || (rc = to_device(pf_dst, &sp->pf_dst)) || (rc = to_device(pf_pdf, &sp->pf_pdf)) ||
+        (rc = to_device(pf_t, &sp->pf_t)) || (rc = to_device(pf_lp, &sp->pf_lp)) ||
+        (e = hipMalloc((void **)&sp->xent_part, sizeof(double) * parts)) != hipSuccess ||
+        (sp->wide && ((e = hipMalloc((void **)&sp->la_own, sizeof(double) * (size_t)NS)) != hipSuccess ||
+                      (e = hipMalloc((void **)&sp->lb_own, sizeof(double) * (size_t)NS)) != hipSuccess))) {
+      tdnnf_supervision_destroy(sp);
+      return rc ? rc : hip_status(e, "supervision_create: hipMalloc");
+    }
+  }
   *out = sp;
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_info(const tdnnf_supervision *sp, int *num_states, int *num_arcs, int *max_states_per_frame, int *wide) {
+  TDNNF_REQUIRE(sp, "supervision_info: null supervision");
+  if (num_states) *num_states = sp->num_states;
+  if (num_arcs) *num_arcs = sp->num_arcs;
+  if (max_states_per_frame) *max_states_per_frame = sp->max_states_per_frame;
+  if (wide) *wide = sp->wide ? 1 : 0;
   return TDNNF_OK;
 }
 
 void tdnnf_supervision_destroy(tdnnf_supervision *sp) {
   if (!sp) return;
   void *ptrs[] = {sp->seq_state_begin, sp->state_time, sp->final_logprob, sp->in_begin, sp->in_src, sp->in_pdf,
-                  sp->in_lp, sp->out_begin, sp->out_dst, sp->out_pdf, sp->out_lp, sp->frame_state_begin};
+                  sp->in_lp, sp->out_begin, sp->out_dst, sp->out_pdf, sp->out_lp, sp->frame_state_begin,
+                  sp->la_own, sp->lb_own, sp->pf_src, sp->pf_dst, sp->pf_pdf, sp->pf_t, sp->pf_lp, sp->xent_part};
   for (void *p : ptrs) hipFree(p);
   delete sp;
 }

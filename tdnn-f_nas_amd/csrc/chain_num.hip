@@ -1,6 +1,9 @@
-// chain_num.hip -- the numerator of the chain objective (one wave per sequence, log domain), the kernels that finish the objective
-// (sum, l2 term, failure path) and the entry point that runs all three parts.  Denominator: chain_den.hip.
+// chain_num.hip -- the numerator of the chain objective (log domain; one wave per sequence for narrow supervisions, num_wide_kernels.h for
+// wide ones), the kernels that finish the objective (sum, l2 term, failure path) and the entry point that runs all three parts.
+// Denominator: chain_den.hip.
 #include <math.h>
+
+#include <algorithm>
 
 #include "chain_plan.h"
 
@@ -144,7 +147,50 @@ __global__ void zero_rows_kernel(MatView m) {
 }  // namespace
 }  // namespace tdnnf
 
+#include "num_wide_kernels.h"
+
 namespace tdnnf {
+namespace {
+
+// Which form a call takes and on which scratch.  A wide supervision (chain_types.h) owns its log alpha / log beta, a narrow one uses the
+// workspace's; both forms write the same values there, so the three parts of one minibatch need not take the same form.
+struct NumCall {
+  bool wide_form;
+  double *la, *lb;
+};
+int num_call(const tdnnf_supervision *sp, const ChainBufs &b, NumCall *c) {
+  const int form = options().num_form;
+  c->wide_form = form == 2 || (form != 1 && sp->wide);
+  TDNNF_REQUIRE(!c->wide_form || sp->pf_src, "chain numerator: option num_form = 2 needs a supervision that was created under it (or a wide one)");
+  c->la = sp->wide ? sp->la_own : b.la;
+  c->lb = sp->wide ? sp->lb_own : b.lb;
+  return TDNNF_OK;
+}
+
+template <int NT>
+int num_wide_recursion(const tdnnf_supervision *sp, const MatView &y, const NumCall &c, double *num_lp, hipStream_t s) {
+  const int W = std::max(sp->max_states_per_frame, 1), A = std::max(sp->max_arcs_per_frame, 1), cap = options().num_frontier_cap;
+  const size_t lds = num_wide_lds(W, A, sp->T);
+  if (lds > kLdsBudget || (cap > 0 && W > cap)) {  // the frontier in global memory: no width is refused
+    hipLaunchKernelGGL(num_wide_recursion_global_kernel<NT>, dim3(sp->B), dim3(NT), 0, s, sup_dev(sp), y, c.la, c.lb, num_lp);
+    return TDNNF_OK;
+  }
+  TDNNF_HIP(hipFuncSetAttribute((const void *)num_wide_recursion_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(num_wide_recursion_kernel<NT>, dim3(sp->B), dim3(NT), lds, s, sup_dev(sp), y, c.la, c.lb, num_lp, W, A);
+  return TDNNF_OK;
+}
+
+// posteriors of the wide form: deriv and / or xent_deriv, the xent objective when do_xent
+void num_wide_posteriors(const tdnnf_supervision *sp, const MatView &y, const MatView &xent_out, const NumCall &c, const ChainBufs &b, const MatView &deriv,
+                         const MatView &xent_deriv, float xent_scale, bool do_xent, hipStream_t s) {
+  const int blocks = (sp->T + kNumWideFrames - 1) / kNumWideFrames;
+  hipLaunchKernelGGL(num_wide_posterior_kernel, dim3(blocks, sp->B), dim3(kNumWidePostThreads), 0, s, sup_dev(sp), sup_wide_dev(sp), y, xent_out, c.la, c.lb,
+                     b.num_lp, deriv, xent_deriv, xent_scale, do_xent ? 1 : 0);
+  if (do_xent) hipLaunchKernelGGL(num_wide_xent_sum_kernel, dim3((sp->B + 63) / 64), dim3(64), 0, s, sp->xent_part, sp->B, blocks, b.xent);
+}
+
+}  // namespace
+
 float chain_supervision_weight(const tdnnf_supervision *sp) { return sp->weight; }
 // (2) numerator recursion; xent_deriv = xent_regularize * gamma_num, xent objective -> workspace.  Does not touch deriv.
 // In two launchable halves: the recursion needs the chain output only (the trainer starts it beside the denominator, under the
@@ -154,7 +200,14 @@ int chain_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph *g, c
   const int B = sp->B, T = sp->T;
   ChainBufs b = chain_bufs(g, B, T, ws);
   const MatView none{nullptr, 0, 0, 0};
-  hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), view(y), none, b.la, b.lb, b.num_lp, b.xent, none, none, 0.f, 1);
+  NumCall c;
+  int rc = num_call(sp, b, &c);
+  if (rc) return rc;
+  if (c.wide_form) {
+    if ((rc = sp->max_states_per_frame <= 64 ? num_wide_recursion<64>(sp, view(y), c, b.num_lp, s) : num_wide_recursion<256>(sp, view(y), c, b.num_lp, s))) return rc;
+  } else {
+    hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), view(y), none, c.la, c.lb, b.num_lp, b.xent, none, none, 0.f, 1);
+  }
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
 }
@@ -169,8 +222,13 @@ int chain_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const 
     if (xdv.stride == xdv.cols) TDNNF_HIP(hipMemsetAsync(xdv.data, 0, sizeof(float) * (size_t)xdv.rows * xdv.cols, s));  // one contiguous fill
     else hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for((long long)xdv.rows * xdv.cols, 256)), dim3(256), 0, s, xdv);
   }
-  hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, xov, b.la, b.lb, b.num_lp, b.xent, MatView{nullptr, 0, 0, 0},
-                     xdv, xent_regularize, 4);
+  NumCall c;
+  int rc = num_call(sp, b, &c);
+  if (rc) return rc;
+  if (c.wide_form) num_wide_posteriors(sp, yv, xov, c, b, MatView{nullptr, 0, 0, 0}, xdv, xent_regularize, true, s);
+  else
+    hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, xov, c.la, c.lb, b.num_lp, b.xent, MatView{nullptr, 0, 0, 0},
+                       xdv, xent_regularize, 4);
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
 }
@@ -187,8 +245,13 @@ int chain_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const td
   ChainBufs b = chain_bufs(g, B, T, ws);
   MatView yv = view(y), dv = view(deriv);
   MatView xdv = xent_deriv ? view(xent_deriv) : MatView{nullptr, 0, 0, 0};
-  hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, MatView{nullptr, 0, 0, 0}, b.la, b.lb, b.num_lp, b.xent, dv,
-                     MatView{nullptr, 0, 0, 0}, 0.f, 2);
+  NumCall c;
+  int rc = num_call(sp, b, &c);
+  if (rc) return rc;
+  if (c.wide_form) num_wide_posteriors(sp, yv, MatView{nullptr, 0, 0, 0}, c, b, dv, MatView{nullptr, 0, 0, 0}, 0.f, false, s);
+  else
+    hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, MatView{nullptr, 0, 0, 0}, c.la, c.lb, b.num_lp, b.xent, dv,
+                       MatView{nullptr, 0, 0, 0}, 0.f, 2);
   if (l2_regularize != 0.f) {
     TDNNF_HIP(hipMemsetAsync(b.l2sum, 0, sizeof(double), s));
     hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for((long long)yv.rows * yv.cols, 256, 1024)), dim3(256), 0, s, yv, b.l2sum);
@@ -215,13 +278,26 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision
   TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P && same_dim(y, deriv), "chain_objf_and_deriv: nnet_output must be (B*T) x num_pdfs, t-major");
   TDNNF_REQUIRE(!xent_deriv || (mat_ok(xent_deriv) && same_dim(y, xent_deriv)), "chain_objf_and_deriv: bad xent_deriv");
   TDNNF_REQUIRE(!xent_output || (mat_ok(xent_output) && same_dim(y, xent_output)), "chain_objf_and_deriv: bad xent_output");
-  TDNNF_REQUIRE(sp->num_states <= B * 4 * (T + 1), "chain_objf_and_deriv: supervision has more than 4*(T+1) states per sequence on average");
   TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_workspace_bytes(g, B, T), "chain_objf_and_deriv: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if ((rc = chain_den(g, sp, y, leaky, deriv, ws, s))) return rc;
   if ((rc = chain_num(g, sp, y, xent_output, xent_regularize, xent_deriv, ws, s))) return rc;
   return chain_finish(g, sp, y, l2_regularize, results, deriv, xent_deriv, ws, s);
+}
+
+int tdnnf_chain_numerator_part(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, int part, double *results, tdnnf_mat *deriv,
+                               tdnnf_mat *xent_deriv, void *ws, size_t ws_bytes, tdnnf_stream stream) {
+  TDNNF_REQUIRE(g && sp && mat_ok(y) && y->rows == sp->B * sp->T && y->cols == g->P, "chain_numerator_part: bad arguments");
+  TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_workspace_bytes(g, sp->B, sp->T), "chain_numerator_part: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  if (part == 1) return chain_num_recursion(sp, g, y, ws, s);
+  if (part == 4) {
+    TDNNF_REQUIRE(mat_ok(xent_deriv) && same_dim(y, xent_deriv), "chain_numerator_part: part 4 needs xent_deriv");
+    return chain_num_xent(g, sp, y, nullptr, 0.1f, xent_deriv, ws, s, true);
+  }
+  TDNNF_REQUIRE(part == 2 && results && mat_ok(deriv) && same_dim(y, deriv), "chain_numerator_part: part is 1, 4 or 2 (which needs results and nnet_output_deriv)");
+  return chain_finish(g, sp, y, 0.f, results, deriv, nullptr, ws, s);
 }
 
 }  // extern "C"

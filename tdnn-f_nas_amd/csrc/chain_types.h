@@ -14,7 +14,10 @@
 //    (forward), by source (beta) and by pdf (occupancies) -- so every arc gather is a coalesced
 //    stream and every sum is a fixed-order per-thread loop: no float atomics, results are bitwise
 //    reproducible.  An arc is 8 bytes: (state | pdf << 16, prob).
-//  * the numerator (tiny time-synchronous graphs) runs one wave per sequence in the log domain.
+//  * the numerator runs in the log domain, in doubles.  A supervision of at most 4 states per frame on average (alignments, the
+//    synthetic graphs) takes one wave per sequence on scratch in the caller's workspace (numerator_kernel).  A wider one (lattices
+//    with a frame tolerance, any width) takes one workgroup per sequence with the frontier in LDS and a posterior pass spread over
+//    (sequence, block of frames) (num_wide_kernels.h); it owns its scratch, so the workspace does not grow with the supervision.
 #pragma once
 #include "common.h"
 
@@ -51,6 +54,16 @@ struct tdnnf_supervision {
   // states of a sequence are sorted by time; frame_state_begin[s*(T+2) + t] = first state with time t
   int *frame_state_begin;
   int max_states_per_seq;
+  // ---- what a supervision wider than the workspace's numerator scratch (4 * (T + 1) states per sequence on average) carries; all null /
+  // zero for a narrow one, unless it was created under option num_form = 2 (then everything but la_own / lb_own)
+  int max_states_per_frame, max_arcs_per_frame;  // widest frame of any sequence; most arcs between two consecutive frames
+  bool wide;                                     // num_states > B * 4 * (T + 1)
+  double *la_own, *lb_own;                       // num_states doubles each: the numerator's log alpha / log beta (wide only)
+  // the arcs that leave frame t of sequence s are [out_begin[fsb[t]], out_begin[fsb[t + 1]]) in the by-source lists; the same range of these
+  // holds them ordered by pdf (stable): source state, destination state, pdf, frame, log-prob
+  int *pf_src, *pf_dst, *pf_pdf, *pf_t;
+  float *pf_lp;
+  double *xent_part;  // B * ceil(T / kNumWideFrames) partial xent objectives of the posterior pass
 };
 
 namespace tdnnf {
@@ -75,6 +88,16 @@ struct SupDev {
   const int *out_begin, *out_dst, *out_pdf;
   const float *out_lp;
 };
+// the posterior pass of the wide numerator: frames per workgroup
+constexpr int kNumWideFrames = 8;
+struct SupWideDev {
+  const int *pf_src, *pf_dst, *pf_pdf, *pf_t;
+  const float *pf_lp;
+  double *xent_part;
+};
+inline SupWideDev sup_wide_dev(const tdnnf_supervision *sp) {
+  return SupWideDev{sp->pf_src, sp->pf_dst, sp->pf_pdf, sp->pf_t, sp->pf_lp, sp->xent_part};
+}
 inline SupDev sup_dev(const tdnnf_supervision *sp) {
   return SupDev{sp->B, sp->T, sp->weight, sp->seq_state_begin, sp->frame_state_begin, sp->final_logprob, sp->in_begin, sp->in_src,
                 sp->in_pdf, sp->in_lp, sp->out_begin, sp->out_dst, sp->out_pdf, sp->out_lp};

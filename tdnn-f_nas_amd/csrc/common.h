@@ -69,6 +69,8 @@ struct Options {
   int ng_diag_skip = 0;   // diagnostics (timing only, results wrong): skip the statistics passes H = X W^T -- bit 0 two-tap inputs >= 1024 wide, bit 1 every other
   int phase_events = 0;   // diagnostics: the trainer records an event on the caller's stream at every phase boundary of a step (tdnnf_net_phase_times)
   int den_split = -1;     // trainer: the denominator's two recursions side by side (then the occupancies of all frames at once): -1 by minibatch size, 0 / 1
+  int num_form = 0;       // the chain numerator: 0 by the supervision's width (numerator_kernel up to 4 states per frame on average, num_wide_kernels.h above), 1 / 2 force one; 2 at tdnnf_supervision_create also gives a narrow supervision the wide form's tables
+  int num_frontier_cap = 0;  // tests: the wide numerator keeps its frontier in global memory for supervisions with a frame of more states than this (0: what the LDS holds)
   int den_gamma_pairs = 0;  // the split form's occupancy pass: 1 one (frame, sequence) per workgroup (den_gamma_kernel), 0 two frames per workgroup where their vectors fit the LDS (den_gamma2_kernel)
 };
 Options &options();

@@ -198,6 +198,13 @@ class Supervision:
                                            k[6][1], k[7][1], float(s.get("weight", 1.0)), C.byref(self.h)))
         self.B, self.T = int(s["B"]), int(s["T"])
 
+    def info(self):
+        """{num_states, num_arcs, max_states_per_frame, wide} (tdnnf_supervision_info); wide: over 4 states per frame on average,
+        the supervision holds its own numerator scratch and takes the numerator's wide form."""
+        v = [C.c_int() for _ in range(4)]
+        check(load().tdnnf_supervision_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("num_states", "num_arcs", "max_states_per_frame", "wide"), (x.value for x in v)))
+
     def __del__(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.tdnnf_supervision_destroy(self.h)

@@ -147,3 +147,86 @@ def tdnn_indexes(time_offsets, num_t_out, B, start_t_in=None, t_step_in=1, t_ste
         mult, rem = rho * (input_t // rho), input_t % rho
         row_offsets.append(mult * B + rem)  # :897-902
     return rho, np.asarray(row_offsets, dtype=np.int32), num_t_in * B, num_t_out * B
+
+
+def _ranges(starts, counts):
+    """Concatenated aranges starts[i] .. starts[i] + counts[i] - 1 and, per element, the index i."""
+    counts = np.maximum(counts, 0)
+    owner = np.repeat(np.arange(len(counts)), counts)
+    first = np.cumsum(counts) - counts
+    return starts[owner] + (np.arange(int(counts.sum())) - first[owner]), owner
+
+
+def make_supervision_lattice(B, T, P, tolerance=2, alternatives=1, mean_dur=3.0, seed=0, weight=1.0):
+    """Per-sequence tolerance lattices, the shape of unconstrained chain egs: `alternatives` unit sequences that share the start
+    state, every unit boundary free to move by +-`tolerance` frames.  Same dict as make_supervision.
+
+    A unit has two pdfs as in the chain topology, one on its entry frame and one on every later frame.  Its nominal duration is
+    1 + floor(Exp(mean_dur - 1)) frames -- the geometric tail a self-loop gives -- and the last unit is cut at T.  The unit that
+    nominally starts at frame b may start at any frame of [b - tolerance, b + tolerance] that leaves every other unit at least one
+    frame; the first starts at 0, the last ends at T.  States: the start, then one per (frame, alternative, unit, entered | looping)
+    on a path from the start to a final state at frame T (the windows are tightened from both ends, which is the pruning of the
+    states that cannot reach a final one), sorted by time.  About 1 + 4 tolerance / E[duration] states per frame and alternative.
+    Arcs carry small random log-weights."""
+    rng = np.random.default_rng(seed)
+    state_time, final, a_src, a_dst, a_pdf = [], [], [], [], []
+    seq_state_begin, seq_arc_begin = [0], [0]
+    ns = na = 0
+    for _ in range(B):
+        times, fin, srcs, dsts, pdfs = [np.zeros(1, np.int64)], [np.zeros(1, bool)], [], [], []
+        n_loc = 1
+        for _alt in range(alternatives):
+            d = 1 + np.floor(rng.exponential(max(mean_dur - 1.0, 1e-9), size=T)).astype(np.int64)
+            b = np.concatenate([[0], np.cumsum(d)])
+            U = int(np.searchsorted(b, T))  # units 0 .. U-1 start before T
+            b = b[:U].copy()
+            e_pdf, l_pdf = rng.integers(0, P, size=U), rng.integers(0, P, size=U)
+            # entry windows [lo, hi] of every unit and of the virtual unit U that "enters" at T
+            lo = np.maximum(b - tolerance, 0)
+            hi = np.minimum(b + tolerance, T - 1)
+            lo[0] = hi[0] = 0
+            lo = np.maximum.accumulate(lo - np.arange(U)) + np.arange(U)              # lo[u] >= lo[u-1] + 1
+            hi = np.append(hi, T)
+            hi = np.minimum.accumulate((hi - np.arange(U + 1))[::-1])[::-1] + np.arange(U + 1)  # hi[u] <= hi[u+1] - 1
+            lo = np.append(lo, T)
+            # entered(t, u): unit u's entry frame was t - 1;  looping(t, u): t - 1 was a later frame of unit u
+            cE = hi[:U] - lo[:U] + 1
+            cL = hi[1:] - lo[:U] - 1
+            tE, uE = _ranges(lo[:U] + 1, cE)
+            tL, uL = _ranges(lo[:U] + 2, cL)
+            offE = n_loc + np.cumsum(cE) - cE
+            offL = n_loc + int(cE.sum()) + np.cumsum(np.maximum(cL, 0)) - np.maximum(cL, 0)
+            idE = offE[uE] + (tE - lo[uE] - 1)
+            idL = offL[uL] + (tL - lo[uL] - 2)
+            t_all, u_all, id_all = np.concatenate([tE, tL]), np.concatenate([uE, uL]), np.concatenate([idE, idL])
+            # stay in the unit (loop pdf)
+            m = t_all + 1 <= hi[u_all + 1]
+            srcs.append(id_all[m]); dsts.append(offL[u_all[m]] + (t_all[m] + 1 - lo[u_all[m]] - 2)); pdfs.append(l_pdf[u_all[m]])
+            # enter the next unit at frame t (its entry pdf)
+            m = (u_all + 1 < U) & (t_all >= lo[u_all + 1]) & (t_all <= hi[u_all + 1])
+            un = u_all[m] + 1
+            srcs.append(id_all[m]); dsts.append(offE[un] + (t_all[m] - lo[un])); pdfs.append(e_pdf[un])
+            # the start state enters unit 0
+            srcs.append(np.zeros(1, np.int64)); dsts.append(offE[:1].copy()); pdfs.append(e_pdf[:1])
+            times += [tE, tL]
+            fin += [(tE == T) & (uE == U - 1), (tL == T) & (uL == U - 1)]
+            n_loc += int(cE.sum() + np.maximum(cL, 0).sum())
+        t_loc, f_loc = np.concatenate(times), np.concatenate(fin)
+        s_loc, d_loc, p_loc = np.concatenate(srcs), np.concatenate(dsts), np.concatenate(pdfs)
+        order = np.argsort(t_loc, kind="stable")  # by time; the start (the only state of time 0) stays first
+        new_id = np.empty(n_loc, np.int64)
+        new_id[order] = np.arange(n_loc)
+        s_loc, d_loc = new_id[s_loc], new_id[d_loc]
+        ao = np.lexsort((d_loc, s_loc))
+        state_time.append(t_loc[order]); final.append(np.where(f_loc[order], 0.0, -np.inf))
+        a_src.append(ns + s_loc[ao]); a_dst.append(ns + d_loc[ao]); a_pdf.append(p_loc[ao])
+        ns += n_loc
+        na += len(ao)
+        seq_state_begin.append(ns)
+        seq_arc_begin.append(na)
+    i32 = lambda x: np.asarray(x, dtype=np.int32)
+    a_lp = (-rng.random(na) * 0.5).astype(np.float32)
+    return {"B": B, "T": T, "seq_state_begin": i32(seq_state_begin), "seq_arc_begin": i32(seq_arc_begin),
+            "state_time": i32(np.concatenate(state_time)), "final_logprob": np.concatenate(final).astype(np.float32),
+            "arc_src": i32(np.concatenate(a_src)), "arc_dst": i32(np.concatenate(a_dst)), "arc_pdf": i32(np.concatenate(a_pdf)),
+            "arc_logprob": a_lp, "weight": float(weight)}
