@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void colmap_kernel(MatView in, MatView z, cons
       if (MODE == 0) o[j] = (x[j] + add[c + j]) * mul[c + j];
       if (MODE == 1) o[j] = x[j] * mul[c + j] + add[c + j];
       if (MODE == 2) o[j] = x[j] * mul[c + j];
-      if (MODE == 3) o[j] = (x[j] + add[c + j]) * mul[c + j] + zz[j] * vdm[c + j];
+      if (MODE == 3) o[j] = fmaf(x[j] + add[c + j], mul[c + j], zz[j] * vdm[c + j]);  // (spelled out: the same roundings whatever VEC is)
     }
     if (VEC == 4)
       *reinterpret_cast<float4 *>(out.data + (long long)r * out.stride + c) = make_float4(o[0], o[1], o[2], o[3]);
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void ew_kernel(MatView a, MatView b, float sa,
     for (int j = 0; j < VEC; j++) {
       if (OP == 0) o[j] = x[j] < 0.f ? 0.f : x[j];
       if (OP == 1) o[j] = (x[j] > 0.f ? 1.f : 0.f) * y[j];
-      if (OP == 2) o[j] = sa * x[j] + sb * y[j];
+      if (OP == 2) o[j] = fmaf(sa, x[j], sb * y[j]);  // (spelled out: left to the compiler, VEC 4 contracted this way and VEC 1 not at all)
       if (OP == 3) o[j] = sa * x[j];
       if (OP == 4) o[j] = y[j] + sa * x[j];
     }

@@ -21,6 +21,18 @@ def padded(a, pad=4):
     return buf[:, :a.shape[1]], buf
 
 
+VIEW_LAYOUTS = ("pitched", "off1", "off1-odd")  # what the oracle-backed entries run on besides their own operands (tests/view_layouts.py)
+
+
+def placed(a, layout=None, writes=False):
+    """(view, check_guards): padded(a) with nothing to check when layout is None, else the guarded view tests/view_layouts.py lays out."""
+    if layout is None:
+        return padded(a)[0], lambda: None
+    from tests.view_layouts import laid_out
+    view, _, check = laid_out(a, layout, writes=writes)
+    return view, check
+
+
 def host(t):
     torch.cuda.synchronize()
     return t.detach().cpu().numpy()

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.gpu_util import F, Hip, dev, host, padded, rel_l2
+from tests.gpu_util import F, VIEW_LAYOUTS, Hip, dev, host, padded, placed, rel_l2
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -407,7 +407,18 @@ def test_chain_objf_and_deriv(hip, ora, pkg, H, P, B, T, leaky, l2, mode):
         pkg.hipabi.load().tdnnf_chain_set_denominator_mode(0)
 
 
-def _chain_case(hip, ora, pkg, H, P, B, T, leaky, l2):
+# nnet_output, xent_output and both derivatives as sub-matrix views (any base pointer, any stride), one small case per denominator form
+@pytest.mark.parametrize("layout", VIEW_LAYOUTS)
+@pytest.mark.parametrize("mode", [1, 2], ids=["persistent", "wide"])
+def test_chain_objf_and_deriv_on_views(hip, ora, pkg, mode, layout):
+    pkg.hipabi.check(pkg.hipabi.load().tdnnf_chain_set_denominator_mode(mode))
+    try:
+        _chain_case(hip, ora, pkg, *CHAIN_CASES[1], layout=layout)
+    finally:
+        pkg.hipabi.load().tdnnf_chain_set_denominator_mode(0)
+
+
+def _chain_case(hip, ora, pkg, H, P, B, T, leaky, l2, layout=None):
     L = ora.lib()
     g = pkg.synth.make_den_graph(H, P, mean_out_degree=6.0, seed=H)
     sup = pkg.synth.make_supervision(B, T, P, seed=T, weight=1.0)
@@ -425,10 +436,13 @@ def _chain_case(hip, ora, pkg, H, P, B, T, leaky, l2):
     ws = hip.ws(nb)
     ws.fill_(float("nan"))  # nothing may depend on what the workspace held
     res = torch.zeros(8, dtype=torch.float64, device="cuda")
-    yd, _ = padded(y)
-    dd, _ = padded(np.full_like(y, 5.0))
-    xdd = torch.full((T * B, P), 5.0, device="cuda")
-    hip.chain_objf_and_deriv(dg.h, ds.h, yd, dev(xo), leaky, l2, 0.1, hip.vec(res), dd, xdd, hip.vec(ws), nb, hip.stream())
+    yd, check_y = placed(y, layout)
+    dd, check_d = placed(np.full_like(y, 5.0), layout, writes=True)
+    xod, check_xo = (dev(xo), lambda: None) if layout is None else placed(xo, layout)
+    xdd, check_xd = (torch.full((T * B, P), 5.0, device="cuda"), lambda: None) if layout is None else placed(np.full_like(y, 5.0), layout, writes=True)
+    hip.chain_objf_and_deriv(dg.h, ds.h, yd, xod, leaky, l2, 0.1, hip.vec(res), dd, xdd, hip.vec(ws), nb, hip.stream())
+    for check in (check_y, check_d, check_xo, check_xd):
+        check()
     r = host(res)
     assert r[5] == 1.0 and r[2] == w.value
     assert abs(r[0] - objf.value) < 1e-4 * abs(objf.value), (r[0], objf.value)   # BASELINE bar: 1e-4 relative
@@ -442,6 +456,7 @@ def _chain_case(hip, ora, pkg, H, P, B, T, leaky, l2):
     dd2 = torch.zeros_like(dd)
     hip.chain_objf_and_deriv(dg.h, ds.h, yd, None, leaky, l2, 0.1, hip.vec(res), dd2, None, hip.vec(ws), nb, hip.stream())
     assert torch.equal(dd2, dd) and host(res)[0] == r[0]
+    check_y()
 
 
 @pytest.mark.parametrize("mode", [1, 2], ids=["persistent", "wide"])
@@ -517,6 +532,16 @@ def test_update_with_max_change(hip, ora):
 def test_natural_gradient(hip, ora):
     """Same minibatch sequence through the oracle and the device implementation: X_hat, scale and the
     low-rank state track each other (the R x R eig is in double on both sides)."""
+    _natural_gradient_case(hip, ora)
+
+
+@pytest.mark.parametrize("layout", VIEW_LAYOUTS)
+def test_natural_gradient_on_views(hip, ora, layout):
+    """The same with X a sub-matrix view (any base pointer, any stride): preconditioned in place, nothing around it touched."""
+    _natural_gradient_case(hip, ora, layout)
+
+
+def _natural_gradient_case(hip, ora, layout=None):
     L = ora.lib()
     rng = np.random.default_rng(15)
     N, D, R = 512, 161, 20
@@ -529,9 +554,10 @@ def test_natural_gradient(hip, ora):
         Xr = X.copy()
         sr = C.c_float()
         L.oracle_ng_precondition(ng_ref, ora.omat(Xr), C.byref(sr))
-        Xd, _ = padded(X)
+        Xd, check_X = placed(X, layout, writes=True)
         sd = C.c_float()
         hip.ng_precondition(ng, Xd, C.byref(sd), hip.stream())
+        check_X()
         assert rel_l2(host(Xd), Xr) < 2e-3, it
         assert abs(sd.value - sr.value) < 2e-3 * sr.value, it
     hip.lib.tdnnf_ng_destroy(ng)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.gpu_util import F, Hip, dev, host, padded, rel_l2
+from tests.gpu_util import F, VIEW_LAYOUTS, Hip, dev, host, padded, placed, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +60,17 @@ CASES = [
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_tdnn_update_natural_gradient(hip, ora, pkg, case):
+    _tdnn_update_ng_case(hip, ora, pkg, case)
+
+
+# in_value / out_deriv as sub-matrix views (any base pointer, any stride): the plain component and the widest DARTS one
+@pytest.mark.parametrize("layout", VIEW_LAYOUTS)
+@pytest.mark.parametrize("case", [CASES[1], CASES[2]], ids=[CASES[1][0], CASES[2][0]])
+def test_tdnn_update_natural_gradient_on_views(hip, ora, pkg, case, layout):
+    _tdnn_update_ng_case(hip, ora, pkg, case, layout)
+
+
+def _tdnn_update_ng_case(hip, ora, pkg, case, layout=None):
     name, offs, B, nt, Di, Do, flags, bias = case
     L = ora.lib()
     rng = np.random.default_rng(zlib.crc32(name.encode()) % 1000)
@@ -94,8 +105,8 @@ def test_tdnn_update_natural_gradient(hip, ora, pkg, case):
         W0, b0, a0 = _rand(rng, Do, K * Di) * 0.1, (_rand(rng, Do) * 0.1 if bias else None), (_rand(rng, K) * 0.1 if darts else None)
         W_ref, b_ref, a_ref = W0.copy(), (b0.copy() if bias else None), (a0.copy() if darts else None)
         _oracle_update_ng(L, ora, x, dy, W, rho, ro, K, Di, Do, coef, eff, fl, share, 0.7, ngi_ref, ngo_ref, lr, W_ref, b_ref, a_ref)
-        xd, _ = padded(x)
-        dyd, _ = padded(dy)
+        xd, check_x = placed(x, layout)
+        dyd, check_dy = placed(dy, layout)
         Wacc = dev(W0)
         bacc = dev(b0) if bias else None
         aacc = dev(a0) if darts else None
@@ -103,6 +114,8 @@ def test_tdnn_update_natural_gradient(hip, ora, pkg, case):
         hip.tdnn_update_natural_gradient(C.byref(ix), xd, dyd, Do, Di, hip.vec(Wd), K * Di, hip.vec(cd) if darts else None,
                                          hip.vec(ed) if darts else None, fl, share, 0.7, ngi, ngo, lr, hip.vec(Wacc), K * Di,
                                          hip.vec(bacc) if bias else None, hip.vec(aacc) if darts else None, hip.vec(ws), nb, hip.stream())
+        check_x()
+        check_dy()
         assert np.linalg.norm(W_ref - W0) > 0
         assert rel_l2(host(Wacc) - W0, W_ref - W0) < 5e-3, (it, rel_l2(host(Wacc) - W0, W_ref - W0))
         if bias:
@@ -117,6 +130,15 @@ def test_tdnn_update_natural_gradient(hip, ora, pkg, case):
 
 @pytest.mark.parametrize("bias", [True, False], ids=["NaturalGradientAffine", "Linear"])
 def test_affine_update_natural_gradient(hip, ora, pkg, bias):
+    _affine_update_ng_case(hip, ora, pkg, bias)
+
+
+@pytest.mark.parametrize("layout", VIEW_LAYOUTS)
+def test_affine_update_natural_gradient_on_views(hip, ora, pkg, layout):
+    _affine_update_ng_case(hip, ora, pkg, True, layout)
+
+
+def _affine_update_ng_case(hip, ora, pkg, bias, layout=None):
     L = ora.lib()
     rng = np.random.default_rng(31 + bias)
     N, Di, Do = 640, 96, 160
@@ -137,9 +159,11 @@ def test_affine_update_natural_gradient(hip, ora, pkg, bias):
         W_ref, b_ref = W0.copy(), (b0.copy() if bias else None)
         _oracle_update_ng(L, ora, x, dy, None, 1, ro, 1, Di, Do, None, None, 0, 0, 1.0, ngi_ref, ngo_ref, 0.02, W_ref, b_ref, None)
         Wacc, bacc = dev(W0), (dev(b0) if bias else None)
-        xd, _ = padded(x)
-        dyd, _ = padded(dy)
+        xd, check_x = placed(x, layout)
+        dyd, check_dy = placed(dy, layout)
         hip.affine_update_natural_gradient(xd, dyd, ngi, ngo, 0.02, hip.vec(Wacc), Di, hip.vec(bacc) if bias else None, hip.vec(ws), nb, hip.stream())
+        check_x()
+        check_dy()
         assert rel_l2(host(Wacc) - W0, W_ref - W0) < 5e-3, it
         if bias:
             assert rel_l2(host(bacc) - b0, b_ref - b0) < 5e-3, it
