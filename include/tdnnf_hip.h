@@ -49,8 +49,8 @@ typedef struct tdnnf_ng tdnnf_ng; /* OnlineNaturalGradient state (A8, below) */
 
 const char *tdnnf_last_error(void);
 int tdnnf_abi_version(void);
-/* Tuning options: process-wide integers selecting between code paths that are all held to the same parity tests (the library reads
-   no environment variable for them).  Unknown names fail with TDNNF_EINVAL.
+/* Tuning options: process-wide integers selecting between code paths (the library reads no environment variable for them; which
+   values the test suite exercises: csrc/common.h, struct Options).  Unknown names fail with TDNNF_EINVAL.
      "ng_grouped"    1 (default) natural-gradient side chain of a gradient bucket as grouped launches, 0 per object   [read by tdnnf_net_create]
      "ng_fuse"       1 (default) output-side statistic inside the BatchNorm / ReLU backward sweep when that pays, 0 own GEMM, 2 always
      "ng_early_in"   1 (default) input-side statistics ahead of the backward pass, 0 with the component's backward call [tdnnf_net_create]
@@ -63,9 +63,31 @@ int tdnnf_abi_version(void);
      "num_form"      0 (default) the numerator by the supervision's width: one wave per sequence for at most 4 states per frame on average,
                      one workgroup per sequence with the frontier in LDS for wider ones; 1 / 2 force one (A/B runs, tests).  A narrow
                      supervision can take form 2 only if it was created while the option was 2 (tdnnf_supervision_create builds the tables then)
-     "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory */
+     "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
+     "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
+                     kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
+                     constraint keep exact f32
+   The GEMM planners' options (gemm_ring, splitk_partial_round, splitk_per_cu, gemm_alt_taps, ng_bk, wgrad_small) are tested value by
+   value against float64 in tests/test_gpu_gemm_forms.py. */
 int tdnnf_set_option(const char *name, int value);
 int tdnnf_get_option(const char *name, int *value_out);
+/* diagnostics, tests: how often the rows GEMM and the weight gradient took each kernel and launch form since the last reset.  Counter i is
+   named tdnnf_gemm_launch_form_name(i) (NULL outside the range; the string is valid until the calling thread's next call):
+     "rows.<tile>.<arithmetic>.<form>"  tile = rows x cols k K-step (128x128k16 ...), arithmetic f32 / bf16x3 / bf16x6, form one of
+         plain, ring, splitk (every tile split over K), partial_s2 .. partial_s8 (one partly filled round, K split by S), main_split_tail /
+         main_plain_tail (whole rounds -- counted as plain or ring as well -- then the last rows as a split-K or a plain launch),
+         sumsq_plain / sumsq_splitk (the passes with the ||row||^2 by-product), post (inference epilogue), grouped;
+     "rows.launches_vec4" / "rows.launches_scalar"  kernel launches of the above that load 16 bytes at a time / float by float;
+     "planes.plain", "planes.main_split_tail", "planes.main_plain_tail"  rows GEMMs routed onto the pre-split plane kernels, ONE of the
+         three per call (here the whole rounds of a main + tail call are not counted as plain as well); "planes.alt_chunked": calls
+         whose two taps went in alternating chunks of K blocks (option gemm_alt_taps 2);
+     "wgrad.<tile>.<arithmetic>" weight gradients per tile, "wgrad.planes" those on the plane kernels, and "wgrad.last_slabs", which is not
+         a count but the number of row slabs of the last weight gradient; "rows.last_slices" likewise: the K slices of the rows GEMM's
+         last split-K launch.
+   Writes min(capacity, count) values to counts (may be NULL), clears all counters when reset != 0 and returns the number of counters.
+   Counting never changes a decision and never synchronises. */
+int tdnnf_gemm_launch_forms(long long *counts, int capacity, int reset);
+const char *tdnnf_gemm_launch_form_name(int index);
 
 /* ---- TdnnDARTSV3Component coefficient flags (nnet-tdnn-component.cc:150-163) */
 #define TDNNF_DARTS_USE_GUMBEL 1

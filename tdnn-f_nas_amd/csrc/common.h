@@ -42,8 +42,12 @@ inline bool vec4_ok(const MatView &m) {
 
 #define TDNNF_LAUNCH_CHECK(name) TDNNF_HIP(hipGetLastError())
 
-// Tuning options (tdnnf_set_option / tdnnf_get_option, include/tdnnf_hip.h): process-wide integers that select between code paths
-// which are all parity-tested; the library reads no environment variable for them.
+// Tuning options (tdnnf_set_option / tdnnf_get_option, include/tdnnf_hip.h): process-wide integers that select between code paths;
+// the library reads no environment variable for them.  What is tested: the GEMM planners' options (gemm_ring, splitk_partial_round,
+// splitk_per_cu, gemm_alt_taps, ng_bk, wgrad_small) value by value and element by element, with the launch-form counters
+// (launch_forms.h) as the witness of the path that ran (tests/test_gpu_gemm_forms.py); ng_fuse, ng_valu, planes, den_split, num_form and
+// the test hooks by the tests that name them.  The trainer's scheduling options (xent_behind_den, ng_early_fork, wgrad_lag,
+// wgrad_on_caller, reverse_passes, ng_pform, ng_early_in, ng_grouped) are tested at their defaults only.
 struct Options {
   int ng_grouped = 1;     // natural gradient: 1 the side chain of a gradient bucket as grouped launches, 0 per object (read by tdnnf_net_create)
   int ng_fuse = 1;        // output-side statistic H = dY Wy^T: 0 by its own GEMM, 1 inside the BatchNorm / ReLU backward sweep when that pays, 2 always
@@ -70,6 +74,7 @@ struct Options {
   int phase_events = 0;   // diagnostics: the trainer records an event on the caller's stream at every phase boundary of a step (tdnnf_net_phase_times)
   int den_split = -1;     // trainer: the denominator's two recursions side by side (then the occupancies of all frames at once): -1 by minibatch size, 0 / 1
   int num_form = 0;       // the chain numerator: 0 by the supervision's width (numerator_kernel up to 4 states per frame on average, num_wide_kernels.h above), 1 / 2 force one; 2 at tdnnf_supervision_create also gives a narrow supervision the wide form's tables
+  int gemm_arith_test = 0;   // tests: 1 / 3 = the stand-alone GEMM entries (no GemmPrecisionScope around them) run the in-kernel split-bf16 kernels bf16x3 / bf16x6 where exact f32 is the default; the exact-f32 scopes (natural gradient, orthonormal constraint) keep f32
   int num_frontier_cap = 0;  // tests: the wide numerator keeps its frontier in global memory for supervisions with a frame of more states than this (0: what the LDS holds)
   int den_gamma_pairs = 0;  // the split form's occupancy pass: 1 one (frame, sequence) per workgroup (den_gamma_kernel), 0 two frames per workgroup where their vectors fit the LDS (den_gamma2_kernel)
 };

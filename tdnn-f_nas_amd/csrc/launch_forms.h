@@ -1,0 +1,56 @@
+// launch_forms.h -- process-wide counters of the kernel and launch form the GEMM planners chose (tdnnf_gemm_launch_forms,
+// include/tdnnf_hip.h).  Observation only: nothing reads them back into a decision, counting is one relaxed atomic add on the host.
+#pragma once
+#include <atomic>
+
+namespace tdnnf {
+
+// ---- rows GEMM (rows_gemm.hip): one counter per (tile, arithmetic, form)
+enum RowsForm {
+  kFormPlain,          // one rows_gemm_kernel launch over all tiles
+  kFormRing,           // the same launch taken by the persistent ring (gemm_ring.hip)
+  kFormSplitK,         // launch_rows_balanced: few tiles, long reduction -- every tile split over K
+  kFormPartialS2,      // launch_rows_balanced: one partly filled round, K split by S = 2 .. 8 (kFormPartialS2 + S - 2)
+  kFormPartialS8 = kFormPartialS2 + 6,
+  kFormMainSplitTail,  // launch_rows_balanced: whole rounds (counted as plain / ring as well), then a split-K launch of the last rows
+  kFormMainPlainTail,  // ... then a plain launch of the last rows (two plain / ring counts)
+  kFormSumsqPlain,     // launch_rows_sumsq without / with the K split
+  kFormSumsqSplitK,
+  kFormPost,           // launch_rows_post (the inference epilogue)
+  kFormGrouped,        // rows_gemm_group
+  kRowsForms
+};
+constexpr int kRowsTiles = 9, kRowsAriths = 3;  // arithmetic 0 exact f32, 1 split-bf16 with two planes (bf16x3), 2 with three (bf16x6)
+
+template <int WM, int WN, int TM, int TN, int BK>
+constexpr int rows_tile_index() {
+  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  constexpr int t = (BM == 128 && BN == 32 && BK == 32) ? 0 : (BM == 128 && BN == 32 && BK == 64) ? 1 : (BM == 128 && BN == 64 && BK == 32) ? 2
+                  : (BM == 128 && BN == 96 && BK == 16) ? 3 : (BM == 128 && BN == 96 && BK == 32) ? 4 : (BM == 128 && BN == 160 && BK == 16) ? 5
+                  : (BM == 64 && BN == 128 && BK == 16) ? 6 : (BM == 128 && BN == 128 && BK == 16) ? 7 : (BM == 128 && BN == 128 && BK == 32) ? 8 : -1;
+  static_assert(t >= 0, "a rows GEMM tile without a counter: add it here and to kRowsTileNames (launch_forms.hip)");
+  return t;
+}
+constexpr int rows_form_index(int tile, int arith, int form) { return (tile * kRowsAriths + arith) * kRowsForms + form; }
+
+// ---- the plane router (planes_try_rows) and the weight gradient (wgrad.hip) behind the rows GEMM's block
+enum {
+  kPlanesPlain = kRowsTiles * kRowsAriths * kRowsForms,
+  kPlanesMainSplitTail,
+  kPlanesMainPlainTail,  // (whole rounds, then a tail whose K range was too short to split)
+  kWgradFirst,           // + variant (wgrad_tile: 0 .. 4) * kRowsAriths + arithmetic
+  kWgradPlanes = kWgradFirst + 5 * kRowsAriths,  // planes_try_wgrad
+  kWgradLastSlabs,       // not a count: the number of row slabs (`splits`) of the last weight gradient
+  kRowsLastSlices,       // not a count: the number of K slices the last split-K launch of the rows GEMM ran with
+  kRowsVec4Launches,     // rows GEMM kernel launches (ring and grouped included) that load 16 bytes at a time / float by float
+  kRowsScalarLaunches,
+  kPlanesAltChunked,     // plane router: calls whose two taps went in alternating chunks of K blocks (option gemm_alt_taps 2)
+  kLaunchFormCounters
+};
+
+std::atomic<long long> *launch_form_counters();  // kLaunchFormCounters of them
+inline void count_form(int index) { launch_form_counters()[index].fetch_add(1, std::memory_order_relaxed); }
+inline void note_rows_slices(int ksplit) { launch_form_counters()[kRowsLastSlices].store(ksplit, std::memory_order_relaxed); }
+inline void note_wgrad_slabs(int splits) { launch_form_counters()[kWgradLastSlabs].store(splits, std::memory_order_relaxed); }
+
+}  // namespace tdnnf

@@ -8,6 +8,7 @@
 #include "device.h"
 #include "gemm_f32.h"
 #include "gemm_ring.h"
+#include "launch_forms.h"
 #include "planes_gemm.h"
 #include "rows_gemm_kernels.h"
 
@@ -60,6 +61,18 @@ constexpr size_t rows_x3_lds_bytes() {
   return sizeof(__bf16) * 2 * NP * (size_t)(BM + BN) * (BK + 8);
 }
 
+// ---- launch-form counters (launch_forms.h).  The launch sites below record what they launched: the arithmetic (0 exact f32, 1 bf16x3,
+// 2 bf16x6) of the calling thread's last kernel, for the planner to count its form under, and vec4 / scalar loads per launch
+thread_local int t_launched_arith = 0;
+inline void note_launch(int arith, bool vec) {
+  t_launched_arith = arith;
+  count_form(vec ? kRowsVec4Launches : kRowsScalarLaunches);
+}
+template <int WM, int WN, int TM, int TN, int BK>
+void count_rows_form(int form) {  // (after the launch: under the arithmetic that ran)
+  count_form(rows_form_index(rows_tile_index<WM, WN, TM, TN, BK>(), t_launched_arith, form));
+}
+
 // ---- kernel launches.  TAG 1 (rows_gemm_kernels.h): the launches booked to the natural-gradient class
 template <int WM, int WN, int TM, int TN, int BK, int NP, int TAG>
 void launch_rows_x3_tagged(dim3 grid, const RowsGemmArgs &a, int ntm, int ntn, hipStream_t s) {
@@ -68,6 +81,7 @@ void launch_rows_x3_tagged(dim3 grid, const RowsGemmArgs &a, int ntm, int ntn, h
   constexpr size_t lds = rows_x3_lds_bytes<WM * TM * 32, WN * TN * 32, BK, NP>();
   static const bool opted = opt_in_lds(rows_gemm_x3_kernel<WM, WN, TM, TN, BK, NP, D, TAG>, lds);
   (void)opted;
+  note_launch(NP - 1, true);
   hipLaunchKernelGGL((rows_gemm_x3_kernel<WM, WN, TM, TN, BK, NP, D, TAG>), grid, dim3(256), lds, s, a, ntm, ntn);
 }
 
@@ -79,6 +93,7 @@ void launch_rows_kernel_tagged(dim3 grid, const RowsGemmArgs &a, int ntm, int nt
                             opt_in_lds(rows_gemm_kernel<WM, WN, TM, TN, BK, false, 4, TAG>, lds_nc) && opt_in_lds(rows_gemm_kernel<WM, WN, TM, TN, BK, false, 1, TAG>, lds_nc);
   (void)opted;
   const dim3 block(256);
+  note_launch(0, vec);
   if (b_kc) {
     if (vec) hipLaunchKernelGGL((rows_gemm_kernel<WM, WN, TM, TN, BK, true, 4, TAG>), grid, block, lds_kc, s, a, ntm, ntn);
     else hipLaunchKernelGGL((rows_gemm_kernel<WM, WN, TM, TN, BK, true, 1, TAG>), grid, block, lds_kc, s, a, ntm, ntn);
@@ -113,14 +128,20 @@ inline bool ring_applies(const RowsGemmArgs &a, bool b_kc, bool vec, int tile_co
   return prof_class_override() != 3 && (tile_cols == 128 || rows_gemm_ring_mode() >= 2) && rows_gemm_ring_ok(a, b_kc, vec);
 }
 
+// (form: what a launch of the tile kernel is counted as; the ring counts as itself)
 template <int WM, int WN, int TM, int TN, int BK>
-hipError_t launch_rows(const RowsGemmArgs &a, bool b_kc, bool vec, hipStream_t s) {
+hipError_t launch_rows(const RowsGemmArgs &a, bool b_kc, bool vec, hipStream_t s, int form = kFormPlain) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
   if constexpr (kRingTile<WM, WN, TM, TN>) {  // the persistent LDS-DMA-ring form (gemm_ring.hip) where it applies
-    if (ring_applies(a, b_kc, vec, BN)) return rows_gemm_ring(a, b_kc, BN, s);
+    if (ring_applies(a, b_kc, vec, BN)) {
+      note_launch(0, true);  // (the ring is exact f32 on 16-byte loads: rows_gemm_ring_ok)
+      count_rows_form<WM, WN, TM, TN, BK>(kFormRing);
+      return rows_gemm_ring(a, b_kc, BN, s);
+    }
   }
   launch_rows_kernel<WM, WN, TM, TN, BK>(dim3(ntm * ntn), a, ntm, ntn, b_kc, vec, s);
+  count_rows_form<WM, WN, TM, TN, BK>(form);
   return hipGetLastError();
 }
 
@@ -132,6 +153,7 @@ void launch_split_k(RowsGemmArgs at, int ntm, int ntn, int S, long long ktot, fl
   at.kchunk = (int)(((kt + S - 1) / S) * BK);
   at.ksplit = (int)((ktot + at.kchunk - 1) / at.kchunk);
   at.partial = scratch;
+  note_rows_slices(at.ksplit);
   launch_rows_kernel<WM, WN, TM, TN, BK>(dim3(ntm * ntn * at.ksplit), at, ntm, ntn, b_kc, vec, s);
   const long long total = (long long)at.M * at.N;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 2048)), dim3(256), 0, s, at);
@@ -220,6 +242,7 @@ hipError_t launch_rows_balanced(const RowsGemmArgs &a, bool b_kc, bool vec, int 
     if (S >= 2 && need <= scratch_bytes) {
       ProfScope ps(cls, flops, s);
       launch_split_k<WM, WN, TM, TN, BK>(a, ntm, ntn, S, ktot, scratch, b_kc, vec, s);
+      count_rows_form<WM, WN, TM, TN, BK>(S_partial >= 2 ? kFormPartialS2 + S_partial - 2 : kFormSplitK);
       return hipGetLastError();
     }
   }
@@ -263,6 +286,7 @@ hipError_t launch_rows_balanced(const RowsGemmArgs &a, bool b_kc, bool vec, int 
       {
         ProfScope ps(cls, flops * at.M / a.M, s);
         launch_split_k<WM, WN, TM, TN, BK>(at, (at.M + BM - 1) / BM, ntn, S_tail, ktot, scratch, b_kc, vec, s);
+        count_rows_form<WM, WN, TM, TN, BK>(kFormMainSplitTail);
       }
       if (stats) {
         MatView ct{at.C, at.M, at.N, (int)at.ldc};
@@ -273,7 +297,9 @@ hipError_t launch_rows_balanced(const RowsGemmArgs &a, bool b_kc, bool vec, int 
     }
     // tail too small to split: plain launch of the remaining rows
     ProfScope ps(cls, flops * at.M / a.M, s);
-    return launch_rows<WM, WN, TM, TN, BK>(at, b_kc, vec, s);
+    const hipError_t e = launch_rows<WM, WN, TM, TN, BK>(at, b_kc, vec, s);
+    count_rows_form<WM, WN, TM, TN, BK>(kFormMainPlainTail);
+    return e;
   }
   ProfScope ps(cls, flops, s);
   if (stats) {
@@ -303,10 +329,11 @@ hipError_t launch_rows_sumsq(const RowsGemmArgs &a, bool b_kc, bool vec, hipStre
     const size_t need = sizeof(float) * (size_t)S * a.M * ((a.N + 3) & ~3);
     if (S >= 2 && need <= scratch_bytes && tiles * S <= a.sumsq_cap) {
       launch_split_k<WM, WN, TM, TN, BK>(a, tiles, 1, S, ktot, scratch, b_kc, vec, s);
+      count_rows_form<WM, WN, TM, TN, BK>(kFormSumsqSplitK);
       return hipGetLastError();
     }
   }
-  return launch_rows<WM, WN, TM, TN, BK>(a, b_kc, vec, s);
+  return launch_rows<WM, WN, TM, TN, BK>(a, b_kc, vec, s, kFormSumsqPlain);
 }
 
 // A launch with the inference epilogue (RowsGemmArgs::col_scale ...): one plain launch of rows_gemm_post_kernel -- no K split (its
@@ -319,6 +346,8 @@ hipError_t launch_rows_post(const RowsGemmArgs &a, bool vec, int cls, double flo
   static const bool opted = opt_in_lds(rows_gemm_post_kernel<WM, WN, TM, TN, BK, 4>, lds) && opt_in_lds(rows_gemm_post_kernel<WM, WN, TM, TN, BK, 1>, lds);
   (void)opted;
   ProfScope ps(cls, flops, s);
+  note_launch(0, vec);
+  count_rows_form<WM, WN, TM, TN, BK>(kFormPost);
   if (vec) hipLaunchKernelGGL((rows_gemm_post_kernel<WM, WN, TM, TN, BK, 4>), dim3(ntm * ntn), dim3(256), lds, s, a, ntm, ntn);
   else hipLaunchKernelGGL((rows_gemm_post_kernel<WM, WN, TM, TN, BK, 1>), dim3(ntm * ntn), dim3(256), lds, s, a, ntm, ntn);
   return hipGetLastError();
@@ -411,6 +440,7 @@ bool planes_try_rows(const RowsGemmArgs &a, bool b_kc, int np, double flops, hip
     }
     g.nseg = n;
     g.alt_seg_order = 0;
+    count_form(kPlanesAltChunked);
   }
   g.skip_coef = a.coef;
   g.C = a.C; g.ldc = a.ldc; g.M = a.M; g.N = a.N;
@@ -471,6 +501,7 @@ bool planes_try_rows(const RowsGemmArgs &a, bool b_kc, int np, double flops, hip
         gt.partial_stride = (long long)tail_rows * ldp;
         gt.ldp_m = ldp;
         gt.ldp_n = 1;
+        count_form(gt.ksplit >= 2 ? kPlanesMainSplitTail : kPlanesMainPlainTail);
         if (gt.ksplit >= 2) {
           *err = planes_gemm(gt, s);
           if (*err == hipSuccess) *err = planes_splitk_finish(gt, s);
@@ -487,6 +518,7 @@ bool planes_try_rows(const RowsGemmArgs &a, bool b_kc, int np, double flops, hip
       }
     }
   }
+  count_form(kPlanesPlain);
   *err = planes_gemm(g, s);
   return true;
 }
@@ -566,7 +598,11 @@ hipError_t rows_gemm(const RowsGemmArgs &a_in, bool b_kc, hipStream_t s) {
     if (ktot <= 512) return launch_rows_post<2, 2, 2, 2, 16>(a, vec, 0, flops, s);
     return launch_rows_post<2, 2, 2, 2, 32>(a, vec, 0, flops, s);
   }
-  if (a.prec == 0) a.prec = g_gemm_prec;
+  if (a.prec == 0) {
+    a.prec = g_gemm_prec;
+    // tests (option gemm_arith_test): the in-kernel split-bf16 kernels for calls outside any GemmPrecisionScope
+    if (a.prec == 0 && (options().gemm_arith_test == 1 || options().gemm_arith_test == 3)) a.prec = options().gemm_arith_test;
+  }
   if (a.prec == 2) a.prec = 0;  // 2 = exact f32 regardless of the default
   if (a.prec == 4 || (a.prec == 3 && options().planes)) {  // pre-split planes (f16x3 / bf16x6) when the caller hinted them for these operands
     hipError_t pe = hipSuccess;
@@ -674,6 +710,8 @@ hipError_t rows_gemm_group(const std::vector<RowsGemmArgs> &calls, RowsGemmGroup
   constexpr size_t lds = rows_lds_bytes<128, 32, 32>(true);
   ProfGemmRange prof(3, flops, bytes, s);
   RowsGemmTasks t{g.d_args, g.d_first, (int)prep.size()};
+  note_launch(0, true);  // (rows_gemm_group_ok: 16-byte aligned operands only)
+  count_rows_form<4, 1, 1, 1, 32>(kFormGrouped);
   hipLaunchKernelGGL((rows_gemm_group_kernel<4, 1, 1, 1, 32, true, 4>), dim3(first.back()), dim3(256), lds, s, t);
   return hipGetLastError();
 }

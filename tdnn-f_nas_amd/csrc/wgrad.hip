@@ -6,6 +6,7 @@
 #include "common.h"
 #include "device.h"
 #include "gemm_f32.h"
+#include "launch_forms.h"
 #include "planes_gemm.h"
 #include "wgrad_kernels.h"
 
@@ -237,6 +238,8 @@ bool planes_try_wgrad(const WgradArgs &a, void *workspace, size_t workspace_byte
   if (*err != hipSuccess) return true;
   *err = wgrad_finish(a, g.partial, splits, g.partial + slab * splits, hy->scale, hx->scale, s);
   g_planes_routed_wgrad++;
+  count_form(kWgradPlanes);
+  note_wgrad_slabs(splits);
   return true;
 }
 
@@ -261,7 +264,10 @@ hipError_t wgrad(const WgradArgs &a, void *workspace, size_t workspace_bytes, hi
   int planes = 0;  // 0: f32 MFMA; 2 / 3: split-bf16 with that many planes per operand
   {
     int prec = a.prec;
-    if (prec == 0) prec = gemm_precision_default();
+    if (prec == 0) {
+      prec = gemm_precision_default();
+      if (prec == 0 && (options().gemm_arith_test == 1 || options().gemm_arith_test == 3)) prec = options().gemm_arith_test;  // (tests: rows_gemm.hip)
+    }
     if (prec == 4 || (prec == 3 && options().planes)) {  // pre-split planes when the caller hinted them for these operands
       hipError_t pe = hipSuccess;
       if (planes_try_wgrad(a, workspace, workspace_bytes, prec == 4 ? 2 : 3, s, &pe)) return pe;
@@ -293,6 +299,8 @@ hipError_t wgrad(const WgradArgs &a, void *workspace, size_t workspace_bytes, hi
                                    (double)a.Do * ktaps * a.Di * (a.accumulate ? 2.0 : 1.0)));
     }
     ProfScope ps(2, flops, s);
+    count_form(kWgradFirst + wt.variant * kRowsAriths + (planes == 2 ? 1 : planes == 3 ? 2 : 0));
+    note_wgrad_slabs(pl.splits);
     if (wt.variant == 4) launch_wgrad<2, 2, 1, 1, false>(l, a, a_x, vec, planes);
     else if (wt.variant == 1) launch_wgrad<1, 4, 5, 1, false>(l, a, a_x, vec, planes);
     else if (wt.variant == 2) launch_wgrad<4, 1, 1, 5, false>(l, a, a_x, vec, planes);

@@ -173,6 +173,15 @@ class option:
         return False
 
 
+def launch_forms(reset=False):
+    """{name: value} of the non-zero GEMM launch-form counters (tdnnf_gemm_launch_forms); reset: clear them all afterwards."""
+    lib = load()
+    n = lib.tdnnf_gemm_launch_forms(None, 0, 0)
+    counts = (C.c_longlong * n)()
+    lib.tdnnf_gemm_launch_forms(counts, n, 1 if reset else 0)
+    return {lib.tdnnf_gemm_launch_form_name(i).decode(): int(counts[i]) for i in range(n) if counts[i]}
+
+
 class DenGraph:
     def __init__(self, g):
         lib = load()

@@ -314,8 +314,13 @@ def test_bench_shape_split_bf16_six_products_against_f32(pkg, bench_egs, arith):
     1e-3 bar; the whole gradient to the size of that tie noise."""
     keep = ["tdnnf2.relu", "tdnnf9.relu", "tdnnf15.relu", "prefinal-chain.relu"]
     f32, ef = run_bench_shape(pkg, bench_egs, 1, keep=keep)
+    pkg.hipabi.launch_forms(reset=True)
     with pkg.hipabi.option("planes", 0 if arith == "bf16x6-in-kernel" else 1):
         x6, ex = run_bench_shape(pkg, bench_egs, 1, keep=keep, gemm_precision=3 if arith == "f16x3-planes" else 2)
+    counted = pkg.hipabi.launch_forms(reset=True)
+    if arith != "bf16x6-in-kernel" and torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        # some layer of the bench net takes the plane router's whole rounds + split-K tail (rows_gemm.hip, planes_try_rows), the others one launch
+        assert counted.get("planes.plain", 0) >= 1 and counted.get("planes.main_split_tail", 0) >= 1, counted
     (ra, ga), (rb, gb) = x6[0], f32[0]
     assert abs(ra[0] - rb[0]) < 1e-4 * abs(rb[0]), (ra[0], rb[0])
     for k in keep:
@@ -338,6 +343,20 @@ def test_bench_shape_split_bf16_six_products_against_f32(pkg, bench_egs, arith):
         assert e < 1e-3, (name, e)
     e = float((ga - gb).double().norm() / gb.double().norm())
     assert e < 3e-2, e
+    if arith == "f16x3-planes":  # option gemm_alt_taps 2 (the two taps of a .linear in alternating chunks of K blocks), held to the same bars
+        pkg.hipabi.launch_forms(reset=True)
+        with pkg.hipabi.option("gemm_alt_taps", 2):
+            alt, _ = run_bench_shape(pkg, bench_egs, 1, gemm_precision=3)
+        counted = pkg.hipabi.launch_forms(reset=True)
+        assert counted.get("planes.alt_chunked", 0) >= 1, counted  # the chunked order did run
+        rc, gc = alt[0]
+        assert abs(rc[0] - rb[0]) < 1e-4 * abs(rb[0]), (rc[0], rb[0])
+        for name in ("output.affine", "prefinal-chain.linear", "output-xent.affine", "prefinal-xent.linear"):
+            sl = component_slice(comps[name])
+            e = float((gc[sl] - gb[sl]).double().norm() / gb[sl].double().norm())
+            assert e < 1e-3, (name, e)
+        e = float((gc - gb).double().norm() / gb.double().norm())
+        assert e < 3e-2, e
 
 
 @pytest.mark.parametrize("name", sorted(SUPERNETS))

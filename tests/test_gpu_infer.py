@@ -200,12 +200,16 @@ def test_model_file_and_updates(pkg, tmp_path):
 def test_fusion_is_real(pkg, name, kw):
     cfg, net = make_model(pkg, kw, seed=5)
     am = pkg.infer.AcousticModel(net, frames_per_chunk=30, max_chunks=4)
+    pkg.hipabi.launch_forms(reset=True)
     am.compute(utterances(np.random.default_rng(2), [90, 31]))
+    counted = pkg.hipabi.launch_forms(reset=True)
     ref = OracleNet(pkg, pkg.trainer.make_config(**dict(kw, frames_per_chunk=30, num_sequences=4, cv_update=1)), net.components)
     strided = sum(1 for L in ref.layers if L["out"][1] != L["inn"][1])
     assert strided >= 1
     fused, fallback = am.counts()
     assert (fused, fallback) == (cfg.num_layers + 3 - strided, strided)
+    # every fused layer is (at least) one GEMM with the inference epilogue: the launch-form counters saw them
+    assert sum(v for k, v in counted.items() if k.endswith(".post")) >= fused, counted
 
 
 @pytest.mark.parametrize("name,extra", [("offset-supernet", dict(darts_num_offsets=3, darts_flags=1 | 16, darts_temp_proportion=0.8)),

@@ -399,7 +399,8 @@ def test_f16_plane_scales_come_from_true_upper_bounds(pkg, ng):
 @pytest.mark.parametrize("arith", ["f32", "f16x3-planes"])
 def test_batchnorm_statistics_out_of_the_gemm_epilogue_at_full_width(pkg, arith):
     """At 1536 columns the affine GEMM forms the BatchNorm statistics of its output while storing it (row tiles of the plain
-    launch + the chunks of a pass over the rows its split-K tail finishes: 10 000+ rows take both routes; the plane GEMMs: one partial
+    launch + the chunks of a pass over the rows its split-K tail finishes: 9 728 rows take both routes, which the launch-form counters
+    confirm on a 256-CU chip; the plane GEMMs: one partial
     row per 256-row tile, or per 128-row tile of the short-reduction form, whose count the caller must take from the launch).
     Checked through the activations: tdnn1.batchnorm must be the normalisation of tdnn1.relu by that matrix's own float64 column statistics
     (9 728 rows, K = 220: the plane path takes the 128-row tiles here)."""
@@ -413,8 +414,17 @@ def test_batchnorm_statistics_out_of_the_gemm_epilogue_at_full_width(pkg, arith)
     feats, iv = T.synthetic_egs(net, seed=3)
     den = pkg.hipabi.DenGraph(pkg.synth.make_den_graph(40, cfg.num_pdfs, mean_out_degree=4.0, seed=5))
     sup = pkg.hipabi.Supervision(pkg.synth.make_supervision(cfg.num_sequences, cfg.frames_per_chunk // 3, cfg.num_pdfs, seed=6))
+    pkg.hipabi.launch_forms(reset=True)
     r = host(net.forward_backward(dev(feats), dev(iv), den, sup, step=0))
+    counted = pkg.hipabi.launch_forms(reset=True)
     assert r[5] == 1.0
+    if torch.cuda.get_device_properties(0).multi_processor_count == 256:  # what the docstring says ran, observed
+        if planes:
+            # (9 728 rows are 38 tiles of 256 rows or 76 of 128: less than one round of the plane kernels, so no layer here has a tail)
+            assert counted.get("planes.plain", 0) >= 1 and not counted.get("planes.main_split_tail") and not counted.get("planes.main_plain_tail"), counted
+            assert not counted.get("rows.128x128k16.f32.main_split_tail"), counted
+        else:
+            assert counted.get("rows.128x128k16.f32.main_split_tail", 0) >= 1, counted
     x = host(net.activation("tdnn1.relu")).astype(np.float64)
     assert x.shape[0] > 8192 + 128 and x.shape[1] == 1536  # more than one round of 128 x 128 tiles plus a tail
     mean, var = x.mean(0), x.var(0)

@@ -627,8 +627,10 @@ def _chain_deriv(hip, pkg, H, P, B, T, leaky):
 
 
 # the persistent LDS-DMA-ring form of the rows GEMM (csrc/gemm_ring.hip) takes launches without tap coefficients whose taps are whole K
-# steps of 16 and whose output gets the 128-wide tile: every init mode, ragged row and column tiles, row strides, a block that walks
-# several tiles (more tiles than the chip has block slots), against a float64 product of the spliced input
+# steps of 16 and whose output gets the 128 x 128 tile: every init mode, ragged row and column tiles, row strides, a block that walks
+# several tiles (more tiles than the chip has block slots), against a float64 product of the spliced input.
+# The launch-form counters say what ran: since launches of fewer than 768 tiles take the 64 x 128 tile, only "many-tiles" reaches the ring
+# on a 256-CU chip; the ring's ragged tiles, strides and init modes are pinned at shapes that do reach it in tests/test_gpu_gemm_forms.py.
 RING_CASES = [
     # name, offsets, num_t_out, B, Di, Do, t_step_out
     ("affine-k2", [0, 1], 37, 16, 160, 1536, 1),          # 592 rows: ragged last row tile
@@ -658,10 +660,18 @@ def test_rows_gemm_persistent_ring_shapes(hip, pkg, case):
     ix = pkg.hipabi.indexes(rho, ro)
     xd, _ = padded(x)
     Wd, bd = dev(W), dev(b)
-    for mode in (1, 0, 2):
+    on_256_cus = torch.cuda.get_device_properties(0).multi_processor_count == 256
+    for ring, mode in ((1, 1), (1, 0), (1, 2), (0, 1)):
         yd, ybuf = padded(y0)
-        hip.tdnn_propagate(C.byref(ix), xd, hip.vec(Wd), K * Di, Do, Di, hip.vec(bd) if mode == 1 else None, None, mode, yd, hip.stream())
+        pkg.hipabi.launch_forms(reset=True)
+        with pkg.hipabi.option("gemm_ring", ring):
+            hip.tdnn_propagate(C.byref(ix), xd, hip.vec(Wd), K * Di, Do, Di, hip.vec(bd) if mode == 1 else None, None, mode, yd, hip.stream())
+        counted = pkg.hipabi.launch_forms(reset=True)
+        ring_counts = sum(v for k, v in counted.items() if k.endswith(".ring"))
+        assert ring or not ring_counts, counted
+        if name == "many-tiles" and on_256_cus:  # 12 800 tiles of 128 x 128 on 768 slots: the ring, or the tile kernel with the option off
+            assert counted == {"rows.128x128k16.f32." + ("ring" if ring else "plain"): 1, "rows.launches_vec4": 1}, counted
         want = ref + (torch.from_numpy(b).cuda().double() if mode == 1 else 0) + (torch.from_numpy(y0).cuda().double() if mode == 0 else 0)
         got = yd.double()
-        assert float((got - want).norm() / want.norm()) < TOL, (name, mode)
+        assert float((got - want).norm() / want.norm()) < TOL, (name, mode, ring)
         assert (host(ybuf)[:, Do:] == 7.0).all(), "wrote outside the view"
