@@ -559,7 +559,8 @@ int tdnnf_net_update(tdnnf_net *, float learning_rate, float l2_regularize_scale
 /* "nnet3-copy --edits='set-dropout-proportion name=* proportion=p'" of train.py's dropout schedule */
 int tdnnf_net_set_dropout_proportion(tdnnf_net *, float proportion);
 int tdnnf_net_set_temperature_proportion(tdnnf_net *, float proportion);
-/* ---- f32-equivalent GEMMs on the 16-bit matrix cores from pre-split operands (csrc/planes_gemm.hip).
+/* ---- f32-equivalent GEMMs on the 16-bit matrix cores from pre-split operands (csrc/abi_planes.hip; the split: csrc/planes_split.hip,
+   the GEMM: csrc/planes_gemm.hip).
    An operand is split ONCE into 16-bit planes laid out for the consumer ("P16": [K block of 16][plane][row][16], 32-byte row
    records, zero rows in front of and behind the matrix so that row-shifted tap views and tile overhang read zeros):
      num_planes 3 ("bf16x6", gemm_precision 2): x = p0 + p1 + p2, three bf16 planes, the six products p_i q_j with i + j <= 2;

@@ -236,10 +236,10 @@ void layout_arena(tdnnf_net *n, Arena &A) {
       for (const Tdnn *td : {&L.lin, &L.aff})
         for (int i = 0; i < td->K; i++) lead_cap = std::max(lead_cap, td->ix.row_offsets[i]);
     auto slot = [&](const float *key, int rows, int cols, bool with_lead) {
-      const long long R = planes_rows_padded((long long)(with_lead ? 2 * ((lead_cap + 15) & ~15) : 0) + rows + 256);
-      const long long Rt = planes_rows_padded(((cols + 255) / 256) * 256LL);
+      const long long R = planes_slot_rows(rows, with_lead ? (lead_cap + 15) & ~15 : 0);
+      const long long Rt = planes_slot_t_rows(cols);
       tdnnf_net::PlaneSlot ps;
-      ps.bytesP = planes_bytes(np, R, (planes_kblocks(cols) + 15) / 16 * 16);  // (whole 256-column tiles of K blocks: the rows-as-K reads of a weight gradient)
+      ps.bytesP = planes_bytes(np, R, planes_slot_kblocks(cols));
       ps.bytesPT = planes_bytes(np, Rt, planes_t_kblocks(rows));
       ps.P = A.take<char>(ps.bytesP + 64);
       ps.PT = A.take<char>(ps.bytesPT + 64);
@@ -274,8 +274,8 @@ void layout_arena(tdnnf_net *n, Arena &A) {
       if (cd.plain || cd.rows < 2 || (int)i == n->c_lda) continue;
       PlanesOperand &o = n->pw[i];
       o.rows = cd.rows; o.cols = cd.cols; o.ld = cd.cols; o.np = np; o.lead = 0;
-      o.R = planes_rows_padded(((cd.rows + 255) / 256) * 256LL);
-      o.Rt = planes_rows_padded(((cd.cols + 255) / 256) * 256LL);
+      o.R = planes_slot_t_rows(cd.rows);  // (a weight matrix's rows are the tile columns of its forward GEMM)
+      o.Rt = planes_slot_t_rows(cd.cols);
       o.P = A.take<char>(planes_bytes(np, o.R, planes_kblocks(cd.cols)) + 64);
       o.PT = A.take<char>(planes_bytes(np, o.Rt, planes_t_kblocks(cd.rows)) + 64);
       n->pw_scale[i] = A.take<float>(4);

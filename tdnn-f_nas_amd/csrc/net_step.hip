@@ -410,6 +410,13 @@ struct Step {
     memcpy(ps.last, cfg5, sizeof(cfg5));
     return same;
   }
+  // the slot was allocated (net.hip, by planes_gemm.h's planes_slot_* sizes) for planes of `m` with R rows, and transposed planes with Rt
+  // rows (0: none are written): anything larger would be written past its end
+  int slot_holds(const tdnnf_net::PlaneSlot &ps, const tdnnf_mat &m, long long R, long long Rt) const {
+    TDNNF_REQUIRE(planes_bytes(np, R, planes_slot_kblocks(m.cols)) <= ps.bytesP && planes_bytes(np, Rt, planes_t_kblocks(m.rows)) <= ps.bytesPT,
+                  "net_forward_backward: plane slot too small for a %d x %d matrix", m.rows, m.cols);
+    return TDNNF_OK;
+  }
   // the row-major planes of `m` in slot `ps`, as a GEMM hint
   PlanesOperand slot_operand(const tdnnf_mat &m, const tdnnf_net::PlaneSlot &ps, long long R, int lead, long long kb_alloc) const {
     PlanesOperand o;
@@ -433,13 +440,12 @@ struct Step {
     }
     lead = (lead + 15) & ~15;  // (a weight gradient reads the row-major planes in K steps of 16 rows: the matrix starts on one)
     a.lead = lead;
-    a.R = planes_rows_padded((long long)2 * lead + m.rows + 256);
-    a.Rt = planes_rows_padded(((m.cols + 255) / 256) * 256LL);
+    a.R = planes_slot_rows(m.rows, lead);
+    a.Rt = planes_slot_t_rows(m.cols);
     a.P = (want & kP) ? ps.P : nullptr;
     a.PT = (want & kT) ? ps.PT : nullptr;
-    const long long kb_alloc = (planes_kblocks(m.cols) + 15) / 16 * 16;
-    TDNNF_REQUIRE(planes_bytes(np, a.R, kb_alloc) <= ps.bytesP && planes_bytes(np, a.Rt, planes_t_kblocks(m.rows)) <= ps.bytesPT,
-                  "net_forward_backward: plane slot too small for a %d x %d matrix", m.rows, m.cols);
+    const long long kb_alloc = planes_slot_kblocks(m.cols);
+    CK(slot_holds(ps, m, a.R, a.Rt));
     a.pads_done = slot_same_shape(ps, m, lead, a.R, want);
     TDNNF_HIP(planes_split(a, st));
     *o = slot_operand(m, ps, a.R, lead, kb_alloc);
@@ -475,8 +481,8 @@ struct Step {
     if (it == n->plane_slots.end()) return TDNNF_OK;
     tdnnf_net::PlaneSlot &ps = it->second;
     lead = (lead + 15) & ~15;
-    const long long R = planes_rows_padded((long long)2 * lead + d.rows + 256), kb_alloc = (planes_kblocks(d.cols) + 15) / 16 * 16;
-    TDNNF_REQUIRE(planes_bytes(np, R, kb_alloc) <= ps.bytesP, "net_forward_backward: plane slot too small for a %d x %d matrix", d.rows, d.cols);
+    const long long R = planes_slot_rows(d.rows, lead), kb_alloc = planes_slot_kblocks(d.cols);
+    CK(slot_holds(ps, d, R, 0));
     if (!slot_same_shape(ps, d, lead, R, kP)) TDNNF_HIP(planes_pad(np, ps.P, planes_kblocks(d.cols), R, lead, d.rows, s));
     *bp = BwdPlanes{ps.P, R, lead, ps.scale};
     *po = slot_operand(d, ps, R, lead, kb_alloc);
@@ -495,8 +501,8 @@ struct Step {
       return TDNNF_OK;
     }
     tdnnf_net::PlaneSlot &ps = it->second;
-    const long long R = planes_rows_padded((long long)out.rows + 256), kb_alloc = (planes_kblocks(out.cols) + 15) / 16 * 16;
-    TDNNF_REQUIRE(planes_bytes(np, R, kb_alloc) <= ps.bytesP, "net_forward_backward: plane slot too small for a %d x %d matrix", out.rows, out.cols);
+    const long long R = planes_slot_rows(out.rows, 0), kb_alloc = planes_slot_kblocks(out.cols);
+    CK(slot_holds(ps, out, R, 0));
     TDNNF_HIP(planes_scale_bound(n->fro_buf, fb.blocks, (double)out.rows * out.cols, fb.mul, fb.add_coef, fb.add_rec, ps.scale, s));
     const bool held = ps.last[0] >= 0;
     if (!slot_same_shape(ps, out, 0, R, kP) && held) {  // (the slot last held another shape: zero rows behind the matrix again)

@@ -1,5 +1,5 @@
-// planes_gemm.h -- host interface of the pre-split plane GEMMs (planes_gemm.hip): f32-equivalent products on the 16-bit matrix cores
-// from operands split ONCE into 16-bit planes in HBM.
+// planes_gemm.h -- host interface of the pre-split plane GEMMs: f32-equivalent products on the 16-bit matrix cores from operands split
+// ONCE into 16-bit planes in HBM.  The split and what goes with it: planes_split.hip; the GEMM and the routing state: planes_gemm.hip.
 //
 //   np = 3  "bf16x6": x = p0 + p1 + p2 (three bf16 planes, 24 mantissa bits), the six products p_i q_j with i + j <= 2.
 //   np = 2  "f16x3" : x s = h + l (two f16 planes of the operand scaled by a power of two s chosen from its Frobenius norm so that
@@ -80,6 +80,14 @@ inline long long planes_t_kblocks(int rows) { return ((rows + 63) / 64) * 4; }  
 // a chunk stride (rows x 32 bytes) that is a multiple of 8 KB puts every plane and K block on the same memory channels (2.7 x slower):
 // the row count to allocate for `rows` data rows + `pad` zero rows
 inline long long planes_rows_padded(long long rows) { return rows % 256 == 0 ? rows + 8 : rows; }
+// The sizes of a plane slot -- buffers that one party allocates and another splits matrices into (net.hip / net_step.hip); said here once,
+// because a user that sized its planes otherwise than the allocation would write past them:
+// rows of the row-major planes of a `rows`-row matrix behind `lead` zero rows (a multiple of 16), a 256-row tile of zero rows behind it
+inline long long planes_slot_rows(long long rows, int lead) { return planes_rows_padded(2LL * lead + rows + 256); }
+// rows of planes whose rows are tile COLUMNS (the transposed planes of a `cols`-column matrix; a weight matrix's outputs): whole 256-column tiles
+inline long long planes_slot_t_rows(int cols) { return planes_rows_padded(((cols + 255) / 256) * 256LL); }
+// K blocks of the row-major planes: whole 256-column tiles of K blocks (the rows-as-K reads of a weight gradient)
+inline long long planes_slot_kblocks(int cols) { return (planes_kblocks(cols) + 15) / 16 * 16; }
 
 struct PlanesSplitArgs {
   int np;
@@ -110,10 +118,13 @@ struct PlanesSplitArgs {
   bool pads_done = false;
 };
 size_t planes_sumsq_ws_bytes();
+// tests (option planes_check_bound): measure ||x||_F and compare it with the bound in rec[2]; counts into what planes_bound_counts reads
+hipError_t planes_check_bound(MatView x, const float *rec, void *sumsq_ws, hipStream_t s);
+// how many bounds were checked so far, and how many were too small (synchronises the device).  Lives beside the device-side counters it
+// reads: without relocatable device code a symbol is only visible in its own translation unit.  (hidden: the library exports the C entry)
+__attribute__((visibility("hidden"))) void planes_bound_counts(long long *checks, long long *violations);
 // the scale record [s, 1 / s, bound] of a matrix of `numel` elements from a norm bound alone (PlanesSplitArgs::fro2_bound): for a producer that
 // writes the planes itself (fused.h PlanesSink)
-// tests (option planes_check_bound): measure ||x||_F and compare it with the bound in rec[2]; counts into tdnnf_planes_bound_checks
-hipError_t planes_check_bound(MatView x, const float *rec, void *sumsq_ws, hipStream_t s);
 hipError_t planes_scale_bound(const double *fro2_bound, int blocks, double numel, float mul, float add_coef, const float *add_rec, float *rec, hipStream_t s);
 hipError_t planes_split(const PlanesSplitArgs &a, hipStream_t s);
 // The splits of several small f16x3 matrices whose zero rows are in place (planes_split_group_ok: np 2, <= 4 M elements, 16-byte aligned rows,
@@ -125,7 +136,7 @@ hipError_t planes_split_group(const std::vector<PlanesSplitArgs> &v, PlanesSplit
 void planes_split_group_destroy(PlanesSplitGroup *g);
 // zero the rows [0, lead) and [lead + rows, R) of every (K block, plane) chunk of a row-major plane buffer (a producer that writes the data rows itself)
 hipError_t planes_pad(int np, void *P, long long k_blocks, long long R, int lead, long long rows, hipStream_t s);
-// tile shape the GEMM uses for an N-column output: the A buffer needs tail >= tile rows beyond the last row read, the B buffer rows padded to the tile's columns
+
 // ---- routing of the f32 GEMM entry points (rows_gemm / wgrad, gemm_f32.h) onto the plane kernels.
 // The caller that owns the matrices (net_step.hip) splits an operand, describes the result in a PlanesOperand and installs it as a hint
 // around the call; rows_gemm() / wgrad() check that the hinted planes really are those of their operands (base pointer, leading
@@ -157,6 +168,8 @@ extern long long g_planes_routed_rows, g_planes_routed_wgrad;
 const PlanesOperand *planes_hint_a();
 const PlanesOperand *planes_hint_b();
 
+// ---- the GEMM
+// tile shape the GEMM uses for an N-column output: the A buffer needs tail >= tile rows beyond the last row read, the B buffer rows padded to the tile's columns
 int planes_gemm_tile_rows(int N);
 // the tile rows planes_gemm() will use for THIS launch (256, or 128 for short reductions into 256-column tiles): what a caller needs to count its row tiles
 int planes_gemm_launch_tile_rows(const PlanesGemmArgs &a);

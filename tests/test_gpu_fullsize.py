@@ -42,7 +42,7 @@ FULL = [
     # 0.3-1.1e-3 measured on the toy nets of test_gpu_net.py was mask flips, not arithmetic
     ("7q-bf16x3", dict(gemm_precision=1)),
     ("bn-supernet-320-onehot-NG-bf16x3", dict(bn_choice_dims=[80, 80, 80, 80], bn_mode=0, use_natural_gradient=1, gemm_precision=1)),
-    # the pre-split plane kernels (planes_gemm.hip) at full width, on the one-stream schedule they need ("planes": see the test): two scaled
+    # the pre-split plane kernels (planes_gemm_kernels.h) at full width, on the one-stream schedule they need ("planes": see the test): two scaled
     # f16 planes / three products and three bf16 planes / six products, both f32-equivalent -> the exact-f32 bars
     ("7q-f16x3-planes", dict(gemm_precision=3, planes=1)),
     ("7q-NG-f16x3-planes", dict(gemm_precision=3, use_natural_gradient=1, planes=1)),

@@ -93,7 +93,7 @@ CASES += [
     ("7q-shape-small-NG-bf16x6", dict(frames_per_chunk=48, num_sequences=8, strides=[1, 1, 1, 0, 3, 3, 3], bottleneck=24, feat_dim=40,
                                       ivector_dim=100, num_pdfs=150, hidden_dim=96, small_dim=48, use_natural_gradient=1, gemm_precision=2), 60),
 ]
-# gemm_precision 3 (two scaled f16 planes, three products) and gemm_precision 2 on the PRE-SPLIT plane kernels (planes_gemm.hip): the
+# gemm_precision 3 (two scaled f16 planes, three products) and gemm_precision 2 on the PRE-SPLIT plane kernels (planes_gemm_kernels.h): the
 # trainer only takes them on one stream, so the tiny nets here switch the weight-gradient stream off ("planes": forced in the test below).
 # Held to the SAME tolerances as exact f32.
 CASES += [

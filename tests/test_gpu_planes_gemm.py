@@ -1,4 +1,4 @@
-"""-m gpu: the pre-split plane GEMMs (csrc/planes_gemm.hip) through the C-ABI against float64 on the same inputs, for both
+"""-m gpu: the pre-split plane GEMMs (csrc/planes_split.hip, csrc/planes_gemm.hip) through the C-ABI (csrc/abi_planes.hip) against float64 on the same inputs, for both
 arithmetics -- three bf16 planes / six products ("bf16x6", gemm_precision 2) and two scaled f16 planes / three products ("f16x3",
 gemm_precision 3): single segments, taps as row-shifted segments, ragged tiles, K not a multiple of 16, the three init modes and
 ReLU, the transposed planes, and data chosen to break a scaled 16-bit split (huge dynamic range, one spike, tiny values).
@@ -223,3 +223,78 @@ def test_planes_gemm_epilogue_addend_and_column_statistics(pkg, np_, M, N, Di, o
     th = 128 if t != (M + 255) // 256 else 256  # the launch's tile height (one partial row per row tile)
     for k in range(t):
         assert np.allclose(st[0, k], g64[k * th:(k + 1) * th].sum(0), rtol=1e-5, atol=1e-3)
+
+
+def _scale_reference(X):
+    """(s, ||X||_F) of the f16x3 scale record in float64.  The record is the norm rounded DOWN to a power of two, so the data must keep both
+    logarithms away from an integer: asserted here, so that a change of seed cannot silently put a case on a rounding edge."""
+    fro = np.sqrt((X.astype(np.float64) ** 2).sum())
+    logs = np.log2(65504.0 / fro), np.log2(64.0 / (fro / np.sqrt(X.size)))
+    for v in logs:
+        assert 0.05 <= v - np.floor(v) <= 0.95, logs
+    return 2.0 ** np.floor(min(logs)), fro
+
+
+def _unswizzle(buf, nkb, np_, R, row0=0):
+    """[K block][plane][row][16] with the halves of the 32-byte records of rows row0 .. whose bit 3 is set swapped back"""
+    P = buf.reshape(nkb, np_, R, 2, 8)
+    sw = ((np.arange(R) + row0) >> 3) & 1
+    return np.where(sw[None, None, :, None, None] == 1, P[:, :, :, ::-1, :], P).reshape(nkb, np_, R, 16)
+
+
+def test_planes_split_of_an_unaligned_view(pkg):
+    """The split of a view whose rows are not 16-byte aligned (137 x 40 at column 1 of a 137 x 45 buffer: the scalar norm pass and the
+    element-wise reads), for both arithmetics, held to what test_planes_split_layout_and_transposed_planes asks of an aligned matrix.
+    The buffer's other columns hold 1e30: one of them read into the norm or a plane shows at once."""
+    rng = np.random.default_rng(4)
+    rows, cols = 137, 40
+    X = (rng.standard_normal((rows, cols)) * np.exp(rng.uniform(-3, 3, (rows, cols)))).astype(np.float32)
+    s_ref, fro = _scale_reference(X)
+    buf = torch.full((rows, 45), 1e30, device="cuda")
+    buf[:, 1:1 + cols] = dev(X)
+    view = buf[:, 1:1 + cols]
+    assert view.data_ptr() % 16 != 0 and view.stride(0) % 4 != 0
+    lead, tail, t_tail = 5, 9, 24
+    for np_, tol in ((3, 2.0 ** -23), (2, 2.0 ** -21)):
+        P, R, PT, Rt, scale = planes_of(pkg, np_, view, lead, tail, t_tail)
+        s, inv, fro_rec = host(scale)[:3]
+        if np_ == 2:
+            assert s == s_ref and inv == 1.0 / s and fro <= fro_rec <= fro * 1.00001, (s, s_ref, fro, fro_rec)
+        else:
+            s = 1.0
+        nkb = (cols + 15) // 16
+        Pn = _unswizzle(host(P.float()), nkb, np_, R)
+        assert not Pn[:, :, :lead].any() and not Pn[:, :, lead + rows:].any()
+        rec = Pn[:, :, lead:lead + rows].astype(np.float64).sum(1).transpose(1, 0, 2).reshape(rows, nkb * 16)
+        assert not rec[:, cols:].any()
+        assert np.abs(rec[:, :cols] / s - X).max() <= tol * np.abs(X).max() and rel_l2(rec[:, :cols] / s, X) < tol
+        nkbt = ((rows + 63) // 64) * 4
+        Tn = _unswizzle(host(PT.float()), nkbt, np_, Rt)
+        assert not Tn[:, :, cols:].any()
+        rect = Tn[:, :, :cols].astype(np.float64).sum(1).transpose(1, 0, 2).reshape(cols, nkbt * 16)
+        assert not rect[:, rows:].any()
+        assert np.array_equal(rect[:, :rows].T, rec[:, :cols])
+    got = host(buf)
+    assert (got[:, 0] == np.float32(1e30)).all() and (got[:, 1 + cols:] == np.float32(1e30)).all() and np.array_equal(got[:, 1:1 + cols], X)  # the input is only read
+
+
+def test_planes_split_just_over_the_small_bound(pkg):
+    """2049 x 2048: the smallest whole-row shape above the 4 M elements up to which a split forms its own scale -- the norm pass on all its
+    1024 blocks and the scale record from a launch of its own.  f16 planes; the first and the last 64 rows against the matrix."""
+    rng = np.random.default_rng(2)
+    rows, cols = 2049, 2048
+    assert (rows - 1) * cols <= 4 << 20 < rows * cols
+    X = rng.standard_normal((rows, cols), dtype=np.float32) * np.float32(0.37)
+    s_ref, fro = _scale_reference(X)
+    lead, tail = 5, 9
+    P, R, _, _, scale = planes_of(pkg, 2, dev(X), lead, tail)
+    s, inv, fro_rec = host(scale)[:3]
+    assert s == s_ref and inv == 1.0 / s and fro <= fro_rec <= fro * 1.00001, (s, s_ref, fro, fro_rec)
+    nkb, tol = cols // 16, 2.0 ** -21
+    Pd = P.view(nkb, 2, R, 16)
+    assert not Pd[:, :, :lead].any().item() and not Pd[:, :, lead + rows:].any().item()
+    for r0 in (0, rows - 64):
+        Pn = _unswizzle(host(Pd[:, :, lead + r0:lead + r0 + 64].float()), nkb, 2, 64, row0=lead + r0)
+        rec = Pn.astype(np.float64).sum(1).transpose(1, 0, 2).reshape(64, cols)
+        Xs = X[r0:r0 + 64]
+        assert np.abs(rec / s - Xs).max() <= tol * np.abs(X).max() and rel_l2(rec / s, Xs) < tol

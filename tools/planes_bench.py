@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the pre-split bf16-plane GEMM (csrc/planes_gemm.hip) on the K = 3072 shapes of the 7q step (the .linear
+"""Micro-benchmark of the pre-split bf16-plane GEMM (csrc/planes_gemm.hip, csrc/planes_gemm_kernels.h) on the K = 3072 shapes of the 7q step (the .linear
 forward / .affine backward-data GEMMs: M rows x 160 columns, two taps of 1536) and on the 1536-wide ones, beside the exact-f32
 kernel.  f32-equivalent TFLOP/s = 2 M N K / time.  Usage (GPU box): python tools/planes_bench.py [reps]"""
 import ctypes as C
