@@ -22,8 +22,6 @@
 namespace tdnnf {
 namespace {
 
-inline int pad4i(int x) { return (x + 3) & ~3; }
-
 // in_value_temp of :482-532: X~[r][i*Di + d] = eff[i] * in[row_off[i] + r*rho][d] (a tap whose effective coefficient is
 // zero is left zero, :512), X~[r][K*Di] = 1 when the component has a bias (:474-477)
 __global__ __launch_bounds__(256) void splice_taps_kernel(MatView in, tdnnf_tdnn_indexes ix, const float *eff, int Di, int ones, MatView out) {
@@ -70,9 +68,9 @@ struct Layout {
 Layout layout(int Do, int Di, int K, int N, int ones, bool alpha) {
   Layout L;
   const int Dx = K * Di + ones;
-  L.ldx = pad4i(Dx);
-  L.ldy = pad4i(Do);
-  L.ldt = pad4i(Dx);
+  L.ldx = pad4(Dx);
+  L.ldy = pad4(Do);
+  L.ldt = pad4(Dx);
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t at = off;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <vector>
 
@@ -114,6 +115,17 @@ inline int rows_gemm_sumsq_blocks(int M) { return (M + 127) / 128 > 1024 ? (M + 
 
 // b_kcontig: B element (k, n) at B[n*ldb + k] (true) or B[k*ldb + n] (false).
 hipError_t rows_gemm(const RowsGemmArgs &args, bool b_kcontig, hipStream_t stream);
+// The plain product C (M x N, ldc) = A (M x K, lda) B as ONE K segment over all M rows; every field not named here is zero.
+// init_mode 2: C = A B; 0: C += coef[0] A B (coef: one device float, null = 1).  sumsq as in RowsGemmArgs, or null.
+inline hipError_t rows_gemm_1seg(const float *A, long long lda, const float *B, long long ldb, bool b_kcontig, float *C, long long ldc, int M, int N, int K,
+                                 int init_mode, const float *coef, double *sumsq, hipStream_t stream) {
+  RowsGemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc; a.M = M; a.N = N;
+  a.init_mode = init_mode; a.coef = coef; a.sumsq = sumsq; a.nseg = 1;
+  a.seg[0].klen = K; a.seg[0].m_lo = 0; a.seg[0].m_hi = M;
+  return rows_gemm(a, b_kcontig, stream);
+}
 
 // Several statistics passes (sumsq set, N <= 32, k-contiguous B, 16-byte aligned operands: rows_gemm_group_ok) as ONE launch: task i runs
 // exactly the blocks a launch of its own without K split would.  *cache keeps the device-side task table between calls (null at first;

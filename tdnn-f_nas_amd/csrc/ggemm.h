@@ -15,8 +15,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-inline int pad4(int x) { return (x + 3) & ~3; }
-
 // ------------------------------------------------------------------------------------------------ generic grouped GEMM
 // One task = one 64 x 64 output tile (x one K slice): C[m][n] (op)= alpha * sum_{k in [k0, k1)} A(m, k) B(k, n) with
 // A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn] (any of the four orientations; the contiguous one is loaded 16 bytes
@@ -252,6 +250,38 @@ T *carve(char *&p, size_t n) {
   T *r = (T *)p;
   p += sizeof(T) * n;
   return r;
+}
+inline size_t carve_room(size_t bytes, size_t b) { return ((bytes + 255) & ~(size_t)255) + b; }  // `bytes` plus what carve() takes for b more
+
+// GemmLists that share one device block and, run one after the other, one buffer of partial tiles -- sizing and upload.
+// devlists_room: `bytes` plus room for every list's tasks and rtasks and for the partial tiles of the list that needs most.
+// devlists_upload: carves the same from `cur`, points the lists' partial slots at the buffer and copies the tables to the device.
+inline size_t devlists_slots(GemmList *const *lists, int n) {
+  size_t max_slots = 0;
+  for (int i = 0; i < n; i++) max_slots = std::max(max_slots, lists[i]->slots);
+  return max_slots;
+}
+inline size_t devlists_room(size_t bytes, GemmList *const *lists, int n) {
+  for (int i = 0; i < n; i++) {
+    bytes = carve_room(bytes, sizeof(GTask) * lists[i]->tasks.size());
+    bytes = carve_room(bytes, sizeof(RTask) * lists[i]->rtasks.size());
+  }
+  return carve_room(bytes, sizeof(float) * devlists_slots(lists, n) * GT * GT);
+}
+inline int devlists_upload(char *&cur, GemmList *const *lists, DevList *const *dls, int n) {
+  for (int i = 0; i < n; i++) {
+    dls[i]->nt = (int)lists[i]->tasks.size();
+    dls[i]->nr = (int)lists[i]->rtasks.size();
+    dls[i]->tasks = carve<GTask>(cur, lists[i]->tasks.size());
+    dls[i]->rtasks = carve<RTask>(cur, lists[i]->rtasks.size());
+  }
+  float *part = carve<float>(cur, devlists_slots(lists, n) * GT * GT);
+  for (int i = 0; i < n; i++) {
+    lists[i]->fixup(part);
+    if (dls[i]->nt) TDNNF_HIP(hipMemcpy(dls[i]->tasks, lists[i]->tasks.data(), sizeof(GTask) * dls[i]->nt, hipMemcpyHostToDevice));
+    if (dls[i]->nr) TDNNF_HIP(hipMemcpy(dls[i]->rtasks, lists[i]->rtasks.data(), sizeof(RTask) * dls[i]->nr, hipMemcpyHostToDevice));
+  }
+  return TDNNF_OK;
 }
 
 }  // namespace

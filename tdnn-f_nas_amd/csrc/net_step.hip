@@ -35,26 +35,6 @@ __global__ void scaled_taps_to_kernel(const float *G, const float *coef, int Do,
     T[(size_t)o * ldT + c] = (coef ? coef[c / Di] : 1.0f) * G[e];
   }
 }
-__global__ void set_column_kernel(const float *v, int rows, float *T, int ldT, int col) {  // (and zeros in the row's padding)
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < rows) {
-    T[(size_t)r * ldT + col] = v[r];
-    for (int c = col + 1; c < ldT; c++) T[(size_t)r * ldT + c] = 0.f;
-  }
-}
-// W_acc[o][c] += a b T[o][c] (c < ldw), bias_acc[o] += a b T[o][ldw]: "local_lrate = scale * learning_rate_"
-// (nnet-tdnn-component.cc:604-624); a, b are the two preconditioners' scales, still on the device
-__global__ void ng_commit_kernel(const float *T, int ldT, int Do, int ldw, const float *sa, const float *sb, float *W_acc, float *bias_acc) {
-  const float sc = sa[0] * sb[0];
-  const int C = ldw + (bias_acc ? 1 : 0);
-  const long long total = (long long)Do * C;
-  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += gridDim.x * 256LL) {
-    const int o = (int)(e / C), c = (int)(e % C);
-    const float v = sc * T[(size_t)o * ldT + c];
-    if (c < ldw) W_acc[(size_t)o * ldw + c] += v;
-    else bias_acc[o] += v;
-  }
-}
 // ---- bottleneck-dimension supernet (scripts/generate_bottleneckCB8share_onehottrain_config.py:10-85).
 struct BnChoice {
   int C, mode;
@@ -994,7 +974,7 @@ struct Step {
     // grouped chain: once both preconditioners exist (from the second minibatch on)
     const bool grouped = n->ng_grouped && ng_dim(n->ng_in[comp]) != 0 && ng_dim(n->ng_out[comp]) != 0;
     // the gradient GEMM writes T[:, :K Di] itself when it computes every tap; the bias column and the row padding come with
-    // set_column_kernel (the group's first launch) -- no zero fill of the 2-20 MB block first.  (With tap coefficients a zero one
+    // ng_set_column (the group's first launch) -- no zero fill of the 2-20 MB block first.  (With tap coefficients a zero one
     // makes the reduce kernel skip its columns: those launches start from zeros.)
     const bool overwrite = !from_tapgrad && !active && eff == nullptr && (ones || ldT == ldw);
     if (!overwrite) TDNNF_HIP(hipMemsetAsync(T, 0, sizeof(float) * (size_t)Do * ldT, sw));
@@ -1004,7 +984,7 @@ struct Step {
       CK(tdnn_update_simple_impl(&ix, x, dyv, Do, Di, eff, 1.0f, T, ldT, nullptr, wsw, n->ws_bytes, active, max_active, sw, overwrite));
     if (ones) {
       if (!bias_done) TDNNF_HIP(colsum_add(view(dyv), 1.0f, C.bsum, wsw, sw));  // (otherwise the fused ReLU backward pass on s filled it)
-      if (!grouped) hipLaunchKernelGGL(set_column_kernel, dim3((Do + 255) / 256), dim3(256), 0, sw, C.bsum, Do, T, ldT, ldw);
+      if (!grouped) ng_set_column(C.bsum, Do, T, ldT, ldw, sw);
     }
     // ---- the passes over the N-sized operands
     NgInput xin;
@@ -1031,7 +1011,7 @@ struct Step {
     yin.x = view(dyv); yin.ix.row_stride = 1; yin.ix.num_offsets = 1; yin.Di = Do; yin.N = N;
     if (fused_comp == comp) {  // H_out and its partials came with the BatchNorm/ReLU backward sweep
       fused_comp = -1;
-      CK(ng_external_end(n->ng_out[comp], yin, C.H_out, wsw, n->ws_bytes, sw));
+      CK(ng_stats_main_finish(n->ng_out[comp], yin, C.H_out, wsw, n->ws_bytes, sw));
     } else {
       CK(ng_stats_main(n->ng_out[comp], yin, C.H_out, C.part_out, wsw, n->ws_bytes, sw));
     }
@@ -1046,12 +1026,9 @@ struct Step {
     TDNNF_HIP(hipStreamWaitEvent(n->s3, n->ev_ngc, 0));
     {
       SplitKScratchOverride side_scratch(n->s3_scratch, n->s3_scratch_bytes);
-      CK(ng_stats_side(n->ng_in[comp], C.H_in, C.part_in, n->ng_side_ws, n->ngset_ws_bytes, n->s3));
-      CK(ng_stats_side(n->ng_out[comp], C.H_out, C.part_out, n->ng_side_ws, n->ngset_ws_bytes, n->s3));
-      CK(ng_project(n->ng_in[comp], n->ng_out[comp], T, Do, Dx, ldT, n->ngTmp, n->s3));
+      CK(ng_chain_one(n->ng_in[comp], n->ng_out[comp], C.H_in, C.part_in, C.H_out, C.part_out, T, Do, Dx, ldT, ldw, net_Wg(n, comp), bias_acc,
+                      n->ng_side_ws, n->ngset_ws_bytes, n->ngTmp, n->s3));
     }
-    hipLaunchKernelGGL(ng_commit_kernel, dim3(grid_for((long long)Do * Dx, 256)), dim3(256), 0, n->s3, T, ldT, Do, ldw, ng_scale_dev(n->ng_in[comp]),
-                       ng_scale_dev(n->ng_out[comp]), net_Wg(n, comp), bias_acc);
     CK(handed_off(sw, on_caller));
     // (the unscaled tap gradients this one reads are rebuilt by the next DARTS component on the caller's stream)
     if (from_tapgrad && n->wg_on) TDNNF_HIP(hipStreamWaitEvent(s, n->ev_pg[(n->pg_count - 1) & 3], 0));

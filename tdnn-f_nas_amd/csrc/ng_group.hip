@@ -1,4 +1,5 @@
-// ng_group.hip -- the latency-bound half of OnlineNaturalGradient for MANY components at once (ng.h, "Grouped side chain").
+// ng_group.hip -- the latency-bound half of OnlineNaturalGradient for MANY components at once (ng.h, "Grouped side chain"): the host
+// code of NgGroup (the chain) and NgFin (the grouped finalize); their kernels and descriptors are in ng_group_kernels.h.
 //
 // Per component and side the reference's PreconditionDirections (UPSTREAM Kaldi nnet3/natural-gradient-online.cc; call sites
 // /root/reference/src/nnet3/nnet-tdnn-component.cc:598-599, nnet-simple-component.cc:3001-3002) needs, after the N-sized pass
@@ -24,279 +25,9 @@
 #include "gemm_f32.h"
 #include "ggemm.h"
 #include "ng.h"
+#include "ng_group_kernels.h"
 
 namespace tdnnf {
-namespace {
-
-// ------------------------------------------------------------------------------------------------ L = H^T H, traces, scale
-struct PairDesc {  // one (component, side)
-  const float *H;
-  const double *part;  // ||X||^2 partials of the pass that formed H
-  float *Ld;
-  const float *WWT;
-  double *scal;
-  float *scale_f;
-  // refresh
-  const float *Kd;
-  float *hK, *hL;  // pinned host memory (device-visible)
-  double *h_tr0;
-  double ones_term;
-  int N, Rp, nt, npart;
-  int slab0, nslab, rows_per_slab;
-};
-__device__ __forceinline__ int ntile_pairs(int nt) { return nt * (nt + 1) / 2; }
-
-// block (pair, slab): the slab's contribution to the upper-triangular 32 x 32 tiles of H^T H, as raw accumulator images
-// [tile pair][register][lane].  A wave takes every fourth pair of rows; lane (li, lh) holds H[row + lh][32 c + li] for the
-// column tiles c, which is both the A fragment (A[i = li][k = lh]) and the B fragment (B[k = lh][j = li]) of the MFMA.
-template <int NT>
-__device__ __forceinline__ void l_partial_body(const PairDesc &p, int slab, float *partial, float *lds) {
-  constexpr int NP = NT * (NT + 1) / 2;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, lh = lane >> 5;
-  const int Rp = p.Rp, r0 = slab * p.rows_per_slab, r1 = min(p.N, r0 + p.rows_per_slab);
-  f32x16 acc[NP];
-#pragma unroll
-  for (int q = 0; q < NP; q++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[q][r] = 0.f;
-  bool cv[NT];
-#pragma unroll
-  for (int c = 0; c < NT; c++) cv[c] = c * 32 + li < Rp;
-  constexpr int U = 4;  // pairs of rows requested together
-  for (int base = r0 + 2 * wave; base < r1; base += 8 * U) {
-    float a[U][NT];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int row = base + 8 * u + lh;
-      const float *h = p.H + (size_t)row * Rp + li;
-#pragma unroll
-      for (int c = 0; c < NT; c++) a[u][c] = (row < r1 && cv[c]) ? h[c * 32] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      int q = 0;
-#pragma unroll
-      for (int i = 0; i < NT; i++)
-#pragma unroll
-        for (int j = i; j < NT; j++, q++) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][i], a[u][j], acc[q], 0, 0, 0);
-    }
-  }
-  // waves 2, 3 -> LDS, waves 0, 1 add; wave 1 -> LDS, wave 0 adds and stores (fixed order)
-  float *mine = lds + (size_t)(wave & 1) * NP * 1024;
-  if (wave >= 2) {
-#pragma unroll
-    for (int q = 0; q < NP; q++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) mine[(q * 16 + r) * 64 + lane] = acc[q][r];
-  }
-  __syncthreads();
-  if (wave < 2) {
-#pragma unroll
-    for (int q = 0; q < NP; q++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[q][r] += mine[(q * 16 + r) * 64 + lane];
-  }
-  __syncthreads();
-  if (wave == 1) {
-#pragma unroll
-    for (int q = 0; q < NP; q++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) lds[(q * 16 + r) * 64 + lane] = acc[q][r];
-  }
-  __syncthreads();
-  if (wave == 0) {
-    float *out = partial + (size_t)(p.slab0 + slab) * 6 * 1024;
-#pragma unroll
-    for (int q = 0; q < NP; q++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) out[(q * 16 + r) * 64 + lane] = acc[q][r] + lds[(q * 16 + r) * 64 + lane];
-  }
-}
-
-__global__ __launch_bounds__(256) void ng_l_partial_kernel(const PairDesc *pairs, int npairs, float *partial) {
-  extern __shared__ float lds[];
-  int pi = 0;
-  {  // block -> (pair, slab): the pairs' slab ranges are consecutive
-    int lo = 0, hi = npairs - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (pairs[mid].slab0 <= (int)blockIdx.x) lo = mid;
-      else hi = mid - 1;
-    }
-    pi = lo;
-  }
-  const PairDesc &p = pairs[pi];
-  const int slab = blockIdx.x - p.slab0;
-  if (p.nt == 1) l_partial_body<1>(p, slab, partial, lds);
-  else if (p.nt == 2) l_partial_body<2>(p, slab, partial, lds);
-  else l_partial_body<3>(p, slab, partial, lds);
-}
-
-// one block (1024 threads: an accumulator image per pass) per (component, side): L from the slab partials (slabs added in order), then
-//   tr0 = sum ||X||^2 partials + ones_term,  tr1 = tr0 - 2 tr(L) + <L, W W^T>,  scale = sqrt(tr0 / tr1)
-__global__ __launch_bounds__(1024) void ng_l_finish_kernel(const PairDesc *pairs, const float *partial) {
-  __shared__ double red[3][16];
-  const PairDesc &p = pairs[blockIdx.x];
-  const int t = threadIdx.x, Rp = p.Rp, nt = p.nt;
-  double a = 0, b = 0, c = 0;
-  for (int i = t; i < p.npart; i += 1024) a += p.part[i];
-  int q = 0;
-  for (int ti = 0; ti < nt; ti++)
-    for (int tj = ti; tj < nt; tj++, q++) {
-      const int e = t, r = e >> 6, lane = e & 63;
-      const int m = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), n = tj * 32 + (lane & 31);
-      if (m >= Rp || n >= Rp) continue;
-      const float *src = partial + (size_t)p.slab0 * 6 * 1024 + (size_t)q * 1024 + e;
-      float v = 0.f;
-      int s = 0;
-      for (; s + 7 < p.nslab; s += 8) {
-        float w[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) w[u] = src[(size_t)(s + u) * 6144];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v += w[u];
-      }
-      for (; s < p.nslab; s++) v += src[(size_t)s * 6144];
-      p.Ld[m * Rp + n] = v;
-      const double w = (double)v * (double)p.WWT[m * Rp + n];
-      if (ti != tj) {
-        p.Ld[n * Rp + m] = v;
-        c += 2.0 * w;
-      } else {
-        c += w;
-        if (m == n) b += v;
-      }
-    }
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-    c += __shfl_xor(c, o, 64);
-  }
-  if ((t & 63) == 0) {
-    red[0][t >> 6] = a;
-    red[1][t >> 6] = b;
-    red[2][t >> 6] = c;
-  }
-  __syncthreads();
-  if (t == 0) {
-    double tr0 = p.ones_term, trL = 0, trLW = 0;
-    for (int w = 0; w < 16; w++) {
-      tr0 += red[0][w];
-      trL += red[1][w];
-      trLW += red[2][w];
-    }
-    const double tr1 = tr0 - 2.0 * trL + trLW;
-    p.scal[0] = tr0;
-    p.scal[1] = tr1;
-    *p.scale_f = (tr0 <= 0.0 || !(tr1 > 0.0)) ? 1.0f : (float)sqrt(tr0 / tr1);
-  }
-}
-
-// refresh: K, L and tr(XX^T) of every pair to the pinned buffers the pool threads read
-__global__ __launch_bounds__(256) void ng_stage_kernel(const PairDesc *pairs) {
-  const PairDesc &p = pairs[blockIdx.x];
-  const int n = p.Rp * p.Rp;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    p.hK[i] = p.Kd[i];
-    p.hL[i] = p.Ld[i];
-  }
-  if (threadIdx.x == 0) *p.h_tr0 = p.scal[0];
-}
-
-// ------------------------------------------------------------------------------------------------ per-component stages
-struct CompDesc {
-  float *T;
-  const float *bsum, *sa, *sb;
-  float *W_acc, *bias_acc;
-  int Do, ldT, ldw, Dx;
-  int blk0;  // first block of this component in the commit launch
-};
-__device__ __forceinline__ int find_comp(const CompDesc *c, int n, int blk) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (c[mid].blk0 <= blk) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-// T[o][ldw] = bsum[o], zeros in the row padding (one block per component)
-__global__ __launch_bounds__(256) void ng_set_columns_kernel(const CompDesc *comps) {
-  const CompDesc &c = comps[blockIdx.x];
-  if (!c.bsum && c.ldT == c.ldw) return;
-  for (int o = threadIdx.x; o < c.Do; o += 256) {
-    float *row = c.T + (size_t)o * c.ldT;
-    int col = c.ldw;
-    if (c.bsum) row[col++] = c.bsum[o];
-    for (; col < c.ldT; col++) row[col] = 0.f;
-  }
-}
-// W_acc[o][c] += a b T[o][c] (c < ldw), bias_acc[o] += a b T[o][ldw]: "local_lrate = scale * learning_rate_"
-// (nnet-tdnn-component.cc:604-624); a, b: the two preconditioners' scales, on the device.  1024 elements per block.
-__global__ __launch_bounds__(256) void ng_commit_group_kernel(const CompDesc *comps, int ncomps) {
-  const int ci = find_comp(comps, ncomps, blockIdx.x);
-  const CompDesc &c = comps[ci];
-  const float sc = c.sa[0] * c.sb[0];
-  const int C = c.Dx;
-  const long long total = (long long)c.Do * C, e0 = (long long)(blockIdx.x - c.blk0) * 1024;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const long long e = e0 + j * 256 + threadIdx.x;
-    if (e >= total) break;
-    const int o = (int)(e / C), col = (int)(e % C);
-    const float v = sc * c.T[(size_t)o * c.ldT + col];
-    if (col < c.ldw) c.W_acc[(size_t)o * c.ldw + col] += v;
-    else c.bias_acc[o] += v;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ grouped finalize
-struct FinDesc {  // one refreshed object
-  float *J, *W, *W1, *WT, *wlast;
-  const float *h_coeff;  // pinned
-  int Rp, D, Dp;
-  int blk0;
-};
-__device__ __forceinline__ int find_fin(const FinDesc *c, int n, int blk) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (c[mid].blk0 <= blk) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-// J[r][d] += coeff[r] W[r][d]   (B_t = J_t + (1 - eta) / (eta / N) (D_t + rho_t I) W_t)
-__global__ __launch_bounds__(256) void ng_fin_adddiag_kernel(const FinDesc *f, int nf) {
-  const FinDesc &p = f[find_fin(f, nf, blockIdx.x)];
-  const long long total = (long long)p.Rp * p.Dp, e0 = (long long)(blockIdx.x - p.blk0) * 1024;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const long long e = e0 + j * 256 + threadIdx.x;
-    if (e >= total) break;
-    p.J[e] += p.h_coeff[e / p.Dp] * p.W[e];
-  }
-}
-// W = W1, W^T, last column
-__global__ __launch_bounds__(256) void ng_fin_derive_kernel(const FinDesc *f, int nf) {
-  const FinDesc &p = f[find_fin(f, nf, blockIdx.x)];
-  const long long total = (long long)p.Rp * p.Dp, e0 = (long long)(blockIdx.x - p.blk0) * 1024;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const long long e = e0 + j * 256 + threadIdx.x;
-    if (e >= total) break;
-    const int r = (int)(e / p.Dp), d = (int)(e % p.Dp);
-    const float v = p.W1[e];
-    p.W[e] = v;
-    if (d < p.D) {
-      p.WT[(size_t)d * p.Rp + r] = v;
-      if (d == p.D - 1) p.wlast[r] = v;
-    }
-  }
-}
-
-
-}  // namespace
 
 struct NgGroup {
   std::vector<NgGroupComp> comps;
@@ -382,11 +113,10 @@ int ng_group_create(const std::vector<NgGroupComp> &comps, NgGroup **out) {
   // Q and P live behind the tables; the projection stages (ng.h: T <- (I - Wy^T Wy) T (I - Wx^T Wx))
   // are built once their addresses are known
   size_t bytes = 0;
-  auto room = [&](size_t b) { bytes = ((bytes + 255) & ~(size_t)255) + b; };
-  room(sizeof(PairDesc) * pairs.size());
-  room(sizeof(CompDesc) * cdesc.size());
-  room(sizeof(float) * (size_t)slab_total * 6 * 1024);
-  room(sizeof(float) * qp_floats);
+  bytes = carve_room(bytes, sizeof(PairDesc) * pairs.size());
+  bytes = carve_room(bytes, sizeof(CompDesc) * cdesc.size());
+  bytes = carve_room(bytes, sizeof(float) * (size_t)slab_total * kLSlabFloats);
+  bytes = carve_room(bytes, sizeof(float) * qp_floats);
   // (task lists are sized after a dry build with null Q / P: their counts do not depend on the addresses)
   auto build = [&](float *qp) {
     for (auto &l : st) l = GemmList();
@@ -401,14 +131,9 @@ int ng_group_create(const std::vector<NgGroupComp> &comps, NgGroup **out) {
     }
   };
   build(nullptr);
-  size_t max_slots = kst.slots;
-  for (auto &l : st) max_slots = std::max(max_slots, l.slots);
-  for (auto *l : {&st[0], &st[1], &st[2], &st[3], &kst}) {
-    room(sizeof(GTask) * l->tasks.size());
-    room(sizeof(RTask) * l->rtasks.size());
-  }
-  room(sizeof(float) * max_slots * GT * GT);
-  bytes += 1024;
+  GemmList *lists[5] = {&st[0], &st[1], &st[2], &st[3], &kst};
+  DevList *dls[5] = {&g->stage[0], &g->stage[1], &g->stage[2], &g->stage[3], &g->kstage};
+  bytes = devlists_room(bytes, lists, 5) + 1024;  // (the stages run one after the other: one partial buffer)
   if (hipMalloc((void **)&g->dev, bytes) != hipSuccess) {
     set_error("ng_group_create: cannot allocate %zu bytes", bytes);
     delete g;
@@ -417,27 +142,15 @@ int ng_group_create(const std::vector<NgGroupComp> &comps, NgGroup **out) {
   char *cur = g->dev;
   g->pairs = carve<PairDesc>(cur, pairs.size());
   g->cdesc = carve<CompDesc>(cur, cdesc.size());
-  g->lpart = carve<float>(cur, (size_t)slab_total * 6 * 1024);
+  g->lpart = carve<float>(cur, (size_t)slab_total * kLSlabFloats);
   float *qp = carve<float>(cur, qp_floats);
   build(qp);
-  GemmList *lists[5] = {&st[0], &st[1], &st[2], &st[3], &kst};
-  DevList *dls[5] = {&g->stage[0], &g->stage[1], &g->stage[2], &g->stage[3], &g->kstage};
-  for (int i = 0; i < 5; i++) {
-    dls[i]->nt = (int)lists[i]->tasks.size();
-    dls[i]->nr = (int)lists[i]->rtasks.size();
-    dls[i]->tasks = carve<GTask>(cur, lists[i]->tasks.size());
-    dls[i]->rtasks = carve<RTask>(cur, lists[i]->rtasks.size());
-  }
-  float *part = carve<float>(cur, max_slots * GT * GT);  // the stages run one after the other: one partial buffer
-  for (int i = 0; i < 5; i++) {
-    lists[i]->fixup(part);
-    if (dls[i]->nt) TDNNF_HIP(hipMemcpy(dls[i]->tasks, lists[i]->tasks.data(), sizeof(GTask) * dls[i]->nt, hipMemcpyHostToDevice));
-    if (dls[i]->nr) TDNNF_HIP(hipMemcpy(dls[i]->rtasks, lists[i]->rtasks.data(), sizeof(RTask) * dls[i]->nr, hipMemcpyHostToDevice));
-  }
+  int rc = devlists_upload(cur, lists, dls, 5);
+  if (rc) return rc;
   TDNNF_HIP(hipMemcpy(g->pairs, pairs.data(), sizeof(PairDesc) * pairs.size(), hipMemcpyHostToDevice));
   TDNNF_HIP(hipMemcpy(g->cdesc, cdesc.data(), sizeof(CompDesc) * cdesc.size(), hipMemcpyHostToDevice));
   TDNNF_HIP(hipEventCreateWithFlags(&g->ev_staged, hipEventDisableTiming | hipEventBlockingSync));
-  g->l_lds = sizeof(float) * 2 * 6 * 1024;
+  g->l_lds = sizeof(float) * 2 * kLSlabFloats;  // two accumulator images (l_partial_body)
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute((const void *)ng_l_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->l_lds);
@@ -479,13 +192,7 @@ int ng_group_run(NgGroup *g, hipStream_t s) {
   hipLaunchKernelGGL(ng_commit_group_kernel, dim3(g->commit_blocks), dim3(256), 0, s, g->cdesc, nc);
   TDNNF_LAUNCH_CHECK();
   for (tdnnf_ng *ng : g->objs) {
-    if (upd) {
-      ng->job_N = ng->cur_N;
-      ng->job_done = 0;
-      ng->pending = 1;
-      ng->ev_wait = g->ev_staged;
-      ng_pool_push(ng);
-    }
+    if (upd) ng_refresh_submit(ng, ng->cur_N, g->ev_staged);
     ng->cur_N = 0;
     ng->t += 1;
   }
@@ -527,15 +234,9 @@ int ng_fin_create(const std::vector<tdnnf_ng *> &objs_in, NgFin **out) {
     *out = f;
     return TDNNF_OK;
   }
-  size_t bytes = 0;
-  auto room = [&](size_t b) { bytes = ((bytes + 255) & ~(size_t)255) + b; };
-  room(sizeof(FinDesc) * fd.size());
-  room(sizeof(GTask) * w1.tasks.size());
-  room(sizeof(RTask) * w1.rtasks.size());
-  room(sizeof(GTask) * wwt.tasks.size());
-  room(sizeof(RTask) * wwt.rtasks.size());
-  room(sizeof(float) * std::max(w1.slots, wwt.slots) * GT * GT);
-  bytes += 1024;
+  GemmList *lists[2] = {&w1, &wwt};
+  DevList *dls[2] = {&f->w1, &f->wwt};
+  const size_t bytes = devlists_room(carve_room(0, sizeof(FinDesc) * fd.size()), lists, 2) + 1024;
   if (hipMalloc((void **)&f->dev, bytes) != hipSuccess) {
     set_error("ng_fin_create: cannot allocate %zu bytes", bytes);
     delete f;
@@ -543,20 +244,9 @@ int ng_fin_create(const std::vector<tdnnf_ng *> &objs_in, NgFin **out) {
   }
   char *cur = f->dev;
   f->fd = carve<FinDesc>(cur, fd.size());
-  f->w1.nt = (int)w1.tasks.size(); f->w1.nr = (int)w1.rtasks.size();
-  f->wwt.nt = (int)wwt.tasks.size(); f->wwt.nr = (int)wwt.rtasks.size();
-  f->w1.tasks = carve<GTask>(cur, w1.tasks.size());
-  f->w1.rtasks = carve<RTask>(cur, w1.rtasks.size());
-  f->wwt.tasks = carve<GTask>(cur, wwt.tasks.size());
-  f->wwt.rtasks = carve<RTask>(cur, wwt.rtasks.size());
-  float *part = carve<float>(cur, std::max(w1.slots, wwt.slots) * GT * GT);
-  w1.fixup(part);
-  wwt.fixup(part);
+  int rc = devlists_upload(cur, lists, dls, 2);
+  if (rc) return rc;
   TDNNF_HIP(hipMemcpy(f->fd, fd.data(), sizeof(FinDesc) * fd.size(), hipMemcpyHostToDevice));
-  if (f->w1.nt) TDNNF_HIP(hipMemcpy(f->w1.tasks, w1.tasks.data(), sizeof(GTask) * f->w1.nt, hipMemcpyHostToDevice));
-  if (f->w1.nr) TDNNF_HIP(hipMemcpy(f->w1.rtasks, w1.rtasks.data(), sizeof(RTask) * f->w1.nr, hipMemcpyHostToDevice));
-  if (f->wwt.nt) TDNNF_HIP(hipMemcpy(f->wwt.tasks, wwt.tasks.data(), sizeof(GTask) * f->wwt.nt, hipMemcpyHostToDevice));
-  if (f->wwt.nr) TDNNF_HIP(hipMemcpy(f->wwt.rtasks, wwt.rtasks.data(), sizeof(RTask) * f->wwt.nr, hipMemcpyHostToDevice));
   *out = f;
   return TDNNF_OK;
 }
@@ -597,11 +287,7 @@ int ng_fin_run(NgFin *f, hipStream_t s, bool wait, int *did) {
   rc = launch_list(f->wwt, s);
   if (rc) return rc;
   TDNNF_LAUNCH_CHECK();
-  for (tdnnf_ng *ng : f->objs) {
-    ng->pending = 0;
-    ng->d = ng->d_next;
-    ng->rho = ng->rho_next;
-  }
+  for (tdnnf_ng *ng : f->objs) ng_refresh_installed(ng);
   return TDNNF_OK;
 }
 

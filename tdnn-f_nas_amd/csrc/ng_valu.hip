@@ -1,7 +1,7 @@
 // ng_valu.hip -- the N-sized statistics pass of OnlineNaturalGradient, H = X~ W^T (rank R = 20 .. 80), on the VECTOR ALUs.
 //
 // Call sites of the reference: PreconditionDirections at /root/reference/src/nnet3/nnet-tdnn-component.cc:598-599 and
-// nnet-simple-component.cc:3001-3002 (UPSTREAM natural-gradient-online.cc forms X W^T first of all); ng.hip restates the algorithm.
+// nnet-simple-component.cc:3001-3002 (UPSTREAM natural-gradient-online.cc forms X W^T first of all); ng_stats.hip restates the algorithm.
 //
 // Why not the matrix cores.  On gfx950 the f32 MFMA (v_mfma_f32_32x32x2_f32) and the f32 VALU (v_fma_f32, 2 cycles per wave64) have the SAME peak,
 // 64 FLOP / clock / SIMD, and they are separate pipes: a vector-only wave and a matrix-only wave of one SIMD run side by side.  Every GEMM of

@@ -181,6 +181,52 @@ def _affine_update_ng_case(hip, ora, pkg, bias, layout=None):
     L.oracle_ng_destroy(ngo_ref)
 
 
+def _one_direction_rows(rng, N, D, direction, noise):
+    """N rows that all point along `direction`, plus a little noise: data of essentially rank one"""
+    return (np.outer(_rand(rng, N), direction) + noise * _rand(rng, N, D)).astype(F)
+
+
+# (seed 5: the oracle sets must_reorthogonalize on calls 0, 2, 3 and 4, on both sides.  Call 0 -- W_0's self-training on the first
+# minibatch -- fails the unit check, Cholesky's inverse exceeds 100 and the rows go through Gram-Schmidt; from call 2 on the doubling
+# of the data's scale keeps max(c) above 1e6 min(c), whose floor follows the previous call's max(c), and the unit check passes)
+ILL_SEED, ILL_NOISE, ILL_CALLS, ILL_GROWTH = 5, 1e-4, 5, 2.0
+
+
+def test_precondition_on_ill_conditioned_input(hip, ora, pkg):
+    """Input with one direction where the preconditioners' ranks (12 and 8) ask for many: Z_t's largest eigenvalue exceeds 1e6 times
+    its smallest, or eigenvalues fall below their floor, so the reference sets must_reorthogonalize (natural-gradient-online.cc,
+    PreconditionDirectionsInternal) and the refresh goes through ReorthogonalizeRt1 on both sides.  Same comparison and bound as
+    _affine_update_ng_case."""
+    L = ora.lib()
+    rng = np.random.default_rng(ILL_SEED)
+    N, Di, Do = 128, 24, 16
+    rin, rout = (Di + 1) // 2, (Do + 1) // 2
+    ngi_ref, ngo_ref = L.oracle_ng_create(rin, 4, 2000.0, 4.0), L.oracle_ng_create(rout, 4, 2000.0, 4.0)
+    ngi, ngo = C.c_void_p(), C.c_void_p()
+    hip.ng_create(rin, 4, 2000.0, 4.0, C.byref(ngi))
+    hip.ng_create(rout, 4, 2000.0, 4.0, C.byref(ngo))
+    nb = hip.lib.tdnnf_affine_update_natural_gradient_workspace_bytes(Do, Di, N, 0)
+    ws = hip.ws(nb)
+    ro = np.zeros(1, np.int32)
+    dir_x, dir_y = _rand(rng, Di), _rand(rng, Do)
+    for it in range(ILL_CALLS):
+        x = (ILL_GROWTH ** it * _one_direction_rows(rng, N, Di, dir_x, ILL_NOISE)).astype(F)
+        dy = (ILL_GROWTH ** it * _one_direction_rows(rng, N, Do, dir_y, ILL_NOISE)).astype(F)
+        W0 = _rand(rng, Do, Di) * 0.1
+        W_ref = W0.copy()
+        _oracle_update_ng(L, ora, x, dy, None, 1, ro, 1, Di, Do, None, None, 0, 0, 1.0, ngi_ref, ngo_ref, 0.02, W_ref, None, None)
+        Wacc = dev(W0)
+        hip.affine_update_natural_gradient(placed(x)[0], placed(dy)[0], ngi, ngo, 0.02, hip.vec(Wacc), Di, None, hip.vec(ws), nb, hip.stream())
+        err = rel_l2(host(Wacc) - W0, W_ref - W0)
+        print("ill-conditioned call %d: rel_l2 %.3e" % (it, err))
+        assert np.linalg.norm(W_ref - W0) > 0
+        assert err < 5e-3, (it, err)
+    hip.lib.tdnnf_ng_destroy(ngi)
+    hip.lib.tdnnf_ng_destroy(ngo)
+    L.oracle_ng_destroy(ngi_ref)
+    L.oracle_ng_destroy(ngo_ref)
+
+
 def test_onehot_backprop(hip, ora, pkg):
     """OnehotFunctionComponent::Backprop nnet-simple-component.cc:9539-9548: output_ += lr * colsum(out_deriv)."""
     rng = np.random.default_rng(3)
