@@ -40,7 +40,7 @@ inline bool vec4_ok(const MatView &m) {
     if (e__ != hipSuccess) return ::tdnnf::hip_status(e__, #expr); \
   } while (0)
 
-#define TDNNF_LAUNCH_CHECK(name) TDNNF_HIP(hipGetLastError())
+#define TDNNF_LAUNCH_CHECK() TDNNF_HIP(hipGetLastError())
 
 // Tuning options (tdnnf_set_option / tdnnf_get_option, include/tdnnf_hip.h): process-wide integers that select between code paths;
 // the library reads no environment variable for them.  What is tested: the GEMM planners' options (gemm_ring, splitk_partial_round,
@@ -99,6 +99,19 @@ inline int grid_for(long long work, int block, int cap = 2048) {
   if (g < 1) g = 1;
   return (int)g;
 }
+#ifdef __HIPCC__
+template <class T>
+struct as_given { typedef T type; };
+// A grid-stride map over a rows x cols matrix, 256 threads a block: `k4` with a float4 per thread where the caller's predicate `vec`
+// holds (every view and column vector it touches allows 16-byte accesses), else `k1` with a float per thread.
+template <class... P>
+__attribute__((visibility("hidden"))) inline hipError_t launch_vec_or_scalar(bool vec, int rows, int cols, void (*k4)(P...), void (*k1)(P...), hipStream_t s, typename as_given<P>::type... args) {
+  const long long work = (long long)rows * (vec ? cols / 4 : cols);
+  void (*k)(P...) = vec ? k4 : k1;
+  hipLaunchKernelGGL(k, dim3(grid_for(work, 256)), dim3(256), 0, s, args...);
+  return hipGetLastError();
+}
+#endif
 
 // Reproducible stand-in for the reference's RandInt()/RandUniform() control decisions (orthonormal
 // schedule nnet-utils.cc:1062, ReLU stats / self-repair coin flips nnet-simple-component.cc:1017,1084):
@@ -110,119 +123,9 @@ inline unsigned long long tdnnf_decision(unsigned long long step, unsigned long 
   return (z ^ (z >> 31)) >> 8;
 }
 
-// Second stage of the column reductions: a 256-thread block owns 8 columns, its 32 lanes per column walk the partial rows
-// four requests deep, then lane 0 adds the lanes' sums in a fixed order (deterministic).  The partial rows are few MB at most,
-// the stage is pure latency: with 4 lanes x 24 blocks it took 45-300 us per call, ~5 ms per training step.  Rounds 2-4 ran it as
-// 1024-thread blocks of 32 columns: beside another stream's kernels such a block waits until one CU has sixteen free wave slots at once
-// (the BatchNorm finalize of the xent head beside the denominator and the statistics passes: 9 us alone, 234 us on average, 4.3 ms
-// at worst in the round-5 trace); four-wave blocks fit wherever anything fits, and there are four times as many of them.
-constexpr int kFinCols = 8, kFinLanes = 32, kFinThreads = kFinCols * kFinLanes;
-inline unsigned finalize_grid(int D) { return (unsigned)((D + kFinCols - 1) / kFinCols); }
-#ifdef __HIPCC__
-// q[k] = sum over c < chunks of partial[((long long)k * qstride_rows + c) * D + d] for the calling thread's column d;
-// valid afterwards in the threads with (threadIdx.x >> 5) == 0.  red: NQ * kFinLanes * (kFinCols + 1) elements of Acc.
-template <int NQ, class Acc>
-__device__ __forceinline__ void finalize_sums(const float *partial, int chunks, long long qstride_rows, int D, int nq, Acc (&q)[NQ], Acc *red) {
-  const int tc = threadIdx.x & (kFinCols - 1), lane = threadIdx.x / kFinCols, d = blockIdx.x * kFinCols + tc;
-#pragma unroll
-  for (int k = 0; k < NQ; k++) q[k] = 0;
-  if (d < D) {
-    // (the NQ quantities side by side: their loads of a round are issued together -- one after the other, five quantities took 15 us
-    // where two took 5)
-    const float *p = partial + d;
-    const long long qs = qstride_rows * D;
-    int c = lane;
-    for (; c + 3 * kFinLanes < chunks; c += 4 * kFinLanes) {
-      float v[NQ][4];
-#pragma unroll
-      for (int k = 0; k < NQ; k++) {
-        if (k < nq) {
-          const float *pk = p + (long long)k * qs;
-          v[k][0] = pk[(long long)c * D]; v[k][1] = pk[(long long)(c + kFinLanes) * D];
-          v[k][2] = pk[(long long)(c + 2 * kFinLanes) * D]; v[k][3] = pk[(long long)(c + 3 * kFinLanes) * D];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < NQ; k++) {
-        if (k < nq) { q[k] += v[k][0]; q[k] += v[k][1]; q[k] += v[k][2]; q[k] += v[k][3]; }
-      }
-    }
-    for (; c < chunks; c += kFinLanes) {
-      float v[NQ];
-#pragma unroll
-      for (int k = 0; k < NQ; k++)
-        if (k < nq) v[k] = p[(long long)k * qs + (long long)c * D];
-#pragma unroll
-      for (int k = 0; k < NQ; k++)
-        if (k < nq) q[k] += v[k];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NQ; k++) red[(k * kFinLanes + lane) * (kFinCols + 1) + tc] = q[k];
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NQ; k++) {
-      Acc s = 0;
-      for (int l = 0; l < kFinLanes; l++) s += red[(k * kFinLanes + l) * (kFinCols + 1) + tc];
-      q[k] = s;
-    }
-  }
-}
-#endif
-
-// Synchronised BatchNorm (data-parallel training): while one of these is installed, every train-mode BatchNorm of the calling thread
-// all-reduces its column sums over the ranks -- forward [sum x, sum x^2], backward [sum z dz, sum dz, sum dz^2] (2 D / 3 D doubles
-// in `buf`) -- through the caller's collective `fn(ctx, buf, count, stream)` before it forms mean / scale and the backward terms
-// with the GLOBAL row count, so that a sharded minibatch normalises exactly as the whole one does
-// (/root/reference/src/nnet3/nnet-normalize-component.cc:433-445 takes its statistics over all rows of the minibatch).
-struct BnSync {
-  int (*fn)(void *ctx, double *buf, long long count, tdnnf_stream stream);
-  void *ctx;
-  double *buf;      // device, >= 5 * max D doubles (the fused BatchNorm / ReLU backward stages five column sums, three are reduced)
-  int world;
-};
-BnSync *bn_sync_current();
-struct BnSyncScope {
-  BnSync *prev;
-  explicit BnSyncScope(BnSync *b);
-  ~BnSyncScope();
-};
-
-// While one of these is installed, the BatchNorm finalize launches of the calling thread -- the forward statistics (memo rows 0-2) and the
-// backward terms of the fused BatchNorm / ReLU sweep -- also write, per block of kFinCols columns, an UPPER BOUND of the squared Frobenius
-// norm of what the pass behind them produces (forward: z = (x - mean) scale, whose column sums of squares are N scale^2 var exactly;
-// backward: the ReLU's input derivative, bounded by the column sums of squares of its output derivative, which the finalize forms
-// anyway, plus the self-repair term).  planes_split takes its scale from such a bound instead of a pass over the matrix.
-// buf: >= finalize_grid(D) doubles; *blocks receives how many were written (0: none -- test-mode BatchNorm has no such bound).
-struct FroBoundScope {
-  double *prev_buf;
-  int *prev_blocks;
-  FroBoundScope(double *buf, int *blocks);
-  ~FroBoundScope();
-};
-double *fro_bound_buf();
-int *fro_bound_blocks();
-
-// two-stage deterministic column reduction (colreduce.hip)
-struct ColReducePlan {
-  int chunks, rows_per_chunk;
-};
-ColReducePlan colreduce_plan(int rows, int cols);
-size_t colreduce_bytes(int rows, int cols);
-// partial[q][chunk][col] for q < nq; kind: 0 = (sum a), 1 = (sum a, sum a*a), 2 = (sum a*b, sum b), 3 = (sum a, sum a>0)
-hipError_t colreduce_partial(int kind, MatView a, MatView b, float *partial, hipStream_t s);
-// the same with the chunking given: partial[c * cols + col] and, second quantity, partial[(sq_row_offset + c) * cols + col], c < chunks
-hipError_t colreduce_partial_into(int kind, MatView a, MatView b, int chunks, int rows_per_chunk, int sq_row_offset, float *partial, hipStream_t s);
-// BatchNorm forward: memo rows 0-2 from column partial sums / sums of squares laid out as above with sq_row_offset == chunks
-// store_stats (optional): BatchNormComponent::StoreStats ([count, sum[D], sumsq[D]] doubles += this minibatch) in the same launch
-hipError_t batchnorm_stats_from_partials(const float *partial, int chunks, int rows, int cols, float epsilon, float target_rms, float *memo, hipStream_t s,
-                                         double *store_stats = nullptr);
-hipError_t batchnorm_stats(MatView a, float epsilon, float target_rms, float *memo, void *ws, hipStream_t s, double *store_stats = nullptr);
-hipError_t colsum_add(MatView a, float scale, float *acc, void *ws, hipStream_t s);  // ws: colreduce_bytes(rows, cols)
-
+// LogSoftmax forward that also leaves aux = aux_scale * softmax(in) (log_softmax.hip); false, nothing launched: not a shape of the one-pass kernel
+bool log_softmax_propagate_with_aux(const tdnnf_mat *in, tdnnf_mat *out, tdnnf_mat *aux, float aux_scale, hipStream_t s);
 // the three separately launchable parts of the chain objective (chain_den.hip, chain_num.hip)
-bool log_softmax_propagate_with_aux(const tdnnf_mat *in, tdnnf_mat *out, tdnnf_mat *aux, float aux_scale, hipStream_t s);  // elementwise.hip
 float chain_supervision_weight(const tdnnf_supervision *sp);
 // beside_other_work: the caller runs other kernels next to the denominator (the trainer: the xent head), so the persistent form keeps
 // its one-kernel backward pass instead of running the two recursions side by side on a further stream

@@ -51,7 +51,7 @@ hipError_t bn_relu_bwd(MatView x, MatView dz, float *memo, float target_rms, boo
                        // oderiv_sumsq[D]] doubles to add this minibatch's count and column sums of squares of the ReLU's
                        // out_deriv to; null = not this minibatch
                        double *oderiv_stats = nullptr,
-                       // d_aff also as two scaled f16 planes (planes_gemm.h), written by the apply pass; needs a FroBoundScope (common.h) around the call
+                       // d_aff also as two scaled f16 planes (planes_gemm.h), written by the apply pass; needs a FroBoundScope (batchnorm.h) around the call
                        const BwdPlanes *planes = nullptr);
 
 }  // namespace tdnnf

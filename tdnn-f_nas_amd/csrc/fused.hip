@@ -13,27 +13,15 @@
 // deterministic.
 #include <algorithm>
 
-#include "common.h"
+#include "batchnorm.h"
 #include "device.h"
+#include "ew_dev.h"
 #include "fused.h"
 #include "gemm_f32.h"
 #include "planes_gemm.h"
 
 namespace tdnnf {
 namespace {
-
-__device__ __forceinline__ void ld(const float *p, float (&v)[4], bool vec) {
-  if (vec) {
-    const float4 t = *reinterpret_cast<const float4 *>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-__device__ __forceinline__ void st(float *p, const float (&v)[4], bool vec) {
-  if (vec) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else p[0] = v[0];
-}
 
 // four consecutive columns c .. c + 3 (c % 4 == 0) of row `ra` of a matrix as two f16 planes of v * s in the P16 layout (planes_gemm.h):
 // K block c / 16, k = c % 16 of the row's 32-byte record, halves swapped when bit 3 of the row is set; `R` rows per chunk
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(MatView x, MatV
 // squares of the ReLU's out_deriv dr = (dz + temp) scale + z vdm.  They need no pass of their own:
 //   sum_r dr^2 = scale^2 (sum dz^2 - (sum dz)^2 / N) + 2 vdm scale sum z dz + vdm^2 sum z^2,   sum z^2 = N var scale^2
 // (train mode: sum z = 0; test mode: temp = vdm = 0) from the quantities this reduction already forms, plus sum dz^2.
-// Synchronised BatchNorm (common.h BnSync): sums_out != null -- only the five column sums, doubles [5][D]; sums_in != null -- the sums
+// Synchronised BatchNorm (batchnorm.h BnSync): sums_out != null -- only the five column sums, doubles [5][D]; sums_in != null -- the sums
 // come from there (the first three all-reduced over the ranks), N is the GLOBAL row count and N_local this rank's (ReLU statistics).
 __global__ __launch_bounds__(kFinThreads) void bn_relu_bwd_finalize_kernel(const float *partial, int chunks, int D, int N, float target_rms,
                                                                            float *memo, double *relu_stats, int test_mode, double *oderiv,
@@ -467,14 +455,6 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_ng_kernel(MatView x, Ma
   else bn_relu_bwd_apply_ng_body<NT, MASK, false, PLANES>(x, dz, memo, D, repair_stats, self_repair_scale, d_aff, partial, mask, B, ng, pk, pk_lead, blk);
 }
 
-__global__ __launch_bounds__(kFinThreads) void colsum_add_kernel(const float *partial, int chunks, int D, float scale, float *acc) {
-  __shared__ float red[kFinLanes * (kFinCols + 1)];
-  const int d = blockIdx.x * kFinCols + (threadIdx.x & (kFinCols - 1));
-  float q[1];
-  finalize_sums<1, float>(partial, chunks, chunks, D, 1, q, red);
-  if (threadIdx.x < kFinCols && d < D) acc[d] += scale * q[0];
-}
-
 }  // namespace
 
 hipError_t bn_apply_bypass(MatView x, const float *memo, int D, int period, MatView prev, float bypass, MatView out, hipStream_t s, const float *mask, int B,
@@ -541,20 +521,15 @@ hipError_t bn_relu_bwd(MatView x, MatView dz, float *memo, float target_rms, boo
   double *fro2 = fro_bound_buf();
   if (fro2 && fro_bound_blocks()) *fro_bound_blocks() = (int)finalize_grid(D);
   const float repair_abs = self_repair ? 2.0f * fabsf(self_repair_scale) : 0.f;  // |repair term| <= self_repair_scale / 0.5
-  if (BnSync *sy = bn_test_mode ? nullptr : bn_sync_current()) {
-    // [sum z dz, sum dz, sum dz^2] over all ranks' rows; the ReLU's value / derivative sums (rows 3, 4) stay this rank's
-    hipLaunchKernelGGL(bn_relu_bwd_finalize_kernel, dim3(finalize_grid(D)), dim3(kFinThreads), 0, s, partial, pl.chunks, D, x.rows, target_rms, memo,
-                       store_relu_stats ? relu_stats : (double *)nullptr, 0, (double *)nullptr, sy->buf, (const double *)nullptr, 0);
-    if (sy->fn(sy->ctx, sy->buf, 3LL * D, (tdnnf_stream)s)) return hipErrorUnknown;
-    hipLaunchKernelGGL(bn_relu_bwd_finalize_kernel, dim3(finalize_grid(D)), dim3(kFinThreads), 0, s, partial, pl.chunks, D, x.rows * sy->world, target_rms, memo,
-                       store_relu_stats ? relu_stats : (double *)nullptr, 0, oderiv_stats, (double *)nullptr, (const double *)sy->buf, x.rows, fro2, repair_abs);
-  } else {
-    hipLaunchKernelGGL(bn_relu_bwd_finalize_kernel, dim3(finalize_grid(D)), dim3(kFinThreads), 0, s, partial, pl.chunks, D, x.rows, target_rms, memo,
-                       store_relu_stats ? relu_stats : (double *)nullptr, bn_test_mode ? 1 : 0, oderiv_stats, (double *)nullptr, (const double *)nullptr, 0, fro2,
-                       repair_abs);
-  }
+  // with a BnSync (train mode only): [sum z dz, sum dz, sum dz^2] over all ranks' rows; the ReLU's value / derivative sums (rows 3, 4) and its
+  // count (N_local = x.rows) stay this rank's.  The launch that only stages the sums reads none of oderiv_stats, fro2, repair_abs.
+  hipError_t fe = bn_finalize_synced(bn_test_mode ? nullptr : bn_sync_current(), 3, D, x.rows, s, [&](double *sums_out, const double *sums_in, int N) {
+    hipLaunchKernelGGL(bn_relu_bwd_finalize_kernel, dim3(finalize_grid(D)), dim3(kFinThreads), 0, s, partial, pl.chunks, D, N, target_rms, memo,
+                       store_relu_stats ? relu_stats : (double *)nullptr, bn_test_mode ? 1 : 0, oderiv_stats, sums_out, sums_in, x.rows, fro2, repair_abs);
+  });
+  if (fe != hipSuccess) return fe;
   const double *rep = self_repair ? relu_stats : nullptr;
-  // planes of d_aff written by the apply pass itself: the scale record first, from the bound the finalize launch just left (common.h FroBoundScope)
+  // planes of d_aff written by the apply pass itself: the scale record first, from the bound the finalize launch just left (batchnorm.h FroBoundScope)
   PlanesSink pk{nullptr, 0, nullptr};
   int pk_lead = 0;
   if (planes && planes->P) {
@@ -577,14 +552,12 @@ hipError_t bn_relu_bwd(MatView x, MatView dz, float *memo, float target_rms, boo
     else if (ng->Rp <= 64) APPLY_NG(2);
     else APPLY_NG(3);
 #undef APPLY_NG
-    if (bias_acc) hipLaunchKernelGGL(colsum_add_kernel, dim3(finalize_grid(D)), dim3(kFinThreads), 0, s, bias_partial, blocks, D, bias_scale, bias_acc);
-    return hipGetLastError();
+    return bias_acc ? colsum_finalize(bias_partial, blocks, D, bias_scale, bias_acc, s) : hipGetLastError();
   }
   if (pk.P) hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<4, true>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, (options().reverse_passes >> 1) & 1);
   else if (vec) hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<4, false>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, (options().reverse_passes >> 1) & 1);
   else hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<1, false>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, (options().reverse_passes >> 1) & 1);
-  if (bias_acc) hipLaunchKernelGGL(colsum_add_kernel, dim3(finalize_grid(D)), dim3(kFinThreads), 0, s, bias_partial, pl.chunks, D, bias_scale, bias_acc);
-  return hipGetLastError();
+  return bias_acc ? colsum_finalize(bias_partial, pl.chunks, D, bias_scale, bias_acc, s) : hipGetLastError();
 }
 
 }  // namespace tdnnf

@@ -9,6 +9,7 @@
 
 #include <map>
 
+#include "batchnorm.h"
 #include "common.h"
 #include "planes_gemm.h"
 #include "tdnnf_hip.h"
@@ -91,7 +92,7 @@ struct tdnnf_net {
   std::vector<tdnnf::PlanesOperand> pw;  // by component
   std::vector<float *> pw_scale;         // their scale records
   void *planes_ws = nullptr;
-  double *fro_buf = nullptr;  // FroBoundScope target: per-block norm bounds a BatchNorm finalize launch leaves for the next split (common.h)
+  double *fro_buf = nullptr;  // FroBoundScope target: per-block norm bounds a BatchNorm finalize launch leaves for the next split (batchnorm.h)
   int B, T, Tout;
   // graph
   tdnnf::Grid g_lda, g_feat;

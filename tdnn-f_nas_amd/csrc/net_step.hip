@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "batchnorm.h"
 #include "common.h"
 #include "fused.h"
 #include "gemm_f32.h"

@@ -106,7 +106,7 @@ struct PlanesSplitArgs {
   // TdnnDARTSV3Component folded into its weight planes (|coef| <= 1: the unscaled norm stays a valid bound for the scale)
   const float *col_coef = nullptr;
   int col_coef_period = 0;
-  // np == 2, optional: the scale from an UPPER BOUND of the matrix's Frobenius norm instead of a pass over it (common.h FroBoundScope):
+  // np == 2, optional: the scale from an UPPER BOUND of the matrix's Frobenius norm instead of a pass over it (batchnorm.h FroBoundScope):
   //   ||X||_F <= fro_mul * sqrt(sum of fro2_bound[0 .. fro2_blocks)) + add_coef * add_rec[2]
   // (add_rec: the scale record [s, 1 / s, norm bound] of a matrix added into this one with coefficient add_coef: the bypass sum).
   const double *fro2_bound = nullptr;

@@ -97,7 +97,7 @@ int nccl_status(int rc, const char *what) {
   return TDNNF_EHIP;
 }
 
-// the BatchNorm hook (common.h BnSync::fn): ctx is the communicator
+// the BatchNorm hook (batchnorm.h BnSync::fn): ctx is the communicator
 int bn_allreduce(void *ctx, double *buf, long long count, tdnnf_stream stream) {
   return rccl().all_reduce(buf, buf, (size_t)count, kNcclDouble, kNcclSum, (Comm)ctx, (hipStream_t)stream) == 0 ? 0 : 1;
 }

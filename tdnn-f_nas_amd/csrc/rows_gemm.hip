@@ -4,6 +4,7 @@
 #include <cstring>
 #include <vector>
 
+#include "colreduce.h"
 #include "common.h"
 #include "device.h"
 #include "gemm_f32.h"

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "colreduce.h"
 #include "common.h"
 #include "device.h"
 #include "gemm_f32.h"

@@ -408,7 +408,9 @@ def test_sum_scaled_rounds_alike_on_the_vector_and_the_scalar_path(hip):
 # ------------------------------------------------------------------------------------------------------ log-softmax
 # (rows, cols): at most 2048 columns -> the one-pass kernel with 2 float4 per thread; 6034 -> 8 per thread; above 8192 -> one block
 # per row in three passes, which every misaligned view takes as well
-LSM_SHAPES = [(5, 8196), (17, 6034), (N, 261)]
+# The last three sit ON the boundaries of that choice: 2048 is the last width 2 float4 per thread hold (every lane full), 2052 the first that
+# needs 8 (sent to 2, its last float4 would be dropped), 8192 the last that 8 hold (8196 above is the first of the three-pass kernel).
+LSM_SHAPES = [(5, 8196), (17, 6034), (N, 261), (3, 2048), (3, 2052), (2, 8192)]
 
 
 def _run_log_softmax(hip, L, d):
@@ -424,7 +426,7 @@ def _run_log_softmax_backprop(hip, L, d):
     return {"in_deriv": host(dd)}
 
 
-@pytest.mark.parametrize("shape", LSM_SHAPES, ids=WIDS)
+@pytest.mark.parametrize("shape", LSM_SHAPES, ids=WIDS + ["nv2-last", "nv8-first", "nv8-last"])
 def test_log_softmax(hip, shape):
     rng = np.random.default_rng(shape[1])
     z = (_rand(rng, *shape) * 3).astype(F)
