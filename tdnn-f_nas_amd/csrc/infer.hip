@@ -1,6 +1,6 @@
 // infer.hip -- forward-only inference of a trained model over whole utterances (tdnnf_infer_*, include/tdnnf_hip.h "inference").
 //
-// nnet3's DecodableNnetSimple (UPSTREAM, not shipped) restated for the TDNN-F graphs of net.hip: utterances are cut into chunks of
+// nnet3's DecodableNnetSimple (UPSTREAM, not shipped) restated for the TDNN-F graphs of net_graph.hip: utterances are cut into chunks of
 // F input frames, a batch of up to max_chunks chunks runs the network once, and the output rows that lie inside their utterance
 // go straight to the caller's stacked output.  The schedule is the trainer's forward pass (net_step.hip) in test mode (cv_update) without the
 // separate elementwise passes: every BatchNorm -- and a TDNN-F layer's bypass -- is applied while the GEMM stores its tile
@@ -15,7 +15,7 @@
 #include "common.h"
 #include "fused.h"
 #include "gemm_f32.h"
-#include "net.h"
+#include "net_model.h"
 
 using namespace tdnnf;
 
@@ -113,19 +113,6 @@ struct tdnnf_infer {
 };
 
 namespace {
-
-struct Arena {
-  size_t off = 0;
-  char *base = nullptr;
-  template <class T>
-  T *take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-    off += sizeof(T) * n;
-    return p;
-  }
-  float *mat(long long rows, int cols) { return take<float>((size_t)rows * ldpad(cols)); }
-};
 
 void layout(tdnnf_infer *q, Arena &A) {
   const tdnnf_net_config &c = q->model->cfg;
@@ -253,11 +240,11 @@ int forward_batch(tdnnf_infer *q, const tdnnf_mat *feats, const tdnnf_mat *iv, c
   for (size_t l = 0; l < q->layers.size(); l++) {
     const TdnnfLayer &L = q->layers[l];
     const TdnnfLayer &ML = n->layers[l];  // component ids, taps
-    std::vector<int> lin_off = L.left > 0 ? std::vector<int>{-L.left, 0} : std::vector<int>{0};
-    std::vector<int> aff_off = L.right > 0 ? std::vector<int>{0, L.right} : std::vector<int>{0};
+    std::vector<int> lin_off, aff_off;
+    layer_taps(c, L, &lin_off, &aff_off);
     Tdnn lin, aff;
-    net_make_tdnn(&lin, ML.lin.comp, Hd, L.bn, lin_off, L.gin, L.glin, B);
-    net_make_tdnn(&aff, ML.aff.comp, L.bn, Hd, aff_off, L.glin, L.gout, B);
+    make_tdnn(&lin, ML.lin.comp, Hd, L.bn, lin_off, L.gin, L.glin, B);
+    make_tdnn(&aff, ML.aff.comp, L.bn, Hd, aff_off, L.glin, L.gout, B);
     tdnnf_mat in = M(q->act[cur], L.gin.n * B, Hd), lo = M(q->lin, lin.rows_out, L.bn);
     CK(tdnn_propagate_impl(&lin.ix, &in, W(lin.comp), lin.K * Hd, L.bn, Hd, nullptr, nullptr, 2, 0, &lo, s));
     tdnnf_mat aff_in = lo;
@@ -339,22 +326,19 @@ int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chu
     delete q;
     return rc;
   }
-  q->g_feat = Grid{q->g_lda.t0 - 1, 1, q->g_lda.n + 2};
+  q->g_feat = feat_grid(q->g_lda);
   // BatchNorm stages: tdnn1, the tdnnf layers, the chosen head's two (the model's statistics, by reference)
   memset(&q->bn, 0, sizeof(q->bn));
   const int Hd = c.hidden_dim, S = c.prefinal_small_dim;
   const long long bstride = 4LL * ldpad(std::max(Hd, S));
   q->nbn = 0;
-  auto add_bn = [&](const double *st, int D) {
-    q->bn.stats[q->nbn] = st;
-    q->bn.D[q->nbn] = D;
+  for (const StatBlock &b : stat_blocks(model)) {
+    if (b.relu || (b.head >= 0 && b.head != which_output)) continue;
+    q->bn.stats[q->nbn] = b.p();
+    q->bn.D[q->nbn] = b.D;
     q->bn.coef_off[q->nbn] = q->nbn * bstride;
     q->nbn++;
-  };
-  add_bn(model->t1_bn_stats, Hd);
-  for (auto &L : model->layers) add_bn(L.bn_stats, Hd);
-  add_bn(model->head[which_output].bn1_stats, Hd);
-  add_bn(model->head[which_output].bn2_stats, S);
+  }
   Arena sizing;
   layout(q, sizing);
   if (hipMalloc((void **)&q->arena, sizing.off + 1024) != hipSuccess) {

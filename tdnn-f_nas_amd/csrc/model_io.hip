@@ -27,7 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "net.h"
+#include "net_model.h"
 #include "tdnnf_kaldi_io.h"
 
 namespace tdnnf {
@@ -45,27 +45,12 @@ struct HostNet {
   std::map<std::string, int> stat_dim;
 };
 
-void stat_layout(const tdnnf_net *n, HostNet *h) {  // the order of tdnnf_net_get_stats (net.hip: stat_blocks)
-  const int Hd = n->cfg.hidden_dim, S = n->cfg.prefinal_small_dim;
+void stat_layout(const tdnnf_net *n, HostNet *h) {  // the order of tdnnf_net_get_stats
   size_t off = 0;
-  auto add = [&](const std::string &name, int D, bool relu = false) {  // relu: [count, value_sum, deriv_sum, oderiv_count, oderiv_sumsq]
-    h->stat_off[name] = off;
-    h->stat_dim[name] = D;
-    off += relu ? 2 + 3 * (size_t)D : 1 + 2 * (size_t)D;
-  };
-  add("tdnn1.batchnorm", Hd);
-  add("tdnn1.relu", Hd, true);
-  for (size_t l = 0; l < n->layers.size(); l++) {
-    const std::string p = "tdnnf" + std::to_string(l + 2);
-    add(p + ".batchnorm", Hd);
-    add(p + ".relu", Hd, true);
-  }
-  const char *hn[2] = {"chain", "xent"};
-  for (int k = 0; k < 2; k++) {
-    const std::string p = std::string("prefinal-") + hn[k];
-    add(p + ".batchnorm1", Hd);
-    add(p + ".relu", Hd, true);
-    add(p + ".batchnorm2", S);
+  for (const StatBlock &b : stat_blocks(n)) {
+    h->stat_off[b.name] = off;
+    h->stat_dim[b.name] = b.D;
+    off += b.doubles();
   }
 }
 
@@ -130,9 +115,8 @@ std::vector<std::string> config_lines(const tdnnf_net_config &c) {
     prev = p + ".noop";
   }
   cn("prefinal-l", prev);
-  const char *hn[2] = {"chain", "xent"};
   for (int k = 0; k < 2; k++) {
-    const std::string p = std::string("prefinal-") + hn[k], o = k == 0 ? "output" : "output-xent";
+    const std::string p = std::string("prefinal-") + head_name(k), o = k == 0 ? "output" : "output-xent";
     cn(p + ".affine", "prefinal-l");
     cn(p + ".relu", p + ".affine");
     cn(p + ".batchnorm1", p + ".relu");
@@ -174,12 +158,6 @@ void updatable_common(Ctx &x, const char *type, const CompDesc &cd) {  // WriteU
 
 const float *pW(Ctx &x, const CompDesc &cd) { return x.h->params.data() + cd.begin; }
 
-void ng_ranks(const CompDesc &cd, int *rank_in, int *rank_out) {  // nnet-tdnn-component.cc:183-210 defaults
-  const int spliced = cd.cols + (cd.has_bias ? 1 : 0);
-  *rank_in = std::min(20, (spliced + 1) / 2);
-  *rank_out = std::min(80, (cd.rows + 1) / 2);
-}
-
 void write_ng_affine(Ctx &x, const CompDesc &cd) {  // nnet-simple-component.cc:2935-2958
   Out &o = *x.o;
   updatable_common(x, "NaturalGradientAffineComponent", cd);
@@ -198,11 +176,11 @@ void write_ng_affine(Ctx &x, const CompDesc &cd) {  // nnet-simple-component.cc:
     o.f32(cd.orthonormal);
   }
   o.token("<UpdatePeriod>");
-  o.i32(4);
+  o.i32(kNgUpdatePeriod);
   o.token("<NumSamplesHistory>");
-  o.f32(2000.0f);
+  o.f32(kNgNumSamplesHistory);
   o.token("<Alpha>");
-  o.f32(4.0f);
+  o.f32(kNgAlpha);
   o.token("</NaturalGradientAffineComponent>");
 }
 
@@ -223,11 +201,11 @@ void write_linear(Ctx &x, const CompDesc &cd) {  // :3161-3188
   o.i32(ri);
   o.i32(ro);
   o.token("<Alpha>");
-  o.f32(4.0f);
+  o.f32(kNgAlpha);
   o.token("<NumSamplesHistory>");
-  o.f32(2000.0f);
+  o.f32(kNgNumSamplesHistory);
   o.token("<UpdatePeriod>");
-  o.i32(4);
+  o.i32(kNgUpdatePeriod);
   o.token("</LinearComponent>");
 }
 
@@ -265,10 +243,10 @@ void write_tdnn(Ctx &x, const CompDesc &cd, const Tdnn &t) {  // nnet-tdnn-compo
   int ri, ro;
   ng_ranks(cd, &ri, &ro);
   o.token("<NumSamplesHistory>");
-  o.f32(2000.0f);
+  o.f32(kNgNumSamplesHistory);
   o.token("<AlphaInOut>");
-  o.f32(4.0f);
-  o.f32(4.0f);
+  o.f32(kNgAlpha);
+  o.f32(kNgAlpha);
   o.token("<RankInOut>");
   o.i32(ri);
   o.i32(ro);
@@ -322,14 +300,14 @@ void write_nonlinear(Ctx &x, const char *type, int D, const std::string &stat_na
   if (!stat_name.empty()) {
     const double *st = x.h->stats.data() + x.h->stat_off.at(stat_name);
     count = st[0];
-    ocount = st[1 + 2 * D];
+    ocount = st[relu_oderiv_at(D)];
     va.resize(D);
     da.resize(D);
     orms.resize(D);
     for (int d = 0; d < D; d++) {
       va[d] = (float)(count != 0 ? st[1 + d] / count : st[1 + d]);
       da[d] = (float)(count != 0 ? st[1 + D + d] / count : st[1 + D + d]);
-      const double v = ocount != 0 ? st[2 + 2 * D + d] / ocount : st[2 + 2 * D + d];  // :658-664: scale, ApplyFloor(0), ApplyPow(0.5)
+      const double os = st[relu_oderiv_at(D) + 1 + d], v = ocount != 0 ? os / ocount : os;  // :658-664: scale, ApplyFloor(0), ApplyPow(0.5)
       orms[d] = (float)sqrt(v > 0 ? v : 0.0);
     }
   }
@@ -511,9 +489,8 @@ int write_components(Ctx &x, bool count_only) {
     write_linear(x, n->comps[n->c_prefinal_l]);
     end();
   }
-  const char *hn[2] = {"chain", "xent"};
   for (int k = 0; k < 2; k++) {
-    const std::string p = std::string("prefinal-") + hn[k], out = k == 0 ? "output" : "output-xent";
+    const std::string p = std::string("prefinal-") + head_name(k), out = k == 0 ? "output" : "output-xent";
     if (begin(p + ".affine")) {
       write_ng_affine(x, n->comps[n->head[k].c_affine]);
       end();
@@ -715,8 +692,8 @@ int tdnnf_net_read_model(tdnnf_net *n, const char *path, tdnnf_stream stream) {
         // NonlinearComponent::Read itf.cc:584-590: oderiv_sumsq_ = rms^2 * oderiv_count_ (an empty vector: nothing stored yet)
         const auto oc = p.num.find("<OderivCount>");
         const double ocount = oc != p.num.end() ? oc->second : 0.0;
-        dstat[1 + 2 * D] = (int)p.oderiv_rms.size() == D ? ocount : 0.0;
-        for (int d = 0; d < D; d++) dstat[2 + 2 * D + d] = (int)p.oderiv_rms.size() == D ? (double)p.oderiv_rms[d] * p.oderiv_rms[d] * ocount : 0.0;
+        dstat[relu_oderiv_at(D)] = (int)p.oderiv_rms.size() == D ? ocount : 0.0;
+        for (int d = 0; d < D; d++) dstat[relu_oderiv_at(D) + 1 + d] = (int)p.oderiv_rms.size() == D ? (double)p.oderiv_rms[d] * p.oderiv_rms[d] * ocount : 0.0;
       }
     }
   }

@@ -1,9 +1,9 @@
-// net_step.hip -- one minibatch of nnet3-chain-train on a tdnnf_net (net.hip): tdnnf_net_forward_backward, as a host-side C++
+// net_step.hip -- one minibatch of nnet3-chain-train on a tdnnf_net (net.h): tdnnf_net_forward_backward, as a host-side C++
 // executor over the component kernels of this library.
 //
 // Mirrors (UPSTREAM) NnetChainTrainer::TrainInternal:  forward through every component's Propagate,
 // chain::ComputeChainObjfAndDeriv, Backprop through every component (raw-gradient / is_gradient_
-// UpdateSimple path); the optimizer helpers that follow are tdnnf_net_update (net.hip).
+// UpdateSimple path); the optimizer helpers that follow are tdnnf_net_update (net_update.hip).
 //
 // The step is one object (Step): its members are the state that lives for one minibatch, its methods the pieces of the schedule,
 // and run() lists the phases between the phase_mark boundaries.  State that lives across minibatches stays in tdnnf_net.
@@ -17,7 +17,7 @@
 #include "common.h"
 #include "fused.h"
 #include "gemm_f32.h"
-#include "net.h"
+#include "net_model.h"
 #include "ng.h"
 
 namespace tdnnf {
@@ -298,11 +298,6 @@ struct FroBound {
   const float *add_rec = nullptr;
 };
 const PlanesOperand *hint_of(const PlanesOperand &o) { return o.base ? &o : nullptr; }
-int max_off(const Tdnn &td) {
-  int m = 0;
-  for (int i = 0; i < td.K; i++) m = std::max(m, td.ix.row_offsets[i]);
-  return m;
-}
 
 struct Step {
   // ---- the call
@@ -391,7 +386,7 @@ struct Step {
     memcpy(ps.last, cfg5, sizeof(cfg5));
     return same;
   }
-  // the slot was allocated (net.hip, by planes_gemm.h's planes_slot_* sizes) for planes of `m` with R rows, and transposed planes with Rt
+  // the slot was allocated (net_arena.hip, by planes_gemm.h's planes_slot_* sizes) for planes of `m` with R rows, and transposed planes with Rt
   // rows (0: none are written): anything larger would be written past its end
   int slot_holds(const tdnnf_net::PlaneSlot &ps, const tdnnf_mat &m, long long R, long long Rt) const {
     TDNNF_REQUIRE(planes_bytes(np, R, planes_slot_kblocks(m.cols)) <= ps.bytesP && planes_bytes(np, Rt, planes_t_kblocks(m.rows)) <= ps.bytesPT,
@@ -857,13 +852,13 @@ struct Step {
   }
   // NonlinearComponent::StoreBackpropStats (nnet-component-itf.cc:461-480): "if (RandInt(0, 3) == 0 && oderiv_count_ != 0) return"
   // -- three minibatches in four, always the first; a decision stream of its own (the k-th ReLU of the backward pass)
-  double *oderiv_of(double *relu_stats, int relu_index) {  // relu_index: 0 tdnn1, 1 + l tdnnf layer l, num_layers + 1 + h head h
+  double *oderiv_of(double *relu_stats, int relu_index) {  // relu_index: the k-th ReLU of stat_blocks() (net_model.h); every ReLU is Hd wide
     std::vector<char> &nz = *n->oderiv_nonzero;
     if ((int)nz.size() < c.num_layers + 3) nz.resize(c.num_layers + 3, 0);
     const bool skip = nz[relu_index] && ::tdnnf::tdnnf_decision((unsigned long long)step, 2 * (4096 + relu_k)) % 4 == 0;
     relu_k++;
     if (!skip) nz[relu_index] = 1;
-    return skip ? nullptr : relu_stats + 1 + 2 * Hd;
+    return skip ? nullptr : relu_stats + relu_oderiv_at(Hd);
   }
   // BatchNorm backward + ReLU backward (+ StoreStats / self-repair coin flips as in the reference:
   // RectifiedLinearComponent::StoreStats nnet-simple-component.cc:1084, RepairGradients :1017) in two fused

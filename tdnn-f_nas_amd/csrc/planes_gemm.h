@@ -80,7 +80,7 @@ inline long long planes_t_kblocks(int rows) { return ((rows + 63) / 64) * 4; }  
 // a chunk stride (rows x 32 bytes) that is a multiple of 8 KB puts every plane and K block on the same memory channels (2.7 x slower):
 // the row count to allocate for `rows` data rows + `pad` zero rows
 inline long long planes_rows_padded(long long rows) { return rows % 256 == 0 ? rows + 8 : rows; }
-// The sizes of a plane slot -- buffers that one party allocates and another splits matrices into (net.hip / net_step.hip); said here once,
+// The sizes of a plane slot -- buffers that one party allocates and another splits matrices into (net_arena.hip / net_step.hip); said here once,
 // because a user that sized its planes otherwise than the allocation would write past them:
 // rows of the row-major planes of a `rows`-row matrix behind `lead` zero rows (a multiple of 16), a 256-row tile of zero rows behind it
 inline long long planes_slot_rows(long long rows, int lead) { return planes_rows_padded(2LL * lead + rows + 256); }

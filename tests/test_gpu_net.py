@@ -566,7 +566,7 @@ def test_nets_for_several_chunk_widths_share_the_model(pkg):
 @pytest.mark.parametrize("kind", ["7q", "darts-softmax", "darts-uniform"])
 @pytest.mark.parametrize("wg", [0, 1], ids=["one-stream", "wgrad-stream"])
 def test_early_input_statistics_are_bit_identical_to_the_in_order_ones(pkg, kind, wg):
-    """The input-side natural-gradient statistics launched ahead of the backward pass (net.hip, option ng_early_in, from the arguments a
+    """The input-side natural-gradient statistics launched ahead of the backward pass (net_arena.hip, option ng_early_in, from the arguments a
     component's backward call recorded one minibatch earlier) against the same statistics formed with the backward call: the same kernels on
     the same operands, so gradients and parameters must agree BIT FOR BIT over a refresh schedule -- a forward activation rewritten in place
     during the backward pass, or stale coefficient / active-tap contents behind an unchanged pointer, would show here."""
@@ -676,3 +676,48 @@ def test_grouped_weight_plane_split_is_bit_identical(pkg, kind):
         assert np.isfinite(ga).all()
         assert np.array_equal(ga, gb), (i, rel_l2(ga, gb))
         assert ra is None or np.array_equal(ra, rb)
+
+
+@pytest.mark.gpu
+def test_statistics_blocks_layout_and_round_trips(pkg, tmp_path):
+    """The model statistics outside the parameter vector are (L + 5) BatchNorm blocks [count, sum[D], sumsq[D]] and (L + 3) ReLU blocks
+    [count, value_sum[D], deriv_sum[D], oderiv_count, oderiv_sumsq[D]] in network order: tdnn1 (batchnorm, relu), every tdnnf layer
+    (batchnorm, relu), both heads (batchnorm1, relu, batchnorm2 -- the last prefinal_small_dim wide, so hidden_dim != prefinal_small_dim
+    tells the blocks apart).  set_stats / get_stats copy them exactly, and a model file gives them back to a second net.  The values of the
+    file round trip are chosen so that what the file holds (float32 means, variances, oderiv rms) is exact: counts are powers of two, the
+    means and variances small integers, the oderiv sums of squares count * integer^2 -- so equality is exact, not a tolerance."""
+    T = pkg.trainer
+    L, Hd, S = 2, 64, 32
+    cfg = T.make_config(frames_per_chunk=24, num_sequences=3, strides=[1, 3], bottleneck=16, feat_dim=8, ivector_dim=4, num_pdfs=10,
+                        hidden_dim=Hd, small_dim=S)
+    net = T.ChainNet(cfg)
+    bn, relu = (lambda D: 1 + 2 * D), (lambda D: 2 + 3 * D)
+    blocks = [("bn", Hd), ("relu", Hd)] * (1 + L) + [("bn", Hd), ("relu", Hd), ("bn", S)] * 2
+    size = sum(bn(D) if kind == "bn" else relu(D) for kind, D in blocks)
+    assert size == (L + 3) * relu(Hd) + (L + 3) * bn(Hd) + 2 * bn(S)
+    assert net.get_stats().size == size
+    ramp = np.arange(size, dtype=np.float64)
+    net.set_stats(ramp)
+    assert np.array_equal(net.get_stats(), ramp)
+    parts = []
+    for k, (kind, D) in enumerate(blocks):
+        d = np.arange(D, dtype=np.float64)
+        c = float(2 ** (k % 3))
+        m, v = (d + k) % 7 - 3, (d + 2 * k) % 5
+        if kind == "bn":
+            parts += [[c], c * m, c * (v + m * m)]
+        else:
+            oc, r = float(2 ** ((k + 1) % 3)), (d + 3 * k) % 6
+            parts += [[c], c * m, c * 0.25 * v, [oc], oc * r * r]
+    stats = np.concatenate([np.asarray(p, np.float64) for p in parts])
+    assert stats.size == size
+    net.set_stats(stats)
+    assert np.array_equal(net.get_stats(), stats)
+    path = tmp_path / "stats.raw"
+    net.write_model(path)
+    net2 = T.ChainNet(cfg)
+    assert not net2.get_stats().any()
+    net2.read_model(path)
+    assert np.array_equal(net2.get_stats(), stats)
+    net.close()
+    net2.close()
