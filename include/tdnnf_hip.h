@@ -726,6 +726,58 @@ int tdnnf_infer_compute(tdnnf_infer *, int num_utts, const int *frames_host, con
    against their output rows) */
 int tdnnf_infer_counts(const tdnnf_infer *, int *fused_layers, int *fallback_passes);
 
+/* ======================================================================== inference (forward only, streaming)
+ * The same output for streams whose features arrive a few frames at a time: nnet3's looped computation
+ * (DecodableNnetLoopedOnline, UPSTREAM, not shipped) restated.  Same models, outputs and BatchNorm as "inference" above, and the
+ * same rejections.  fsf = frame_subsampling.
+ *  - Slots: num_slots streams, each with its own clock (an input frame index) and its own carried state on the device.
+ *    Parameters and BatchNorm statistics are bound by reference (read at every step).
+ *  - Context: left / right = the model's true context in input frames, from the taps (lda splice 1 + every layer's left /
+ *    right tap), not from a chunk's rho-padded grids.  Latency D = right rounded up to a multiple of fsf.
+ *  - Reset starts a new utterance in a slot: its carried state is zeroed (no value of an earlier utterance can be read
+ *    again) and its clock set to -W, W = left rounded up to a multiple of F = frames_per_step.
+ *  - Step: a list of active slots, each at most once, in any order; per slot a row count n_b, a `final` flag and one i-vector
+ *    row; feats = the passed rows of the active slots stacked in list order (sum n_b x feat_dim); out = num_active * F / fsf
+ *    rows.  Every active slot advances by one window of F input frames [clock, clock + F); the others keep state and clock.
+ *     . The rows passed for a slot are the real frames of its window, in order.  A window position before the first passed row
+ *       takes the first passed row, one after the last passed row takes the last (nnet3's edge padding).  So: the W warm-up
+ *       frames (clock < 0) pass frame 0 alone, not final; a window at clock >= 0 that is not final passes exactly F rows; the
+ *       window in which the utterance ends passes its remaining 1..F rows with `final` set (T = clock + n_b from then on);
+ *       every later (flush) window passes the last frame alone with `final` set.  Anything else -- also a slot out of range
+ *       or listed twice, or matrices of other dimensions -- fails with TDNNF_EINVAL before any launch and leaves every slot
+ *       as it was.
+ *     . The library keeps on the device whatever earlier frames and activations it still needs: a frame is never sent
+ *       again, except as a clamp source.
+ *     . Outputs: the step computes the head's outputs at input frames [clock - D, clock - D + F), stepping fsf; rows at
+ *       frames below 0, or at or past T once `final` has been seen, are dropped.  Slot i's kept rows are written at
+ *       out[i * F / fsf ...] (the rest of its F / fsf rows is not written); out_first_host[i] = the output index of the first
+ *       one (row j of an utterance = input frame j * fsf), out_count_host[i] their number.  A slot is done once
+ *       clock - D >= T; stepping it further emits nothing.
+ *     . I-vector: the input-layer rows first computed in a step (frames clock - (D - right) - 1 onwards) use the i-vector
+ *       passed in that step -- the online i-vector of the looped decodable.  With a constant i-vector the output equals the
+ *       whole-utterance output of tdnnf_infer_compute.
+ *     . Everything runs on the caller's stream; nothing synchronises (the step's table has a fixed size).
+ *  - Schedule (host only, like tdnnf_chunk_plan): the steps of one utterance of T frames, 5 ints each: clock, first passed
+ *    frame, passed rows, first output row, kept output rows; from clock -W while clock - D < T.  tdnnf_online_step follows
+ *    exactly this arithmetic (one function serves both).
+ *  - Counts of the last step: gemm_rows = output rows of all GEMM launches (each computes only the new rows);
+ *    carried_rows = time rows x streams moved from the slots' state into the step's buffers (as many go back);
+ *    fused / fallback = the BatchNorm stages as in tdnnf_infer_counts. */
+typedef struct tdnnf_online tdnnf_online;
+int tdnnf_online_create(const tdnnf_net *model, int frames_per_step, int num_slots, int which_output, tdnnf_online **out);
+void tdnnf_online_destroy(tdnnf_online *);
+int tdnnf_online_context(const tdnnf_online *, int *left, int *right, int *latency);
+int tdnnf_online_reset(tdnnf_online *, int slot, tdnnf_stream);
+/* a slot's clock and its utterance's length T (-1: `final` not seen yet) */
+int tdnnf_online_slot(const tdnnf_online *, int slot, int *clock, int *frames);
+/* more than `capacity` steps: the first `capacity` are written and the call fails (TDNNF_EINVAL) with *num_steps still set */
+int tdnnf_online_schedule(int frames_per_step, int frame_subsampling, int left, int right, int frames, int *steps_out, int capacity,
+                          int *num_steps);
+int tdnnf_online_step(tdnnf_online *, int num_active, const int *slots_host, const int *rows_host, const int *final_host,
+                      const tdnnf_mat *feats, const tdnnf_mat *ivectors, tdnnf_mat *out, int *out_first_host, int *out_count_host,
+                      tdnnf_stream);
+int tdnnf_online_counts(const tdnnf_online *, long long *gemm_rows, long long *carried_rows, int *fused, int *fallback);
+
 /* ======================================================================== profiling
  * Optional per-launch timing of the MFMA GEMM kernels with HIP events recorded on the launch stream
  * (bench.py's live roofline measurement).  Classes: 0 = rows_gemm 128x128 tile, 1 = rows_gemm 128x160 tile,

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "fused.h"
 #include "gemm_f32.h"
+#include "infer_parts.h"
 #include "net_model.h"
 
 using namespace tdnnf;
@@ -55,7 +56,7 @@ __global__ void infer_row_map_kernel(const int *tab, int B, int Tout, int *row_m
   row_map[m] = j < tab[kTab * b + 5] ? tab[kTab * b + 4] + j : -1;
 }
 
-// out[row_map[m]] = in[m] for the rows that have one (the log-softmax of the xent head)
+// infer_scatter_rows: out[row_map[m]] = in[m] for the rows that have one (the log-softmax of the xent head)
 template <int VEC>
 __global__ __launch_bounds__(256) void infer_scatter_kernel(MatView in, const int *row_map, MatView out) {
   const int cv = in.cols / VEC;
@@ -68,15 +69,8 @@ __global__ __launch_bounds__(256) void infer_scatter_kernel(MatView in, const in
   }
 }
 
-// Test-mode BatchNorm of every stage from the model's statistics [count, sum[D], sumsq[D]]: block i of `coef` = [mean | variance |
-// scale | offset] (D each; mean and scale where bn_apply_bypass reads them, offset = -mean * scale for the GEMM epilogue).  The
-// arithmetic of bn_test_memo_kernel (BatchNormComponent::ComputeDerived, nnet-normalize-component.cc:682-715).
-constexpr int kMaxBn = TDNNF_NET_MAX_LAYERS + 3;
-struct BnTable {
-  const double *stats[kMaxBn];
-  int D[kMaxBn];
-  long long coef_off[kMaxBn];
-};
+// infer_bn_coef (infer_parts.h): the arithmetic of bn_test_memo_kernel (BatchNormComponent::ComputeDerived,
+// nnet-normalize-component.cc:682-715).
 __global__ void infer_bn_coef_kernel(BnTable tb, float *coef) {
   const int i = blockIdx.y, D = tb.D[i], d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= D) return;
@@ -95,6 +89,91 @@ __global__ void infer_bn_coef_kernel(BnTable tb, float *coef) {
 }
 
 }  // namespace
+
+namespace tdnnf {
+
+int infer_check_model(const tdnnf_net_config &c, int frames, const char *who, const char *frames_name) {
+  TDNNF_REQUIRE(c.darts_num_offsets < 2, "%s: the offset supernet (darts_num_offsets = %d) is not supported: derive a child first", who,
+                c.darts_num_offsets);
+  TDNNF_REQUIRE(c.bn_num_choices == 0, "%s: the bottleneck supernet (bn_num_choices = %d) is not supported: derive a child first", who,
+                c.bn_num_choices);
+  TDNNF_REQUIRE(c.gemm_precision == 0, "%s: gemm_precision %d: inference runs exact f32 only (gemm_precision 0)", who, c.gemm_precision);
+  TDNNF_REQUIRE(frames > 0 && frames % c.frame_subsampling == 0, "%s: %s %d must be a positive multiple of frame_subsampling %d", who, frames_name,
+                frames, c.frame_subsampling);
+  return TDNNF_OK;
+}
+
+int infer_bn_table(const tdnnf_net *model, int which_output, BnTable *bn) {
+  memset(bn, 0, sizeof(*bn));
+  const long long bstride = infer_bn_stride(model->cfg);
+  int nbn = 0;
+  for (const StatBlock &b : stat_blocks(model)) {
+    if (b.relu || (b.head >= 0 && b.head != which_output)) continue;
+    bn->stats[nbn] = b.p();
+    bn->D[nbn] = b.D;
+    bn->coef_off[nbn] = nbn * bstride;
+    nbn++;
+  }
+  return nbn;
+}
+
+hipError_t infer_bn_coef(const BnTable &bn, int nbn, float *coef, hipStream_t s) {
+  int dmax = 0;
+  for (int i = 0; i < nbn; i++) dmax = std::max(dmax, bn.D[i]);
+  hipLaunchKernelGGL(infer_bn_coef_kernel, dim3((dmax + 255) / 256, nbn), dim3(256), 0, s, bn, coef);
+  return hipGetLastError();
+}
+
+hipError_t infer_scatter_rows(const MatView &in, const int *row_map, const MatView &out, hipStream_t s) {
+  const bool v4 = vec4_ok(in) && vec4_ok(out);
+  const long long work = (long long)in.rows * in.cols / (v4 ? 4 : 1);
+  if (v4) hipLaunchKernelGGL(infer_scatter_kernel<4>, dim3(grid_for(work, 256)), dim3(256), 0, s, in, row_map, out);
+  else hipLaunchKernelGGL(infer_scatter_kernel<1>, dim3(grid_for(work, 256)), dim3(256), 0, s, in, row_map, out);
+  return hipGetLastError();
+}
+
+// rows GEMM of one TdnnComponent (or affine: ix = one tap) with the inference epilogue
+int gemm_post(const tdnnf_tdnn_indexes &ix, const tdnnf_mat &in, const float *W, int ldw, int Do, int Di, const float *bias, int relu,
+              const float *coef, const tdnnf_mat *add, float add_scale, const int *row_map, const tdnnf_mat &out, hipStream_t s) {
+  RowsGemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = in.data;
+  a.lda = (long long)in.stride * ix.row_stride;
+  a.B = W;
+  a.ldb = ldw;
+  a.C = out.data;
+  a.ldc = out.stride;
+  a.M = out.rows;
+  a.N = Do;
+  a.bias = bias;
+  a.init_mode = bias ? 1 : 2;
+  a.relu = relu;
+  a.nseg = ix.num_offsets;
+  for (int i = 0; i < a.nseg; i++) {
+    a.seg[i].a_off = (long long)ix.row_offsets[i] * in.stride;
+    a.seg[i].b_off = (long long)i * Di;
+    a.seg[i].klen = Di;
+    a.seg[i].m_lo = 0;
+    a.seg[i].m_hi = a.M;
+  }
+  if (coef) {  // [mean | variance | scale | offset]
+    a.col_scale = coef + 2 * Do;
+    a.col_offset = coef + 3 * Do;
+  }
+  if (add) {
+    a.add = add->data;
+    a.ldadd = add->stride;
+    a.add_scale = add_scale;
+    a.add_lo = 0;
+    a.add_hi = a.M;
+    a.post_add = 1;
+  }
+  a.row_map = row_map;
+  TDNNF_HIP(rows_gemm(a, true, s));
+  return TDNNF_OK;
+}
+
+}  // namespace tdnnf
 
 struct tdnnf_infer {
   const tdnnf_net *model;
@@ -162,47 +241,6 @@ int make_plan(int F, int fsf, int num_utts, const int *frames, const int *iv_row
       plan.insert(plan.end(), {u, k * F, row, n});
     }
   }
-  return TDNNF_OK;
-}
-
-// rows GEMM of one TdnnComponent (or affine: ix = one tap) with the inference epilogue
-int gemm_post(const tdnnf_tdnn_indexes &ix, const tdnnf_mat &in, const float *W, int ldw, int Do, int Di, const float *bias, int relu,
-              const float *coef, const tdnnf_mat *add, float add_scale, const int *row_map, const tdnnf_mat &out, hipStream_t s) {
-  RowsGemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.A = in.data;
-  a.lda = (long long)in.stride * ix.row_stride;
-  a.B = W;
-  a.ldb = ldw;
-  a.C = out.data;
-  a.ldc = out.stride;
-  a.M = out.rows;
-  a.N = Do;
-  a.bias = bias;
-  a.init_mode = bias ? 1 : 2;
-  a.relu = relu;
-  a.nseg = ix.num_offsets;
-  for (int i = 0; i < a.nseg; i++) {
-    a.seg[i].a_off = (long long)ix.row_offsets[i] * in.stride;
-    a.seg[i].b_off = (long long)i * Di;
-    a.seg[i].klen = Di;
-    a.seg[i].m_lo = 0;
-    a.seg[i].m_hi = a.M;
-  }
-  if (coef) {  // [mean | variance | scale | offset]
-    a.col_scale = coef + 2 * Do;
-    a.col_offset = coef + 3 * Do;
-  }
-  if (add) {
-    a.add = add->data;
-    a.ldadd = add->stride;
-    a.add_scale = add_scale;
-    a.add_lo = 0;
-    a.add_hi = a.M;
-    a.post_add = 1;
-  }
-  a.row_map = row_map;
-  TDNNF_HIP(rows_gemm(a, true, s));
   return TDNNF_OK;
 }
 
@@ -281,12 +319,7 @@ int forward_batch(tdnnf_infer *q, const tdnnf_mat *feats, const tdnnf_mat *iv, c
     tdnnf_mat y = M(q->y, No, P), lsm = M(q->lsm, No, P);
     CK(tdnnf_affine_propagate(&b2, W(H.c_output), S, bias(H.c_output), P, &y, s));
     CK(tdnnf_log_softmax_propagate(&y, &lsm, s));
-    const MatView lv = view(&lsm), ov = view(out);
-    const bool v4 = vec4_ok(lv) && vec4_ok(ov);
-    const long long work = (long long)No * P / (v4 ? 4 : 1);
-    if (v4) hipLaunchKernelGGL(infer_scatter_kernel<4>, dim3(grid_for(work, 256)), dim3(256), 0, s, lv, q->row_map, ov);
-    else hipLaunchKernelGGL(infer_scatter_kernel<1>, dim3(grid_for(work, 256)), dim3(256), 0, s, lv, q->row_map, ov);
-    TDNNF_LAUNCH_CHECK();
+    TDNNF_HIP(infer_scatter_rows(view(&lsm), q->row_map, view(out), s));
   }
   if (count) {
     q->fused = fused;
@@ -302,13 +335,7 @@ extern "C" {
 int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, tdnnf_infer **out) {
   TDNNF_REQUIRE(model && out, "infer_create: null argument");
   const tdnnf_net_config &c = model->cfg;
-  TDNNF_REQUIRE(c.darts_num_offsets < 2, "infer_create: the offset supernet (darts_num_offsets = %d) is not supported: derive a child first",
-                c.darts_num_offsets);
-  TDNNF_REQUIRE(c.bn_num_choices == 0, "infer_create: the bottleneck supernet (bn_num_choices = %d) is not supported: derive a child first",
-                c.bn_num_choices);
-  TDNNF_REQUIRE(c.gemm_precision == 0, "infer_create: gemm_precision %d: inference runs exact f32 only (gemm_precision 0)", c.gemm_precision);
-  TDNNF_REQUIRE(frames_per_chunk > 0 && frames_per_chunk % c.frame_subsampling == 0,
-                "infer_create: frames_per_chunk %d must be a positive multiple of frame_subsampling %d", frames_per_chunk, c.frame_subsampling);
+  CK(infer_check_model(c, frames_per_chunk, "infer_create", "frames_per_chunk"));
   TDNNF_REQUIRE(max_chunks >= 1 && which_output >= 0 && which_output <= 1, "infer_create: max_chunks must be >= 1, which_output 0 or 1");
   tdnnf_infer *q = new tdnnf_infer();
   q->model = model;
@@ -328,17 +355,7 @@ int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chu
   }
   q->g_feat = feat_grid(q->g_lda);
   // BatchNorm stages: tdnn1, the tdnnf layers, the chosen head's two (the model's statistics, by reference)
-  memset(&q->bn, 0, sizeof(q->bn));
-  const int Hd = c.hidden_dim, S = c.prefinal_small_dim;
-  const long long bstride = 4LL * ldpad(std::max(Hd, S));
-  q->nbn = 0;
-  for (const StatBlock &b : stat_blocks(model)) {
-    if (b.relu || (b.head >= 0 && b.head != which_output)) continue;
-    q->bn.stats[q->nbn] = b.p();
-    q->bn.D[q->nbn] = b.D;
-    q->bn.coef_off[q->nbn] = q->nbn * bstride;
-    q->nbn++;
-  }
+  q->nbn = infer_bn_table(model, which_output, &q->bn);
   Arena sizing;
   layout(q, sizing);
   if (hipMalloc((void **)&q->arena, sizing.off + 1024) != hipSuccess) {
@@ -428,12 +445,7 @@ int tdnnf_infer_compute(tdnnf_infer *q, int num_utts, const int *frames_host, co
   }
   TDNNF_HIP(hipMemcpyAsync(q->table, q->host_table.data(), sizeof(int) * q->host_table.size(), hipMemcpyHostToDevice, s));
   // ---- the model's BatchNorm statistics as test-mode scale / offset (read at every call)
-  {
-    int dmax = 0;
-    for (int i = 0; i < q->nbn; i++) dmax = std::max(dmax, q->bn.D[i]);
-    hipLaunchKernelGGL(infer_bn_coef_kernel, dim3((dmax + 255) / 256, q->nbn), dim3(256), 0, s, q->bn, q->coef);
-    TDNNF_LAUNCH_CHECK();
-  }
+  TDNNF_HIP(infer_bn_coef(q->bn, q->nbn, q->coef, s));
   for (int k0 = 0; k0 < nch; k0 += q->max_chunks) {
     const int B = std::min(q->max_chunks, nch - k0);
     CK(forward_batch(q, feats, ivectors, q->table + (size_t)kTab * k0, B, out, s, k0 == 0));

@@ -1,8 +1,9 @@
-"""The model's output for decoding (include/tdnnf_hip.h, "inference"): plumbing around tdnnf_infer_*.
+"""The model's output for decoding (include/tdnnf_hip.h, "inference"): plumbing around tdnnf_infer_* and tdnnf_online_*.
 
 AcousticModel computes, for whole utterances of any length, what nnet3's DecodableNnetSimple hands to
 latgen-faster-mapped (steps/nnet3/decode.sh --acwt 1.0, run_tdnn_fbk_40_iv_sp_7q.sh:254-258); write_matrix_archive
-stores it as a Kaldi binary float-matrix archive.  Every computation is a call into the HIP library.
+stores it as a Kaldi binary float-matrix archive.  OnlineAcousticModel computes the same rows for streams whose frames arrive a
+few at a time (nnet3's looped decodable).  Every computation is a call into the HIP library.
 """
 import ctypes as C
 import struct
@@ -86,6 +87,179 @@ class AcousticModel:
         a, b = C.c_int(), C.c_int()
         hipabi.check(self.lib.tdnnf_infer_counts(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+
+def online_schedule(frames_per_step, frame_subsampling, left, right, frames):
+    """The steps of one streamed utterance (tdnnf_online_schedule, host only): int array (num_steps, 5) of (clock, first passed
+    frame, passed rows, first output row, kept output rows)."""
+    lib = hipabi.load()
+    n = C.c_int()
+    lib.tdnnf_online_schedule(int(frames_per_step), int(frame_subsampling), int(left), int(right), int(frames), None, 0, C.byref(n))
+    out = np.zeros((max(n.value, 1), 5), np.int32)
+    hipabi.check(lib.tdnnf_online_schedule(int(frames_per_step), int(frame_subsampling), int(left), int(right), int(frames),
+                                           out.ctypes.data_as(C.POINTER(C.c_int)), n.value, C.byref(n)))
+    return out[:n.value]
+
+
+class OnlineAcousticModel:
+    """Streaming view of a ChainNet's model (include/tdnnf_hip.h, "inference (forward only, streaming)"): num_slots concurrent
+    streams, each fed a few frames at a time; a step advances every stream that has a window ready by frames_per_step input
+    frames and returns its new output rows.  Plumbing only: queues of device tensors and the calls into tdnnf_online_*."""
+
+    def __init__(self, net, frames_per_step=30, num_slots=16, output="output"):
+        self.lib = hipabi.load()
+        self.net = net  # keeps the model alive
+        self.frames_per_step, self.num_slots, self.output = int(frames_per_step), int(num_slots), output
+        self.fsf = int(net.cfg.frame_subsampling)
+        self.num_pdfs = int(net.cfg.num_pdfs)
+        self.h = C.c_void_p()
+        hipabi.check(self.lib.tdnnf_online_create(net.h, self.frames_per_step, self.num_slots, OUTPUTS[output], C.byref(self.h)))
+        left, right, lat = C.c_int(), C.c_int(), C.c_int()
+        hipabi.check(self.lib.tdnnf_online_context(self.h, C.byref(left), C.byref(right), C.byref(lat)))
+        self.left, self.right, self.latency = left.value, right.value, lat.value
+        self.free = list(range(self.num_slots))
+        self.streams = {}  # slot -> dict(buf: unconsumed frames (device), base: frame index of buf[0], total: frames pushed, final, last, iv)
+
+    @classmethod
+    def from_model_file(cls, path, frames_per_step=30, num_slots=16, output="output"):
+        """A model read from an nnet3 raw model file (tdnnf_net_config_from_model + tdnnf_net_read_model)."""
+        cfg = trainer.config_from_model(path, frames_per_chunk=frames_per_step, num_sequences=1)
+        cfg.cv_update = 1  # (no dropout masks; the statistics are only read)
+        net = trainer.ChainNet(cfg)
+        net.read_model(path)
+        return cls(net, frames_per_step, num_slots, output)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tdnnf_online_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def context(self):
+        """(left, right, latency) in input frames (tdnnf_online_context)."""
+        return self.left, self.right, self.latency
+
+    def slot_state(self, slot):
+        """(clock, T) of a slot; T = -1 until its last frame has been stepped."""
+        a, b = C.c_int(), C.c_int()
+        hipabi.check(self.lib.tdnnf_online_slot(self.h, int(slot), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def open(self):
+        """Starts a new utterance in a free slot (tdnnf_online_reset) and returns the slot."""
+        if not self.free:
+            raise RuntimeError("OnlineAcousticModel: all %d slots are in use" % self.num_slots)
+        slot = self.free.pop(0)
+        hipabi.check(self.lib.tdnnf_online_reset(self.h, slot, hipabi.stream()))
+        self.streams[slot] = dict(buf=None, base=0, total=0, final=False, last=None, iv=None)
+        return slot
+
+    def push(self, slot, feats, ivector, final=False):
+        """Queues the stream's next frames (n x feat_dim, numpy or torch; n may be 0) on the device; `ivector` is the stream's
+        i-vector from the next step on.  final: these are the utterance's last frames -- it must come with at least one frame
+        that no step has consumed yet (the window in which an utterance ends is marked when it is stepped)."""
+        import torch
+        st = self.streams[slot]
+        if st["final"]:
+            raise ValueError("push: slot %d has had its final frames" % slot)
+        f = torch.as_tensor(feats, dtype=torch.float32).cuda().reshape(-1, self.net.cfg.feat_dim)
+        st["buf"] = f if st["buf"] is None else torch.cat([st["buf"], f])
+        st["total"] += f.shape[0]
+        st["iv"] = torch.as_tensor(ivector, dtype=torch.float32).cuda().reshape(1, self.net.cfg.ivector_dim)
+        if final:
+            clock = self.slot_state(slot)[0]
+            if st["total"] == 0 or st["total"] <= clock:
+                raise ValueError("push: final must come with a frame that has not been stepped yet")
+            st["final"] = True
+
+    def finished(self, slot):
+        """True once every output row of the slot's utterance has been returned."""
+        clock, T = self.slot_state(slot)
+        return T >= 0 and clock - self.latency >= T
+
+    def release(self, slot):
+        del self.streams[slot]
+        self.free.append(slot)
+
+    def _window(self, slot):
+        """(rows to pass, final) of the slot's next window, or None while it has to wait for frames."""
+        st = self.streams[slot]
+        F = self.frames_per_step
+        clock, T = self.slot_state(slot)
+        if st["total"] == 0 or self.finished(slot):
+            return None
+        if T >= 0:  # flush
+            return st["last"], True
+        if clock < 0:  # warm-up
+            return st["buf"][:1], False
+        have = st["total"] - clock
+        if st["final"]:
+            n = min(F, have)
+        elif have >= F:
+            n = F
+        else:
+            return None
+        lo = clock - st["base"]
+        rows = st["buf"][lo:lo + n]
+        return rows, st["final"] and have <= F
+
+    def step(self, slots=None):
+        """One tdnnf_online_step over every open slot (or those of `slots`, in that order) that has a full window or is
+        finishing -- warm-up and flush windows included.  Returns {slot: new output rows (torch CUDA, k x num_pdfs, k >= 0)}."""
+        import torch
+        order = list(self.streams) if slots is None else list(slots)
+        act, feats, ivs, rows, fins = [], [], [], [], []
+        for slot in order:
+            w = self._window(slot)
+            if w is None:
+                continue
+            act.append(slot)
+            feats.append(w[0])
+            rows.append(w[0].shape[0])
+            fins.append(int(w[1]))
+            ivs.append(self.streams[slot]["iv"])
+        if not act:
+            return {}
+        first, count, out = self.step_raw(act, rows, fins, torch.cat(feats).contiguous(), torch.cat(ivs).contiguous())
+        Tout = self.frames_per_step // self.fsf
+        res = {}
+        for i, slot in enumerate(act):
+            st = self.streams[slot]
+            clock = self.slot_state(slot)[0]  # (already advanced)
+            if clock > 0 and st["buf"].shape[0]:  # frames before the clock are consumed: keep the last of them for the flush windows
+                used = min(clock, st["total"]) - st["base"]
+                if used > 0:
+                    st["last"] = st["buf"][used - 1:used]
+                    st["buf"] = st["buf"][used:]
+                    st["base"] += used
+            res[slot] = out[i * Tout:i * Tout + count[i]]
+        return res
+
+    def step_raw(self, slots, rows, finals, feats, ivectors):
+        """tdnnf_online_step as it is: the active slots, their passed row counts and final flags, the passed rows stacked and one
+        i-vector row per slot.  Returns (first output index per slot, kept rows per slot, out of len(slots) * F / fsf rows)."""
+        import torch
+        B = len(slots)
+        out = torch.zeros(B * (self.frames_per_step // self.fsf), self.num_pdfs, dtype=torch.float32, device="cuda")
+        sl, slp = hipabi.iarr(slots)
+        rw, rwp = hipabi.iarr(rows)
+        fn, fnp = hipabi.iarr(finals)
+        first, firstp = hipabi.iarr(np.zeros(max(B, 1), np.int32))
+        count, countp = hipabi.iarr(np.zeros(max(B, 1), np.int32))
+        hipabi.check(self.lib.tdnnf_online_step(self.h, B, slp, rwp, fnp, hipabi.pmat(feats), hipabi.pmat(ivectors), hipabi.pmat(out),
+                                                firstp, countp, hipabi.stream()))
+        return first[:B], count[:B], out
+
+    def counts(self):
+        """(gemm_rows, carried_rows, fused, fallback) of the last step (tdnnf_online_counts)."""
+        a, b, c, d = C.c_longlong(), C.c_longlong(), C.c_int(), C.c_int()
+        hipabi.check(self.lib.tdnnf_online_counts(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
 
 
 def write_matrix_archive(path, items):

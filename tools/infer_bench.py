@@ -4,7 +4,10 @@
 Prints one JSON line: input frames/s and ms per call, the GEMM rate against the 157.3 TFLOP/s exact-f32 MFMA peak (GEMM FLOPs
 from the library's own launch accounting, tdnnf_profile_*, in a separate call), the chunk-context overhead (F + context) / F
 and the fused / fallback counts.
-usage (GPU box): python tools/infer_bench.py [--calls K] [--utts N] [--max-chunks M]"""
+--online adds streaming inference (tdnnf_online_step) of the same model: steady-state steps of F in {30, 150} input frames for 1, 16
+and 64 concurrent streams -- input frames/s and ms per step -- and the algorithmic row ratio: the GEMM rows of a chunk of width F
+(from the chunk grids) over those of a step (tdnnf_online_counts).
+usage (GPU box): python tools/infer_bench.py [--calls K] [--utts N] [--max-chunks M] [--online [--steps K]]"""
 import argparse
 import ctypes as C
 import json
@@ -32,12 +35,71 @@ def model_stats(cfg):
     return np.concatenate(out)
 
 
+def chunk_gemm_rows(cfg, F):
+    """GEMM output rows of one chunk of width F per sequence, from the chunk grids (net_layer_grids restated: a layer's .linear runs
+    on the grid of step gcd(output step, left, right), padded to whole blocks where that is finer than the output grid)."""
+    from math import gcd
+    fsf = cfg.frame_subsampling
+    step, n = fsf, F // fsf
+    rows = 4 * n  # prefinal-l and the head's affine, linear, output
+    for l in reversed(range(cfg.num_layers)):
+        a = cfg.offset_left[l] if cfg.use_layer_offsets else cfg.time_stride[l]
+        b = cfg.offset_right[l] if cfg.use_layer_offsets else cfg.time_stride[l]
+        rows += n  # .affine
+        if a or b:
+            ls = gcd(gcd(step, a), b)
+            if ls == step:
+                n_lin = n + b // step
+            else:
+                rho = step // ls
+                n_lin = -(-(((n - 1) * step + b) // ls + 1) // rho) * rho
+            step, n = ls, n_lin + a // ls
+        else:
+            n_lin = n
+        rows += n_lin  # .linear
+    return rows + 2 * n  # lda, tdnn1
+
+
+def online(pkg, net, steps):
+    """Steady-state streaming steps: every slot warmed up, then `steps` full windows for all slots at once."""
+    res = {}
+    for F in (30, 150):
+        for slots in (1, 16, 64):
+            om = pkg.infer.OnlineAcousticModel(net, frames_per_step=F, num_slots=slots)
+            rng = np.random.default_rng(2)
+            feats = torch.from_numpy(rng.standard_normal((slots * F, 40)).astype(np.float32)).cuda()
+            ivs = torch.from_numpy(rng.standard_normal((slots, 100)).astype(np.float32)).cuda()
+            ids = list(range(slots))
+            for sl in ids:
+                om.open()
+            while om.slot_state(0)[0] < 0:  # warm-up windows: frame 0 alone
+                om.step_raw(ids, [1] * slots, [0] * slots, feats[:slots], ivs)
+            for _ in range(3):
+                om.step_raw(ids, [F] * slots, [0] * slots, feats, ivs)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps):
+                om.step_raw(ids, [F] * slots, [0] * slots, feats, ivs)
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1) / steps
+            gemm_rows, carried_rows, fused, fallback = om.counts()
+            res[f"F{F}_slots{slots}"] = dict(frames_per_s=round(slots * F / (ms / 1e3)), ms_per_step=round(ms, 3), gemm_rows=gemm_rows,
+                                             carried_rows=carried_rows, row_ratio=round(slots * chunk_gemm_rows(net.cfg, F) / gemm_rows, 3),
+                                             fused_layers=fused, fallback_passes=fallback)
+            om.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--utts", type=int, default=200)
     ap.add_argument("--max-chunks", type=int, default=256)
     ap.add_argument("--widths", default="51,150")
+    ap.add_argument("--online", action="store_true", help="also time streaming steps (F 30 / 150, 1 / 16 / 64 streams)")
+    ap.add_argument("--steps", type=int, default=50, help="--online: timed steps per configuration")
     args = ap.parse_args()
     pkg = ge.load_package()
     lib = pkg.hipabi.load()
@@ -78,6 +140,8 @@ def main():
                            gemm_tflops_per_s=round(flops / (ms / 1e3) / 1e12, 1), of_peak=round(flops / (ms / 1e3) / 1e12 / PEAK_TFLOPS, 3),
                            context_overhead=round((F + context) / F, 3), fused_layers=fused, fallback_passes=fallback)
         am.close()
+    if args.online:
+        res["online"] = online(pkg, net, args.steps)
     print(json.dumps(res))
 
 
