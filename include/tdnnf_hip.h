@@ -700,13 +700,25 @@ int tdnnf_net_activation_dims(const tdnnf_net *, const char *name, int *rows, in
  *    against Kaldi).
  *  - BatchNorm in test mode from the model's stored statistics (BatchNormTestComponent: epsilon 1e-3, target rms 1),
  *    dropout off, no ReLU statistics; nothing in the model is written.
- *  - Models: the 7q graph and derived children (layer offsets, per-layer bottleneck, strided affine rows), gemm_precision 0.
- *    The offset supernet (darts_num_offsets >= 2), the bottleneck supernet (bn_num_choices > 0) and any other gemm_precision
- *    fail with TDNNF_EINVAL. */
+ *  - Models: the 7q graph and derived children (layer offsets, per-layer bottleneck, strided affine rows).  The offset supernet
+ *    (darts_num_offsets >= 2) and the bottleneck supernet (bn_num_choices > 0) fail with TDNNF_EINVAL.
+ *  - Arithmetic: a property of the inference object, not of the model (whose parameters are f32 either way).
+ *    tdnnf_infer_create builds exact f32 and accepts only models whose own gemm_precision is 0 (any other: TDNNF_EINVAL).
+ *    tdnnf_infer_create_arith takes the arithmetic as an argument and does not consult the model's: gemm_precision 0 is exactly
+ *    the f32 object, 3 is f16x3 -- every GEMM of the forward pass on the 16-bit matrix cores from operands split once into two
+ *    scaled f16 planes (three products, f32 accumulation; held to the f32 tolerances), the weights split at the top of every
+ *    compute, each activation as it is produced.  1 and 2 (the split-bf16 forms) and bf16x6 are not built for inference:
+ *    TDNNF_EINVAL.  Streaming (tdnnf_online_*, below) is exact f32 only: its GEMMs run on a few rows per slot and step, where
+ *    a 256-row plane tile is mostly padding. */
 typedef struct tdnnf_infer tdnnf_infer;
 /* binds the model net's parameter buffer and statistics by reference (read at every compute: an update or set_stats on the
    model is seen by the next call); max_chunks bounds the chunks of one batch (the arena is sized for it) */
 int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, tdnnf_infer **out);
+/* the same object in the arithmetic gemm_precision (0: f32, what tdnnf_infer_create builds; 3: f16x3; 1, 2, anything else:
+   TDNNF_EINVAL); the model is checked as above except for its own cfg.gemm_precision.  The scalar arguments are checked
+   first, before the model is looked at and before any device call. */
+int tdnnf_infer_create_arith(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, int gemm_precision,
+                             tdnnf_infer **out);
 void tdnnf_infer_destroy(tdnnf_infer *);
 /* host only, no device call: the chunk plan above -- per chunk 4 ints (utterance, first input frame k F, i-vector row within
    the utterance, valid output rows n_k); *num_chunks = the number of chunks.  More than `capacity` chunks: the first
@@ -725,6 +737,11 @@ int tdnnf_infer_compute(tdnnf_infer *, int num_utts, const int *frames_host, con
    -- with the layer's bypass --, and those applied by a separate elementwise pass (tdnnf layers whose bypass rows are strided
    against their output rows) */
 int tdnnf_infer_counts(const tdnnf_infer *, int *fused_layers, int *fallback_passes);
+/* of the last compute, summed over its batches: GEMM launches of the forward pass that ran from f16 planes, and those that
+   ran on the f32 kernels -- all of them in an f32 object; in an f16x3 object the ones whose operands did not fit the plane
+   kernels.  The splits of the weights and activations are not counted.  A forward pass is 2 num_layers + 6 GEMMs per batch:
+   lda, tdnn1, every layer's .linear and .affine, prefinal-l, the head's affine and linear, the output. */
+int tdnnf_infer_gemm_counts(const tdnnf_infer *, long long *plane_gemms, long long *f32_gemms);
 
 /* ======================================================================== inference (forward only, streaming)
  * The same output for streams whose features arrive a few frames at a time: nnet3's looped computation

@@ -6,7 +6,8 @@
 // separate elementwise passes: every BatchNorm -- and a TDNN-F layer's bypass -- is applied while the GEMM stores its tile
 // (RowsGemmArgs::col_scale / col_offset / post_add, gemm_f32.h).  Memory: two ping-pong activation buffers (a layer's input
 // dies once its bypass is consumed), the linear and head temporaries and the chunk table; no gradients, natural-gradient
-// state, chain workspace or side streams.  Everything runs on the caller's stream.
+// state, chain workspace or side streams.  Everything runs on the caller's stream.  An object made by tdnnf_infer_create_arith with
+// gemm_precision 3 runs the same schedule from f16 planes: infer_planes.hip (the object itself: infer_state.h).
 #include <math.h>
 #include <string.h>
 
@@ -16,6 +17,7 @@
 #include "fused.h"
 #include "gemm_f32.h"
 #include "infer_parts.h"
+#include "infer_state.h"
 #include "net_model.h"
 
 using namespace tdnnf;
@@ -132,6 +134,21 @@ hipError_t infer_scatter_rows(const MatView &in, const int *row_map, const MatVi
   return hipGetLastError();
 }
 
+int infer_batch_input(tdnnf_infer *q, const tdnnf_mat *feats, const tdnnf_mat *iv, const int *tab, int B, hipStream_t s) {
+  const tdnnf_net_config &c = q->model->cfg;
+  const int lda_dim = 3 * c.feat_dim + c.ivector_dim, N0 = q->g_lda.n * B, No = q->Tout * B;
+  tdnnf_mat lda_in = M(q->lda_in, N0, lda_dim);
+  const MatView fv = view(feats), ivv = view(iv), ov = view(&lda_in);
+  const bool v4 = vec4_ok(fv) && vec4_ok(ivv) && vec4_ok(ov);
+  const long long work = (long long)N0 * lda_dim / (v4 ? 4 : 1);
+  if (v4) hipLaunchKernelGGL(infer_gather_kernel<4>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, tab, B, q->g_lda.n, q->g_feat.t0, ov);
+  else hipLaunchKernelGGL(infer_gather_kernel<1>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, tab, B, q->g_lda.n, q->g_feat.t0, ov);
+  TDNNF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(infer_row_map_kernel, dim3((No + 255) / 256), dim3(256), 0, s, tab, B, q->Tout, q->row_map);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+
 // rows GEMM of one TdnnComponent (or affine: ix = one tap) with the inference epilogue
 int gemm_post(const tdnnf_tdnn_indexes &ix, const tdnnf_mat &in, const float *W, int ldw, int Do, int Di, const float *bias, int relu,
               const float *coef, const tdnnf_mat *add, float add_scale, const int *row_map, const tdnnf_mat &out, hipStream_t s) {
@@ -174,22 +191,6 @@ int gemm_post(const tdnnf_tdnn_indexes &ix, const tdnnf_mat &in, const float *W,
 }
 
 }  // namespace tdnnf
-
-struct tdnnf_infer {
-  const tdnnf_net *model;
-  int F, Tout, fsf, max_chunks, which;
-  std::vector<TdnnfLayer> layers;  // grids at chunk width F (component ids from the model)
-  Grid g_lda, g_feat;
-  int nbn;
-  BnTable bn;
-  char *arena = nullptr;
-  float *lda_in, *lda_out, *act[2], *lin, *lin_perm, *relu_tmp, *pl, *b2, *y, *lsm, *coef;
-  int *row_map;
-  int *table = nullptr;  // device chunk table of the last compute
-  size_t table_cap = 0;  // (ints)
-  std::vector<int> host_table;
-  int fused = 0, fallback = 0;
-};
 
 namespace {
 
@@ -255,17 +256,8 @@ int forward_batch(tdnnf_infer *q, const tdnnf_mat *feats, const tdnnf_mat *iv, c
   auto W = [&](int comp) { return net_W(n, comp); };
   auto bias = [&](int comp) { return net_bias(n, comp); };
   // ---- input: clamped chunk windows + i-vector, spliced for the lda layer in one pass
+  CK(infer_batch_input(q, feats, iv, tab, B, s));
   tdnnf_mat lda_in = M(q->lda_in, N0, lda_dim), lda_out = M(q->lda_out, N0, lda_dim);
-  {
-    const MatView fv = view(feats), ivv = view(iv), ov = view(&lda_in);
-    const bool v4 = vec4_ok(fv) && vec4_ok(ivv) && vec4_ok(ov);
-    const long long work = (long long)N0 * lda_dim / (v4 ? 4 : 1);
-    if (v4) hipLaunchKernelGGL(infer_gather_kernel<4>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, tab, B, q->g_lda.n, q->g_feat.t0, ov);
-    else hipLaunchKernelGGL(infer_gather_kernel<1>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, tab, B, q->g_lda.n, q->g_feat.t0, ov);
-    TDNNF_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(infer_row_map_kernel, dim3((No + 255) / 256), dim3(256), 0, s, tab, B, Tout, q->row_map);
-  TDNNF_LAUNCH_CHECK();
   CK(tdnnf_affine_propagate(&lda_in, W(n->c_lda), lda_dim, bias(n->c_lda), lda_dim, &lda_out, s));
   tdnnf_tdnn_indexes ix1;
   memset(&ix1, 0, sizeof(ix1));
@@ -325,17 +317,13 @@ int forward_batch(tdnnf_infer *q, const tdnnf_mat *feats, const tdnnf_mat *iv, c
     q->fused = fused;
     q->fallback = fallback;
   }
+  q->f32_gemms += 2 * (long long)q->layers.size() + 6;  // lda, tdnn1, two per layer, prefinal-l, the head's three
   return TDNNF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, tdnnf_infer **out) {
-  TDNNF_REQUIRE(model && out, "infer_create: null argument");
+// the object behind both create entries (the model is checked): grids, BatchNorm table, arena; gemm_precision 3: the plane buffers as well
+int create_object(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, int gemm_precision, tdnnf_infer **out) {
   const tdnnf_net_config &c = model->cfg;
-  CK(infer_check_model(c, frames_per_chunk, "infer_create", "frames_per_chunk"));
   TDNNF_REQUIRE(max_chunks >= 1 && which_output >= 0 && which_output <= 1, "infer_create: max_chunks must be >= 1, which_output 0 or 1");
   tdnnf_infer *q = new tdnnf_infer();
   q->model = model;
@@ -367,12 +355,42 @@ int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chu
   Arena real;
   real.base = q->arena;
   layout(q, real);
+  if (gemm_precision == 3) {
+    rc = infer_planes_create(q);
+    if (rc != TDNNF_OK) {
+      tdnnf_infer_destroy(q);
+      return rc;
+    }
+  }
   *out = q;
   return TDNNF_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int tdnnf_infer_create(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, tdnnf_infer **out) {
+  TDNNF_REQUIRE(model && out, "infer_create: null argument");
+  CK(infer_check_model(model->cfg, frames_per_chunk, "infer_create", "frames_per_chunk"));
+  return create_object(model, frames_per_chunk, max_chunks, which_output, 0, out);
+}
+
+int tdnnf_infer_create_arith(const tdnnf_net *model, int frames_per_chunk, int max_chunks, int which_output, int gemm_precision, tdnnf_infer **out) {
+  TDNNF_REQUIRE(gemm_precision == 0 || gemm_precision == 3,
+                "infer_create_arith: gemm_precision %d: inference runs exact f32 (gemm_precision 0) or f16x3 (gemm_precision 3)", gemm_precision);
+  TDNNF_REQUIRE(max_chunks >= 1 && which_output >= 0 && which_output <= 1, "infer_create_arith: max_chunks must be >= 1, which_output 0 or 1");
+  TDNNF_REQUIRE(model && out, "infer_create_arith: null argument");
+  // the model's own cfg.gemm_precision is the trainer's arithmetic: this object reads the f32 parameters and statistics only
+  tdnnf_net_config c = model->cfg;
+  c.gemm_precision = 0;
+  CK(infer_check_model(c, frames_per_chunk, "infer_create_arith", "frames_per_chunk"));
+  return create_object(model, frames_per_chunk, max_chunks, which_output, gemm_precision, out);
+}
+
 void tdnnf_infer_destroy(tdnnf_infer *q) {
   if (!q) return;
+  infer_planes_destroy(q->planes);
   hipFree(q->arena);
   hipFree(q->table);
   delete q;
@@ -420,6 +438,7 @@ int tdnnf_infer_compute(tdnnf_infer *q, int num_utts, const int *frames_host, co
   TDNNF_REQUIRE(sumT < (1LL << 31) && sumR < (1LL << 31), "infer_compute: too many rows");
   const int nch = (int)(plan.size() / 4);
   q->fused = q->fallback = 0;
+  q->plane_gemms = q->f32_gemms = 0;
   if (nch == 0) return TDNNF_OK;
   hipStream_t s = (hipStream_t)stream;
   // ---- the chunk table of the whole call, uploaded once
@@ -446,9 +465,16 @@ int tdnnf_infer_compute(tdnnf_infer *q, int num_utts, const int *frames_host, co
   TDNNF_HIP(hipMemcpyAsync(q->table, q->host_table.data(), sizeof(int) * q->host_table.size(), hipMemcpyHostToDevice, s));
   // ---- the model's BatchNorm statistics as test-mode scale / offset (read at every call)
   TDNNF_HIP(infer_bn_coef(q->bn, q->nbn, q->coef, s));
+  if (q->planes) CK(infer_planes_begin(q, s));  // ... and its weights as f16 planes
   for (int k0 = 0; k0 < nch; k0 += q->max_chunks) {
     const int B = std::min(q->max_chunks, nch - k0);
-    CK(forward_batch(q, feats, ivectors, q->table + (size_t)kTab * k0, B, out, s, k0 == 0));
+    const int *tab = q->table + (size_t)kTab * k0;
+    if (q->planes) {
+      CK(infer_batch_input(q, feats, ivectors, tab, B, s));
+      CK(infer_planes_forward(q, tab, B, out, s, k0 == 0));
+    } else {
+      CK(forward_batch(q, feats, ivectors, tab, B, out, s, k0 == 0));
+    }
   }
   return TDNNF_OK;
 }
@@ -457,6 +483,13 @@ int tdnnf_infer_counts(const tdnnf_infer *q, int *fused_layers, int *fallback_pa
   TDNNF_REQUIRE(q, "infer_counts: null argument");
   if (fused_layers) *fused_layers = q->fused;
   if (fallback_passes) *fallback_passes = q->fallback;
+  return TDNNF_OK;
+}
+
+int tdnnf_infer_gemm_counts(const tdnnf_infer *q, long long *plane_gemms, long long *f32_gemms) {
+  TDNNF_REQUIRE(q, "infer_gemm_counts: null argument");
+  if (plane_gemms) *plane_gemms = q->plane_gemms;
+  if (f32_gemms) *f32_gemms = q->f32_gemms;
   return TDNNF_OK;
 }
 

@@ -68,6 +68,12 @@ struct PlanesGemmArgs {
   float *partial;
   long long partial_stride, ldp_m, ldp_n;
   int alt_seg_order;  // odd row tiles visit the K segments in reverse order (two taps = row shifts of one matrix; rows_gemm_kernels.h)
+  // The inference epilogue (planes_gemm_post() only -- planes_gemm() does not read these; plain launches, init_mode 1 or 2), in the order
+  // of RowsGemmArgs' col_scale / col_offset / post_add / row_map (gemm_f32.h):
+  //   v = acc / (s s') + bias;  ReLU;  v = v col_scale[n] + col_offset[n];  v += add_scale add[m][n];  C[row_map ? row_map[m] : m][n] = v
+  // (a row whose row_map entry is negative is not stored; `colstats` then covers the stored rows only)
+  const float *col_scale, *col_offset;  // both or neither (test-mode BatchNorm)
+  const int *row_map;
 };
 
 // P16 layout of an R x C matrix:  e16 P[kb][plane][row][16],  kb = c / 16, plane 0..np-1, row 0..R-1, R = lead + rows + tail
@@ -175,6 +181,8 @@ int planes_gemm_tile_rows(int N);
 int planes_gemm_launch_tile_rows(const PlanesGemmArgs &a);
 int planes_gemm_tile_cols(int N);
 hipError_t planes_gemm(const PlanesGemmArgs &a, hipStream_t s);
+// the same f16x3 product (np 2, row-major A planes, plain launch) with the inference epilogue (infer_planes.hip): same tiles as planes_gemm()
+hipError_t planes_gemm_post(const PlanesGemmArgs &a, hipStream_t s);
 // epilogue of a split-K launch whose slabs hold whole output rows (ksplit > 1, ntap <= 1, ldp_n == 1): C[m][n] = f(scale * sum_sp partial[sp][m][n])
 // with the launch's init / bias / addend / ReLU rules
 hipError_t planes_splitk_finish(const PlanesGemmArgs &a, hipStream_t s);

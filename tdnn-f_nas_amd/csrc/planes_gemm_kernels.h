@@ -35,7 +35,9 @@ struct PlanesTile {
 // columns are 16 K-block chunks of 16 x 32-byte row records, staged as [chunk pair][row 0..15][chunk parity][32 bytes] and read
 // with ds_read_b64_tr_b16 (gfx950's transposing LDS read: a 16-lane group fetches 4 rows x 16 columns and every lane receives one
 // column), two reads per operand register pair; rows of a 32-lane half cover 256 contiguous bytes: conflict-free.
-template <int NP, int WM, int WN, int TM, int TN, bool ATR = false>
+// POST: the inference epilogue (PlanesGemmArgs::col_scale / col_offset / row_map and the addend AFTER the ReLU); the other
+// instantiations do not read those fields and compile to what they were without it.
+template <int NP, int WM, int WN, int TM, int TN, bool ATR = false, bool POST = false>
 __global__ __launch_bounds__(WM *WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void planes_gemm_kernel(const PlanesGemmArgs p, int ntm, int ntn) {
   typedef typename Plane<NP>::V8 V8;
   typedef PlanesTile<NP, WM, WN, TM, TN> Tile;
@@ -371,6 +373,16 @@ __global__ __launch_bounds__(WM *WN * 64) __attribute__((amdgpu_waves_per_eu(2, 
         const int n = nw + c4;
         float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p.init_mode == 1 && col_on) bias4 = *reinterpret_cast<const float4 *>(p.bias + n);
+        float csc[4] = {1.f, 1.f, 1.f, 1.f}, cof[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (POST) {
+          if (p.col_scale && col_on) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+              csc[e] = p.col_scale[n + e];
+              cof[e] = p.col_offset[n + e];
+            }
+          }
+        }
         const int mrow0 = m0 + (wm * TM + i) * 32 + rr;
         float4 addv[8], cold[8];
 #pragma unroll
@@ -390,6 +402,23 @@ __global__ __launch_bounds__(WM *WN * 64) __attribute__((amdgpu_waves_per_eu(2, 
           const float4 a4 = *reinterpret_cast<const float4 *>(scr + (rr + 4 * q) * LDW + c4);
           float v[4] = {a4.x * sc + bias4.x + cold[q].x + p.add_scale * addv[q].x, a4.y * sc + bias4.y + cold[q].y + p.add_scale * addv[q].y,
                         a4.z * sc + bias4.z + cold[q].z + p.add_scale * addv[q].z, a4.w * sc + bias4.w + cold[q].w + p.add_scale * addv[q].w};
+          if constexpr (POST) {
+            const float b4[4] = {bias4.x, bias4.y, bias4.z, bias4.w}, s4[4] = {a4.x, a4.y, a4.z, a4.w}, d4[4] = {addv[q].x, addv[q].y, addv[q].z, addv[q].w};
+            const int mo = p.row_map ? p.row_map[m] : m;
+            if (mo < 0) continue;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+              float x = s4[e] * sc + b4[e];
+              if (p.relu) x = floor_keep_nan(x, 0.f);
+              if (p.col_scale) x = x * csc[e] + cof[e];
+              if (p.add) x += p.add_scale * d4[e];
+              v[e] = x;
+              vs1[ch][e] += x;
+              vs2[ch][e] += x * x;
+            }
+            *reinterpret_cast<float4 *>(p.C + (long long)mo * p.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
+            continue;
+          }
 #pragma unroll
           for (int e = 0; e < 4; e++) {
             if (p.relu) v[e] = floor_keep_nan(v[e], 0.f);
@@ -409,6 +438,18 @@ __global__ __launch_bounds__(WM *WN * 64) __attribute__((amdgpu_waves_per_eu(2, 
           for (int r = 0; r < 16; r++) {
             const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
             if (m >= p.M) continue;
+            if constexpr (POST) {
+              const int mo = p.row_map ? p.row_map[m] : m;
+              if (mo < 0) continue;
+              float x = acc[i][j][r] * sc + bias;
+              if (p.relu) x = floor_keep_nan(x, 0.f);
+              if (p.col_scale) x = x * p.col_scale[n] + p.col_offset[n];
+              if (p.add && m >= p.add_lo && m < p.add_hi) x += p.add_scale * p.add[(long long)(m - p.add_lo) * p.ldadd + n];
+              p.C[(long long)mo * p.ldc + n] = x;
+              cs1[j] += x;
+              cs2[j] += x * x;
+              continue;
+            }
             float *c = p.C + (long long)m * p.ldc + (long long)tap * p.tap_off_c + n;
             float v = acc[i][j][r] * sc + bias;
             if (p.init_mode == 0) v += *c;

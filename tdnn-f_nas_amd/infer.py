@@ -13,28 +13,45 @@ import numpy as np
 from . import hipabi, trainer
 
 OUTPUTS = {"output": 0, "output-xent": 1}
+ARITHMETICS = {"f32": 0, "f16x3": 3}  # name -> gemm_precision of tdnnf_infer_create_arith
+
+
+def arithmetic_precision(name):
+    """gemm_precision of an arithmetic name; ValueError for any other (no library call)."""
+    if not isinstance(name, str) or name not in ARITHMETICS:
+        raise ValueError("arithmetic must be one of %s, not %r" % (sorted(ARITHMETICS), name))
+    return ARITHMETICS[name]
 
 
 class AcousticModel:
-    """Forward-only view of a ChainNet's model: reads its parameters and BatchNorm statistics at every compute."""
+    """Forward-only view of a ChainNet's model: reads its parameters and BatchNorm statistics at every compute.
+    arithmetic "f32" (default): exact f32 GEMMs; "f16x3": every GEMM on the 16-bit matrix cores from operands split into two
+    scaled f16 planes (three products, f32 accumulation), whatever arithmetic the model was trained in."""
 
-    def __init__(self, net, frames_per_chunk=150, max_chunks=256, output="output"):
+    def __init__(self, net, frames_per_chunk=150, max_chunks=256, output="output", arithmetic="f32"):
+        precision = arithmetic_precision(arithmetic)
+        self.arithmetic = arithmetic
         self.lib = hipabi.load()
         self.net = net  # keeps the model alive
         self.frames_per_chunk, self.max_chunks, self.output = int(frames_per_chunk), int(max_chunks), output
         self.fsf = int(net.cfg.frame_subsampling)
         self.num_pdfs = int(net.cfg.num_pdfs)
         self.h = C.c_void_p()
-        hipabi.check(self.lib.tdnnf_infer_create(net.h, self.frames_per_chunk, self.max_chunks, OUTPUTS[output], C.byref(self.h)))
+        if precision == 0:
+            hipabi.check(self.lib.tdnnf_infer_create(net.h, self.frames_per_chunk, self.max_chunks, OUTPUTS[output], C.byref(self.h)))
+        else:
+            hipabi.check(self.lib.tdnnf_infer_create_arith(net.h, self.frames_per_chunk, self.max_chunks, OUTPUTS[output], precision,
+                                                           C.byref(self.h)))
 
     @classmethod
-    def from_model_file(cls, path, frames_per_chunk=150, max_chunks=256, output="output"):
+    def from_model_file(cls, path, frames_per_chunk=150, max_chunks=256, output="output", arithmetic="f32"):
         """A model read from an nnet3 raw model file (tdnnf_net_config_from_model + tdnnf_net_read_model)."""
+        arithmetic_precision(arithmetic)
         cfg = trainer.config_from_model(path, frames_per_chunk=frames_per_chunk, num_sequences=1)
         cfg.cv_update = 1  # (no dropout masks; the statistics are only read)
         net = trainer.ChainNet(cfg)
         net.read_model(path)
-        return cls(net, frames_per_chunk, max_chunks, output)
+        return cls(net, frames_per_chunk, max_chunks, output, arithmetic)
 
     def close(self):
         if getattr(self, "h", None):
@@ -86,6 +103,12 @@ class AcousticModel:
         """(fused_layers, fallback_passes) of the last compute."""
         a, b = C.c_int(), C.c_int()
         hipabi.check(self.lib.tdnnf_infer_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def gemm_counts(self):
+        """(plane_gemms, f32_gemms) of the last compute: GEMM launches that ran from f16 planes / on the f32 kernels."""
+        a, b = C.c_longlong(), C.c_longlong()
+        hipabi.check(self.lib.tdnnf_infer_gemm_counts(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
 

@@ -4,10 +4,12 @@
 Prints one JSON line: input frames/s and ms per call, the GEMM rate against the 157.3 TFLOP/s exact-f32 MFMA peak (GEMM FLOPs
 from the library's own launch accounting, tdnnf_profile_*, in a separate call), the chunk-context overhead (F + context) / F
 and the fused / fallback counts.
+--gemm f16x3 runs the same calls in f16x3 (AcousticModel(arithmetic="f16x3")) and adds the plane / f32 GEMM launch counts and, from the
+profiled call's HIP events, the time of the GEMMs and of the splits into planes (split_share = splits / (GEMMs + splits)).
 --online adds streaming inference (tdnnf_online_step) of the same model: steady-state steps of F in {30, 150} input frames for 1, 16
 and 64 concurrent streams -- input frames/s and ms per step -- and the algorithmic row ratio: the GEMM rows of a chunk of width F
 (from the chunk grids) over those of a step (tdnnf_online_counts).
-usage (GPU box): python tools/infer_bench.py [--calls K] [--utts N] [--max-chunks M] [--online [--steps K]]"""
+usage (GPU box): python tools/infer_bench.py [--calls K] [--utts N] [--max-chunks M] [--gemm f32|f16x3] [--online [--steps K]]"""
 import argparse
 import ctypes as C
 import json
@@ -98,9 +100,12 @@ def main():
     ap.add_argument("--utts", type=int, default=200)
     ap.add_argument("--max-chunks", type=int, default=256)
     ap.add_argument("--widths", default="51,150")
+    ap.add_argument("--gemm", default="f32", choices=["f32", "f16x3"], help="arithmetic of the whole-utterance GEMMs")
     ap.add_argument("--online", action="store_true", help="also time streaming steps (F 30 / 150, 1 / 16 / 64 streams)")
     ap.add_argument("--steps", type=int, default=50, help="--online: timed steps per configuration")
     args = ap.parse_args()
+    if args.online and args.gemm != "f32":
+        ap.error("--gemm %s: streaming inference runs exact f32 only; --online takes --gemm f32" % args.gemm)
     pkg = ge.load_package()
     lib = pkg.hipabi.load()
     cfg = pkg.trainer.make_config(frames_per_chunk=150, num_sequences=1, cv_update=1)  # 7q graph, 1536 / 6034
@@ -111,9 +116,9 @@ def main():
     lengths = rng.integers(300, 1501, size=args.utts)
     utts = [(rng.standard_normal((int(T), 40)).astype(np.float32), rng.standard_normal((-(-int(T) // 10), 100)).astype(np.float32)) for T in lengths]
     frames = int(lengths.sum())
-    res = dict(metric="infer_7q_full_width", utterances=args.utts, input_frames=frames, max_chunks=args.max_chunks, peak_tflops=PEAK_TFLOPS)
+    res = dict(metric="infer_7q_full_width", gemm=args.gemm, utterances=args.utts, input_frames=frames, max_chunks=args.max_chunks, peak_tflops=PEAK_TFLOPS)
     for F in [int(w) for w in args.widths.split(",")]:
-        am = pkg.infer.AcousticModel(net, frames_per_chunk=F, max_chunks=args.max_chunks)
+        am = pkg.infer.AcousticModel(net, frames_per_chunk=F, max_chunks=args.max_chunks, arithmetic=args.gemm)
         probe = pkg.trainer.ChainNet(pkg.trainer.make_config(frames_per_chunk=F, num_sequences=1, cv_update=1), share=net)
         context = probe.num_t_in - F
         probe.close()
@@ -129,16 +134,24 @@ def main():
         pkg.hipabi.check(lib.tdnnf_profile_enable(1))
         am.compute(utts)
         torch.cuda.synchronize()
-        flops = 0.0
-        for k in range(4):
+        flops, gemm_ms, split_ms = 0.0, 0.0, 0.0
+        for k in (0, 1, 2, 3, 7):  # the GEMM classes; 7: the splits into planes
             n, t, fl = C.c_double(), C.c_double(), C.c_double()
             pkg.hipabi.check(lib.tdnnf_profile_read(k, C.byref(n), C.byref(t), C.byref(fl)))
-            flops += fl.value
+            if k == 7:
+                split_ms = t.value
+            else:
+                flops += fl.value
+                gemm_ms += t.value
         pkg.hipabi.check(lib.tdnnf_profile_enable(0))
         fused, fallback = am.counts()
         res[f"F{F}"] = dict(frames_per_s=round(frames / (ms / 1e3)), ms_per_call=round(ms, 2), gemm_tflop=round(flops / 1e12, 3),
                            gemm_tflops_per_s=round(flops / (ms / 1e3) / 1e12, 1), of_peak=round(flops / (ms / 1e3) / 1e12 / PEAK_TFLOPS, 3),
                            context_overhead=round((F + context) / F, 3), fused_layers=fused, fallback_passes=fallback)
+        if args.gemm != "f32":
+            planes, f32 = am.gemm_counts()
+            res[f"F{F}"].update(plane_gemms=planes, f32_gemms=f32, gemm_ms=round(gemm_ms, 2), split_ms=round(split_ms, 2),
+                                split_share=round(split_ms / max(gemm_ms + split_ms, 1e-9), 3))
         am.close()
     if args.online:
         res["online"] = online(pkg, net, args.steps)
