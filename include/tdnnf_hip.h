@@ -324,6 +324,23 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *, const tdnnf_supervision 
                                float l2_regularize, float xent_regularize, double *results_dev,
                                tdnnf_mat *nnet_output_deriv, tdnnf_mat *xent_deriv, void *workspace_dev,
                                size_t workspace_bytes, tdnnf_stream);
+/* The objective alone -- chain::ComputeChainObjfAndDeriv with null derivative pointers, what nnet3-chain-compute-prob and
+   nnet3-chain-combine call.  results_dev as above, the failure path included (an objf that is not finite: [0] = -10 * weight, [5] = 0,
+   [6] = 0); nothing but results_dev and the workspace is written.  nnet_output and xent_output may be sub-matrix views.
+   The denominator runs its forward recursion only and keeps no alpha per frame: the persistent form alternates between two state
+   vectors (in LDS, or in the workspace for graphs whose vectors do not fit), the wide form between two alpha frames.  The form follows
+   tdnnf_chain_set_denominator_mode and the graph's size as for tdnnf_chain_objf_and_deriv, except that the persistent form is ALWAYS one
+   workgroup per sequence (modes 1 and 3 are the same here): an evaluation call should not need its workgroups co-resident, as the
+   multi-workgroup recursion does, and its result should not depend on how many sequences the minibatch has, as the choice of that
+   recursion does.  Everything runs on the caller's stream.  The numerator runs its recursion, and its posterior pass only when
+   xent_output is given (it then forms the xent objective and writes no posterior matrix).
+   The workspace holds the per-sequence sums, the numerator's scratch and the denominator's two vectors (wide form: also its
+   transposed exp(nnet_output) and partial rows) -- at 4 000 states, 128 x 500 frames a few MB against 1 GB; a workspace of
+   tdnnf_chain_workspace_bytes is never smaller and is accepted too.  The l2 term is summed in a fixed order: two calls give the same bits. */
+size_t tdnnf_chain_objf_workspace_bytes(const tdnnf_den_graph *, int num_sequences, int frames_per_sequence);
+int tdnnf_chain_objf(const tdnnf_den_graph *, const tdnnf_supervision *, const tdnnf_mat *nnet_output,
+                     const tdnnf_mat *xent_output /* may be NULL */, float leaky_hmm_coefficient, float l2_regularize,
+                     double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
 /* diagnostics (tools/num_bench.py): ONE part of the numerator's work as tdnnf_chain_objf_and_deriv enqueues it -- part 1 the forward-backward
    recursion, 4 the posterior pass behind the xent head (xent_deriv, xent objective), 2 the pass that adds the posteriors to nnet_output_deriv
    (with the kernels that finish the objective).  Parts 4 and 2 read what part 1 left in the workspace / the supervision. */
@@ -541,6 +558,20 @@ int tdnnf_net_set_buffers(tdnnf_net *, float *params_dev, float *grads_dev);
    (ReLU stats / self-repair coin flips). */
 int tdnnf_net_forward_backward(tdnnf_net *, const tdnnf_mat *feats, const tdnnf_mat *ivectors, const tdnnf_den_graph *,
                                const tdnnf_supervision *, double *results_dev, long long step, tdnnf_stream);
+/* The objective of one minibatch without derivatives (nnet3-chain-compute-prob, the evaluations of nnet3-chain-combine): the forward
+   pass of tdnnf_net_forward_backward on the same buffers, then tdnnf_chain_objf -- the denominator beside the xent head's forward pass,
+   everything joined onto `stream` before the call returns.  Every configuration tdnnf_net_forward_backward accepts; draws from
+   tdnnf_net_set_random_draws as there.  Only the parameter buffer is used: the gradient buffer is neither read nor written.  No backward-data GEMM, weight
+   gradient, natural-gradient pass or refresh upload, ReLU statistics or self-repair, gradient-scratch fill, W^T transpose; no
+   derivative buffer is written.
+   flags = 0: the call leaves no trace in the net -- parameters, gradients, BatchNorm and ReLU statistics, preconditioner state and the
+   step count are as before, and a training run with such calls between its steps has the bits of the run without them.
+   TDNNF_OBJECTIVE_STORE_BATCHNORM_STATS (ignored when cv_update != 0): the BatchNorm statistics accumulate exactly as in the forward
+   half of tdnnf_net_forward_backward (RecomputeStats); ReLU statistics stay untouched -- they come from the backward sweep.
+   The call marks no phase boundaries: tdnnf_net_phase_times keeps reporting the last training step's times. */
+#define TDNNF_OBJECTIVE_STORE_BATCHNORM_STATS 1
+int tdnnf_net_objective(tdnnf_net *, const tdnnf_mat *feats, const tdnnf_mat *ivectors, const tdnnf_den_graph *,
+                        const tdnnf_supervision *, double *results_dev, int flags, tdnnf_stream);
 /* Data-parallel callers may overlap the gradient all-reduce with the backward pass: the flat gradient buffer is final
    bucket by bucket -- contiguous ranges, whole layers, >= 16 MB where the model allows, in the order backward finishes
    them (heads + prefinal-l first, then tdnnf layers from the top down, tdnn1 last; together they cover the buffer).

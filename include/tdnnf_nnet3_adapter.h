@@ -360,6 +360,17 @@ inline void ChainObjfAndDeriv(const tdnnf_den_graph *den_graph, const tdnnf_supe
   Check(tdnnf_chain_objf_and_deriv(den_graph, supervision, &vy, xent_output ? &vx : nullptr, leaky_hmm_coefficient, l2_regularize,
                                    xent_regularize, results_dev, &vd, xent_deriv ? &vdx : nullptr, workspace_dev, workspace_bytes, stream));
 }
+// The same call with null derivative pointers (what nnet3-chain-compute-prob and nnet3-chain-combine make): the objective only, nothing
+// written but results_dev.  workspace: tdnnf_chain_objf_workspace_bytes(graph, num_sequences, frames) -- no per-frame alpha array.
+template <class CuMat>
+inline void ChainObjf(const tdnnf_den_graph *den_graph, const tdnnf_supervision *supervision, const CuMat &nnet_output, const CuMat *xent_output,
+                      float leaky_hmm_coefficient, float l2_regularize, double *results_dev, void *workspace_dev, size_t workspace_bytes,
+                      tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output), vx;
+  if (xent_output) vx = View(*xent_output);
+  Check(tdnnf_chain_objf(den_graph, supervision, &vy, xent_output ? &vx : nullptr, leaky_hmm_coefficient, l2_regularize, results_dev, workspace_dev,
+                         workspace_bytes, stream));
+}
 
 // ConstrainOrthonormalInternal nnet-utils.cc:914-1032 on a CuMatrixBase with rows <= cols (pass the transpose otherwise, :1068-1075)
 template <class CuMat>

@@ -2003,5 +2003,18 @@ inline Component *Component::NewComponentOfType(const std::string &t) {
   return nullptr;  // (the reference returns NULL for unknown types as well, :279)
 }
 
+// ------------------------------------------------------------------------------------------------ objective without derivatives
+// What NnetChainComputeProb::ProcessOutputs (nnet3-chain-compute-prob, nnet3-chain-combine; UPSTREAM) asks of
+// chain::ComputeChainObjfAndDeriv when it computes no derivatives: the objective of one minibatch into results_dev (8 device doubles,
+// tdnnf_hip.h), on the hooks' stream.  `workspace` grows to tdnnf_chain_objf_workspace_bytes -- it holds no alpha per frame -- and is reused
+// from call to call.
+inline void ComputeChainObjf(const tdnnf_den_graph *den_graph, const tdnnf_supervision *supervision, int32 num_sequences, int32 frames_per_sequence,
+                             const CuMatrixBase &nnet_output, const CuMatrixBase *xent_output, float leaky_hmm_coefficient, float l2_regularize,
+                             double *results_dev, Scratch *workspace) {
+  const size_t bytes = tdnnf_chain_objf_workspace_bytes(den_graph, num_sequences, frames_per_sequence);
+  tdnnf_adapter::ChainObjf(den_graph, supervision, nnet_output, xent_output, leaky_hmm_coefficient, l2_regularize, results_dev, workspace->Get(bytes), bytes,
+                           Hooks().stream);
+}
+
 }  // namespace tdnnf_nnet3
 #endif  // TDNNF_NNET3_COMPONENTS_H_

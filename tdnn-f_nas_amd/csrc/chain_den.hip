@@ -96,6 +96,38 @@ ChainBufs chain_bufs(const tdnnf_den_graph *g, int B, int T, void *ws) {
   return b;
 }
 
+ChainBufs chain_objf_bufs(const tdnnf_den_graph *g, int B, int T, void *ws, size_t *bytes) {
+  ChainBufs b;
+  b.p = chain_plan(g, B, T, B * 4 * (T + 1));  // (form, Hs, groups and la_floats as the full entry's; the denominator's arrays are this entry's own)
+  ChainPlan &p = b.p;
+  const size_t Bw = (size_t)p.NG * p.SG;
+  p.split = false;
+  p.lds_fwd = den_lds(g, p.lds_state ? 2 : 0);
+  p.lds_bwd = 0;
+  p.alpha_floats = p.wide ? 2 * Bw * p.Hs : 0;
+  p.asum_floats = p.wide ? ((size_t)B * (T + 1) + 31) & ~(size_t)31 : 0;
+  p.gstate_floats = p.wide ? 2 * Bw * p.wide_blocks + (size_t)T * g->P * Bw : (p.lds_state ? 0 : 2 * (size_t)B * p.Hs);
+  uintptr_t at = (uintptr_t)ws;
+  auto take = [&at](size_t n, size_t align) {
+    at = (at + align - 1) & ~(uintptr_t)(align - 1);
+    const uintptr_t r = at;
+    at += n;
+    return r;
+  };
+  b.den_lp = (double *)take(sizeof(double) * (3 * (size_t)B + 2 + kObjfL2Parts), 8);
+  b.num_lp = b.den_lp + B;
+  b.xent = b.num_lp + B;
+  b.l2sum = b.xent + B;
+  b.l2part = b.l2sum + 2;
+  b.la = (double *)take(sizeof(float) * p.la_floats, 8);
+  b.lb = b.la + (p.la_floats - 2) / 4;
+  b.alpha = (float *)take(sizeof(float) * p.alpha_floats, 128);  // (the wide form gathers 64- / 128-byte runs: whole lines)
+  b.asum = (float *)take(sizeof(float) * p.asum_floats, 128);
+  b.gstate = (float *)take(sizeof(float) * p.gstate_floats, 128);
+  if (bytes) *bytes = (size_t)(at - (uintptr_t)ws) + 3 * 128;  // (three alignments, each may skip up to 127 bytes more under another base address)
+  return b;
+}
+
 // Bytes at the END of the workspace that only the split persistent form (den_forward beside den_beta, then den_gamma) touches: a caller
 // that always passes beside_other_work = true to chain_den may allocate that much less.
 size_t chain_split_region_bytes(const tdnnf_den_graph *g, int B, int T) {
@@ -346,6 +378,38 @@ int den_split(const DenCall &c, hipStream_t caller_aux, hipEvent_t ev_recursions
   return TDNNF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- objective only
+template <bool LDS_STATE, bool FAST>
+int den_logprob(const DenCall &c) {
+  TDNNF_HIP(lds_opt_in(den_logprob_kernel<LDS_STATE, FAST>, c.b.p.lds_fwd));
+  hipLaunchKernelGGL((den_logprob_kernel<LDS_STATE, FAST>), dim3(c.B), dim3(kDenThreads), c.b.p.lds_fwd, c.s, c.gd, c.y, c.B, c.T, c.leaky, c.b.p.Hs, c.b.den_lp,
+                     c.b.gstate);
+  return TDNNF_OK;
+}
+// den_wide's forward recursion on two alpha frames, on one stream
+int den_wide_logprob(const DenCall &c) {
+  const tdnnf_den_graph *g = c.g;
+  const ChainBufs &b = c.b;
+  const int B = c.B, T = c.T, Hs = b.p.Hs, P = g->P, nsl = kWideSlices;
+  const WideDims d{B, b.p.NG, b.p.SG};
+  const size_t Bw = (size_t)d.NG * d.SG, frame = Bw * Hs, prow = Bw * b.p.wide_blocks;
+  const int nb_dst = (g->by_dst.nslices + nsl - 1) / nsl;
+  float *part = b.gstate, *xT = part + 2 * prow;
+  const dim3 blk(256), tr((P + 63) / 64, (B + 63) / 64, T), ini(grid_for((long long)frame, 256));
+  hipLaunchKernelGGL(den_wide_prep_kernel, tr, blk, 0, c.s, c.y, d, P, xT);
+  hipLaunchKernelGGL(den_wide_init_kernel, ini, blk, 0, c.s, c.gd, d, Hs, false, b.alpha, b.asum);
+  for (int t = 1; t <= T; t++) {
+    const float *part_prev = t > 1 ? part + (size_t)((t - 1) & 1) * prow : nullptr;
+    float *part_cur = part + (size_t)(t & 1) * prow;
+    if (d.SG == 16) hipLaunchKernelGGL((den_wide_fwd_kernel<16, true>), dim3(nb_dst * d.NG), blk, 0, c.s, c.gd, d, t, c.leaky, xT, b.alpha, b.asum, Hs, part_prev, nb_dst, nsl, part_cur);
+    else hipLaunchKernelGGL((den_wide_fwd_kernel<32, true>), dim3(nb_dst * d.NG), blk, 0, c.s, c.gd, d, t, c.leaky, xT, b.alpha, b.asum, Hs, part_prev, nb_dst, nsl, part_cur);
+  }
+  if (d.SG == 16) hipLaunchKernelGGL(den_wide_sum_kernel<16>, dim3(d.NG), blk, 0, c.s, part + (size_t)(T & 1) * prow, nb_dst, d, b.asum + (size_t)T * B);
+  else hipLaunchKernelGGL(den_wide_sum_kernel<32>, dim3(d.NG), blk, 0, c.s, part + (size_t)(T & 1) * prow, nb_dst, d, b.asum + (size_t)T * B);
+  hipLaunchKernelGGL(den_wide_total_kernel, dim3((B + 255) / 256), blk, 0, c.s, c.gd, B, T, c.leaky, b.asum, b.den_lp);
+  return TDNNF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- serial
 template <bool FAST>
 int den_serial_forward(const DenCall &c, size_t lds) {
@@ -390,6 +454,21 @@ int chain_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
   return TDNNF_OK;
 }
 
+// The denominator of tdnnf_chain_objf: den log-probs -> the objective-only workspace (chain_objf_bufs), nothing else written.  The form follows
+// the plan (persistent or wide); the persistent form is always ONE workgroup per sequence, on this stream alone.
+int chain_objf_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, float leaky, void *ws, hipStream_t s) {
+  const int B = sp->B, T = sp->T;
+  const DenCall c{g, den_dev(g), view(y), MatView{nullptr, 0, 0, 0}, B, T, leaky, 0.f, chain_objf_bufs(g, B, T, ws), s};
+  ProfHbmRange prof(6, (double)B * T * (8.0 * g->A + 4.0 * g->P), s);  // (the arcs once and the output row once per (frame, sequence))
+  int rc;
+  if (c.b.p.wide) rc = den_wide_logprob(c);
+  else if (!c.b.p.lds_state) rc = den_logprob<false, false>(c);
+  else rc = den_fast(g, {&g->by_dst}) ? den_logprob<true, true>(c) : den_logprob<true, false>(c);
+  if (rc) return rc;
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+
 }  // namespace tdnnf
 
 using namespace tdnnf;
@@ -420,6 +499,13 @@ size_t tdnnf_chain_workspace_bytes(const tdnnf_den_graph *g, int B, int T) {
   if (!g || B <= 0 || T <= 0) return 0;
   ChainPlan p = chain_plan(g, B, T, B * 4 * (T + 1));
   return sizeof(double) * (3 * (size_t)B + 2) + sizeof(float) * (p.alpha_floats + p.asum_floats + p.gstate_floats + p.la_floats) + 768;
+}
+
+size_t tdnnf_chain_objf_workspace_bytes(const tdnnf_den_graph *g, int B, int T) {
+  if (!g || B <= 0 || T <= 0) return 0;
+  size_t bytes = 0;
+  chain_objf_bufs(g, B, T, nullptr, &bytes);
+  return bytes;
 }
 
 }  // extern "C"

@@ -138,6 +138,30 @@ __global__ __launch_bounds__(256) void sumsq_kernel(MatView y, double *out) {
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
 }
+// the same sum without atomics (tdnnf_chain_objf: the l2 term has the same bits on every call): part[block], then their sum in order
+__global__ __launch_bounds__(1024) void sumsq_parts_kernel(MatView y, double *part) {
+  __shared__ double red[16];
+  double s = 0;
+  const long long total = (long long)y.rows * y.cols;
+  for (long long e = blockIdx.x * 1024LL + threadIdx.x; e < total; e += gridDim.x * 1024LL) {
+    const double v = y.data[(size_t)(e / y.cols) * y.stride + e % y.cols];
+    s += v * v;
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0;
+    for (int w = 0; w < 16; w++) t += red[w];
+    part[blockIdx.x] = t;
+  }
+}
+__global__ void sum_parts_kernel(const double *part, int n, double *out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double t = 0;
+  for (int i = 0; i < n; i++) t += part[i];
+  out[0] = t;
+}
 __global__ void zero_rows_kernel(MatView m) {
   const long long total = (long long)m.rows * m.cols;
   for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += gridDim.x * 256LL)
@@ -196,9 +220,9 @@ float chain_supervision_weight(const tdnnf_supervision *sp) { return sp->weight;
 // In two launchable halves: the recursion needs the chain output only (the trainer starts it beside the denominator, under the
 // xent head's forward pass: 1.35 ms of one wave per sequence walking 2 x 500 dependent frames that the step otherwise waited for),
 // the xent posteriors need the recursion and the xent head's log-softmax.
-int chain_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph *g, const tdnnf_mat *y, void *ws, hipStream_t s) {
-  const int B = sp->B, T = sp->T;
-  ChainBufs b = chain_bufs(g, B, T, ws);
+namespace {
+int num_recursion(const tdnnf_supervision *sp, const tdnnf_mat *y, const ChainBufs &b, hipStream_t s) {
+  const int B = sp->B;
   const MatView none{nullptr, 0, 0, 0};
   NumCall c;
   int rc = num_call(sp, b, &c);
@@ -211,10 +235,9 @@ int chain_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph *g, c
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
 }
-int chain_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, float xent_regularize,
-                   tdnnf_mat *xent_deriv, void *ws, hipStream_t s, bool xent_deriv_initialised) {
-  const int B = sp->B, T = sp->T;
-  ChainBufs b = chain_bufs(g, B, T, ws);
+int num_xent(const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, float xent_regularize, tdnnf_mat *xent_deriv, const ChainBufs &b,
+             hipStream_t s, bool xent_deriv_initialised) {
+  const int B = sp->B;
   MatView yv = view(y);
   MatView xdv = xent_deriv ? view(xent_deriv) : MatView{nullptr, 0, 0, 0};
   MatView xov = xent_output ? view(xent_output) : MatView{nullptr, 0, 0, 0};
@@ -231,6 +254,14 @@ int chain_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const 
                        xdv, xent_regularize, 4);
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
+}
+}  // namespace
+int chain_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph *g, const tdnnf_mat *y, void *ws, hipStream_t s) {
+  return num_recursion(sp, y, chain_bufs(g, sp->B, sp->T, ws), s);
+}
+int chain_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, float xent_regularize,
+                   tdnnf_mat *xent_deriv, void *ws, hipStream_t s, bool xent_deriv_initialised) {
+  return num_xent(sp, y, xent_output, xent_regularize, xent_deriv, chain_bufs(g, sp->B, sp->T, ws), s, xent_deriv_initialised);
 }
 int chain_num(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output,
               float xent_regularize, tdnnf_mat *xent_deriv, void *ws, hipStream_t s, bool xent_deriv_initialised) {
@@ -263,6 +294,30 @@ int chain_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const td
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
 }
+// ---- the objective alone (tdnnf_chain_objf, tdnnf_net_objective), on the objective-only workspace (chain_plan.h): the same recursion, the
+// posterior pass with no derivative to write -- it then forms the xent objective only -- and the kernels that finish the objective
+int chain_objf_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph *g, const tdnnf_mat *y, void *ws, hipStream_t s) {
+  return num_recursion(sp, y, chain_objf_bufs(g, sp->B, sp->T, ws), s);
+}
+// xent_output null: the xent objective is zero
+int chain_objf_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, void *ws, hipStream_t s) {
+  const ChainBufs b = chain_objf_bufs(g, sp->B, sp->T, ws);
+  if (xent_output) return num_xent(sp, y, xent_output, 0.f, nullptr, b, s, false);
+  TDNNF_HIP(hipMemsetAsync(b.xent, 0, sizeof(double) * sp->B, s));
+  return TDNNF_OK;
+}
+int chain_objf_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, float l2_regularize, double *results, void *ws, hipStream_t s) {
+  const int B = sp->B, T = sp->T;
+  const ChainBufs b = chain_objf_bufs(g, B, T, ws);
+  if (l2_regularize != 0.f) {
+    hipLaunchKernelGGL(sumsq_parts_kernel, dim3(kObjfL2Parts), dim3(1024), 0, s, view(y), b.l2part);
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(64), 0, s, b.l2part, kObjfL2Parts, b.l2sum);
+  }
+  hipLaunchKernelGGL(chain_finalize_kernel, dim3(1), dim3(64), 0, s, b.num_lp, b.den_lp, b.xent, l2_regularize != 0.f ? b.l2sum : nullptr, B, T, sp->weight,
+                     l2_regularize, results);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
 }  // namespace tdnnf
 
 using namespace tdnnf;
@@ -284,6 +339,21 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision
   if ((rc = chain_den(g, sp, y, leaky, deriv, ws, s))) return rc;
   if ((rc = chain_num(g, sp, y, xent_output, xent_regularize, xent_deriv, ws, s))) return rc;
   return chain_finish(g, sp, y, l2_regularize, results, deriv, xent_deriv, ws, s);
+}
+
+int tdnnf_chain_objf(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, float leaky, float l2_regularize,
+                     double *results, void *ws, size_t ws_bytes, tdnnf_stream stream) {
+  TDNNF_REQUIRE(g && sp && mat_ok(y) && results, "chain_objf: bad arguments");
+  const int B = sp->B, T = sp->T;
+  TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P, "chain_objf: nnet_output must be (B*T) x num_pdfs, t-major");
+  TDNNF_REQUIRE(!xent_output || (mat_ok(xent_output) && same_dim(y, xent_output)), "chain_objf: bad xent_output");
+  TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_objf_workspace_bytes(g, B, T), "chain_objf: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = chain_objf_den(g, sp, y, leaky, ws, s))) return rc;
+  if ((rc = chain_objf_num_recursion(sp, g, y, ws, s))) return rc;
+  if ((rc = chain_objf_num_xent(g, sp, y, xent_output, ws, s))) return rc;
+  return chain_objf_finish(g, sp, y, l2_regularize, results, ws, s);
 }
 
 int tdnnf_chain_numerator_part(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, int part, double *results, tdnnf_mat *deriv,

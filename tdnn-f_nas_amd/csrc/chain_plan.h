@@ -27,10 +27,17 @@ struct ChainPlan {
 struct ChainBufs {
   ChainPlan p;
   double *den_lp, *num_lp, *xent, *l2sum;
+  double *l2part = nullptr;  // objective-only layout: kObjfL2Parts partial sums of the l2 term
   float *alpha, *asum, *gstate;
   double *la, *lb;  // numerator log alpha / log beta
 };
 // (not part of the library's symbol table: chain_den.hip and chain_num.hip only)
 __attribute__((visibility("hidden"))) ChainBufs chain_bufs(const tdnnf_den_graph *g, int B, int T, void *ws);
+// The objective-only layout (tdnnf_chain_objf): [doubles: den_lp[B], num_lp[B], xent[B], l2sum[2], l2part[kObjfL2Parts]] [la, lb] and what the
+// denominator form of the plan needs for TWO state vectors -- nothing (persistent, vectors in LDS), gstate = 2 Hs floats per sequence
+// (persistent, vectors in global memory), or alpha = two frames, asum = the (T + 1) x B normalisers, gstate = two partial rows and xT (wide).
+// No per-frame alpha array.  *bytes (optional): what a workspace must hold, alignment slack included.
+constexpr int kObjfL2Parts = 32;  // (few: with them and the alignment slack the layout still fits every workspace of tdnnf_chain_workspace_bytes)
+__attribute__((visibility("hidden"))) ChainBufs chain_objf_bufs(const tdnnf_den_graph *g, int B, int T, void *ws, size_t *bytes = nullptr);
 
 }  // namespace tdnnf

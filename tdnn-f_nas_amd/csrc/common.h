@@ -141,6 +141,12 @@ int chain_num(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
               float xent_regularize, tdnnf_mat *xent_deriv, void *ws, hipStream_t s, bool xent_deriv_initialised = false);
 int chain_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, float l2_regularize, double *results,
                  tdnnf_mat *deriv, tdnnf_mat *xent_deriv, void *ws, hipStream_t s);
+// the parts of tdnnf_chain_objf (objective only, no derivative; workspace of tdnnf_chain_objf_workspace_bytes, or any larger one): the denominator's
+// log-probabilities on s alone, the numerator recursion, the xent objective (xent_output null: zero), and the kernels that finish the objective
+int chain_objf_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, float leaky, void *ws, hipStream_t s);
+int chain_objf_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph *g, const tdnnf_mat *y, void *ws, hipStream_t s);
+int chain_objf_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, void *ws, hipStream_t s);
+int chain_objf_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, float l2_regularize, double *results, void *ws, hipStream_t s);
 
 // trainer-internal variants of the TDNN entry points (abi_tdnn.hip)
 int tdnn_propagate_impl(const tdnnf_tdnn_indexes *ix, const tdnnf_mat *in, const float *W, int ldw, int Do, int Di,

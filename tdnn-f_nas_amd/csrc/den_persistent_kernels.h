@@ -135,6 +135,105 @@ __global__ __launch_bounds__(kDenThreads) void den_forward_kernel(DenDev g, MatV
   }
 }
 
+// Objective only (tdnnf_chain_objf): den_forward_kernel's recursion with nothing kept per frame -- no backward pass will read alpha or its
+// sums, so the two state vectors it alternates between are all the state there is, and the only thing written is logprob[s].  The arithmetic
+// is den_forward_kernel's, term by term, so the log-probability has its bits.
+// LDS_STATE: both vectors in LDS behind the output row (P + 2 Hs floats); otherwise in `gstate`, 2 Hs floats per sequence.  The plain loop forms
+// the frame's new vector in the second buffer as FAST does (den_forward_kernel's stages it in its global alpha row and reads it back).
+// FAST needs LDS_STATE.
+template <bool LDS_STATE, bool FAST = false>
+__global__ __launch_bounds__(kDenThreads) void den_logprob_kernel(DenDev g, MatView y, int B, int T, float leaky, int Hs, double *logprob, float *gstate) {
+  static_assert(LDS_STATE || !FAST, "den_logprob_kernel: the FAST loop keeps its vectors in LDS");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ float red[kDenThreads / 64];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int H = g.H, P = g.P;
+  float *x = smem;  // P
+  float *prev = LDS_STATE ? smem + ((P + 3) & ~3) : gstate + (size_t)s * 2 * Hs;
+  float *nxt = prev + Hs;  // the frame's new vector
+  int sb0[kDenFastSlots], sw[kDenFastSlots];
+  unsigned srow[kDenFastSlots];
+  float hinit[kDenFastStates];
+  if constexpr (FAST) {
+#pragma unroll
+    for (int k = 0; k < kDenFastSlots; k++) {
+      const int slot = tid + k * kDenThreads;
+      sb0[k] = 0;
+      sw[k] = 0;
+      srow[k] = 0xffffffffu;
+      if (slot < g.by_dst.nslices * 64) {
+        sb0[k] = g.by_dst.base[slot >> 6];
+        sw[k] = (g.by_dst.base[(slot >> 6) + 1] - sb0[k]) >> 6;
+        srow[k] = g.by_dst.row[slot];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kDenFastStates; i++) hinit[i] = tid + i * kDenThreads < H ? g.init[tid + i * kDenThreads] : 0.f;
+  }
+  for (int h = tid; h < H; h += kDenThreads) prev[h] = g.init[h] + leaky * g.init_sum * g.init[h];  // AlphaFirstFrame + AlphaDash(0)
+  float prev_sum = g.init_sum;
+  double logcorr = 0.0;
+  RowAhead ra;
+  ra.load(y.data + (size_t)s * y.stride, P, tid);
+  __syncthreads();
+  for (int t = 1; t <= T; t++) {
+#pragma unroll
+    for (int i = 0; i < kDenRowRegs; i++)
+      if (tid + i * kDenThreads < P) x[tid + i * kDenThreads] = exp_limited(ra.v[i]);
+    for (int p = tid + kDenRowRegs * kDenThreads; p < P; p += kDenThreads) x[p] = exp_limited(y.data[(size_t)((t - 1) * B + s) * y.stride + p]);
+    if (t < T) ra.load(y.data + (size_t)(t * B + s) * y.stride, P, tid);
+    __syncthreads();
+    const float inv = 1.0f / prev_sum;
+    logcorr += (double)logf(prev_sum);
+    float local = 0.f;
+    auto term = [&](const uint2 a) { return prev[a.x & 0xffffu] * __uint_as_float(a.y) * x[a.x >> 16]; };
+    if constexpr (FAST) {
+      const int ln = tid & 63;
+#pragma unroll
+      for (int k = 0; k < kDenFastSlots; k++) {
+        if (srow[k] == 0xffffffffu && sw[k] == 0) continue;
+        float acc = sell_row_sum(g.by_dst.arc + sb0[k] + ln, sw[k], term);
+        if (srow[k] != 0xffffffffu) {
+          acc *= inv;
+          nxt[srow[k]] = acc;  // alpha(t,h) before the leaky term
+          local += acc;
+        }
+      }
+    } else {
+      for (int slot = tid; slot < g.by_dst.nslices * 64; slot += kDenThreads) {
+        const int sl = slot >> 6, ln = slot & 63;
+        const int b0 = g.by_dst.base[sl], w = (g.by_dst.base[sl + 1] - b0) >> 6;
+        float acc = sell_row_sum(g.by_dst.arc + b0 + ln, w, term);
+        const unsigned h = g.by_dst.row[slot];
+        if (h != 0xffffffffu) {
+          acc *= inv;
+          nxt[h] = acc;
+          local += acc;
+        }
+      }
+    }
+    const float sum = block_sum(local, red, kDenThreads / 64);  // (its barriers: prev is no longer read, every row of nxt is written)
+    if constexpr (FAST) {
+#pragma unroll
+      for (int i = 0; i < kDenFastStates; i++) {  // AlphaDash(t)
+        const int h = tid + i * kDenThreads;
+        if (h < H) nxt[h] = nxt[h] + leaky * sum * hinit[i];
+      }
+    } else {
+      for (int h = tid; h < H; h += kDenThreads) nxt[h] = nxt[h] + leaky * sum * g.init[h];
+    }
+    float *other = prev;
+    prev = nxt;
+    nxt = other;
+    prev_sum = sum;
+    __syncthreads();
+  }
+  float local = 0.f;
+  for (int h = tid; h < H; h += kDenThreads) local += prev[h];
+  const float tot = block_sum(local, red, kDenThreads / 64);
+  if (tid == 0) logprob[s] = (double)logf(tot) + logcorr;
+}
+
 // Backward: deriv[t*B+s][p] = deriv_weight * gamma_den(t, p)   (overwrites the whole row)
 template <bool LDS_STATE>
 __global__ __launch_bounds__(kDenThreads) void den_backward_kernel(DenDev g, MatView y, int B, int T, float leaky,

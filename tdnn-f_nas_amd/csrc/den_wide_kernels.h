@@ -203,15 +203,17 @@ __device__ __forceinline__ void wide_slice(const tdnnf_den_graph::Sell &T, int s
 // alpha(t, h, s) = 1/A(t-1, s) sum_arcs alpha_dash(t-1, src, s) p x(t-1, pdf, s)
 //               = (1/A) sum_arcs alpha(t-1, src, s) p x + leaky sum_arcs p init_src x        (alpha_dash = alpha + leaky A init).
 // part_prev: launch t-1's partial sums of A(t-1) (null at t = 1: A(0) is in asum[0] already); nsl: slices per block
-template <int SG>
+// TWO_FRAMES (tdnnf_chain_objf: objective only, no backward pass will read the other T - 1): alphaT holds two frames, frame t in alphaT[t & 1];
+// the normalisers keep their (T + 1) x B array, den_wide_total_kernel sums their logarithms
+template <int SG, bool TWO_FRAMES = false>
 __global__ __launch_bounds__(256) void den_wide_fwd_kernel(DenDev g, WideDims d, int t, float leaky, const float *xT, float *alphaT, float *asum, int Hs,
                                                            const float *part_prev, int nblk, int nsl, float *part) {
   using WL = WideLane<SG>;
   __shared__ float red[256];
   const WL L(d, blockIdx.x % d.NG, blockIdx.x / d.NG);
   const size_t frame = (size_t)d.NG * Hs * SG;
-  const float *prev = alphaT + (size_t)(t - 1) * frame + (size_t)L.grp * Hs * SG;  // uniform; lanes add (state * SG + sl)
-  float *cur = alphaT + (size_t)t * frame + (size_t)L.grp * Hs * SG;
+  const float *prev = alphaT + (size_t)(TWO_FRAMES ? (t - 1) & 1 : t - 1) * frame + (size_t)L.grp * Hs * SG;  // uniform; lanes add (state * SG + sl)
+  float *cur = alphaT + (size_t)(TWO_FRAMES ? t & 1 : t) * frame + (size_t)L.grp * Hs * SG;
   const float *x = xT + ((size_t)(t - 1) * d.NG + L.grp) * g.P * SG;
   const int s0 = L.blk * nsl, s1 = min(s0 + nsl, g.by_dst.nslices);
   const float Aprev = part_prev ? wide_norm<SG>(part_prev, nblk, asum + (size_t)(t - 1) * d.B, red, L) : (L.on ? asum[(size_t)(t - 1) * d.B + L.sq] : 1.f);

@@ -191,7 +191,8 @@ int bn_test_memo(float *memo, const double *stats, int cols, hipStream_t s) {
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
 }
-int bn_fwd(tdnnf_net *n, float *in, float *out, int rows, int cols, float *memo, double *stats, hipStream_t s) {
+// (store = false, train mode: the statistics block is left as it is -- tdnnf_net_objective without its store flag)
+int bn_fwd(tdnnf_net *n, float *in, float *out, int rows, int cols, float *memo, double *stats, hipStream_t s, bool store = true) {
   tdnnf_mat a = M(in, rows, cols), o = M(out, rows, cols);
   if (n->cfg.cv_update) {
     CK(bn_test_memo(memo, stats, cols, s));
@@ -200,17 +201,19 @@ int bn_fwd(tdnnf_net *n, float *in, float *out, int rows, int cols, float *memo,
     return TDNNF_OK;
   }
   CK(tdnnf_batchnorm_propagate(&a, 1.0e-3f, 1.0f, &o, memo, n->ws, n->ws_bytes, s));
+  if (!store) return TDNNF_OK;
   return tdnnf_batchnorm_store_stats(memo, cols, rows, stats, s);  // StoreStats runs on every minibatch
 }
 // Affine (+ bias) + ReLU into `out` and the BatchNorm statistics of that output; the GEMM's epilogue forms the column sums
 // while it stores the tile when it can (exact-f32 128-wide tile), otherwise a pass over `out` does.  The normalisation itself
 // is applied later by a fused pass.
 int affine_relu_bn_stats(tdnnf_net *n, const tdnnf_tdnn_indexes *ix, const tdnnf_mat *in, const float *W, int ldw, int Do, int Di, const float *bias,
-                         const float *eff, tdnnf_mat *out, float *memo, double *stats, hipStream_t s) {
+                         const float *eff, tdnnf_mat *out, float *memo, double *stats, hipStream_t s, bool store = true) {
   if (n->cfg.cv_update) {
     CK(tdnn_propagate_impl(ix, in, W, ldw, Do, Di, bias, eff, 1, 1, out, s));
     return bn_test_memo(memo, stats, Do, s);
   }
+  if (!store) stats = nullptr;  // (bn_fwd)
   int prows = 0;
   const bool room = n->ws_bytes >= sizeof(float) * 2 * (size_t)Do * rows_gemm_colstats_cap(out->rows);
   CK(tdnn_propagate_impl(ix, in, W, ldw, Do, Di, bias, eff, 1, 1, out, s, room ? (float *)n->ws : nullptr, room ? &prows : nullptr));
@@ -308,12 +311,16 @@ struct Step {
   double *const results;
   const long long step;
   const hipStream_t s;
+  const int objective_flags;  // tdnnf_net_objective's flags; -1: a training step
   // ---- fixed for the step
   const tdnnf_net_config &c = n->cfg;
   const int B = n->B, Hd = c.hidden_dim, S = c.prefinal_small_dim, P = c.num_pdfs, lda_dim = 3 * c.feat_dim + c.ivector_dim;
   const int N0 = N_of(n->g_lda, B), No = n->Tout * B, np = n->planes_np, Ltop = c.num_layers - 1;
   const bool cv = c.cv_update != 0;  // BatchNorm components are BatchNormTestComponents
   const bool use_ng = c.use_natural_gradient != 0;
+  // tdnnf_net_objective: the forward phases only, no state of the net touched but (with the flag, train mode) the BatchNorm statistics
+  const bool objective = objective_flags >= 0;
+  const bool store_bn = !objective || (objective_flags & TDNNF_OBJECTIVE_STORE_BATCHNORM_STATS) != 0;
   // (the weight-gradient stream reads operands while the caller's stream moves on: plane slots are reused per layer -- small minibatches keep the f32 kernels)
   const bool pl_on = np != 0 && !n->wg_on;
   // Weight gradients up to three components behind the caller's stream (option wgrad_lag, default 3; 1 = rounds 2-4: one behind).  A
@@ -351,8 +358,8 @@ struct Step {
   float *d_cur = n->dA, *d_next = n->dB;  // d_cur: deriv w.r.t. the current layer's output (noop)
 
   Step(tdnnf_net *n_, const tdnnf_mat *feats_, const tdnnf_mat *ivectors_, const tdnnf_den_graph *den_, const tdnnf_supervision *sup_, double *results_,
-       long long step_, hipStream_t s_)
-      : n(n_), feats(feats_), ivectors(ivectors_), den(den_), sup(sup_), results(results_), step(step_), s(s_) {
+       long long step_, hipStream_t s_, int objective_flags_ = -1)
+      : n(n_), feats(feats_), ivectors(ivectors_), den(den_), sup(sup_), results(results_), step(step_), s(s_), objective_flags(objective_flags_) {
     memset(&ix1, 0, sizeof(ix1));
     ix1.row_stride = 1;
     ix1.num_offsets = 1;
@@ -360,6 +367,7 @@ struct Step {
 
   // the reference's RandInt()/RandUniform() coin flips, made reproducible: k-th decision of this minibatch
   int coin() { return (int)(::tdnnf::tdnnf_decision((unsigned long long)step, 2 * coin_k++) & 1); }
+  int mark(int k) { return objective ? TDNNF_OK : phase_mark(n, k, s); }  // (an objective call marks no phase boundaries)
   const float *mask_of(int m) const { return drop ? n->dropout_masks + (size_t)m * B * Hd : nullptr; }
   const PlanesOperand *wplanes(int comp) const { return pl_on && n->pw[comp].P ? &n->pw[comp] : nullptr; }
   float *dC_of(int l) const { return !lag3 ? n->dC : (((Ltop - l) & 1) ? n->dC2 : n->dC); }  // d affine-out of tdnnf layer l
@@ -586,14 +594,14 @@ struct Step {
       PlanesHintScope ph(hint_of(po_lda), wplanes(n->tdnn1.comp));
       FroBoundScope fbs(pl_on ? n->fro_buf : nullptr, &fb_next.blocks);
       CK(affine_relu_bn_stats(n, &ix1, &lda_out, net_W(n, n->tdnn1.comp), lda_dim, Hd, lda_dim, net_bias(n, n->tdnn1.comp), nullptr, &t1r, n->t1_bn_memo,
-                              n->t1_bn_stats, s));
+                              n->t1_bn_stats, s, store_bn));
     }
     fb_next.mul = mask_max;
     CK(bn_apply_planes(t1r, n->t1_bn_memo, none, 0.f, t1b, mask_of(0), fb_next, &po_next));
     prev = n->t1_bn;
     int layer_no = 0;
     for (auto &L : n->layers) CK(forward_layer(L, ++layer_no));
-    return phase_mark(n, 1, s);
+    return mark(1);
   }
   int forward_layer(TdnnfLayer &L, int layer_no) {
     TraceRange trace_layer(("forward tdnnf" + std::to_string(layer_no + 1)).c_str());
@@ -642,7 +650,8 @@ struct Step {
     {
       PlanesHintScope ph(hint_of(p_lin), wplanes(L.aff.comp));
       FroBoundScope fbs(pl_on ? n->fro_buf : nullptr, &fb_next.blocks);
-      CK(affine_relu_bn_stats(n, &L.aff.ix, &aff_in, net_W(n, L.aff.comp), L.aff.K * L.bn, Hd, L.bn, net_bias(n, L.aff.comp), aff_eff, &relu, L.bn_memo, L.bn_stats, s));
+      CK(affine_relu_bn_stats(n, &L.aff.ix, &aff_in, net_W(n, L.aff.comp), L.aff.K * L.bn, Hd, L.bn, net_bias(n, L.aff.comp), aff_eff, &relu, L.bn_memo, L.bn_stats, s,
+                              store_bn));
     }
     // noop = mask * batchnorm(relu) + bypass_scale * (rows of the layer input): its norm bound from the two parts
     fb_next.mul = mask_max;
@@ -736,7 +745,7 @@ struct Step {
   }
 
   int forward_heads_and_objective() {
-    if (early_at_fork) {
+    if (early_at_fork && !objective) {
       CK(finish_refreshes());
       CK(launch_early_in(0));
     }
@@ -750,9 +759,16 @@ struct Step {
     CK(split(pl, 0, kP | kT, &po_pl, s));
     for (int h = 0; h < 2; h++) {
       CK(forward_head(h));
-      if (h == 0) CK(fork_objective());
+      if (h == 0) CK(objective ? fork_objective_only() : fork_objective());
     }
     tdnnf_mat yx = M(n->head[1].y, No, P);
+    if (objective) {  // no derivative: the plain LogSoftmax, the xent objective from the posterior pass, then the join of both side streams
+      CK(tdnnf_log_softmax_propagate(&yx, &lsm, s));
+      TDNNF_HIP(hipStreamWaitEvent(s, n->ev_num, 0));
+      CK(chain_objf_num_xent(den, sup, &y, &lsm, n->chain_ws, s));
+      TDNNF_HIP(hipStreamWaitEvent(s, n->ev_den, 0));
+      return chain_objf_finish(den, sup, &y, c.chain_l2_regularize, results, n->chain_ws, s);
+    }
     // xent head: LogSoftmax, numerator posteriors, LogSoftmax backward.  The derivative handed to LogSoftmax is xent_regularize *
     // weight * (posteriors of a frame: they sum to 1), so its backward pass is -xent_regularize * weight * softmax -- written by the
     // forward kernel while the row is in registers -- plus the posteriors the numerator kernel adds on top.
@@ -762,7 +778,7 @@ struct Step {
     TDNNF_HIP(hipStreamWaitEvent(s, n->ev_num, 0));
     CK(chain_num_xent(den, sup, &y, &lsm, c.xent_regularize, &dx, n->chain_ws, s, dense_first));
     if (!dense_first) CK(tdnnf_log_softmax_backprop(&lsm, &dx, &dx, s));  // in place into d_xent
-    return phase_mark(n, 2, s);
+    return mark(2);
   }
   int forward_head(int h) {
     auto &H = n->head[h];
@@ -771,7 +787,7 @@ struct Step {
     {
       PlanesHintScope ph(hint_of(po_pl), wplanes(H.c_affine));
       FroBoundScope fbs(pl_on ? n->fro_buf : nullptr, &fb_b1.blocks);
-      CK(affine_relu_bn_stats(n, &ix1, &pl, net_W(n, H.c_affine), S, Hd, S, net_bias(n, H.c_affine), nullptr, &ar, H.bn1_memo, H.bn1_stats, s));
+      CK(affine_relu_bn_stats(n, &ix1, &pl, net_W(n, H.c_affine), S, Hd, S, net_bias(n, H.c_affine), nullptr, &ar, H.bn1_memo, H.bn1_stats, s, store_bn));
     }
     CK(bn_apply_planes(ar, H.bn1_memo, none, 0.f, b1, nullptr, fb_b1, &po_b1[h]));
     if (!po_b1[h].base) CK(split(b1, 0, kP | kT, &po_b1[h], s, fb_b1));
@@ -779,7 +795,7 @@ struct Step {
       PlanesHintScope ph(hint_of(po_b1[h]), wplanes(H.c_linear));
       CK(tdnnf_affine_propagate(&b1, net_W(n, H.c_linear), Hd, nullptr, S, &lo, s));
     }
-    CK(bn_fwd(n, H.lin_out, H.bn2_out, No, S, H.bn2_memo, H.bn2_stats, s));
+    CK(bn_fwd(n, H.lin_out, H.bn2_out, No, S, H.bn2_memo, H.bn2_stats, s, store_bn));
     CK(split(b2, 0, kP | kT, &po_b2[h], s));
     PlanesHintScope ph(hint_of(po_b2[h]), wplanes(H.c_output));
     return tdnnf_affine_propagate(&b2, net_W(n, H.c_output), S, net_bias(n, H.c_output), P, &yh, s);
@@ -816,6 +832,20 @@ struct Step {
     }
     CK(chain_num_recursion(sup, den, &y, n->chain_ws, sn));
     TDNNF_HIP(hipEventRecord(n->ev_num, sn));
+    return TDNNF_OK;
+  }
+
+  // tdnnf_net_objective: the denominator's forward recursion alone on n->s2, the numerator's recursion on n->s3 (both idle in such a call),
+  // beside the xent head's forward pass; forward_heads_and_objective joins both
+  int fork_objective_only() {
+    TraceRange trace_den("chain denominator forward (second stream)");
+    TDNNF_HIP(hipEventRecord(n->ev_fork, s));
+    TDNNF_HIP(hipStreamWaitEvent(n->s2, n->ev_fork, 0));
+    TDNNF_HIP(hipStreamWaitEvent(n->s3, n->ev_fork, 0));
+    CK(chain_objf_den(den, sup, &y, c.leaky_hmm, n->chain_ws, n->s2));
+    TDNNF_HIP(hipEventRecord(n->ev_den, n->s2));
+    CK(chain_objf_num_recursion(sup, den, &y, n->chain_ws, n->s3));
+    TDNNF_HIP(hipEventRecord(n->ev_num, n->s3));
     return TDNNF_OK;
   }
 
@@ -1294,6 +1324,20 @@ struct Step {
     CK(backward_trunk());
     return join();
   }
+  // tdnnf_net_objective: run() without begin() (the step count, the gradient scratch, the refresh uploads), the W^T transpose, the backward
+  // phases and the join of the gradient streams
+  int run_objective() {
+    BnSyncScope bn_sync_scope(n->bn_sync.fn && !c.cv_update ? &n->bn_sync : nullptr);
+    GemmPrecisionScope gemm_arith(c.gemm_precision == 2 ? 3 : c.gemm_precision == 3 ? 4 : c.gemm_precision);
+    CK(weight_planes());
+    size_t objf_bytes = tdnnf_chain_objf_workspace_bytes(den, B, n->Tout);
+    TDNNF_REQUIRE(n->chain_ws_bytes >= objf_bytes, "net_objective: denominator graph changed size");
+    TraceRange trace_step("tdnnf_net_objective");
+    CK(forward_trunk());
+    CK(forward_heads_and_objective());
+    TDNNF_LAUNCH_CHECK();
+    return TDNNF_OK;
+  }
 };
 
 }  // namespace
@@ -1310,6 +1354,18 @@ int tdnnf_net_forward_backward(tdnnf_net *n, const tdnnf_mat *feats, const tdnnf
   TDNNF_REQUIRE(ivectors->rows == n->B && ivectors->cols == c.ivector_dim, "net_forward_backward: ivectors must be %d x %d", n->B, c.ivector_dim);
   if (!n->chain_ws) CK(create_streams_and_events(n, den));
   return Step(n, feats, ivectors, den, sup, results, step, (hipStream_t)stream).run();
+}
+
+int tdnnf_net_objective(tdnnf_net *n, const tdnnf_mat *feats, const tdnnf_mat *ivectors, const tdnnf_den_graph *den, const tdnnf_supervision *sup,
+                        double *results, int flags, tdnnf_stream stream) {
+  TDNNF_REQUIRE(n && n->params, "net_objective: call net_set_buffers first");
+  TDNNF_REQUIRE(mat_ok(feats) && mat_ok(ivectors) && den && sup && results, "net_objective: bad arguments");
+  TDNNF_REQUIRE((flags & ~TDNNF_OBJECTIVE_STORE_BATCHNORM_STATS) == 0, "net_objective: unknown flags %d", flags);
+  const tdnnf_net_config &c = n->cfg;
+  TDNNF_REQUIRE(feats->rows == n->g_feat.n * n->B && feats->cols == c.feat_dim, "net_objective: feats must be %d x %d (t-major)", n->g_feat.n * n->B, c.feat_dim);
+  TDNNF_REQUIRE(ivectors->rows == n->B && ivectors->cols == c.ivector_dim, "net_objective: ivectors must be %d x %d", n->B, c.ivector_dim);
+  if (!n->chain_ws) CK(create_streams_and_events(n, den));
+  return Step(n, feats, ivectors, den, sup, results, 0, (hipStream_t)stream, flags).run_objective();
 }
 
 int tdnnf_net_phase_times(tdnnf_net *n, double *ms_out, int capacity, int *count) {

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtdnnf_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tdnnf_hip.h")
 MAX_OFFSETS = 16
+OBJECTIVE_STORE_BATCHNORM_STATS = 1  # TDNNF_OBJECTIVE_STORE_BATCHNORM_STATS (tdnnf_net_objective's flags)
 
 _lib = None
 

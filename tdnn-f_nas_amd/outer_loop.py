@@ -105,7 +105,8 @@ def evaluation_config(config, batchnorm_test_mode):
     return c
 
 
-def _objective(net, minibatches, seed=0):
+def _objective(net, minibatches, seed=0, forward_only=False):
+    """Sums of the 7 result doubles over the minibatches; forward_only: by ChainNet.objective (no derivative, no trace in the net)."""
     import torch
     g = torch.Generator(device="cuda")
     g.manual_seed(seed)
@@ -113,28 +114,33 @@ def _objective(net, minibatches, seed=0):
     for m, (feats, iv, den, sup) in enumerate(minibatches):
         if net.num_draws:
             net.set_random_draws(generator=g)
-        tot += net.forward_backward(feats, iv, den, sup, step=m).cpu().numpy()[:7]
+        r = net.objective(feats, iv, den, sup) if forward_only else net.forward_backward(feats, iv, den, sup, step=m)
+        tot += r.cpu().numpy()[:7]
     return tot
 
 
 def compute_prob(net, minibatches):
     """nnet3-chain-compute-prob on a net built from evaluation_config(cfg, True) that holds the model: per-frame objective of
     the chain output (objf + l2 term) and of the xent output, as the "Overall log-probability for 'output' / 'output-xent'"
-    log lines give them."""
+    log lines give them.  Evaluated by ChainNet.objective: no derivative is formed and the net is left as it was.  The contract is
+    the three numbers returned; against an evaluation through forward_backward they may differ by rounding only (relative 1e-6), because
+    the objective-only denominator may take another form of the same recursion."""
     if net.cfg.use_dropout:
         net.set_dropout_proportion(0.0)  # dropout test mode
-    t = _objective(net, minibatches)
+    t = _objective(net, minibatches, forward_only=True)
     return dict(output=(t[0] + t[1]) / t[2], output_xent=t[6] / t[2], weight=t[2])
 
 
-def combine_models(net, models, num_models, minibatches, max_objective_evaluations=30, log=None):
+def combine_models(net, models, num_models, minibatches, max_objective_evaluations=30, log=None, forward_only=False):
     """nnet3-chain-combine (UPSTREAM, restated from its usage text and log lines): models = an iterable of num_models (parameters,
     statistics) pairs, latest first (train.py hands the files over in reversed order); a running average A_n = A_{n-1} (n-1)/n + M_n / n over parameters and statistics; the
     objective (objf + l2 term) / weight of 'output' on the combine egs -- BatchNorm in TRAINING mode, dropout in test mode, the
     binary's defaults -- is evaluated for n = 1 and then every `mod` models, mod = ceil(num_models / max_objective_evaluations);
     the best average wins and its BatchNorm statistics are recomputed on the same egs.  net: built from
     evaluation_config(cfg, False).  Leaves the winner in net (parameters + statistics); returns (number combined, objf before,
-    objf after)."""
+    objf after).  forward_only: the objective evaluations go through ChainNet.objective (no derivatives); the final pass that recomputes
+    the statistics stays on forward_backward either way, because the ReLU statistics come from the backward sweep.  Off by default: the
+    search picks an argmax, and rounding may move an objective (compute_prob)."""
     minibatches = list(minibatches)
     if net.cfg.use_dropout:
         net.set_dropout_proportion(0.0)
@@ -150,7 +156,7 @@ def combine_models(net, models, num_models, minibatches, max_objective_evaluatio
         if n == 0 or (n - 1) % mod == 0:
             net.set_params(avg_p.astype(np.float32))
             net.set_stats(avg_s)
-            t = _objective(net, minibatches)
+            t = _objective(net, minibatches, forward_only=forward_only)
             objf = (t[0] + t[1]) / t[2]
             if log:
                 log("Combining last %d models, objective function is %.6f" % (n + 1, objf))
@@ -171,7 +177,7 @@ def combine_models(net, models, num_models, minibatches, max_objective_evaluatio
 def run(net_factory, egs_for_archive, work_dir, num_epochs, num_archives, minibatches_per_archive, frame_subsampling_factor=3, num_jobs_initial=1,
         num_jobs_final=1, initial_effective_lrate=2.5e-4, final_effective_lrate=2.5e-5, proportional_shrink=0.0, temperature_schedule=False,
         do_final_combination=True, max_models_combine=20, srand=0, binary=True, log=None, dropout_schedule=None, combine_egs=None,
-        diagnostic_egs=None):
+        diagnostic_egs=None, forward_only=False):
     """Runs the whole schedule.  net_factory() -> a ChainNet with initial parameters set (called once per job: a fresh process in
     the reference, so fresh natural-gradient state; BatchNorm / ReLU statistics and parameters come from <iter>.mdl).
     As upstream's train_one_iteration (absent from the reference, restated from what train.py passes): every job starts from
@@ -183,7 +189,8 @@ def run(net_factory, egs_for_archive, work_dir, num_epochs, num_archives, miniba
     ChainNet.forward_backward.  Writes <work_dir>/<iter>.mdl for every iteration and final.mdl; returns the plan with the
     per-iteration mean objective added.  combine_egs: minibatches [(feats, ivectors, den_graph, supervision)] for the final
     combination (combine_models; without them the plain average); diagnostic_egs: {"valid": minibatches, "train": ...}
-    evaluated on every iteration's model by compute_prob (train.py's compute_train_cv_probabilities), results in the plan.  Ranks of an initialised torch.distributed group share the jobs of an iteration."""
+    evaluated on every iteration's model by compute_prob (train.py's compute_train_cv_probabilities), results in the plan.
+    forward_only: passed on to combine_models.  Ranks of an initialised torch.distributed group share the jobs of an iteration."""
     import torch
     import torch.distributed as dist
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_available() and dist.is_initialized() else (1, 0)
@@ -271,7 +278,7 @@ def run(net_factory, egs_for_archive, work_dir, num_epochs, num_archives, miniba
                     net.read_model(path(i))
                     yield net.params.detach().cpu().numpy().copy(), net.get_stats().copy()
 
-            combine_models(comb, models_latest_first(), len(combine), combine_egs, log=log)
+            combine_models(comb, models_latest_first(), len(combine), combine_egs, log=log, forward_only=forward_only)
             net.params.copy_(comb.params)
             net.set_stats(comb.get_stats())
             comb.close()

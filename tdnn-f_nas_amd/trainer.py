@@ -278,6 +278,15 @@ class ChainNet:
                                                          supervision.h, hipabi.ptr(self.results), int(step), hipabi.stream()))
         return self.results
 
+    def objective(self, feats, ivectors, den_graph, supervision, store_stats=False):
+        """The objective of one minibatch without derivatives (tdnnf_net_objective): the forward pass and the chain objective only; the
+        same 8 doubles as forward_backward.  Leaves no trace in the net, unless store_stats (training-mode BatchNorm only): then the
+        BatchNorm statistics accumulate as in forward_backward; the ReLU statistics never do."""
+        hipabi.check(self.lib.tdnnf_net_objective(self.h, hipabi.pmat(feats), hipabi.pmat(ivectors), den_graph.h, supervision.h,
+                                                  hipabi.ptr(self.results), hipabi.OBJECTIVE_STORE_BATCHNORM_STATS if store_stats else 0,
+                                                  hipabi.stream()))
+        return self.results
+
     def update(self, learning_rate, l2_regularize_scale=None, step=0):
         if l2_regularize_scale is None:  # GetNumNvalues(eg.inputs) * l2_regularize_factor (UPSTREAM trainer)
             l2_regularize_scale = float(self.cfg.num_sequences)
