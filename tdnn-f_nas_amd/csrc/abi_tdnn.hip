@@ -65,7 +65,7 @@ TraceRange::~TraceRange() {
 }
 
 // rows of `in` needed by tap views: GetInputPart's assert, nnet-tdnn-component.cc:811-813
-static bool tdnn_rows_ok(const tdnnf_tdnn_indexes *ix, int rows_in, int N) {
+bool tdnn_rows_ok(const tdnnf_tdnn_indexes *ix, int rows_in, int N) {
   if (!ix || ix->num_offsets < 1 || ix->num_offsets > TDNNF_MAX_OFFSETS || ix->row_stride < 1) return false;
   for (int i = 0; i < ix->num_offsets; i++) {
     const long long need = (long long)ix->row_offsets[i] + (long long)ix->row_stride * N - (ix->row_stride - 1);

@@ -148,7 +148,8 @@ int chain_objf_num_recursion(const tdnnf_supervision *sp, const tdnnf_den_graph 
 int chain_objf_num_xent(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, void *ws, hipStream_t s);
 int chain_objf_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, float l2_regularize, double *results, void *ws, hipStream_t s);
 
-// trainer-internal variants of the TDNN entry points (abi_tdnn.hip)
+// trainer-internal variants of the TDNN entry points (abi_tdnn.hip); tdnn_rows_ok: `in` has the rows the taps read for N output rows
+bool tdnn_rows_ok(const tdnnf_tdnn_indexes *ix, int rows_in, int N);
 int tdnn_propagate_impl(const tdnnf_tdnn_indexes *ix, const tdnnf_mat *in, const float *W, int ldw, int Do, int Di,
                         const float *bias, const float *eff_coef, int init_mode, int relu, tdnnf_mat *out, tdnnf_stream stream,
                         float *colstats = nullptr, int *colstats_rows = nullptr);

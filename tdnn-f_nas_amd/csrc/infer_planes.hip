@@ -1,6 +1,6 @@
 // infer_planes.hip -- the f16x3 forward pass of the whole-utterance inference (tdnnf_infer_create_arith with gemm_precision 3; the
-// entries and the exact-f32 pass: infer.hip).  Same schedule, same f32 activations (the bypass and the BatchNorm pass of a strided layer
-// read them); every GEMM runs from f16 planes (planes_gemm.h, np 2):
+// entries: infer.hip).  The one schedule (infer_forward.hip), the same f32 activations (the bypass and the BatchNorm pass of a strided
+// layer read them); every GEMM runs from f16 planes (planes_gemm.h, np 2), behind a split of its input:
 //   weights      the matrices of the chosen head's path, split at the top of every compute into planes this object owns (the model is read
 //                at every compute, as in f32); every tap's column block sits at its own 16-aligned K block, so a bottleneck that is no
 //                multiple of 16 needs no other kernel (such a matrix is first copied with its tap blocks padded: infer_pad_taps_kernel).
@@ -21,9 +21,8 @@
 #include <vector>
 
 #include "common.h"
-#include "fused.h"
 #include "gemm_f32.h"
-#include "infer_parts.h"
+#include "infer_forward.h"
 #include "infer_planes_kernels.h"
 #include "infer_state.h"
 #include "net_model.h"
@@ -128,44 +127,10 @@ bool a_geometry(long long rows, int cols, const tdnnf_tdnn_indexes &ix, AGeo *g)
   return g->R < (1LL << 31);
 }
 
-struct Roles {
-  int lda = 0, tdnn1 = 1, prefinal_l, affine, linear, output;
-  int lin(int l) const { return 2 + 2 * l; }
-  int aff(int l) const { return 3 + 2 * l; }
-};
-Roles roles(const tdnnf_infer *q) {
-  Roles r;
-  const int L = (int)q->layers.size();
-  r.prefinal_l = 2 + 2 * L;
-  r.affine = r.prefinal_l + 1;
-  r.linear = r.prefinal_l + 2;
-  r.output = r.prefinal_l + 3;
-  return r;
-}
-
-tdnnf_tdnn_indexes one_tap() {
-  tdnnf_tdnn_indexes ix;
-  memset(&ix, 0, sizeof(ix));
-  ix.row_stride = 1;
-  ix.num_offsets = 1;
-  return ix;
-}
-
-// the two TdnnComponents of layer l at batch size B (as infer.hip's forward_batch makes them)
-void layer_tdnns(const tdnnf_infer *q, int l, int B, Tdnn *lin, Tdnn *aff) {
-  const tdnnf_net_config &c = q->model->cfg;
-  const TdnnfLayer &L = q->layers[l], &ML = q->model->layers[l];
-  std::vector<int> lin_off, aff_off;
-  layer_taps(c, L, &lin_off, &aff_off);
-  make_tdnn(lin, ML.lin.comp, c.hidden_dim, L.bn, lin_off, L.gin, L.glin, B);
-  make_tdnn(aff, ML.aff.comp, L.bn, c.hidden_dim, aff_off, L.glin, L.gout, B);
-}
-
 void layout(tdnnf_infer *q, InferPlanes *ip, Arena &A) {
   const tdnnf_net *n = q->model;
   const tdnnf_net_config &c = n->cfg;
   const int B = q->max_chunks, Hd = c.hidden_dim, S = c.prefinal_small_dim, P = c.num_pdfs, lda_dim = 3 * c.feat_dim + c.ivector_dim;
-  const int nl = (int)q->layers.size();
   const auto &H = n->head[q->which];
   ip->w.clear();
   auto add_w = [&](int comp, int Do, int K, int Di) {
@@ -179,7 +144,7 @@ void layout(tdnnf_infer *q, InferPlanes *ip, Arena &A) {
     w.rec = A.take<float>(4);
     ip->w.push_back(w);
   };
-  // (the order of Roles)
+  // (the order of FwdGemm's roles)
   add_w(n->c_lda, lda_dim, 1, lda_dim);
   add_w(n->tdnn1.comp, Hd, 1, lda_dim);
   size_t xbytes = 0;
@@ -192,9 +157,8 @@ void layout(tdnnf_infer *q, InferPlanes *ip, Arena &A) {
   };
   const tdnnf_tdnn_indexes ix1 = one_tap();
   use((long long)q->g_lda.n * B, lda_dim, ix1);
-  for (int l = 0; l < nl; l++) {
-    Tdnn lin, aff;
-    layer_tdnns(q, l, B, &lin, &aff);
+  for (const FwdLayer &Ly : infer_buffers(q, B).layers) {  // (the largest batch)
+    const Tdnn &lin = Ly.lin, &aff = Ly.aff;
     add_w(lin.comp, lin.Do, lin.K, lin.Di);
     add_w(aff.comp, aff.Do, aff.K, aff.Di);
     use(lin.rows_in, Hd, lin.ix);
@@ -344,6 +308,14 @@ int gemm(Fwd &f, int wi, const tdnnf_tdnn_indexes &ix, const tdnnf_mat &in, int 
   return TDNNF_OK;
 }
 
+// the FwdGemm of this pass: the planes of the GEMM's input, then the GEMM (role = the index of its weight planes)
+int split_and_gemm(void *ctx, hipStream_t, int role, int comp, const tdnnf_tdnn_indexes &ix, const tdnnf_mat &in, int relu, const float *coef, const tdnnf_mat *add,
+                   float add_scale, const int *row_map, const tdnnf_mat &out, bool wants_stats) {
+  Fwd &f = *static_cast<Fwd *>(ctx);
+  CK(split_for(f, in, ix));
+  return gemm(f, role, ix, in, relu, coef, add, add_scale, row_map, out, wants_stats);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------ create / begin / forward
@@ -405,79 +377,12 @@ int infer_planes_begin(tdnnf_infer *q, hipStream_t s) {
   return TDNNF_OK;
 }
 
-int infer_planes_forward(tdnnf_infer *q, const int *tab, int B, tdnnf_mat *out, hipStream_t s, bool count) {
-  const tdnnf_net *n = q->model;
-  const tdnnf_net_config &c = n->cfg;
-  const int Hd = c.hidden_dim, S = c.prefinal_small_dim, P = c.num_pdfs, lda_dim = 3 * c.feat_dim + c.ivector_dim, Tout = q->Tout;
-  const int N0 = q->g_lda.n * B, No = Tout * B;
-  const long long bstride = infer_bn_stride(c);
-  auto coef = [&](int i) { return q->coef + i * bstride; };
-  const Roles R = roles(q);
-  const tdnnf_tdnn_indexes ix1 = one_tap();
+int infer_planes_forward(tdnnf_infer *q, int B, tdnnf_mat *out, hipStream_t s, FwdCounts *counts) {
   Fwd f;
   f.q = q;
   f.ip = q->planes;
   f.s = s;
-  tdnnf_mat lda_in = M(q->lda_in, N0, lda_dim), lda_out = M(q->lda_out, N0, lda_dim);
-  CK(split_for(f, lda_in, ix1));
-  CK(gemm(f, R.lda, ix1, lda_in, 0, nullptr, nullptr, 0.f, nullptr, lda_out, true));
-  // ---- tdnn1: affine + ReLU + BatchNorm in one GEMM
-  int cur = 0;
-  tdnnf_mat a0 = M(q->act[0], N0, Hd);
-  CK(split_for(f, lda_out, ix1));
-  CK(gemm(f, R.tdnn1, ix1, lda_out, 1, coef(0), nullptr, 0.f, nullptr, a0, true));
-  int fused = 1, fallback = 0;
-  for (size_t l = 0; l < q->layers.size(); l++) {
-    const TdnnfLayer &L = q->layers[l];
-    Tdnn lin, aff;
-    layer_tdnns(q, (int)l, B, &lin, &aff);
-    tdnnf_mat in = M(q->act[cur], L.gin.n * B, Hd), lo = M(q->lin, lin.rows_out, L.bn);
-    CK(split_for(f, in, lin.ix));
-    CK(gemm(f, R.lin((int)l), lin.ix, in, 0, nullptr, nullptr, 0.f, nullptr, lo, true));
-    tdnnf_mat aff_in = lo;
-    if (L.perm) {  // (a row order: the sums of squares stay those of the matrix)
-      aff_in = M(q->lin_perm, lin.rows_out, L.bn);
-      CK(tdnnf_reorder_rows(&lo, B, aff.ix.row_stride, 1, &aff_in, s));
-    }
-    CK(split_for(f, aff_in, aff.ix));
-    tdnnf_mat byp = sub_grid_view(q->act[cur], L.gin, L.gout, B, Hd), o = M(q->act[cur ^ 1], aff.rows_out, Hd);
-    if (L.gout.step == L.gin.step) {  // noop = Sum(Scale(bypass, input rows), batchnorm(relu(affine))) while the tile is stored
-      CK(gemm(f, R.aff((int)l), aff.ix, aff_in, 1, coef(1 + (int)l), &byp, c.bypass_scale, nullptr, o, true));
-      fused++;
-    } else {  // bypass rows strided against the output rows: ReLU in the GEMM, BatchNorm + bypass in the trainer's pass (its output gets a norm pass)
-      tdnnf_mat r = M(q->relu_tmp, aff.rows_out, Hd);
-      CK(gemm(f, R.aff((int)l), aff.ix, aff_in, 1, nullptr, nullptr, 0.f, nullptr, r, false));
-      const tdnnf_mat x{q->relu_tmp, L.gout.n, byp.cols, B * ldpad(Hd)}, ov{q->act[cur ^ 1], L.gout.n, byp.cols, B * ldpad(Hd)};
-      TDNNF_HIP(bn_apply_bypass(view(&x), coef(1 + (int)l), Hd, ldpad(Hd), view(&byp), c.bypass_scale, view(&ov), s, nullptr, B));
-      fallback++;
-    }
-    cur ^= 1;
-  }
-  // ---- the chosen head: prefinal-l, affine + ReLU + batchnorm1, linear + batchnorm2, output
-  const int nb = (int)q->layers.size() + 1;
-  tdnnf_mat top = M(q->act[cur], No, Hd), pl = M(q->pl, No, S), b1 = M(q->act[cur ^ 1], No, Hd), b2 = M(q->b2, No, S);
-  CK(split_for(f, top, ix1));
-  CK(gemm(f, R.prefinal_l, ix1, top, 0, nullptr, nullptr, 0.f, nullptr, pl, true));
-  CK(split_for(f, pl, ix1));
-  CK(gemm(f, R.affine, ix1, pl, 1, coef(nb), nullptr, 0.f, nullptr, b1, true));
-  CK(split_for(f, b1, ix1));
-  CK(gemm(f, R.linear, ix1, b1, 0, coef(nb + 1), nullptr, 0.f, nullptr, b2, true));
-  CK(split_for(f, b2, ix1));
-  fused += 2;
-  if (q->which == 0) {  // rows inside their utterance straight into the caller's output
-    tdnnf_mat ym = *out;
-    ym.rows = No;
-    CK(gemm(f, R.output, ix1, b2, 0, nullptr, nullptr, 0.f, q->row_map, ym, false));
-  } else {
-    tdnnf_mat y = M(q->y, No, P), lsm = M(q->lsm, No, P);
-    CK(gemm(f, R.output, ix1, b2, 0, nullptr, nullptr, 0.f, nullptr, y, false));
-    CK(tdnnf_log_softmax_propagate(&y, &lsm, s));
-    TDNNF_HIP(infer_scatter_rows(view(&lsm), q->row_map, view(out), s));
-  }
-  if (count) {
-    q->fused = fused;
-    q->fallback = fallback;
-  }
+  CK(infer_forward(q->model, q->head.coef, q->which, B, infer_buffers(q, B), out, split_and_gemm, &f, s, counts));
   q->plane_gemms += f.pg;
   q->f32_gemms += f.fg;
   return TDNNF_OK;

@@ -1,4 +1,4 @@
-// infer_planes_kernels.h -- the small kernels around the plane GEMMs of the f16x3 inference (host side: infer_planes.hip).  The GEMM itself
+// infer_planes_kernels.h -- the small kernels around the plane GEMMs of the f16x3 inference (host side: infer_planes.hip, the f16x3 reader of infer_forward.hip's schedule).  The GEMM itself
 // is planes_gemm_kernel<.., POST = true> (planes_gemm_kernels.h); the splits are those of planes_split.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,12 +1,13 @@
 // infer_state.h -- the whole-utterance inference object (tdnnf_infer, include/tdnnf_hip.h "inference") for its two units: infer.hip (the
-// entries, the chunk plan, the exact-f32 forward pass) and infer_planes.hip (the f16x3 forward pass on the plane kernels).
+// entries, the chunk plan, a batch's input and buffer description, the exact-f32 pass) and infer_planes.hip (the f16x3 pass on the plane
+// kernels).  Both passes walk the one schedule of infer_forward.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "common.h"
-#include "infer_parts.h"
+#include "infer_forward.h"
 #include "net_model.h"
 
 namespace tdnnf {
@@ -21,8 +22,10 @@ struct tdnnf_infer {
   int nbn;
   tdnnf::BnTable bn;
   char *arena = nullptr;
-  float *lda_in, *lda_out, *act[2], *lin, *lin_perm, *relu_tmp, *pl, *b2, *y, *lsm, *coef;
-  int *row_map;
+  float *lda_in, *lda_out, *act[2], *lin, *lin_perm, *relu_tmp;
+  tdnnf::FwdHead head;
+  tdnnf::FwdBuffers fwd;  // where a batch of fwd_B chunks lives (infer_buffers)
+  int fwd_B = 0;
   int *table = nullptr;  // device chunk table of the last compute
   size_t table_cap = 0;  // (ints)
   std::vector<int> host_table;
@@ -33,14 +36,16 @@ struct tdnnf_infer {
 
 namespace tdnnf {
 
-// infer.hip: the batch's spliced lda input (q->lda_in, N0 x lda_dim) and its row map (q->row_map) from the chunk table entries at `tab`
+// infer.hip: the batch's spliced lda input (q->lda_in, N0 x lda_dim) and its row map (q->head.row_map) from the chunk table entries at `tab`;
+// the description of the buffers of a batch of B chunks, for either pass
 int infer_batch_input(tdnnf_infer *q, const tdnnf_mat *feats, const tdnnf_mat *iv, const int *tab, int B, hipStream_t s);
+const FwdBuffers &infer_buffers(tdnnf_infer *q, int B);
 
 // infer_planes.hip.  create: the plane buffers of an object whose layers and buffers are laid out (q->planes); begin: the split of the
-// weights of the chosen head's path, at the top of every compute; forward: one batch of B chunks, as infer.hip's forward_batch.
+// weights of the chosen head's path, at the top of every compute; forward: one batch of B chunks whose input is in place (infer_batch_input), GEMM counts added to q's.
 int infer_planes_create(tdnnf_infer *q);
 void infer_planes_destroy(InferPlanes *p);
 int infer_planes_begin(tdnnf_infer *q, hipStream_t s);
-int infer_planes_forward(tdnnf_infer *q, const int *tab, int B, tdnnf_mat *out, hipStream_t s, bool count);
+int infer_planes_forward(tdnnf_infer *q, int B, tdnnf_mat *out, hipStream_t s, FwdCounts *counts);
 
 }  // namespace tdnnf

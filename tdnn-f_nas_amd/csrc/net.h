@@ -1,8 +1,8 @@
 // net.h -- data structures of the chain trainer, shared with the model reader / writer (model_io.hip) and the forward-only inference
-// (infer.hip).  What the model IS (statistics blocks, ranks, component walk, taps, head names) is described once, in net_model.h.
+// (infer_forward.hip and its readers).  What the model IS (statistics blocks, ranks, component walk, taps, head names) is described once, in net_model.h.
 //
 // File map of the trainer's net object:
-//   net_model.h     the one description of the model that the units below, net_step.hip, model_io.hip and infer.hip read
+//   net_model.h     the one description of the model that the units below, net_step.hip, model_io.hip and the inference read
 //   net_graph.hip   host only, no HIP call: config checks, time grids, TdnnComponent indexes, the component list with its draw plan,
 //                   cv-update factors, the "same model" check, gradient-bucket ranges, and the lists net_model.h declares
 //   net_arena.hip   the arena layout as a sequence of named parts (sizing pass and real pass run the same function), named activations

@@ -1,6 +1,6 @@
 // net_model.h -- the one description of the model behind a tdnnf_net, for its four readers: the net's own units (net_graph.hip,
 // net_arena.hip, net_create.hip, net_update.hip), the step (net_step.hip), the model reader / writer (model_io.hip) and the
-// forward-only inference (infer.hip).  Whoever adds a statistics block, a component kind or a head changes THIS file and net_graph.hip.
+// forward-only inference (infer_forward.hip: the one schedule; infer.hip, infer_planes.hip, online.hip: its three readers).  Whoever adds a statistics block, a component kind or a head changes THIS file and net_graph.hip.
 #pragma once
 #include <string>
 #include <vector>

@@ -5,7 +5,7 @@
 // advances every active stream by one window of F input frames and computes, per layer, only the F / step time rows that are new; what
 // the taps above a buffer still need from earlier steps is kept per slot on the device.  In the t-major row order (row = time * B +
 // position in the active list) the time-concatenation [carried tail | new rows] of a layer's input is one contiguous row range, so
-// the GEMMs are those of infer.hip -- BatchNorm and bypass in the epilogue (infer_parts.h gemm_post) -- on fewer rows.
+// the schedule is the whole-utterance one (infer_forward.hip: BatchNorm and bypass in the GEMM epilogue) on fewer rows, in exact f32.
 //
 // Windows, relative to the step's first output frame clock - D and derived downwards as net_layer_grids derives a chunk's grids:
 // a layer's .linear output (and its input) starts `right tap` later than the layer's output, so at the bottom the input-layer rows
@@ -24,9 +24,7 @@
 #include <vector>
 
 #include "common.h"
-#include "fused.h"
-#include "gemm_f32.h"
-#include "infer_parts.h"
+#include "infer_forward.h"
 #include "net_model.h"
 
 using namespace tdnnf;
@@ -159,8 +157,10 @@ struct tdnnf_online {
   int nbn;
   BnTable bn;
   char *arena = nullptr;
-  float *lda_in, *lda_out, *lin_tmp, *relu_tmp, *pl, *b1, *b2, *y, *lsm, *coef, *state;
-  int *row_map, *table;
+  float *lda_in, *lda_out, *lin_tmp, *relu_tmp, *state;
+  FwdHead head;
+  FwdBuffers fwd;  // where a step of fwd_B active streams lives (step_buffers)
+  int fwd_B = 0;
   CarryDesc *descs;
   std::vector<CarryDesc> host_descs;
   long long slot_floats = 0, tail_off = 0, carry_max = 0;  // carry_max: the largest h * unit / 4 of a descriptor
@@ -179,7 +179,7 @@ namespace {
 void layout(tdnnf_online *q, Arena &A) {
   const tdnnf_net_config &c = q->model->cfg;
   const long long B = q->num_slots;
-  const int Hd = c.hidden_dim, S = c.prefinal_small_dim, P = c.num_pdfs, lda_dim = 3 * c.feat_dim + c.ivector_dim, L = (int)q->layers.size();
+  const int Hd = c.hidden_dim, lda_dim = 3 * c.feat_dim + c.ivector_dim, L = (int)q->layers.size();
   const long long N0 = (long long)q->F * B, No = (long long)q->Tout * B;
   q->host_descs.clear();
   long long so = 0, lin_rows = 0, relu_rows = 0;
@@ -209,14 +209,7 @@ void layout(tdnnf_online *q, Arena &A) {
   }
   q->lin_tmp = lin_rows ? A.mat(lin_rows, bn_max) : nullptr;
   q->relu_tmp = relu_rows ? A.mat(relu_rows, Hd) : nullptr;
-  q->pl = A.mat(No, S);
-  q->b1 = A.mat(No, Hd);
-  q->b2 = A.mat(No, S);
-  q->y = q->which == 1 ? A.mat(No, P) : nullptr;
-  q->lsm = q->which == 1 ? A.mat(No, P) : nullptr;
-  q->row_map = A.take<int>((size_t)No);
-  q->table = A.take<int>((size_t)kTab * B);
-  q->coef = A.take<float>((size_t)q->nbn * infer_bn_stride(c));
+  infer_head_layout(c, q->which, q->nbn, No, true, (size_t)kTab * B, A, &q->head);
   q->descs = A.take<CarryDesc>(q->host_descs.size() + 1);
   q->fdp = (c.feat_dim + 3) & ~3;
   q->tail_off = so;
@@ -236,110 +229,84 @@ void model_context(const std::vector<TdnnfLayer> &layers, int *left, int *right)
   }
 }
 
+// Where a step of B active streams lives: [carried | new] rows of X[l] and Y[l], the GEMMs storing the new rows.  The buffers are the
+// object's, so the description changes with B alone and is kept from one step to the next.
+const FwdBuffers &step_buffers(tdnnf_online *q, int B) {
+  FwdBuffers &b = q->fwd;
+  if (q->fwd_B == B) return b;
+  const tdnnf_net_config &c = q->model->cfg;
+  const int Hd = c.hidden_dim, S = c.prefinal_small_dim, P = c.num_pdfs, lda_dim = 3 * c.feat_dim + c.ivector_dim;
+  const int N0 = q->F * B, No = q->Tout * B, L = (int)q->layers.size(), ldH = ldpad(Hd);
+  // the new rows of X[l]
+  auto Xnew = [&](int l) {
+    const int h = l < L ? q->layers[l].hx : 0, m = l < L ? q->layers[l].mx : q->Tout;
+    return M(q->X[l] + (size_t)h * B * ldH, m * B, Hd);
+  };
+  b.lda_in = M(q->lda_in, N0, lda_dim);
+  b.lda_out = M(q->lda_out, N0, lda_dim);
+  b.x0 = Xnew(0);
+  for (int l = 0; l < L; l++) {
+    const tdnnf_online::Layer &Ly = q->layers[l];
+    FwdLayer &f = b.layers[l];
+    // time 0 = the first new row of X[l] and Y[l]; the layer's new output rows start at -b
+    const Grid gx{-Ly.hx * Ly.ls, Ly.ls, Ly.hx + Ly.mx}, gy_new{0, Ly.ls, Ly.my}, gy{-Ly.hy * Ly.ls, Ly.ls, Ly.hy + Ly.my}, go{-Ly.b, Ly.s_out, Ly.m_out};
+    layer_tdnns(q->model, l, gx, gy_new, gy, go, B, &f.lin, &f.aff);
+    const tdnnf_mat ynew = M(Ly.Y + (size_t)Ly.hy * B * ldpad(Ly.bn), Ly.my * B, Ly.bn);
+    f.lin_in = M(q->X[l], gx.n * B, Hd);
+    // the .affine reads blocks of rho time steps: the new rows in plain order, then into the rho row order
+    f.lin_out = Ly.rho > 1 ? M(q->lin_tmp, Ly.my * B, Ly.bn) : ynew;
+    f.perm_out = ynew;
+    f.aff_in = M(Ly.Y, gy.n * B, Ly.bn);
+    f.byp = sub_grid_view(q->X[l], gx, go, B, Hd);
+    f.out = Xnew(l + 1);
+    f.relu = Ly.s_out != Ly.ls ? M(q->relu_tmp, f.aff.rows_out, Hd) : tdnnf_mat{nullptr, 0, 0, 0};
+    f.out_times = Ly.m_out;
+  }
+  b.top = Xnew(L);
+  b.pl = M(q->head.pl, No, S);
+  b.b1 = M(q->head.b1, No, Hd);
+  b.b2 = M(q->head.b2, No, S);
+  b.y = M(q->head.y, No, P);
+  b.lsm = M(q->head.lsm, No, P);
+  b.row_map = q->head.row_map;
+  q->fwd_B = B;
+  return b;
+}
+
 int forward_step(tdnnf_online *q, const tdnnf_mat *feats, const tdnnf_mat *iv, int B, tdnnf_mat *out, hipStream_t s) {
-  const tdnnf_net *n = q->model;
-  const tdnnf_net_config &c = n->cfg;
-  const int Hd = c.hidden_dim, S = c.prefinal_small_dim, P = c.num_pdfs, lda_dim = 3 * c.feat_dim + c.ivector_dim, Tout = q->Tout;
-  const int N0 = q->F * B, No = Tout * B, L = (int)q->layers.size(), ldH = ldpad(Hd);
-  const long long bstride = infer_bn_stride(c);
-  auto coef = [&](int i) { return q->coef + i * bstride; };
-  auto W = [&](int comp) { return net_W(n, comp); };
-  auto bias = [&](int comp) { return net_bias(n, comp); };
+  const tdnnf_net_config &c = q->model->cfg;
+  const int lda_dim = 3 * c.feat_dim + c.ivector_dim, N0 = q->F * B, No = q->Tout * B;
   const int ndesc = (int)q->host_descs.size();
-  long long rows = 0;
-  TDNNF_HIP(infer_bn_coef(q->bn, q->nbn, q->coef, s));
+  const FwdBuffers &b = step_buffers(q, B);
+  TDNNF_HIP(infer_bn_coef(q->bn, q->nbn, q->head.coef, s));
   // ---- every buffer's carried tail into its head
   if (ndesc) {
-    hipLaunchKernelGGL(online_carry_kernel<false>, dim3(grid_for(q->carry_max * B, 256), ndesc), dim3(256), 0, s, q->descs, q->table, B, q->state, q->slot_floats);
+    hipLaunchKernelGGL(online_carry_kernel<false>, dim3(grid_for(q->carry_max * B, 256), ndesc), dim3(256), 0, s, q->descs, q->head.table, B, q->state, q->slot_floats);
     TDNNF_LAUNCH_CHECK();
   }
   // ---- input: carried frames + clamped windows + i-vectors, spliced for the lda layer in one pass (which also carries the frames on)
-  tdnnf_mat lda_in = M(q->lda_in, N0, lda_dim), lda_out = M(q->lda_out, N0, lda_dim);
   {
-    const MatView fv = view(feats), ivv = view(iv), ov = view(&lda_in);
+    const MatView fv = view(feats), ivv = view(iv), ov = view(&b.lda_in);
     const bool v4 = vec4_ok(fv) && vec4_ok(ivv) && vec4_ok(ov);
     const long long work = ((long long)N0 * lda_dim + (long long)B * q->hf * c.feat_dim) / (v4 ? 4 : 1);
-    if (v4) hipLaunchKernelGGL(online_gather_kernel<4>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, q->table, B, q->F, q->hf, q->state, q->slot_floats, q->tail_off, q->fdp, ov);
-    else hipLaunchKernelGGL(online_gather_kernel<1>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, q->table, B, q->F, q->hf, q->state, q->slot_floats, q->tail_off, q->fdp, ov);
+    if (v4) hipLaunchKernelGGL(online_gather_kernel<4>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, q->head.table, B, q->F, q->hf, q->state, q->slot_floats, q->tail_off, q->fdp, ov);
+    else hipLaunchKernelGGL(online_gather_kernel<1>, dim3(grid_for(work, 256)), dim3(256), 0, s, fv, ivv, q->head.table, B, q->F, q->hf, q->state, q->slot_floats, q->tail_off, q->fdp, ov);
     TDNNF_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(online_row_map_kernel, dim3((No + 255) / 256), dim3(256), 0, s, q->table, B, Tout, q->row_map);
+  hipLaunchKernelGGL(online_row_map_kernel, dim3((No + 255) / 256), dim3(256), 0, s, q->head.table, B, q->Tout, q->head.row_map);
   TDNNF_LAUNCH_CHECK();
-  CK(tdnnf_affine_propagate(&lda_in, W(n->c_lda), lda_dim, bias(n->c_lda), lda_dim, &lda_out, s));
-  rows += N0;
-  tdnnf_tdnn_indexes ix1;
-  memset(&ix1, 0, sizeof(ix1));
-  ix1.row_stride = 1;
-  ix1.num_offsets = 1;
-  // the new rows of X[l]
-  auto Xnew = [&](int l) {
-    const int h = l < L ? q->layers[l].hx : 0, m = l < L ? q->layers[l].mx : Tout;
-    return M(q->X[l] + (size_t)h * B * ldH, m * B, Hd);
-  };
-  // ---- tdnn1: affine + ReLU + BatchNorm in one GEMM
-  CK(gemm_post(ix1, lda_out, W(n->tdnn1.comp), lda_dim, Hd, lda_dim, bias(n->tdnn1.comp), 1, coef(0), nullptr, 0.f, nullptr, Xnew(0), s));
-  rows += N0;
-  int fused = 1, fallback = 0;
-  for (int l = 0; l < L; l++) {
-    const tdnnf_online::Layer &Ly = q->layers[l];
-    const TdnnfLayer &ML = n->layers[l];  // component ids, taps
-    std::vector<int> lin_off, aff_off;
-    layer_taps(c, ML, &lin_off, &aff_off);
-    // time 0 = the first new row of X[l] and Y[l]; the layer's new output rows start at -b
-    const Grid gx{-Ly.hx * Ly.ls, Ly.ls, Ly.hx + Ly.mx}, gy_new{0, Ly.ls, Ly.my}, gy{-Ly.hy * Ly.ls, Ly.ls, Ly.hy + Ly.my}, go{-Ly.b, Ly.s_out, Ly.m_out};
-    Tdnn lin, aff;
-    make_tdnn(&lin, ML.lin.comp, Hd, Ly.bn, lin_off, gx, gy_new, B);
-    make_tdnn(&aff, ML.aff.comp, Ly.bn, Hd, aff_off, gy, go, B);
-    tdnnf_mat in = M(q->X[l], gx.n * B, Hd), ynew = M(Ly.Y + (size_t)Ly.hy * B * ldpad(Ly.bn), Ly.my * B, Ly.bn);
-    if (Ly.rho > 1) {  // the .affine reads blocks of rho time steps: the new rows in plain order, then into the rho row order
-      tdnnf_mat lo = M(q->lin_tmp, Ly.my * B, Ly.bn);
-      CK(tdnn_propagate_impl(&lin.ix, &in, W(lin.comp), lin.K * Hd, Ly.bn, Hd, nullptr, nullptr, 2, 0, &lo, s));
-      CK(tdnnf_reorder_rows(&lo, B, Ly.rho, 1, &ynew, s));
-    } else {
-      CK(tdnn_propagate_impl(&lin.ix, &in, W(lin.comp), lin.K * Hd, Ly.bn, Hd, nullptr, nullptr, 2, 0, &ynew, s));
-    }
-    rows += ynew.rows;
-    tdnnf_mat aff_in = M(Ly.Y, gy.n * B, Ly.bn), byp = sub_grid_view(q->X[l], gx, go, B, Hd), o = Xnew(l + 1);
-    if (Ly.s_out == Ly.ls) {  // noop = Sum(Scale(bypass, input rows), batchnorm(relu(affine))) while the tile is stored
-      CK(gemm_post(aff.ix, aff_in, W(aff.comp), aff.K * Ly.bn, Hd, Ly.bn, bias(aff.comp), 1, coef(1 + l), &byp, c.bypass_scale, nullptr, o, s));
-      fused++;
-    } else {  // bypass rows strided against the output rows: ReLU in the GEMM, BatchNorm + bypass in the trainer's pass
-      tdnnf_mat r = M(q->relu_tmp, aff.rows_out, Hd);
-      CK(tdnn_propagate_impl(&aff.ix, &aff_in, W(aff.comp), aff.K * Ly.bn, Hd, Ly.bn, bias(aff.comp), nullptr, 1, 1, &r, s));
-      const tdnnf_mat x{q->relu_tmp, Ly.m_out, byp.cols, B * ldH}, ov{o.data, Ly.m_out, byp.cols, B * ldH};
-      TDNNF_HIP(bn_apply_bypass(view(&x), coef(1 + l), Hd, ldH, view(&byp), c.bypass_scale, view(&ov), s, nullptr, B));
-      fallback++;
-    }
-    rows += o.rows;
-  }
-  // ---- the chosen head: prefinal-l, affine + ReLU + batchnorm1, linear + batchnorm2, output
-  const auto &H = n->head[q->which];
-  const int nb = L + 1;
-  tdnnf_mat top = Xnew(L), pl = M(q->pl, No, S), b1 = M(q->b1, No, Hd), b2 = M(q->b2, No, S);
-  CK(tdnnf_affine_propagate(&top, W(n->c_prefinal_l), Hd, nullptr, S, &pl, s));
-  CK(gemm_post(ix1, pl, W(H.c_affine), S, Hd, S, bias(H.c_affine), 1, coef(nb), nullptr, 0.f, nullptr, b1, s));
-  CK(gemm_post(ix1, b1, W(H.c_linear), Hd, S, Hd, nullptr, 0, coef(nb + 1), nullptr, 0.f, nullptr, b2, s));
-  fused += 2;
-  if (q->which == 0) {  // the kept rows straight into the caller's output
-    tdnnf_mat ym = *out;
-    ym.rows = No;
-    CK(gemm_post(ix1, b2, W(H.c_output), S, P, S, bias(H.c_output), 0, nullptr, nullptr, 0.f, q->row_map, ym, s));
-  } else {
-    tdnnf_mat y = M(q->y, No, P), lsm = M(q->lsm, No, P);
-    CK(tdnnf_affine_propagate(&b2, W(H.c_output), S, bias(H.c_output), P, &y, s));
-    CK(tdnnf_log_softmax_propagate(&y, &lsm, s));
-    TDNNF_HIP(infer_scatter_rows(view(&lsm), q->row_map, view(out), s));
-  }
-  rows += 4LL * No;
+  // ---- the schedule of infer_forward.hip on the new rows, in exact f32 (the kept rows go straight into the caller's output)
+  FwdCounts cnt;
+  CK(infer_forward(q->model, q->head.coef, q->which, B, b, out, infer_gemm_f32, const_cast<tdnnf_net *>(q->model), s, &cnt));
   // ---- the last h time rows of every buffer back to their slots
   if (ndesc) {
-    hipLaunchKernelGGL(online_carry_kernel<true>, dim3(grid_for(q->carry_max * B, 256), ndesc), dim3(256), 0, s, q->descs, q->table, B, q->state, q->slot_floats);
+    hipLaunchKernelGGL(online_carry_kernel<true>, dim3(grid_for(q->carry_max * B, 256), ndesc), dim3(256), 0, s, q->descs, q->head.table, B, q->state, q->slot_floats);
     TDNNF_LAUNCH_CHECK();
   }
-  q->gemm_rows = rows;
+  q->gemm_rows = cnt.rows;
   q->carried_rows = (long long)q->carried_per_stream * B;
-  q->fused = fused;
-  q->fallback = fallback;
+  q->fused = cnt.fused;
+  q->fallback = cnt.fallback;
   return TDNNF_OK;
 }
 
@@ -359,6 +326,7 @@ int tdnnf_online_create(const tdnnf_net *model, int frames_per_step, int num_slo
   q->Tout = frames_per_step / c.frame_subsampling;
   q->num_slots = num_slots;
   q->which = which_output;
+  q->fwd.layers.resize(c.num_layers);
   std::vector<TdnnfLayer> grids;
   Grid g_lda;
   int rc = net_layer_grids(c, q->Tout, grids, &g_lda);  // (for the steps, which do not depend on the width)
@@ -512,7 +480,7 @@ int tdnnf_online_step(tdnnf_online *q, int num_active, const int *slots_host, co
   q->fused = q->fallback = 0;
   if (B == 0) return TDNNF_OK;
   hipStream_t s = (hipStream_t)stream;
-  TDNNF_HIP(hipMemcpyAsync(q->table, q->host_table.data(), sizeof(int) * kTab * B, hipMemcpyHostToDevice, s));
+  TDNNF_HIP(hipMemcpyAsync(q->head.table, q->host_table.data(), sizeof(int) * kTab * B, hipMemcpyHostToDevice, s));
   CK(forward_step(q, feats, ivectors, B, out, s));
   for (int i = 0; i < B; i++) {
     tdnnf_online::Slot &st = q->slots[slots_host[i]];

@@ -181,7 +181,7 @@ int planes_gemm_tile_rows(int N);
 int planes_gemm_launch_tile_rows(const PlanesGemmArgs &a);
 int planes_gemm_tile_cols(int N);
 hipError_t planes_gemm(const PlanesGemmArgs &a, hipStream_t s);
-// the same f16x3 product (np 2, row-major A planes, plain launch) with the inference epilogue (infer_planes.hip): same tiles as planes_gemm()
+// the same f16x3 product (np 2, row-major A planes, plain launch) with the inference epilogue (infer_planes.hip, as the GEMM of infer_forward.hip's schedule): same tiles as planes_gemm()
 hipError_t planes_gemm_post(const PlanesGemmArgs &a, hipStream_t s);
 // epilogue of a split-K launch whose slabs hold whole output rows (ksplit > 1, ntap <= 1, ldp_n == 1): C[m][n] = f(scale * sum_sp partial[sp][m][n])
 // with the launch's init / bias / addend / ReLU rules

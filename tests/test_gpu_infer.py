@@ -1,4 +1,4 @@
-"""-m gpu: forward-only inference over whole utterances (csrc/infer.hip, include/tdnnf_hip.h "inference").
+"""-m gpu: forward-only inference over whole utterances (csrc/infer.hip on the schedule of csrc/infer_forward.hip, include/tdnnf_hip.h "inference").
 
 The expectation is built in numpy from the contract: each chunk's clamped input window and i-vector, the CPU oracle's
 forward pass in test mode (OracleNet, cv_update) over those chunks, and the valid rows scattered into the stacked output."""

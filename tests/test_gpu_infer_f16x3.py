@@ -1,4 +1,4 @@
-"""-m gpu: whole-utterance inference in f16x3 (csrc/infer_planes.hip, tdnnf_infer_create_arith with gemm_precision 3): every GEMM of
+"""-m gpu: whole-utterance inference in f16x3 (csrc/infer_planes.hip on the schedule of csrc/infer_forward.hip, tdnnf_infer_create_arith with gemm_precision 3): every GEMM of
 the forward pass from f16 planes, held to the same expectation and the same bars as the f32 path (tests/test_gpu_infer.py).
 
 Shapes: the smallest at which a tile's overhang (fewer rows than one 256-row tile, a batch of one after a full batch), the taps'

@@ -1,4 +1,4 @@
-"""-m gpu: streaming inference with per-stream state carried between calls (csrc/online.hip, include/tdnnf_hip.h "inference (forward
+"""-m gpu: streaming inference with per-stream state carried between calls (csrc/online.hip on the schedule of csrc/infer_forward.hip, include/tdnnf_hip.h "inference (forward
 only, streaming)").
 
 The expectation is always the CPU oracle over whole utterances (tests/test_gpu_infer.py `expected`): streaming a constant i-vector
