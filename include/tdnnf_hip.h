@@ -58,7 +58,7 @@ int tdnnf_abi_version(void);
      "gemm_ring"     1 (default) persistent LDS-DMA-ring rows GEMM where it applies, 0 the plain tile kernel
      "planes"        1 (default) gemm_precision 2 runs the pre-split bf16-plane GEMMs where they apply, 0 the in-kernel split
      "den_mw_test_abort", "planes_check_bound": test hooks (0 = off), see tests/test_gpu_parity.py, tests/test_gpu_net.py
-     "den_split"     -1 (default) the trainer runs the denominator's two recursions side by side for <= 96 sequences, 0 never, 1 always
+     "den_split"     -1 (default) and 1: the trainer runs the denominator's two recursions side by side; 0 never (read at a net's first step)
                      (set before the first tdnnf_net_forward_backward of a net: it sizes the chain workspace)
      "num_form"      0 (default) the numerator by the supervision's width: one wave per sequence for at most 4 states per frame on average,
                      one workgroup per sequence with the frontier in LDS for wider ones; 1 / 2 force one (A/B runs, tests).  A narrow
@@ -308,13 +308,20 @@ int tdnnf_supervision_info(const tdnnf_supervision *, int *num_states, int *num_
    graph size (default), 1 / 2 force one (tests, experiments); 3 = the persistent form with ONE workgroup per sequence even for
    few sequences (otherwise up to 32 sequences take four workgroups each, which must be co-resident: checked against the
    occupancy calculator before the launch, a bounded poll behind it, and the one-workgroup kernels redo a minibatch whose
-   multi-workgroup launch gave up -- reported on stderr once, not used again in the process).  Affects the workspace size:
-   set it before tdnnf_chain_workspace_bytes / tdnnf_net_create. */
+   multi-workgroup launch gave up -- reported on stderr once, not used again in the process); 4 = persistent, forward then
+   one-kernel backward on one stream (the trainer's den_split 0 form): tdnnf_chain_objf_and_deriv runs the forward recursion and
+   then ONE kernel for the backward recursion and the occupancies, where modes 1 and 3 run the two recursions side by side and an
+   occupancy pass over all frames; plan, workspace size and the fallback to state vectors in global memory are mode 1's, and
+   tdnnf_chain_objf is unaffected.  Affects the workspace size: set it before tdnnf_chain_workspace_bytes / tdnnf_net_create. */
 int tdnnf_chain_set_denominator_mode(int mode);
 /* diagnostics: minibatches the one-workgroup kernels redid behind a multi-workgroup launch that gave up; whether that form is switched off for
    the process; reset != 0 clears both (synchronises the device) */
 int tdnnf_chain_den_mw_status(int *fallbacks, int *disabled, int reset);
 size_t tdnnf_chain_workspace_bytes(const tdnnf_den_graph *, int num_sequences, int frames_per_sequence);
+/* diagnostics: bytes at the END of a workspace of tdnnf_chain_workspace_bytes that only the side-by-side recursions and their occupancy pass
+   touch (0 where the plan has no such form).  The one-kernel backward pass (mode 4, the trainer's den_split 0) leaves them alone, which is
+   why a trainer that never runs the side-by-side form allocates that much less. */
+size_t tdnnf_chain_split_region_bytes(const tdnnf_den_graph *, int num_sequences, int frames_per_sequence);
 /* results_dev (device doubles): [0] objf, [1] l2_term, [2] weight, [3] num logprob (weighted),
    [4] den logprob (weighted), [5] ok flag (1.0 / 0.0), [6] xent objf when xent_output given.
    nnet_output_deriv is OVERWRITTEN; xent_deriv (may be NULL) receives the numerator posteriors

@@ -14,7 +14,9 @@
 namespace tdnnf {
 namespace {
 
-int g_den_mode = 0;  // tdnnf_chain_set_denominator_mode: 0 automatic, 1 persistent, 2 wide, 3 persistent with one workgroup per sequence
+// tdnnf_chain_set_denominator_mode: 0 automatic, 1 persistent, 2 wide, 3 persistent with one workgroup per sequence, 4 persistent with the
+// forward recursion, then the one-kernel backward pass on one stream (plan and workspace as mode 1)
+int g_den_mode = 0;
 // per device (a process may drive several): a time-out on one device says nothing about the others
 struct MwDev {
   unsigned *fallbacks = nullptr;  // pinned host memory, written by den_mw_check_kernel
@@ -447,8 +449,8 @@ int chain_den(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf
   ProfHbmRange prof(6, (double)B * T * (24.0 * g->A + 12.0 * g->P), s);
   int rc;
   if (c.b.p.wide) rc = den_wide(c);  // mode 2, or automatic and the state vectors do not fit the LDS
-  else if (c.b.p.split && !beside_other_work) rc = den_split(c, caller_aux, ev_recursions, ev_recorded);
-  else rc = den_serial(c);
+  else if (c.b.p.split && !beside_other_work && g_den_mode != 4) rc = den_split(c, caller_aux, ev_recursions, ev_recorded);
+  else rc = den_serial(c);  // the trainer without option den_split, mode 4, or the state vectors in global memory
   if (rc) return rc;
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
@@ -476,7 +478,8 @@ using namespace tdnnf;
 extern "C" {
 
 int tdnnf_chain_set_denominator_mode(int mode) {
-  TDNNF_REQUIRE(mode >= 0 && mode <= 3, "chain_set_denominator_mode: 0 automatic, 1 persistent, 2 wide, 3 persistent with one workgroup per sequence");
+  TDNNF_REQUIRE(mode >= 0 && mode <= 4, "chain_set_denominator_mode: 0 automatic, 1 persistent, 2 wide, 3 persistent with one workgroup per sequence, "
+                                        "4 persistent, forward then one-kernel backward on one stream");
   g_den_mode = mode;
   return TDNNF_OK;
 }
@@ -500,6 +503,8 @@ size_t tdnnf_chain_workspace_bytes(const tdnnf_den_graph *g, int B, int T) {
   ChainPlan p = chain_plan(g, B, T, B * 4 * (T + 1));
   return sizeof(double) * (3 * (size_t)B + 2) + sizeof(float) * (p.alpha_floats + p.asum_floats + p.gstate_floats + p.la_floats) + 768;
 }
+
+size_t tdnnf_chain_split_region_bytes(const tdnnf_den_graph *g, int B, int T) { return chain_split_region_bytes(g, B, T); }
 
 size_t tdnnf_chain_objf_workspace_bytes(const tdnnf_den_graph *g, int B, int T) {
   if (!g || B <= 0 || T <= 0) return 0;

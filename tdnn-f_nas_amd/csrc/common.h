@@ -45,9 +45,11 @@ inline bool vec4_ok(const MatView &m) {
 // Tuning options (tdnnf_set_option / tdnnf_get_option, include/tdnnf_hip.h): process-wide integers that select between code paths;
 // the library reads no environment variable for them.  What is tested: the GEMM planners' options (gemm_ring, splitk_partial_round,
 // splitk_per_cu, gemm_alt_taps, ng_bk, wgrad_small) value by value and element by element, with the launch-form counters
-// (launch_forms.h) as the witness of the path that ran (tests/test_gpu_gemm_forms.py); ng_fuse, ng_valu, planes, den_split, num_form and
-// the test hooks by the tests that name them.  The trainer's scheduling options (xent_behind_den, ng_early_fork, wgrad_lag,
-// wgrad_on_caller, reverse_passes, ng_pform, ng_early_in, ng_grouped) are tested at their defaults only.
+// (launch_forms.h) as the witness of the path that ran (tests/test_gpu_gemm_forms.py); ng_fuse, ng_valu, planes, num_form and
+// the test hooks by the tests that name them; den_split and xent_behind_den at 0 and 1 by the trainer test that names them
+// (tests/test_gpu_net.py: a small net under den_split x xent_behind_den x wgrad_stream), and den_split 0's kernels stand-alone as
+// denominator mode 4 (tests/test_gpu_chain_hostile.py, tests/test_gpu_parity.py).  The trainer's other scheduling options (ng_early_fork,
+// wgrad_lag, wgrad_on_caller, reverse_passes, ng_pform, ng_early_in, ng_grouped) are tested at their defaults only.
 struct Options {
   int ng_grouped = 1;     // natural gradient: 1 the side chain of a gradient bucket as grouped launches, 0 per object (read by tdnnf_net_create)
   int ng_fuse = 1;        // output-side statistic H = dY Wy^T: 0 by its own GEMM, 1 inside the BatchNorm / ReLU backward sweep when that pays, 2 always
@@ -67,12 +69,12 @@ struct Options {
   int wgrad_small = 0;    // weight gradients of launches with at most this many rows on 64 x 64 tiles (0: off)
   int ng_bk = 0;          // natural-gradient statistics passes H = X W^T, longer K steps: bit 0 = 64 instead of 32 for rank <= 32, bit 1 = 32 instead of 16 for rank <= 96
   int ng_early_fork = 1;  // trainer, minibatches without weight-gradient streams: the trunk components' early input statistics start where the trunk's forward pass ends (beside the denominator's recursions) instead of behind the xent head's backward pass
-  int xent_behind_den = -1;  // trainer: the xent head's forward pass waits for the denominator's two recursions (their 1024-thread workgroups pin half the CUs): -1 minibatches without weight-gradient streams, 0 never, 1 always
+  int xent_behind_den = -1;  // trainer: the xent head's forward pass waits for the denominator's two recursions (their 1024-thread workgroups pin half the CUs): -1 minibatches without weight-gradient streams, 0 never, 1 always; only with den_split on (the one-kernel backward pass has no point between its recursions to wait at)
   int ng_pform = 1;       // natural-gradient statistics of a component whose K taps are row shifts of one matrix (the .linear inputs): one pass over the matrix for all taps' products (ng_stats.hip ng_pform_pass) instead of K
   int ng_valu = 0;        // natural-gradient statistics passes H = X W^T on the vector ALUs (ng_valu.hip) where the rank is 20 / 40 / 80 (measured: no gain, docs/experiments.md r5-n); 0: the MFMA rows GEMM
   int ng_diag_skip = 0;   // diagnostics (timing only, results wrong): skip the statistics passes H = X W^T -- bit 0 two-tap inputs >= 1024 wide, bit 1 every other
   int phase_events = 0;   // diagnostics: the trainer records an event on the caller's stream at every phase boundary of a step (tdnnf_net_phase_times)
-  int den_split = -1;     // trainer: the denominator's two recursions side by side (then the occupancies of all frames at once): -1 by minibatch size, 0 / 1
+  int den_split = -1;     // trainer: the denominator's two recursions side by side (then the occupancies of all frames at once): -1 and 1 always, 0 never (forward recursion, then the one-kernel backward pass, beside the xent head; the workspace is shorter by chain_split_region_bytes); latched at the net's first step
   int num_form = 0;       // the chain numerator: 0 by the supervision's width (numerator_kernel up to 4 states per frame on average, num_wide_kernels.h above), 1 / 2 force one; 2 at tdnnf_supervision_create also gives a narrow supervision the wide form's tables
   int gemm_arith_test = 0;   // tests: 1 / 3 = the stand-alone GEMM entries (no GemmPrecisionScope around them) run the in-kernel split-bf16 kernels bf16x3 / bf16x6 where exact f32 is the default; the exact-f32 scopes (natural gradient, orthonormal constraint) keep f32
   int num_frontier_cap = 0;  // tests: the wide numerator keeps its frontier in global memory for supervisions with a frame of more states than this (0: what the LDS holds)

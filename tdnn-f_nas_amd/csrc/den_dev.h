@@ -44,9 +44,12 @@ struct RowAhead {
 // The sum over one row of a sliced-ELL table (ap: the lane's first arc, w: the slice's width, uniform over the wave), arcs in order.  A row is a chain
 // of dependent-latency loads from L2: batches of eight, then four, then ONE batch for the last one to three arcs (indices clamped, the surplus terms
 // replaced by exact zeros) -- "#pragma unroll 4" left up to three single loads behind every row, "#pragma unroll 8" up to seven (measured: slower).
-template <class Term>
-__device__ __forceinline__ float sell_row_sum(const uint2 *ap, int w, Term term) {
-  float acc = 0.f;
+// Acc: the accumulator.  float everywhere but the occupancy rows of den_backward_kernel: a by-pdf row holds arcs / pdfs terms (1 300 at 13 000 states
+// and 40 pdfs), and their sequential float sum alone put a frame's occupancies up to 6e-6 from summing to 1 where the recursions' rows (the
+// in- and out-degree, a handful of arcs) cost nothing -- measured on peaky outputs (tests/test_gpu_chain_hostile.py, docs/experiments.md r6-n).
+template <class Acc = float, class Term>
+__device__ __forceinline__ Acc sell_row_sum(const uint2 *ap, int w, Term term) {
+  Acc acc = 0;
   int j = 0;
   for (; j + 8 <= w; j += 8) {
     uint2 a[8];

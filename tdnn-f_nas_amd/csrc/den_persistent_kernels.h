@@ -289,7 +289,8 @@ __global__ __launch_bounds__(kDenThreads) void den_backward_kernel(DenDev g, Mat
       const int sl = slot >> 6, ln = slot & 63;
       const int b0 = g.by_pdf.base[sl], w = (g.by_pdf.base[sl + 1] - b0) >> 6;
       const uint2 *ap = g.by_pdf.arc + b0 + ln;
-      const float acc0 = sell_row_sum(ap, w, [&](const uint2 a) { return __uint_as_float(a.y) * ad[a.x & 0xffffu] * bnext[a.x >> 16]; });
+      // (summed in double: the long rows of the three tables, and nothing renormalises a frame's occupancies behind this kernel)
+      const float acc0 = (float)sell_row_sum<double>(ap, w, [&](const uint2 a) { return __uint_as_float(a.y) * ad[a.x & 0xffffu] * bnext[a.x >> 16]; });
       float acc = acc0;
       const unsigned p = g.by_pdf.row[slot];
       if (p != 0xffffffffu) dr[p] = deriv_weight * acc * x[p];

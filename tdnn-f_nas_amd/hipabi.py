@@ -183,6 +183,12 @@ def launch_forms(reset=False):
     return {lib.tdnnf_gemm_launch_form_name(i).decode(): int(counts[i]) for i in range(n) if counts[i]}
 
 
+def chain_split_region_bytes(den_graph, num_sequences, frames_per_sequence):
+    """Diagnostics (tdnnf_chain_split_region_bytes): the bytes at the end of the chain workspace that only the denominator's side-by-side
+    recursions and their occupancy pass touch -- what a trainer under option den_split 0 leaves out.  Follows tdnnf_chain_set_denominator_mode."""
+    return int(load().tdnnf_chain_split_region_bytes(den_graph.h, int(num_sequences), int(frames_per_sequence)))
+
+
 class DenGraph:
     def __init__(self, g):
         lib = load()

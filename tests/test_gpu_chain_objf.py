@@ -152,7 +152,7 @@ def test_chain_objf_workspace_has_no_alpha_array(hip, pkg):
     assert full > 1 << 30 and 0 < small < full / 10
     # never larger than the full entry's, down to the smallest shapes (a full-size workspace is always accepted)
     tiny = pkg.hipabi.DenGraph(pkg.synth.make_den_graph(4, 3, mean_out_degree=2.0, seed=1))
-    for mode in (0, 1, 2, 3):
+    for mode in (0, 1, 2, 3, 4):
         with _Mode(pkg, mode):
             for B, T in ((1, 1), (2, 3), (17, 1), (40, 2)):
                 assert 0 < hip.chain_objf_workspace_bytes(tiny.h, B, T) <= hip.chain_workspace_bytes(tiny.h, B, T), (mode, B, T)

@@ -610,6 +610,117 @@ def test_early_input_statistics_are_bit_identical_to_the_in_order_ones(pkg, kind
     assert v.value == 1  # the context managers restored the defaults
 
 
+# ---- the trainer's two denominator schedules (option den_split) and where the xent head waits for them (option xent_behind_den)
+_DEN_KW = dict(frames_per_chunk=30, num_sequences=8, strides=[1, 1, 0, 3, 3], bottleneck=16, feat_dim=8, ivector_dim=4, hidden_dim=64, small_dim=32,
+               num_pdfs=50, use_natural_gradient=1)  # (the 7q-shaped config of test_early_input_statistics_are_bit_identical_to_the_in_order_ones)
+_DEN_VARIANTS = [(ds, xbd, wg) for ds in (0, 1) for xbd in (0, 1) for wg in (0, 2)]
+_den_runs = {}
+
+
+def _den_inputs(pkg, net, i):
+    T = pkg.trainer
+    feats, iv = T.synthetic_egs(net, seed=100 + i)
+    sup = pkg.synth.make_supervision(net.cfg.num_sequences, net.cfg.frames_per_chunk // 3, net.cfg.num_pdfs, seed=200 + i)
+    draws = np.random.default_rng(300 + i).uniform(1e-3, 1 - 1e-3, max(net.num_draws, 1)).astype(np.float32)
+    return feats, iv, sup, draws
+
+
+def _den_variant(pkg, den_split, xbd, wg):
+    """Three steps with updates of a small natural-gradient net on a 60-state graph under the three options: per step (gradients, results,
+    output.deriv), then the parameters; step 0 also against OracleNet.  Cached: the variants are compared with each other below.
+    Option den_split is latched at the net's FIRST STEP, not at its creation (net_step.hip: that step sizes the chain workspace, shorter by
+    tdnnf_chain_split_region_bytes without the side-by-side form), and xent_behind_den is read at every step: the options stay set over all
+    three steps, not only around the constructor."""
+    key = (den_split, xbd, wg)
+    if key in _den_runs:
+        return _den_runs[key]
+    T = pkg.trainer
+    den = pkg.synth.make_den_graph(60, _DEN_KW["num_pdfs"], mean_out_degree=4.0, seed=5)
+    with pkg.hipabi.option("den_split", den_split), pkg.hipabi.option("xent_behind_den", xbd), pkg.hipabi.option("wgrad_stream", wg):
+        net = T.ChainNet(T.make_config(**_DEN_KW))
+        params0 = net.init_params_numpy(seed=1, output_stddev=0.1)
+        net.set_params(params0)
+        dg = pkg.hipabi.DenGraph(den)
+        out = dict(steps=[], params0=params0, den=den, components=net.components, cfg=net.cfg)
+        for i in range(3):
+            feats, iv, sup, draws = _den_inputs(pkg, net, i)
+            net.set_random_draws(draws)
+            net.grads.zero_()
+            r = host(net.forward_backward(dev(feats), dev(iv), dg, pkg.hipabi.Supervision(sup), step=i))
+            out["steps"].append((host(net.grads).copy(), r.copy(), host(net.activation("output.deriv")).copy()))
+            net.update(1e-3, step=i)
+            if i == 0:
+                out["inputs0"] = (feats, iv, sup, draws)
+                out["params1"] = host(net.params).copy()
+        out["params"] = host(net.params).copy()
+        net.close()
+    _den_runs[key] = out
+    return out
+
+
+_den_oracle = {}
+
+
+def _den_oracle_step0(pkg, run):
+    if not _den_oracle:
+        ref = OracleNet(pkg, run["cfg"], run["components"])
+        feats, iv, sup, draws = run["inputs0"]
+        res, g, acts = ref.forward_backward(run["params0"], feats, iv, run["den"], sup, step=0, draws=draws)
+        _den_oracle.update(res=res, g=g, deriv=acts["output.deriv"], params1=ref.update(run["params0"], g, 1e-3, float(run["cfg"].num_sequences), 0))
+    return _den_oracle
+
+
+@pytest.mark.parametrize("den_split,xbd,wg", _DEN_VARIANTS, ids=["den_split%d-xent_behind_den%d-wgrad_stream%d" % v for v in _DEN_VARIANTS])
+def test_denominator_schedules_match_oracle(pkg, den_split, xbd, wg):
+    """(i) every variant of den_split x xent_behind_den x wgrad_stream holds test_net_step_matches_oracle's bars against OracleNet on step 0."""
+    run = _den_variant(pkg, den_split, xbd, wg)
+    o = _den_oracle_step0(pkg, run)
+    g, r, deriv = run["steps"][0]
+    e_obj, e_g = abs(r[0] - o["res"]["objf"]) / abs(o["res"]["objf"]), rel_l2(g, o["g"])
+    e_up = rel_l2(run["params1"] - run["params0"], o["params1"] - run["params0"])
+    print("PARITY test_gpu_net den_split %d xent_behind_den %d wgrad_stream %d step 0 gradient %.3e (bar 1e-3) objective %.2e output.deriv %.2e update %.3e"
+          % (den_split, xbd, wg, e_g, e_obj, rel_l2(deriv, o["deriv"]), e_up))
+    assert r[5] == 1.0 and r[2] == o["res"]["weight"]
+    assert e_obj < 1e-4
+    assert abs(r[6] - o["res"]["xent_objf"]) < 1e-4 * abs(o["res"]["xent_objf"])
+    assert rel_l2(deriv, o["deriv"]) < 1e-4
+    assert e_g < 1e-3
+    for c in run["components"][1:]:
+        sl = slice(c["begin"], c["begin"] + c["rows"] * c["cols"] + c["num_alpha"] + (c["rows"] if c["has_bias"] else 0))
+        assert rel_l2(g[sl], o["g"][sl]) < 2e-3, (c["name"], rel_l2(g[sl], o["g"][sl]))
+    assert e_up < 2e-3
+    for gi, ri, _ in run["steps"]:
+        assert np.isfinite(gi).all() and ri[5] == 1.0
+
+
+@pytest.mark.parametrize("wg", [0, 2], ids=["one-stream", "wgrad-streams"])
+@pytest.mark.parametrize("den_split", [0, 1])
+def test_xent_behind_den_moves_waits_only(pkg, den_split, wg):
+    """(ii) xent_behind_den 0 / 1: the same kernels on the same operands, only the events the xent head's stream waits on differ (and with
+    den_split 0 the option has nothing to move) -- gradients, results and parameters of all three steps bit for bit."""
+    a, b = _den_variant(pkg, den_split, 0, wg), _den_variant(pkg, den_split, 1, wg)
+    for i, ((ga, ra, da), (gb, rb, db)) in enumerate(zip(a["steps"], b["steps"])):
+        assert np.array_equal(ga, gb), (i, rel_l2(ga, gb))
+        assert np.array_equal(ra, rb) and np.array_equal(da, db), i
+    assert np.array_equal(a["params"], b["params"])
+
+
+@pytest.mark.parametrize("wg", [0, 2], ids=["one-stream", "wgrad-streams"])
+@pytest.mark.parametrize("xbd", [0, 1])
+def test_den_split_forms_agree_in_the_trainer(pkg, xbd, wg):
+    """(iii) den_split 0 (forward recursion, then den_backward_kernel, on a workspace without the split region) against 1 (the recursions side
+    by side, then the occupancy pass): other arithmetic, held to test_bench_shape_denominator_forms_agree's bars on the first step (the later
+    steps start from parameters that already differ)."""
+    a, b = _den_variant(pkg, 0, xbd, wg), _den_variant(pkg, 1, xbd, wg)
+    (_, ra, da), (_, rb, db) = a["steps"][0], b["steps"][0]
+    print("PARITY test_gpu_net den_split 0 against 1 (xent_behind_den %d wgrad_stream %d): den log-prob %.2e (bar 1e-6) output.deriv %.2e (bar 1e-4)"
+          % (xbd, wg, abs(ra[4] - rb[4]) / abs(rb[4]), rel_l2(da, db)))
+    assert not np.array_equal(da, db)  # the option did select the other kernels
+    assert abs(ra[4] - rb[4]) <= 1e-6 * abs(rb[4])
+    assert rel_l2(da, db) < 1e-4
+    assert ra[3] == rb[3]  # the numerator is the same kernel on the same logits
+
+
 def test_three_weight_gradient_streams_give_the_same_step(pkg):
     """Option wgrad_stream 3 (a third weight-gradient stream beside s4 / s2): the same kernels on the same operands in another stream
     order -- gradients, objective and parameters bit for bit those of the default two streams, natural gradient on, over a refresh."""

@@ -396,8 +396,10 @@ CHAIN_CASES = [(50, 40, 3, 8, 0.1, 0.0), (300, 200, 6, 30, 0.1, 5e-5), (2000, 60
 
 
 # both forms of the denominator recursion: one persistent workgroup per sequence (state vectors in LDS), one launch per frame
-# over all sequences on sequence-minor arrays (the form large graphs get); B = 70 and 130 put sequences in a second chunk of lanes
-@pytest.mark.parametrize("mode", [1, 2], ids=["persistent", "wide"])
+# over all sequences on sequence-minor arrays (the form large graphs get); B = 70 and 130 put sequences in a second chunk of lanes.
+# Mode 4 is the persistent form with the trainer's den_split 0 schedule: forward recursion, then den_backward_kernel (backward recursion and
+# occupancies in one kernel, beta scaled by 1 / tot and 1 / A(t)) where modes 1 and 3 run the self-normalised recursions side by side
+@pytest.mark.parametrize("mode", [1, 2, 4], ids=["persistent", "wide", "persistent-one-kernel-backward"])
 @pytest.mark.parametrize("H,P,B,T,leaky,l2", CHAIN_CASES + [(500, 300, 70, 6, 0.1, 0.0), (120, 90, 130, 4, 0.05, 1e-5)])
 def test_chain_objf_and_deriv(hip, ora, pkg, H, P, B, T, leaky, l2, mode):
     pkg.hipabi.check(pkg.hipabi.load().tdnnf_chain_set_denominator_mode(mode))
@@ -409,7 +411,7 @@ def test_chain_objf_and_deriv(hip, ora, pkg, H, P, B, T, leaky, l2, mode):
 
 # nnet_output, xent_output and both derivatives as sub-matrix views (any base pointer, any stride), one small case per denominator form
 @pytest.mark.parametrize("layout", VIEW_LAYOUTS)
-@pytest.mark.parametrize("mode", [1, 2], ids=["persistent", "wide"])
+@pytest.mark.parametrize("mode", [1, 2, 4], ids=["persistent", "wide", "persistent-one-kernel-backward"])
 def test_chain_objf_and_deriv_on_views(hip, ora, pkg, mode, layout):
     pkg.hipabi.check(pkg.hipabi.load().tdnnf_chain_set_denominator_mode(mode))
     try:
@@ -459,7 +461,7 @@ def _chain_case(hip, ora, pkg, H, P, B, T, leaky, l2, layout=None):
     check_y()
 
 
-@pytest.mark.parametrize("mode", [1, 2], ids=["persistent", "wide"])
+@pytest.mark.parametrize("mode", [1, 2, 4], ids=["persistent", "wide", "persistent-one-kernel-backward"])
 def test_chain_failure_path(hip, ora, pkg, mode):
     pkg.hipabi.check(pkg.hipabi.load().tdnnf_chain_set_denominator_mode(mode))
     try:

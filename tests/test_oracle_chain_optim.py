@@ -32,21 +32,14 @@ def _den_logprob_torch(g, y, B, leaky):
     return torch.stack(tot)
 
 
-def test_denominator_vs_brute_force_paths(ora, pkg):
-    """H=3, T=3, no leaky transitions: enumerate every state path."""
-    L = ora.lib()
-    g = pkg.synth.make_den_graph(3, 4, mean_out_degree=2.0, seed=11)
-    rng = np.random.default_rng(0)
-    B, T, P = 2, 3, 4
-    y = rng.standard_normal((T * B, P)).astype(F)
-    tot = C.c_double()
-    gs = ora.den_graph_struct(g)
-    L.oracle_chain_denominator(C.byref(gs), ora.omat(y), B, 0.0, 0.0, C.byref(tot), None)
-    ref = 0.0
+def _den_brute_force_logprobs(g, y, B):
+    """log p_den per sequence without leaky transitions: every start state and every arc path enumerated (tiny graphs only)."""
+    T = y.shape[0] // B
     arcs = list(zip(g["src"], g["dst"], g["pdf"], g["prob"]))
+    out = []
     for s in range(B):
         p = 0.0
-        for h0 in range(3):
+        for h0 in range(g["H"]):
             for path in itertools.product(range(len(arcs)), repeat=T):
                 w, cur, ok = float(g["init"][h0]), h0, True
                 for t, ai in enumerate(path):
@@ -58,7 +51,40 @@ def test_denominator_vs_brute_force_paths(ora, pkg):
                     cur = a[1]
                 if ok:
                     p += w
-        ref += np.log(p)
+        out.append(np.log(p))
+    return out
+
+
+def _num_brute_force_logprobs(sup, yt):
+    """log p_num per sequence as torch float64 scalars (differentiable in yt): every arc path of the supervision enumerated."""
+    B, T = sup["B"], sup["T"]
+    out = []
+    for s in range(B):
+        a0, a1 = sup["seq_arc_begin"][s], sup["seq_arc_begin"][s + 1]
+        by_time = [[a for a in range(a0, a1) if sup["state_time"][sup["arc_src"][a]] == t] for t in range(T)]
+        terms = []
+        for path in itertools.product(*by_time):
+            okp = sup["arc_src"][path[0]] == sup["seq_state_begin"][s]
+            for u, v in zip(path[:-1], path[1:]):
+                okp = okp and sup["arc_dst"][u] == sup["arc_src"][v]
+            if okp:
+                terms.append(sum(float(sup["arc_logprob"][a]) + yt[sup["state_time"][sup["arc_src"][a]] * B + s,
+                                                                  int(sup["arc_pdf"][a])] for a in path))
+        out.append(torch.logsumexp(torch.stack(terms), 0))
+    return out
+
+
+def test_denominator_vs_brute_force_paths(ora, pkg):
+    """H=3, T=3, no leaky transitions: enumerate every state path."""
+    L = ora.lib()
+    g = pkg.synth.make_den_graph(3, 4, mean_out_degree=2.0, seed=11)
+    rng = np.random.default_rng(0)
+    B, T, P = 2, 3, 4
+    y = rng.standard_normal((T * B, P)).astype(F)
+    tot = C.c_double()
+    gs = ora.den_graph_struct(g)
+    L.oracle_chain_denominator(C.byref(gs), ora.omat(y), B, 0.0, 0.0, C.byref(tot), None)
+    ref = sum(_den_brute_force_logprobs(g, y, B))
     assert abs(tot.value - ref) < 1e-5 * max(1, abs(ref))
 
 
@@ -94,19 +120,7 @@ def test_numerator_vs_brute_force_and_autograd(ora, pkg):
     tot = L.oracle_chain_numerator(C.byref(ss), ora.omat(y), ora.omat(post))
     # brute force: enumerate arc paths per sequence
     yt = torch.tensor(y, dtype=torch.float64, requires_grad=True)
-    total = 0
-    for s in range(B):
-        a0, a1 = sup["seq_arc_begin"][s], sup["seq_arc_begin"][s + 1]
-        by_time = [[a for a in range(a0, a1) if sup["state_time"][sup["arc_src"][a]] == t] for t in range(T)]
-        terms = []
-        for path in itertools.product(*by_time):
-            okp = sup["arc_src"][path[0]] == sup["seq_state_begin"][s]
-            for u, v in zip(path[:-1], path[1:]):
-                okp = okp and sup["arc_dst"][u] == sup["arc_src"][v]
-            if okp:
-                terms.append(sum(float(sup["arc_logprob"][a]) + yt[sup["state_time"][sup["arc_src"][a]] * B + s,
-                                                                  int(sup["arc_pdf"][a])] for a in path))
-        total = total + torch.logsumexp(torch.stack(terms), 0)
+    total = sum(_num_brute_force_logprobs(sup, yt))
     assert abs(tot - float(total.detach())) < 1e-5 * abs(float(total.detach()))
     total.backward()
     np.testing.assert_allclose(post, yt.grad.numpy(), rtol=1e-4, atol=1e-6)
