@@ -63,6 +63,8 @@ int tdnnf_abi_version(void);
      "num_form"      0 (default) the numerator by the supervision's width: one wave per sequence for at most 4 states per frame on average,
                      one workgroup per sequence with the frontier in LDS for wider ones; 1 / 2 force one (A/B runs, tests).  A narrow
                      supervision can take form 2 only if it was created while the option was 2 (tdnnf_supervision_create builds the tables then)
+     "align_form"    0 (default) best-path alignment keeps its two state vectors in LDS where they fit, in the workspace otherwise; 1 / 2
+                     force one (tests); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path
      "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
      "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
                      kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
@@ -353,6 +355,55 @@ int tdnnf_chain_objf(const tdnnf_den_graph *, const tdnnf_supervision *, const t
    (with the kernels that finish the objective).  Parts 4 and 2 read what part 1 left in the workspace / the supervision. */
 int tdnnf_chain_numerator_part(const tdnnf_den_graph *, const tdnnf_supervision *, const tdnnf_mat *nnet_output, int part, double *results_dev,
                                tdnnf_mat *nnet_output_deriv, tdnnf_mat *xent_deriv, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
+
+/* ------------------------------------------------------------------ A7, best-path alignment
+ * The best path (Viterbi) of a cyclic, epsilon-free acceptor with pdf-ids on its arcs, scored on rows of the model's output: forced
+ * alignment on transcript graphs (what nnet3-align-compiled | ali-to-pdf prints) and the free best path through the denominator graph.
+ * Not a decoder: no beam, no lattice, no word labels, no transition-ids; compiling graphs from transcripts stays the caller's job.
+ *
+ *   term(arc, t)  = (double)arc_logprob + (double)acoustic_scale * (double)y[t, arc_pdf]
+ *   alpha_0[s]    = (double)initial_logprob[s]
+ *   alpha_t+1[d]  = max over arcs into d of  alpha_t[src] + term(arc, t)
+ *   score         = max over s of  alpha_T[s] + (double)final_logprob[s]
+ * No clamp on y.  -inf marks "not reachable" / "not final"; an arc is a candidate only if its sum is greater than -inf (a NaN never is).
+ * Ties: among equal candidates the arc that comes first in the caller's arc list wins; among equal final states the lowest state.
+ * An utterance with no accepting path of its length gets ok = 0, score = -inf and every pdf-id (and state) -1, the other utterances of the
+ * call are unaffected; a score that is not finite for another reason (+inf) gives ok = 0 and the -1s too.
+ *
+ * One workgroup per utterance walks its frames; the state scores are doubles, two vectors alternating, in LDS when 2 * S * 8 bytes fit
+ * (about 9 600 states), in the workspace otherwise.  Option "align_form": 0 (default) chosen by size, 1 LDS, 2 workspace (read by
+ * tdnnf_align_workspace_bytes and tdnnf_align_best_path alike: set it before both).  The workgroup has 64 threads when the largest graph
+ * that an utterance of the call names has at most 64 states, 256 up to 1024 states, 1024 above.  In the LDS form the output row of the
+ * next frame is loaded coalesced one frame ahead and gathered from LDS where two rows of num_pdfs floats fit beside the vectors and
+ * num_pdfs <= 8 * threads; otherwise y[t, pdf] is gathered from global memory.  Same results either way. */
+typedef struct tdnnf_align_graphs tdnnf_align_graphs; /* device-resident set of graphs */
+
+/* host arrays in, device copy out.  States are numbered as tdnnf_supervision_create numbers a sequence's: graph g owns the states
+   [graph_state_begin[g], graph_state_begin[g + 1]) and the arcs [graph_arc_begin[g], graph_arc_begin[g + 1]); arc_src / arc_dst are these
+   global state numbers; initial_logprob / final_logprob have one entry per state (-inf: not initial / not final).
+   TDNNF_EINVAL: a pdf outside [0, num_pdfs) (so: an epsilon arc), a state outside its graph, a graph without a state whose
+   initial_logprob is above -inf or without one whose final_logprob is. */
+int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                              const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
+                              const float *final_logprob, tdnnf_align_graphs **out);
+void tdnnf_align_graphs_destroy(tdnnf_align_graphs *);
+/* states, arcs and largest in-degree of one graph; any out-pointer may be NULL */
+int tdnnf_align_graphs_info(const tdnnf_align_graphs *, int graph, int *num_states, int *num_arcs, int *max_in_degree);
+/* utt_graph[u] (host) names the graph of utterance u -- many utterances may share one; NULL: graph 0 if there is one graph, else graph u
+   (then num_utts must be num_graphs).  utt_frames[u] >= 0.  With S_u the states of utterance u's graph:
+     bytes = 16 + roundup(32 * num_utts, 256) + 4 * sum_u roundup(utt_frames[u] * S_u, 2)  [+ 16 * sum_u S_u in the workspace form]
+   (alignment slack; the per-utterance table; one back-pointer per (frame, state); the two state vectors).  0 for bad arguments. */
+size_t tdnnf_align_workspace_bytes(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames);
+/* Frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output (which may be a sub-matrix view): row_stride 1 reads the
+   concatenated utterances tdnnf_infer_compute writes, row_stride B a t-major minibatch of B sequences (utt_row_begin[u] = u).
+   pdf_out_dev: sum(utt_frames) ints, utterance after utterance.  state_out_dev (may be NULL): the path's states, local to the graph,
+   utt_frames[u] + 1 per utterance, utterance after utterance.  results_dev: two doubles per utterance, the score and the ok flag
+   (1.0 / 0.0).  Everything runs on the caller's stream and nothing waits for the device (the per-utterance table goes to the workspace
+   by hipMemcpyAsync from pageable memory).  TDNNF_EINVAL: a workspace smaller than tdnnf_align_workspace_bytes, a row outside the
+   matrix, fewer columns than num_pdfs. */
+int tdnnf_align_best_path(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                          int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,
+                          double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
 
 /* ========================================================================== A8
  * OnlineNaturalGradient::PreconditionDirections (UPSTREAM; call sites

@@ -372,6 +372,19 @@ inline void ChainObjf(const tdnnf_den_graph *den_graph, const tdnnf_supervision 
                          workspace_bytes, stream));
 }
 
+// Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
+// denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
+// pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance
+// (score, ok).  workspace: tdnnf_align_workspace_bytes(graphs, num_utts, utt_graph, utt_frames).
+template <class CuMat>
+inline void AlignBestPath(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                          int row_stride, const CuMat &nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev, double *results_dev,
+                          void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output);
+  Check(tdnnf_align_best_path(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, &vy, acoustic_scale, pdf_out_dev, state_out_dev,
+                              results_dev, workspace_dev, workspace_bytes, stream));
+}
+
 // ConstrainOrthonormalInternal nnet-utils.cc:914-1032 on a CuMatrixBase with rows <= cols (pass the transpose otherwise, :1068-1075)
 template <class CuMat>
 inline void ConstrainOrthonormal(float scale, CuMat *M, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {

@@ -2016,5 +2016,17 @@ inline void ComputeChainObjf(const tdnnf_den_graph *den_graph, const tdnnf_super
                            Hooks().stream);
 }
 
+// ------------------------------------------------------------------------------------------------ best-path alignment
+// What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
+// utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames
+// ints), score and ok flag into results_dev (two device doubles per utterance), on the hooks' stream.  `workspace` grows to
+// tdnnf_align_workspace_bytes -- one back-pointer per (frame, state) -- and is reused from call to call.
+inline void AlignBestPath(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames, const int32 *utt_row_begin,
+                          const CuMatrixBase &nnet_output, float acoustic_scale, int32 *pdf_out_dev, double *results_dev, Scratch *workspace) {
+  const size_t bytes = tdnnf_align_workspace_bytes(graphs, num_utts, utt_graph, utt_frames);
+  tdnnf_adapter::AlignBestPath(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, 1, nnet_output, acoustic_scale, pdf_out_dev, nullptr, results_dev,
+                               workspace->Get(bytes), bytes, Hooks().stream);
+}
+
 }  // namespace tdnnf_nnet3
 #endif  // TDNNF_NNET3_COMPONENTS_H_

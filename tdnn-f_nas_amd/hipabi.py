@@ -225,3 +225,66 @@ class Supervision:
         if getattr(self, "h", None) and _lib is not None:
             _lib.tdnnf_supervision_destroy(self.h)
             self.h = None
+
+
+class AlignGraphs:
+    """Device-resident set of pdf-labelled graphs for best-path alignment (tdnnf_align_graphs).  `graphs`: one graph or a list of graphs,
+    each a dict {S, P, src, dst, pdf, logprob, init, final} with states numbered from 0 (synth.make_alignment_graph,
+    synth.alignment_graph_from_den); they are stacked with the state numbering of tdnnf_align_graphs_create."""
+
+    def __init__(self, graphs, num_pdfs=None):
+        import numpy as np
+        lib = load()
+        graphs = [graphs] if isinstance(graphs, dict) else list(graphs)
+        self.h = C.c_void_p()
+        self.G = len(graphs)
+        self.P = int(num_pdfs if num_pdfs is not None else max(int(g["P"]) for g in graphs))
+        sb = np.concatenate([[0], np.cumsum([int(g["S"]) for g in graphs])])
+        ab = np.concatenate([[0], np.cumsum([len(g["src"]) for g in graphs])])
+        cat = lambda key, off=None: np.concatenate([np.asarray(g[key]) + (0 if off is None else off[i]) for i, g in enumerate(graphs)])
+        self._keep = [iarr(sb), iarr(ab), iarr(cat("src", sb)), iarr(cat("dst", sb)), iarr(cat("pdf")), farr(cat("logprob")),
+                      farr(cat("init")), farr(cat("final"))]
+        check(lib.tdnnf_align_graphs_create(self.G, self.P, *[k[1] for k in self._keep], C.byref(self.h)))
+        self.num_states = [int(g["S"]) for g in graphs]
+
+    @classmethod
+    def from_den_graph(cls, g):
+        """The graph of the free best path through a denominator graph: arcs log(prob), initial log(init) (-inf where init is 0),
+        every state final at 0."""
+        from . import synth
+        return cls(synth.alignment_graph_from_den(g))
+
+    def info(self, graph=0):
+        """{num_states, num_arcs, max_in_degree} of one graph (tdnnf_align_graphs_info)."""
+        v = [C.c_int() for _ in range(3)]
+        check(load().tdnnf_align_graphs_info(self.h, int(graph), *[C.byref(x) for x in v]))
+        return dict(zip(("num_states", "num_arcs", "max_in_degree"), (x.value for x in v)))
+
+    def workspace_bytes(self, utt_graph, utt_frames):
+        ug = iarr(utt_graph)[1] if utt_graph is not None else None
+        return int(load().tdnnf_align_workspace_bytes(self.h, len(utt_frames), ug, iarr(utt_frames)[1]))
+
+    def best_path(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, states=False):
+        """tdnnf_align_best_path on the current stream.  Returns (pdf_out int32 [sum frames], state_out int32 [sum frames + utterances]
+        or None, results float64 [utterances, 2]) as CUDA tensors; nothing is synchronised."""
+        import torch
+        n = len(utt_frames)
+        fr, frp = iarr(utt_frames)
+        rb, rbp = iarr(utt_row_begin)
+        ug = iarr(utt_graph) if utt_graph is not None else (None, None)
+        nbytes = int(load().tdnnf_align_workspace_bytes(self.h, n, ug[1], frp))
+        if nbytes == 0:
+            raise HipAbiError(f"tdnnf_align_workspace_bytes: {load().tdnnf_last_error().decode()}")
+        ws = workspace(nbytes)
+        total = int(fr.sum())
+        pdf_out = torch.empty(max(total, 1), dtype=torch.int32, device="cuda")
+        state_out = torch.empty(total + n, dtype=torch.int32, device="cuda") if states else None
+        results = torch.empty((n, 2), dtype=torch.float64, device="cuda")
+        check(load().tdnnf_align_best_path(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), ptr(pdf_out),
+                                           ptr(state_out), ptr(results), ptr(ws), nbytes, stream()))
+        return pdf_out[:total], state_out, results
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.tdnnf_align_graphs_destroy(self.h)
+            self.h = None

@@ -79,6 +79,12 @@ class AcousticModel:
         """utterances: list of (feats T_u x feat_dim, ivectors R_u x ivector_dim) (numpy or torch).  ivector_period <= 0: one
         i-vector per utterance (its first row).  Returns a list of torch CUDA tensors, O_u = ceil(T_u / fsf) x num_pdfs."""
         import torch
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return list(torch.split(out, outs)) if outs else []
+
+    def _compute_stacked(self, utterances, ivector_period):
+        """compute's work: (the outputs of all utterances stacked in one matrix, rows per utterance)"""
+        import torch
         feats, ivs, frames, ivrows = [], [], [], []
         for f, iv in utterances:
             f = torch.as_tensor(f, dtype=torch.float32).cuda()
@@ -97,7 +103,12 @@ class AcousticModel:
         ivr, ivp = hipabi.iarr(ivrows)
         hipabi.check(self.lib.tdnnf_infer_compute(self.h, len(frames), frp, hipabi.pmat(F), ivp, hipabi.pmat(IV), int(ivector_period),
                                                   hipabi.pmat(out), hipabi.stream()))
-        return list(torch.split(out, outs)) if outs else []
+        return out, outs
+
+    def align(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
+        """compute, then the best path of every utterance through its graph (align below); the output stays on the device in between."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale) if outs else []
 
     def counts(self):
         """(fused_layers, fallback_passes) of the last compute."""
@@ -298,3 +309,39 @@ def write_matrix_archive(path, items):
             f.write(key.encode() + b" \0BFM ")
             f.write(struct.pack("<bibi", 4, m.shape[0], 4, m.shape[1]))
             f.write(m.tobytes())
+
+
+def align(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
+    """Best-path alignment (include/tdnnf_hip.h, "best-path alignment") of the model's outputs, a list of O_u x num_pdfs CUDA tensors as
+    AcousticModel.compute returns them, through `graphs` (hipabi.AlignGraphs): utterance u takes graph utt_graph[u] -- None: the one
+    graph there is, or graph u.  Returns a list of (pdf-ids as torch int32 CUDA tensor, score, ok); an utterance without an accepting
+    path of its length has score -inf, ok False and pdf-ids of -1.  What ali-to-pdf would print; no beam, no lattice."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _align_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale)
+
+
+def _align_stacked(y, frames, graphs, utt_graph, acoustic_scale):
+    """align on the utterances' rows stacked in one matrix (what tdnnf_infer_compute writes): row_stride 1"""
+    import torch
+    rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    pdfs, _, results = graphs.best_path(y, frames, rows, 1, utt_graph, acoustic_scale)
+    res = results.cpu().numpy()  # (waits for the stream)
+    return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(pdfs, frames))]
+
+
+def write_int_vector_archive(path, items):
+    """Kaldi binary archive of vector<int32>: per item `key ' ' \\0B \\4 n` then n little-endian int32 (WriteIntegerVector; the intvec
+    encoding of include/tdnnf_kaldi_io.h, what the egs reader takes for <AlignmentPdfs>); what ali-to-pdf writes and copy-int-vector
+    reads with ark:path.  items: iterable of (key, ints) with sequences, numpy arrays or torch tensors."""
+    with open(path, "wb") as f:
+        for key, v in items:
+            if hasattr(v, "detach"):
+                v = v.detach().cpu().numpy()
+            v = np.ascontiguousarray(v, dtype="<i4").reshape(-1)
+            assert " " not in key and key
+            f.write(key.encode() + b" \0B")
+            f.write(struct.pack("<bi", 4, v.shape[0]))
+            f.write(v.tobytes())

@@ -230,3 +230,79 @@ def make_supervision_lattice(B, T, P, tolerance=2, alternatives=1, mean_dur=3.0,
             "state_time": i32(np.concatenate(state_time)), "final_logprob": np.concatenate(final).astype(np.float32),
             "arc_src": i32(np.concatenate(a_src)), "arc_dst": i32(np.concatenate(a_dst)), "arc_pdf": i32(np.concatenate(a_pdf)),
             "arc_logprob": a_lp, "weight": float(weight)}
+
+
+def make_alignment_graph(pdf_sequence, self_loops=True, optional=(), alternatives=None, seed=0, num_pdfs=None):
+    """Left-to-right transcript graph for best-path alignment: the shape of a compile-train-graphs output reduced to pdf labels.
+    Epsilon-free, so a state is "inside a unit": state 0 is the start, unit k is one state, every arc INTO it carries its pdf --
+    the entering arc and, with self_loops, its loop.  The main chain is one unit per entry of pdf_sequence.
+      alternatives  {k: [pdfs]}: a parallel branch of units with these pdfs beside main unit k (entered from k's predecessors,
+                    left to k's successors);
+      optional      main units that may be skipped: their predecessors also enter their successors (one unit per skip; with
+                    the last unit optional its predecessors are final, with the first the start enters unit 1).
+    Arcs are ordered by (source, destination) and carry small random log-weights (seed).  Returns {S, P, src, dst, pdf, logprob,
+    init, final} with states numbered from 0: init is 0 at the start state, final 0 at the last units, -inf elsewhere."""
+    rng = np.random.default_rng(seed)
+    pdfs = [int(p) for p in pdf_sequence]
+    n = len(pdfs)
+    assert n >= 1
+    edges = {(k - 1, k) for k in range(n)}  # unit -1 is the start
+    finals = {n - 1}
+    for k, branch in sorted((alternatives or {}).items()):
+        assert 0 <= k < n and len(branch) >= 1
+        first = len(pdfs)
+        pdfs += [int(p) for p in branch]
+        last = len(pdfs) - 1
+        edges |= {(b, b + 1) for b in range(first, last)}
+        edges.add((k - 1, first))
+        if k + 1 < n:
+            edges.add((last, k + 1))
+        else:
+            finals.add(last)
+    for k in sorted(set(optional)):
+        assert 0 <= k < n
+        pred = [u for (u, v) in edges if v == k]
+        succ = [v for (u, v) in edges if u == k and v != k]
+        edges |= {(u, v) for u in pred for v in succ}
+        if k in finals:
+            finals |= set(pred)
+    if self_loops:
+        edges |= {(u, u) for u in range(len(pdfs))}
+    arcs = sorted((u + 1, v + 1) for (u, v) in edges)
+    S = len(pdfs) + 1
+    src = np.asarray([a[0] for a in arcs], dtype=np.int32)
+    dst = np.asarray([a[1] for a in arcs], dtype=np.int32)
+    init = np.full(S, -np.inf, dtype=np.float32)
+    init[0] = 0.0
+    final = np.full(S, -np.inf, dtype=np.float32)
+    final[[f + 1 for f in finals]] = 0.0
+    P = int(num_pdfs if num_pdfs is not None else max(pdfs) + 1)
+    return {"S": S, "P": P, "src": src, "dst": dst, "pdf": np.asarray(pdfs, dtype=np.int32)[dst - 1],
+            "logprob": (-rng.random(len(arcs)) * 0.5).astype(np.float32), "init": init, "final": final}
+
+
+def alignment_graph_from_den(den):
+    """The graph of the free best path through a denominator graph (make_den_graph's dict), in make_alignment_graph's form: arcs
+    log(prob), initial log(init) with -inf where init is 0, every state final at 0."""
+    with np.errstate(divide="ignore"):
+        logprob = np.log(np.asarray(den["prob"], dtype=np.float64)).astype(np.float32)
+        init = np.log(np.asarray(den["init"], dtype=np.float64)).astype(np.float32)
+    return {"S": int(den["H"]), "P": int(den["P"]), "src": np.asarray(den["src"], dtype=np.int32), "dst": np.asarray(den["dst"], dtype=np.int32),
+            "pdf": np.asarray(den["pdf"], dtype=np.int32), "logprob": logprob, "init": init, "final": np.zeros(int(den["H"]), dtype=np.float32)}
+
+
+def alignment_graphs_from_supervision(sup):
+    """One graph per sequence of a supervision dict (make_supervision ...), in make_alignment_graph's form: the sequence's states and
+    arcs as they are, its time-0 state initial at 0, final_logprob as given."""
+    out = []
+    for s in range(int(sup["B"])):
+        s0, s1 = int(sup["seq_state_begin"][s]), int(sup["seq_state_begin"][s + 1])
+        a0, a1 = int(sup["seq_arc_begin"][s]), int(sup["seq_arc_begin"][s + 1])
+        init = np.full(s1 - s0, -np.inf, dtype=np.float32)
+        init[0] = 0.0
+        pdf = np.asarray(sup["arc_pdf"][a0:a1], dtype=np.int32)
+        out.append({"S": s1 - s0, "P": int(pdf.max()) + 1 if len(pdf) else 1, "src": np.asarray(sup["arc_src"][a0:a1], dtype=np.int32) - s0,
+                    "dst": np.asarray(sup["arc_dst"][a0:a1], dtype=np.int32) - s0, "pdf": pdf,
+                    "logprob": np.asarray(sup["arc_logprob"][a0:a1], dtype=np.float32), "init": init,
+                    "final": np.asarray(sup["final_logprob"][s0:s1], dtype=np.float32)})
+    return out

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Timing of best-path alignment (tdnnf_align_best_path) in its two uses:
+  forced  64 utterances x 500 frames, each on its own transcript graph of a few hundred states (synth.make_alignment_graph);
+  free    128 utterances x 500 frames sharing the bench's 4 000-state / 48 k-arc denominator graph.
+Prints ms per call and us per frame (ms / frames of one utterance: the utterances run side by side, one workgroup each) for both, and
+for the free decode the yardstick: tdnnf_chain_objf on the same graph and shape -- the denominator's forward recursion (the same
+per-frame gather with a sum in float, no back-pointer) with the numerator's recursion beside it -- and the ratio.  One JSON line.
+usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2]"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import __graft_entry__ as ge  # noqa: E402
+
+
+def timed(fn, calls):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=3)
+    ap.add_argument("--pdfs", type=int, default=6034)
+    ap.add_argument("--form", type=int, default=0, help="option align_form")
+    args = ap.parse_args()
+    pkg = ge.load_package()
+    abi = pkg.hipabi
+    lib = abi.load()
+    abi.check(lib.tdnnf_set_option(b"align_form", args.form))
+    P, T = args.pdfs, 500
+    rng = np.random.default_rng(0)
+    res = dict(metric="align_best_path", pdfs=P, frames=T, form=args.form, repeats=args.repeats, calls=args.calls)
+
+    def case(ag, B, utt_graph):
+        y = torch.randn(B * T, P, device="cuda")
+        frames, rows = abi.iarr([T] * B), abi.iarr(np.arange(B) * T)
+        ug = abi.iarr(utt_graph)
+        nb = int(lib.tdnnf_align_workspace_bytes(ag.h, B, ug[1], frames[1]))
+        ws = abi.workspace(nb)
+        pdfs = torch.zeros(B * T, dtype=torch.int32, device="cuda")
+        out = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+        s = abi.stream()
+
+        def run():
+            abi.check(lib.tdnnf_align_best_path(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, abi.ptr(pdfs), None, abi.ptr(out), abi.ptr(ws), nb, s))
+
+        run(), run()
+        torch.cuda.synchronize()
+        ms = [timed(run, args.calls) for _ in range(args.repeats)]
+        r = out.cpu().numpy()
+        return y, dict(utterances=B, workspace_bytes=nb, ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms],
+                       us_per_frame=round(1e3 * float(np.median(ms)) / T, 3), ok=int(r[:, 1].sum()))
+
+    # forced alignment: transcripts of 120 units with optional units and alternative branches -- a few hundred states each
+    graphs = [pkg.synth.make_alignment_graph(rng.integers(0, P, size=120).tolist(), optional=list(range(5, 120, 10)),
+                                             alternatives={k: rng.integers(0, P, size=12).tolist() for k in range(3, 120, 8)}, num_pdfs=P, seed=u)
+              for u in range(64)]
+    ag = abi.AlignGraphs(graphs, num_pdfs=P)
+    _, res["forced"] = case(ag, 64, np.arange(64))
+    res["forced"]["states_per_graph"] = int(np.mean(ag.num_states))
+    del ag
+    # free decode on the bench's denominator graph
+    den = pkg.synth.make_den_graph(4000, P, mean_out_degree=12.0, seed=1)
+    ag = abi.AlignGraphs.from_den_graph(den)
+    B = 128
+    y, res["free"] = case(ag, B, np.zeros(B, np.int32))
+    res["free"].update(ag.info())
+    # the yardstick: the objective-only chain computation (forward recursions only) on the same graph and shape, rows read as a t-major minibatch
+    dg = abi.DenGraph(den)
+    ds = abi.Supervision(pkg.synth.make_supervision_from_den(den, B, T, num_paths=2, seed=2))
+    nb = int(lib.tdnnf_chain_objf_workspace_bytes(dg.h, B, T))
+    ws = abi.workspace(nb)
+    out = torch.zeros(8, dtype=torch.float64, device="cuda")
+    s = abi.stream()
+
+    def objf():
+        abi.check(lib.tdnnf_chain_objf(dg.h, ds.h, abi.pmat(y), None, 0.1, 0.0, abi.ptr(out), abi.ptr(ws), nb, s))
+
+    objf(), objf()
+    torch.cuda.synchronize()
+    ms = [timed(objf, args.calls) for _ in range(args.repeats)]
+    res["chain_objf"] = dict(ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms], us_per_frame=round(1e3 * float(np.median(ms)) / T, 3))
+    res["free_over_chain_objf"] = round(res["free"]["ms"] / res["chain_objf"]["ms"], 3)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
