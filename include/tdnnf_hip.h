@@ -64,7 +64,8 @@ int tdnnf_abi_version(void);
                      one workgroup per sequence with the frontier in LDS for wider ones; 1 / 2 force one (A/B runs, tests).  A narrow
                      supervision can take form 2 only if it was created while the option was 2 (tdnnf_supervision_create builds the tables then)
      "align_form"    0 (default) best-path alignment keeps its two state vectors in LDS where they fit, in the workspace otherwise; 1 / 2
-                     force one (tests); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path
+                     force one (tests); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path, and in the same way by
+                     tdnnf_align_posteriors_workspace_bytes and tdnnf_align_posteriors
      "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
      "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
                      kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
@@ -382,7 +383,8 @@ typedef struct tdnnf_align_graphs tdnnf_align_graphs; /* device-resident set of 
    [graph_state_begin[g], graph_state_begin[g + 1]) and the arcs [graph_arc_begin[g], graph_arc_begin[g + 1]); arc_src / arc_dst are these
    global state numbers; initial_logprob / final_logprob have one entry per state (-inf: not initial / not final).
    TDNNF_EINVAL: a pdf outside [0, num_pdfs) (so: an epsilon arc), a state outside its graph, a graph without a state whose
-   initial_logprob is above -inf or without one whose final_logprob is. */
+   initial_logprob is above -inf or without one whose final_logprob is.  The device copy holds the arcs three times -- by destination
+   (best path, forward recursion), by source (backward recursion) and by pdf (posteriors) -- 48 bytes an arc plus the padding of the slices. */
 int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
                               const float *final_logprob, tdnnf_align_graphs **out);
@@ -404,6 +406,51 @@ size_t tdnnf_align_workspace_bytes(const tdnnf_align_graphs *, int num_utts, con
 int tdnnf_align_best_path(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                           int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,
                           double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
+
+/* ------------------------------------------------------------------ A7, forward-backward
+ * The summing counterpart of the best path on the same graphs (a tdnnf_align_graphs holds its arcs three times: by destination, by source,
+ * by pdf): the total log-likelihood of each utterance through its graph and, on request, the per-frame pdf posteriors -- the score of a
+ * transcript graph to set against the free path, soft alignments (what ali-to-post and its relatives consume), and the numerator of
+ * flat-start ("end-to-end") LF-MMI: GenericNumeratorComputation's recursion on cyclic per-utterance graphs, deriv = weight * posterior
+ * plus a log-prob.  No beam, epsilon-free graphs, pdf level (no transition-ids), as above.  All in double; term is the best path's:
+ *
+ *   term(arc, t)   = (double)arc_logprob + (double)acoustic_scale * (double)y[t, arc_pdf]
+ *   alpha_0[s]     = (double)initial_logprob[s]
+ *   alpha_t+1[d]   = LSE over arcs into d   of  alpha_t[src] + term(arc, t)
+ *   logprob        = LSE over s             of  alpha_T[s] + (double)final_logprob[s]
+ *   beta_T[s]      = (double)final_logprob[s]
+ *   beta_t[s]      = LSE over arcs out of s of  term(arc, t) + beta_t+1[dst]
+ *   gamma[t, p]    = sum over arcs with pdf p of exp(alpha_t[src] + term(arc, t) + beta_t+1[dst] - logprob)
+ *   post[t, p]     = (float)(weight * gamma[t, p])          for every p in [0, num_pdfs)
+ *
+ * LSE(v_1..v_n) = m + log(sum exp(v_i - m)) with m the greatest candidate; an empty or all -inf set gives -inf.  As for the best path a
+ * candidate counts only if it compares greater than -inf: a NaN or -inf one contributes nothing and a NaN never enters a state vector.
+ * No clamp on y.  ok = 1 iff logprob is finite (+inf in y can make it +inf, which is reported as it is); with ok = 0 every post element
+ * of that utterance's rows is 0, the other utterances of the call are unaffected.  A zero-frame utterance has logprob = LSE(init + final)
+ * and writes no row.  The order of a sum is the library's, so results are held to a tolerance (tests/test_gpu_posteriors.py), but it is
+ * fixed: every (t, p) element has one owner, there are no atomics, and two calls on the same inputs give the same bits, in either form.
+ *
+ * One workgroup per utterance with the best path's thread counts and option "align_form" for where the two state vectors live (read by
+ * both functions below: set it before both).  Where they fit, a third vector (alpha_t) and two output rows are staged in LDS beside
+ * them; otherwise those gathers read global memory.  Same results either way. */
+/* With S_u the states of utterance u's graph:
+     bytes = 16 + roundup(32 * num_utts, 256)  [+ 8 * sum_u (utt_frames[u] + 1) * S_u with want_posteriors]
+                                               [+ 16 * sum_u S_u in the workspace form]
+   (alignment slack; the per-utterance table; alpha of every frame; the two state vectors).  The alpha region is twice the best path's
+   back-pointers: about 2 GB for 128 x 500 frames on 4 000 states.  0 for bad arguments. */
+size_t tdnnf_align_posteriors_workspace_bytes(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames,
+                                              int want_posteriors);
+/* utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale as for tdnnf_align_best_path.  results_dev: two doubles per
+   utterance, logprob and the ok flag (1.0 / 0.0).  post_out (may be NULL) is addressed like nnet_output -- row utt_row_begin[u] + t *
+   row_stride; it may be a sub-matrix view and may have more than num_pdfs columns: columns [0, num_pdfs) of each of the call's frame rows
+   are OVERWRITTEN (zeros for the pdfs no arc names), nothing else of it is touched.  post_out == NULL (workspace: want_posteriors = 0):
+   only the forward recursion runs, on its two alternating vectors, and keeps no alpha per frame.  Everything runs on the caller's stream
+   and nothing waits for the device.  TDNNF_EINVAL: as for tdnnf_align_best_path (a workspace smaller than
+   tdnnf_align_posteriors_workspace_bytes, a row outside the matrix, fewer columns than num_pdfs), and a post_out with fewer than num_pdfs
+   columns or without one of the call's rows. */
+int tdnnf_align_posteriors(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                           int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, tdnnf_mat *post_out /* may be NULL */,
+                           double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
 
 /* ========================================================================== A8
  * OnlineNaturalGradient::PreconditionDirections (UPSTREAM; call sites

@@ -385,6 +385,21 @@ inline void AlignBestPath(const tdnnf_align_graphs *graphs, int num_utts, const 
                               results_dev, workspace_dev, workspace_bytes, stream));
 }
 
+// Forward-backward on the same graphs (tdnnf_hip.h, "forward-backward"): logprob and ok flag of every utterance into results_dev (2 doubles
+// per utterance) and, with post_out, weight x the per-frame pdf posteriors into columns [0, num_pdfs) of post_out's rows utt_row_begin[u] +
+// t * row_stride -- soft alignments, or the flat-start numerator's derivative (GenericNumeratorComputation: deriv = weight * posterior).
+// post_out null: the forward recursion alone.  workspace: tdnnf_align_posteriors_workspace_bytes(graphs, num_utts, utt_graph, utt_frames,
+// post_out != null).
+template <class CuMat>
+inline void AlignPosteriors(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                            int row_stride, const CuMat &nnet_output, float acoustic_scale, float weight, CuMat *post_out, double *results_dev,
+                            void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output), vp;
+  if (post_out) vp = View(*post_out);
+  Check(tdnnf_align_posteriors(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, &vy, acoustic_scale, weight,
+                               post_out ? &vp : nullptr, results_dev, workspace_dev, workspace_bytes, stream));
+}
+
 // ConstrainOrthonormalInternal nnet-utils.cc:914-1032 on a CuMatrixBase with rows <= cols (pass the transpose otherwise, :1068-1075)
 template <class CuMat>
 inline void ConstrainOrthonormal(float scale, CuMat *M, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {

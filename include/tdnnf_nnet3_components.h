@@ -2028,5 +2028,19 @@ inline void AlignBestPath(const tdnnf_align_graphs *graphs, int32 num_utts, cons
                                workspace->Get(bytes), bytes, Hooks().stream);
 }
 
+// ------------------------------------------------------------------------------------------------ forward-backward
+// The summing counterpart on the same stacked rows: the total log-likelihood of every utterance through its graph and its ok flag into
+// results_dev (two device doubles per utterance) and, with post_out, weight x the per-frame pdf posteriors into the same rows of post_out
+// (columns [0, num_pdfs) overwritten) -- what ali-to-post consumers read, and the numerator of flat-start LF-MMI
+// (GenericNumeratorComputation: deriv = weight * posterior).  post_out null: the forward recursion alone, no per-frame memory.
+// `workspace` grows to tdnnf_align_posteriors_workspace_bytes -- with post_out one double per (frame, state).
+inline void AlignPosteriors(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames, const int32 *utt_row_begin,
+                            const CuMatrixBase &nnet_output, float acoustic_scale, float weight, CuMatrixBase *post_out, double *results_dev,
+                            Scratch *workspace) {
+  const size_t bytes = tdnnf_align_posteriors_workspace_bytes(graphs, num_utts, utt_graph, utt_frames, post_out ? 1 : 0);
+  tdnnf_adapter::AlignPosteriors(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, 1, nnet_output, acoustic_scale, weight, post_out, results_dev,
+                                 workspace->Get(bytes), bytes, Hooks().stream);
+}
+
 }  // namespace tdnnf_nnet3
 #endif  // TDNNF_NNET3_COMPONENTS_H_

@@ -6,16 +6,8 @@
 #include <algorithm>
 #include <vector>
 
-#include "align_kernels.h"
+#include "align_graphs.h"
 #include "chain_plan.h"
-
-struct tdnnf_align_graphs {
-  int G, P;
-  std::vector<int> state_begin, num_arcs, max_in_degree;  // host: [G + 1], [G], [G]
-  tdnnf::AlignGraphDev *graphs;
-  int4 *slots, *heavy, *arcs;
-  float *init, *final;
-};
 
 namespace tdnnf {
 namespace {
@@ -157,6 +149,8 @@ int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_sta
   g->slots = g->heavy = nullptr;
   g->arcs = nullptr;
   g->init = g->final = nullptr;
+  g->fb_graphs = nullptr;
+  g->src_slots = g->src_heavy = g->src_arcs = g->pdf_slots = g->pdf_heavy = g->pdf_arcs = nullptr;
   g->state_begin.assign(graph_state_begin, graph_state_begin + num_graphs + 1);
   std::vector<AlignGraphDev> gd(num_graphs);
   std::vector<int4> arcs, slots, heavy;
@@ -205,7 +199,8 @@ int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_sta
   std::vector<float> init(initial_logprob, initial_logprob + NS), fin(final_logprob, final_logprob + NS);
   int rc;
   if ((rc = align_to_device(gd, &g->graphs)) || (rc = align_to_device(slots, &g->slots)) || (rc = align_to_device(heavy, &g->heavy)) ||
-      (rc = align_to_device(arcs, &g->arcs)) || (rc = align_to_device(init, &g->init)) || (rc = align_to_device(fin, &g->final))) {
+      (rc = align_to_device(arcs, &g->arcs)) || (rc = align_to_device(init, &g->init)) || (rc = align_to_device(fin, &g->final)) ||
+      (rc = align_fb_tables_create(g, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob))) {
     tdnnf_align_graphs_destroy(g);
     return rc;
   }
@@ -217,6 +212,7 @@ void tdnnf_align_graphs_destroy(tdnnf_align_graphs *g) {
   if (!g) return;
   void *ptrs[] = {g->graphs, g->slots, g->heavy, g->arcs, g->init, g->final};
   for (void *p : ptrs) hipFree(p);
+  align_fb_tables_free(g);
   delete g;
 }
 

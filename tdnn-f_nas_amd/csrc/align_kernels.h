@@ -1,5 +1,6 @@
 // align_kernels.h -- best path (Viterbi) through cyclic, epsilon-free acceptors with pdf-ids on their arcs: forced alignment on transcript
-// graphs, free decoding on the denominator graph.  Included by align.hip only.
+// graphs, free decoding on the denominator graph.  Included through align_graphs.h by align.hip, which launches the kernel, and by
+// align_fb.hip, which reads the same tables (AlignGraphDev, AlignDev) and constants.
 //
 // Arithmetic (held bit for bit by tests/test_gpu_align.py against tests/viterbi_ref64.py):
 //     term(arc, t) = (double)arc_logprob + (double)acoustic_scale * (double)y[t, arc_pdf]      (the product of two floats is exact in double,

@@ -228,7 +228,7 @@ class Supervision:
 
 
 class AlignGraphs:
-    """Device-resident set of pdf-labelled graphs for best-path alignment (tdnnf_align_graphs).  `graphs`: one graph or a list of graphs,
+    """Device-resident set of pdf-labelled graphs for best-path alignment and forward-backward (tdnnf_align_graphs).  `graphs`: one graph or a list of graphs,
     each a dict {S, P, src, dst, pdf, logprob, init, final} with states numbered from 0 (synth.make_alignment_graph,
     synth.alignment_graph_from_den); they are stacked with the state numbering of tdnnf_align_graphs_create."""
 
@@ -283,6 +283,37 @@ class AlignGraphs:
         check(load().tdnnf_align_best_path(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), ptr(pdf_out),
                                            ptr(state_out), ptr(results), ptr(ws), nbytes, stream()))
         return pdf_out[:total], state_out, results
+
+    def posteriors_workspace_bytes(self, utt_graph, utt_frames, want_posteriors=True):
+        ug = iarr(utt_graph)[1] if utt_graph is not None else None
+        return int(load().tdnnf_align_posteriors_workspace_bytes(self.h, len(utt_frames), ug, iarr(utt_frames)[1], 1 if want_posteriors else 0))
+
+    def _forward_backward(self, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post):
+        import torch
+        n = len(utt_frames)
+        fr, frp = iarr(utt_frames)
+        rb, rbp = iarr(utt_row_begin)
+        ug = iarr(utt_graph) if utt_graph is not None else (None, None)
+        nbytes = int(load().tdnnf_align_posteriors_workspace_bytes(self.h, n, ug[1], frp, 0 if post is None else 1))
+        if nbytes == 0:
+            raise HipAbiError(f"tdnnf_align_posteriors_workspace_bytes: {load().tdnnf_last_error().decode()}")
+        ws = workspace(nbytes)
+        results = torch.empty((n, 2), dtype=torch.float64, device="cuda")
+        check(load().tdnnf_align_posteriors(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), float(weight),
+                                            pmat(post), ptr(results), ptr(ws), nbytes, stream()))
+        return results
+
+    def posteriors(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0, out=None):
+        """tdnnf_align_posteriors on the current stream.  Returns (post, results): post float32, addressed like nnet_output (row
+        utt_row_begin[u] + t * row_stride) -- `out` if given, else a new zeroed [rows of nnet_output, num_pdfs] matrix; results float64
+        [utterances, 2] (logprob, ok).  CUDA tensors; nothing is synchronised."""
+        import torch
+        post = out if out is not None else torch.zeros((nnet_output.shape[0], self.P), dtype=torch.float32, device="cuda")
+        return post, self._forward_backward(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post)
+
+    def logprob(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0):
+        """The same call without a posterior matrix: the forward recursion alone.  Returns results float64 [utterances, 2] (logprob, ok)."""
+        return self._forward_backward(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, 1.0, None)
 
     def __del__(self):
         if getattr(self, "h", None) and _lib is not None:

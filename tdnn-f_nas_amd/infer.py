@@ -110,6 +110,17 @@ class AcousticModel:
         out, outs = self._compute_stacked(utterances, ivector_period)
         return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale) if outs else []
 
+    def posteriors(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10):
+        """compute, then forward-backward of every utterance through its graph (posteriors below): [(post [O_u, num_pdfs] CUDA tensor,
+        logprob, ok)]; the output stays on the device in between."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _posteriors_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight) if outs else []
+
+    def logprob(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
+        """compute, then the total log-likelihood of every utterance through its graph (logprob below): [(logprob, ok)]."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _logprob_stacked(out, outs, graphs, utt_graph, acoustic_scale) if outs else []
+
     def counts(self):
         """(fused_layers, fallback_passes) of the last compute."""
         a, b = C.c_int(), C.c_int()
@@ -345,3 +356,86 @@ def write_int_vector_archive(path, items):
             f.write(key.encode() + b" \0B")
             f.write(struct.pack("<bi", 4, v.shape[0]))
             f.write(v.tobytes())
+
+
+def posteriors(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+    """Forward-backward (include/tdnnf_hip.h, "forward-backward") of the model's outputs, a list of O_u x num_pdfs CUDA tensors as
+    AcousticModel.compute returns them, through `graphs` (hipabi.AlignGraphs; utt_graph as for align).  Returns a list of (post float32
+    [O_u, num_pdfs] CUDA tensor = weight x the per-frame pdf posteriors, logprob, ok): logprob is the log-sum over all paths of the
+    utterance's length; without a finite one ok is False and post all zeros.  Soft alignments and the flat-start numerator's derivative;
+    no beam, pdf level."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _posteriors_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight)
+
+
+def logprob(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
+    """The total log-likelihood alone (the forward recursion, no per-frame memory): a list of (logprob, ok)."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _logprob_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale)
+
+
+def _posteriors_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight):
+    """posteriors on the utterances' rows stacked in one matrix (what tdnnf_infer_compute writes): row_stride 1"""
+    import torch
+    rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    post, results = graphs.posteriors(y, frames, rows, 1, utt_graph, acoustic_scale, weight)
+    res = results.cpu().numpy()  # (waits for the stream)
+    return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(post, frames))]
+
+
+def _logprob_stacked(y, frames, graphs, utt_graph, acoustic_scale):
+    rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    res = graphs.logprob(y, frames, rows, 1, utt_graph, acoustic_scale).cpu().numpy()  # (waits for the stream)
+    return [(float(res[u, 0]), bool(res[u, 1] == 1.0)) for u in range(len(frames))]
+
+
+def write_posterior_archive(path, items, min_post=0.0):
+    """Kaldi binary archive of Posterior (vector<vector<pair<int32, BaseFloat>>>): per item `key ' ' \\0B`, then the frame count, and per
+    frame the pair count and the (pdf-id, posterior) pairs -- every int32 and float as `\\4` + 4 little-endian bytes, the size-prefixed
+    basic-type encoding include/tdnnf_kaldi_io.h restates; what ali-to-post writes and copy-post reads with ark:path.  The layout is
+    written AS RECALLED (hmm/posterior.cc WritePosterior), not checked against a Kaldi build.  items: iterable of (key, post [frames,
+    num_pdfs]) with numpy or torch matrices; entries with post <= min_post are dropped, pdf-ids ascend within a frame."""
+    with open(path, "wb") as f:
+        for key, m in items:
+            if hasattr(m, "detach"):
+                m = m.detach().cpu().numpy()
+            m = np.asarray(m, dtype=np.float32)
+            assert m.ndim == 2 and " " not in key and key
+            f.write(key.encode() + b" \0B")
+            f.write(struct.pack("<bi", 4, m.shape[0]))
+            for row in m:
+                ids = np.nonzero(row > min_post)[0]
+                f.write(struct.pack("<bi", 4, len(ids)))
+                pairs = np.zeros(len(ids), dtype=[("a", "i1"), ("pdf", "<i4"), ("b", "i1"), ("post", "<f4")])
+                pairs["a"], pairs["b"], pairs["pdf"], pairs["post"] = 4, 4, ids, row[ids]
+                f.write(pairs.tobytes())
+
+
+def read_posterior_archive(path):
+    """What write_posterior_archive wrote: {key: [frames][(pdf-id, posterior)]} (tests)."""
+    data, pos, out = open(path, "rb").read(), 0, {}
+
+    def basic(fmt):
+        nonlocal pos
+        assert data[pos] == 4, (pos, data[pos])
+        v, = struct.unpack_from(fmt, data, pos + 1)
+        pos += 5
+        return v
+
+    while pos < len(data):
+        end = data.index(b" ", pos)
+        key = data[pos:end].decode()
+        assert data[end + 1:end + 3] == b"\0B", key
+        pos = end + 3
+        frames = []
+        for _ in range(basic("<i")):
+            n = basic("<i")
+            frames.append([(basic("<i"), basic("<f")) for _ in range(n)])
+        out[key] = frames
+    return out

@@ -5,7 +5,10 @@
 Prints ms per call and us per frame (ms / frames of one utterance: the utterances run side by side, one workgroup each) for both, and
 for the free decode the yardstick: tdnnf_chain_objf on the same graph and shape -- the denominator's forward recursion (the same
 per-frame gather with a sum in float, no back-pointer) with the numerator's recursion beside it -- and the ratio.  One JSON line.
-usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2]"""
+--posteriors: instead of the yardstick, forward-backward (tdnnf_align_posteriors) on the same two workloads and the same data, with the
+posterior matrix ("posteriors") and without ("logprob": the forward recursion alone), timed INTERLEAVED with the best path (one
+repeat of each after the other), and the two ratios to the best path.
+usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors]"""
 import argparse
 import json
 import os
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--pdfs", type=int, default=6034)
     ap.add_argument("--form", type=int, default=0, help="option align_form")
+    ap.add_argument("--posteriors", action="store_true", help="time tdnnf_align_posteriors beside the best path")
     args = ap.parse_args()
     pkg = ge.load_package()
     abi = pkg.hipabi
@@ -58,10 +62,44 @@ def main():
 
         run(), run()
         torch.cuda.synchronize()
+        if args.posteriors:
+            return y, posteriors_case(ag, B, y, frames, rows, ug, run, out)
         ms = [timed(run, args.calls) for _ in range(args.repeats)]
         r = out.cpu().numpy()
         return y, dict(utterances=B, workspace_bytes=nb, ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms],
                        us_per_frame=round(1e3 * float(np.median(ms)) / T, 3), ok=int(r[:, 1].sum()))
+
+    def posteriors_case(ag, B, y, frames, rows, ug, best_path, bp_out):
+        nb = [int(lib.tdnnf_align_posteriors_workspace_bytes(ag.h, B, ug[1], frames[1], want)) for want in (0, 1)]
+        ws = abi.workspace(nb[1])
+        post = torch.zeros(B * T, P, device="cuda")
+        out = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+        s = abi.stream()
+
+        def full():
+            abi.check(lib.tdnnf_align_posteriors(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, abi.pmat(post), abi.ptr(out), abi.ptr(ws), nb[1], s))
+
+        def forward():
+            abi.check(lib.tdnnf_align_posteriors(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, None, abi.ptr(out), abi.ptr(ws), nb[0], s))
+
+        fns = dict(best_path=best_path, posteriors=full, logprob=forward)
+        for fn in fns.values():
+            fn(), fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in fns}
+        for _ in range(args.repeats):
+            for k, fn in fns.items():
+                ms[k].append(timed(fn, args.calls))
+        full()
+        r, rb = out.cpu().numpy(), bp_out.cpu().numpy()
+        d = dict(utterances=B, workspace_bytes=nb[1], workspace_bytes_logprob=nb[0], ok=int(r[:, 1].sum()),
+                 logprob_minus_best_path_min=round(float((r[:, 0] - rb[:, 0]).min()), 3),
+                 row_sum_err=float((post.sum(1, dtype=torch.float64) - 1.0).abs().max()))
+        for k, v in ms.items():
+            d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v], us_per_frame=round(1e3 * float(np.median(v)) / T, 3))
+        d["posteriors_over_best_path"] = round(d["posteriors"]["ms"] / d["best_path"]["ms"], 3)
+        d["logprob_over_best_path"] = round(d["logprob"]["ms"] / d["best_path"]["ms"], 3)
+        return d
 
     # forced alignment: transcripts of 120 units with optional units and alternative branches -- a few hundred states each
     graphs = [pkg.synth.make_alignment_graph(rng.integers(0, P, size=120).tolist(), optional=list(range(5, 120, 10)),
@@ -77,6 +115,10 @@ def main():
     B = 128
     y, res["free"] = case(ag, B, np.zeros(B, np.int32))
     res["free"].update(ag.info())
+    if args.posteriors:
+        res["metric"] = "align_posteriors"
+        print(json.dumps(res))
+        return
     # the yardstick: the objective-only chain computation (forward recursions only) on the same graph and shape, rows read as a t-major minibatch
     dg = abi.DenGraph(den)
     ds = abi.Supervision(pkg.synth.make_supervision_from_den(den, B, T, num_paths=2, seed=2))
