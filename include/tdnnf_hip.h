@@ -305,6 +305,41 @@ void tdnnf_supervision_destroy(tdnnf_supervision *);
    (16 bytes per state) and a second copy of its arcs (20 bytes per arc); the chain workspace does not depend on the supervision.
    Any of the out-pointers may be NULL; *wide: 1 if the supervision is over that mark. */
 int tdnnf_supervision_info(const tdnnf_supervision *, int *num_states, int *num_arcs, int *max_states_per_frame, int *wide);
+/* The second kind of supervision: flat-start ("end-to-end") LF-MMI, Kaldi's GenericNumeratorComputation branch of
+   chain::ComputeChainObjfAndDeriv.  Per sequence ONE cyclic, epsilon-free acceptor with pdf-ids on its arcs (a transcript graph with
+   self-loops), every path of exactly frames_per_sequence arcs from an initial to a final state counts.  Host arrays in, device copy out;
+   state and arc numbering and the -inf conventions are tdnnf_align_graphs_create's (below): sequence s owns the states
+   [seq_state_begin[s], seq_state_begin[s + 1]) and the arcs [seq_arc_begin[s], seq_arc_begin[s + 1]).  TDNNF_EINVAL as there: a pdf outside
+   [0, num_pdfs), a state outside its sequence, a sequence with no initial or no final state.  A graph without a path of exactly
+   frames_per_sequence arcs is NOT refused here: its sequence's log-prob is -inf at run time, which is the objective's failure path
+   ([0] = -10 * weight * B * T, [5] = 0, [6] = 0, both derivative matrices zero).
+   Every function that takes a tdnnf_supervision works with this kind (the chain entries below, tdnnf_net_forward_backward,
+   tdnnf_net_objective); they require num_pdfs <= the denominator graph's.  With y_t = row t * B + s of nnet_output, all in double
+   (tdnnf_align_posteriors' arithmetic with acoustic_scale 1, see "forward-backward" below):
+     term(arc, t) = arc_logprob + y_t[arc_pdf]          no clamp
+     alpha_0 = initial_logprob;  alpha_t+1[d] = LSE over arcs into d of alpha_t[src] + term(arc, t)
+     num_lp[s] = LSE_st alpha_T[st] + final_logprob[st]
+     beta_T = final_logprob;     beta_t[st] = LSE over arcs out of st of term(arc, t) + beta_t+1[dst]
+     gamma[t, p] = sum over arcs with pdf p of exp(alpha_t[src] + term + beta_t+1[dst] - num_lp[s])
+   results[3] = weight * sum_s num_lp[s]; nnet_output_deriv[row, p] += (float)(weight * gamma) on top of the denominator's term (elements
+   whose pdf no arc of the sequence names are not touched); xent_deriv gets xent_regularize times the same float; results[6] = the sum of
+   that float times xent_output[row, p].  One owner per (t, p), no atomics: two calls give the same bits.
+   The device copy holds the arcs three times (48 bytes an arc, as a tdnnf_align_graphs) and the numerator's scratch, alpha_t and beta_t
+   of every frame:  16 * (frames_per_sequence + 1) * sum_s S_s bytes  [+ 16 * sum_s S_s where the two state vectors of the recursion do
+   not live in LDS: option "align_form" 2, or a graph of more than about 9 600 states; the option is read HERE] -- 150 output frames x
+   128 transcripts of 200 states: 62 MB.  The chain workspace formulas do not change.
+   tdnnf_supervision_info: the total states and arcs, max_states_per_frame = the largest graph's states, wide = 0.
+   Not built: reading end-to-end egs (the egs readers below still refuse <End2End> supervisions), compiling graphs from transcripts,
+   transition-id level output.  All sequences of a call share frames_per_sequence. */
+int tdnnf_supervision_create_e2e(int num_sequences, int frames_per_sequence, int num_pdfs, const int *seq_state_begin, const int *seq_arc_begin,
+                                 const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
+                                 const float *initial_logprob, const float *final_logprob, float weight, tdnnf_supervision **out);
+/* 0 time-synchronous (tdnnf_supervision_create), 1 end-to-end (tdnnf_supervision_create_e2e); -1 for NULL */
+int tdnnf_supervision_kind(const tdnnf_supervision *);
+/* diagnostics, end-to-end kind only: the launch form of its recursion -- threads per workgroup (64 up to 64 states in the largest graph,
+   256 up to 1024, 1024 above), whether the two state vectors live in LDS, whether the output rows are staged in LDS one frame ahead
+   (two rows of num_pdfs floats fit beside the vectors and num_pdfs <= 8 * threads).  Any out-pointer may be NULL. */
+int tdnnf_supervision_e2e_form(const tdnnf_supervision *, int *threads, int *vectors_in_lds, int *rows_in_lds);
 
 /* The denominator recursion has two forms: one persistent workgroup per sequence with the state vectors in LDS (graphs up
    to ~10 000 states), and one launch per frame over all sequences on sequence-minor arrays (larger graphs).  0 = chosen by
@@ -328,7 +363,9 @@ size_t tdnnf_chain_split_region_bytes(const tdnnf_den_graph *, int num_sequences
 /* results_dev (device doubles): [0] objf, [1] l2_term, [2] weight, [3] num logprob (weighted),
    [4] den logprob (weighted), [5] ok flag (1.0 / 0.0), [6] xent objf when xent_output given.
    nnet_output_deriv is OVERWRITTEN; xent_deriv (may be NULL) receives the numerator posteriors
-   already multiplied by xent_regularize (NnetChainTrainer::ProcessOutputs). */
+   already multiplied by xent_regularize (NnetChainTrainer::ProcessOutputs).
+   The l2 term is summed in a fixed order (per-workgroup partial sums in 2 KB that every supervision owns, added in ascending order): two
+   calls on the same inputs give the same bits in results_dev[1], with either kind of supervision. */
 int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *, const tdnnf_supervision *, const tdnnf_mat *nnet_output,
                                const tdnnf_mat *xent_output /* may be NULL */, float leaky_hmm_coefficient,
                                float l2_regularize, float xent_regularize, double *results_dev,
@@ -410,9 +447,9 @@ int tdnnf_align_best_path(const tdnnf_align_graphs *, int num_utts, const int *u
 /* ------------------------------------------------------------------ A7, forward-backward
  * The summing counterpart of the best path on the same graphs (a tdnnf_align_graphs holds its arcs three times: by destination, by source,
  * by pdf): the total log-likelihood of each utterance through its graph and, on request, the per-frame pdf posteriors -- the score of a
- * transcript graph to set against the free path, soft alignments (what ali-to-post and its relatives consume), and the numerator of
- * flat-start ("end-to-end") LF-MMI: GenericNumeratorComputation's recursion on cyclic per-utterance graphs, deriv = weight * posterior
- * plus a log-prob.  No beam, epsilon-free graphs, pdf level (no transition-ids), as above.  All in double; term is the best path's:
+ * transcript graph to set against the free path, soft alignments (what ali-to-post and its relatives consume).  It is also the arithmetic of
+ * the numerator of flat-start ("end-to-end") LF-MMI; to TRAIN on such graphs use tdnnf_supervision_create_e2e above, whose kernels run the
+ * same recursion beside the denominator and add the posteriors into the chain derivative.  No beam, epsilon-free graphs, pdf level (no transition-ids), as above.  All in double; term is the best path's:
  *
  *   term(arc, t)   = (double)arc_logprob + (double)acoustic_scale * (double)y[t, arc_pdf]
  *   alpha_0[s]     = (double)initial_logprob[s]

@@ -372,6 +372,18 @@ inline void ChainObjf(const tdnnf_den_graph *den_graph, const tdnnf_supervision 
                          workspace_bytes, stream));
 }
 
+// An end-to-end (flat-start) supervision for the two calls above, which take it unchanged: one cyclic, epsilon-free pdf-labelled graph per
+// sequence (what Kaldi's Supervision holds as e2e_fsts once its transition-ids are mapped to pdf-ids), host arrays in the numbering of
+// tdnnf_supervision_create_e2e (tdnnf_hip.h).  Throws on the argument errors listed there; release with tdnnf_supervision_destroy.
+inline tdnnf_supervision *SupervisionCreateE2e(int num_sequences, int frames_per_sequence, int num_pdfs, const int *seq_state_begin,
+                                               const int *seq_arc_begin, const int *arc_src, const int *arc_dst, const int *arc_pdf,
+                                               const float *arc_logprob, const float *initial_logprob, const float *final_logprob, float weight) {
+  tdnnf_supervision *sup = nullptr;
+  Check(tdnnf_supervision_create_e2e(num_sequences, frames_per_sequence, num_pdfs, seq_state_begin, seq_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob,
+                                     initial_logprob, final_logprob, weight, &sup));
+  return sup;
+}
+
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance

@@ -2016,6 +2016,18 @@ inline void ComputeChainObjf(const tdnnf_den_graph *den_graph, const tdnnf_super
                            Hooks().stream);
 }
 
+// An end-to-end (flat-start) supervision for the chain calls -- ComputeChainObjf above, tdnnf_adapter::ChainObjfAndDeriv -- which take it as
+// they take a time-synchronous one: per sequence one cyclic, epsilon-free graph with pdf-ids on its arcs (chain::Supervision::e2e_fsts with
+// the transition-ids mapped to pdf-ids; that mapping and the graph compilation stay the caller's), stacked in the numbering of
+// tdnnf_supervision_create_e2e.  Release with tdnnf_supervision_destroy.
+inline tdnnf_supervision *CreateEnd2EndSupervision(int32 num_sequences, int32 frames_per_sequence, int32 num_pdfs, const std::vector<int32> &seq_state_begin,
+                                                   const std::vector<int32> &seq_arc_begin, const std::vector<int32> &arc_src,
+                                                   const std::vector<int32> &arc_dst, const std::vector<int32> &arc_pdf, const std::vector<float> &arc_logprob,
+                                                   const std::vector<float> &initial_logprob, const std::vector<float> &final_logprob, float weight) {
+  return tdnnf_adapter::SupervisionCreateE2e(num_sequences, frames_per_sequence, num_pdfs, seq_state_begin.data(), seq_arc_begin.data(), arc_src.data(),
+                                             arc_dst.data(), arc_pdf.data(), arc_logprob.data(), initial_logprob.data(), final_logprob.data(), weight);
+}
+
 // ------------------------------------------------------------------------------------------------ best-path alignment
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames
@@ -2031,8 +2043,8 @@ inline void AlignBestPath(const tdnnf_align_graphs *graphs, int32 num_utts, cons
 // ------------------------------------------------------------------------------------------------ forward-backward
 // The summing counterpart on the same stacked rows: the total log-likelihood of every utterance through its graph and its ok flag into
 // results_dev (two device doubles per utterance) and, with post_out, weight x the per-frame pdf posteriors into the same rows of post_out
-// (columns [0, num_pdfs) overwritten) -- what ali-to-post consumers read, and the numerator of flat-start LF-MMI
-// (GenericNumeratorComputation: deriv = weight * posterior).  post_out null: the forward recursion alone, no per-frame memory.
+// (columns [0, num_pdfs) overwritten) -- what ali-to-post consumers read.  (Training on such graphs, flat-start LF-MMI, goes through
+// tdnnf_adapter::SupervisionCreateE2e and the chain entries instead.)  post_out null: the forward recursion alone, no per-frame memory.
 // `workspace` grows to tdnnf_align_posteriors_workspace_bytes -- with post_out one double per (frame, state).
 inline void AlignPosteriors(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames, const int32 *utt_row_begin,
                             const CuMatrixBase &nnet_output, float acoustic_scale, float weight, CuMatrixBase *post_out, double *results_dev,

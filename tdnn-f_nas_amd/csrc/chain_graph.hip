@@ -266,7 +266,7 @@ int tdnnf_supervision_create(int B, int T, const int *seq_state_begin, const int
       (rc = to_device(in_src, &sp->in_src)) || (rc = to_device(in_pdf, &sp->in_pdf)) || (rc = to_device(in_lp, &sp->in_lp)) ||
       (rc = to_device(out_begin, &sp->out_begin)) || (rc = to_device(out_dst, &sp->out_dst)) ||
       (rc = to_device(out_pdf, &sp->out_pdf)) || (rc = to_device(out_lp, &sp->out_lp)) ||
-      (rc = to_device(fsb, &sp->frame_state_begin))) {
+      (rc = to_device(fsb, &sp->frame_state_begin)) || (rc = to_device(std::vector<double>(kFinishL2Parts, 0.0), &sp->l2_part))) {
     tdnnf_supervision_destroy(sp);
     return rc;
   }
@@ -299,8 +299,10 @@ void tdnnf_supervision_destroy(tdnnf_supervision *sp) {
   if (!sp) return;
   void *ptrs[] = {sp->seq_state_begin, sp->state_time, sp->final_logprob, sp->in_begin, sp->in_src, sp->in_pdf,
                   sp->in_lp, sp->out_begin, sp->out_dst, sp->out_pdf, sp->out_lp, sp->frame_state_begin,
-                  sp->la_own, sp->lb_own, sp->pf_src, sp->pf_dst, sp->pf_pdf, sp->pf_t, sp->pf_lp, sp->xent_part};
+                  sp->la_own, sp->lb_own, sp->pf_src, sp->pf_dst, sp->pf_pdf, sp->pf_t, sp->pf_lp, sp->xent_part,
+                  sp->e2e_alpha, sp->e2e_beta, sp->e2e_vecs, sp->l2_part};
   for (void *p : ptrs) hipFree(p);
+  tdnnf_align_graphs_destroy(sp->e2e_graphs);  // (end-to-end kind: chain_num_e2e.hip; null otherwise)
   delete sp;
 }
 

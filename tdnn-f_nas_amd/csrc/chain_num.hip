@@ -1,6 +1,7 @@
 // chain_num.hip -- the numerator of the chain objective (log domain; one wave per sequence for narrow supervisions, num_wide_kernels.h for
 // wide ones), the kernels that finish the objective (sum, l2 term, failure path) and the entry point that runs all three parts.
-// Denominator: chain_den.hip.
+// Denominator: chain_den.hip.  An end-to-end supervision (kind 1: one cyclic graph per sequence) takes the kernels of chain_num_e2e.hip
+// instead: the host functions here dispatch on the kind, everything else -- zero-fill, l2 term, finish, failure path -- is shared.
 #include <math.h>
 
 #include <algorithm>
@@ -125,20 +126,10 @@ __global__ void chain_guard_kernel(const double *results, MatView y, float l2_sc
     }
   }
 }
-__global__ __launch_bounds__(256) void sumsq_kernel(MatView y, double *out) {
-  __shared__ double red[4];
-  double s = 0;
-  const long long total = (long long)y.rows * y.cols;
-  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += gridDim.x * 256LL) {
-    const double v = y.data[(size_t)(e / y.cols) * y.stride + e % y.cols];
-    s += v * v;
-  }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
-}
-// the same sum without atomics (tdnnf_chain_objf: the l2 term has the same bits on every call): part[block], then their sum in order
+// the l2 term's sum of squares without atomics (the term has the same bits on every call): part[block], then their sum in order.  Until the
+// end-to-end supervision came, chain_finish added per-block sums with atomicAdd on a double, in the order the blocks arrived: the term's
+// last bits differed between two calls on the same inputs (1 - 4 ulps, tests/test_gpu_chain_e2e.py), which no two calls can then be
+// compared by.  tdnnf_chain_objf always summed this way.
 __global__ __launch_bounds__(1024) void sumsq_parts_kernel(MatView y, double *part) {
   __shared__ double red[16];
   double s = 0;
@@ -221,7 +212,9 @@ float chain_supervision_weight(const tdnnf_supervision *sp) { return sp->weight;
 // xent head's forward pass: 1.35 ms of one wave per sequence walking 2 x 500 dependent frames that the step otherwise waited for),
 // the xent posteriors need the recursion and the xent head's log-softmax.
 namespace {
-int num_recursion(const tdnnf_supervision *sp, const tdnnf_mat *y, const ChainBufs &b, hipStream_t s) {
+// forward_only (tdnnf_chain_objf without an xent_output): an end-to-end supervision keeps nothing per frame; the other kind runs as ever
+int num_recursion(const tdnnf_supervision *sp, const tdnnf_mat *y, const ChainBufs &b, hipStream_t s, bool forward_only = false) {
+  if (sp->kind == 1) return num_e2e_recursion(sp, view(y), b.num_lp, forward_only, s);
   const int B = sp->B;
   const MatView none{nullptr, 0, 0, 0};
   NumCall c;
@@ -245,6 +238,7 @@ int num_xent(const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *x
     if (xdv.stride == xdv.cols) TDNNF_HIP(hipMemsetAsync(xdv.data, 0, sizeof(float) * (size_t)xdv.rows * xdv.cols, s));  // one contiguous fill
     else hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for((long long)xdv.rows * xdv.cols, 256)), dim3(256), 0, s, xdv);
   }
+  if (sp->kind == 1) return num_e2e_posteriors(sp, yv, xov, b.num_lp, b.xent, MatView{nullptr, 0, 0, 0}, xdv, xent_regularize, true, s);
   NumCall c;
   int rc = num_call(sp, b, &c);
   if (rc) return rc;
@@ -276,16 +270,20 @@ int chain_finish(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const td
   ChainBufs b = chain_bufs(g, B, T, ws);
   MatView yv = view(y), dv = view(deriv);
   MatView xdv = xent_deriv ? view(xent_deriv) : MatView{nullptr, 0, 0, 0};
-  NumCall c;
-  int rc = num_call(sp, b, &c);
-  if (rc) return rc;
-  if (c.wide_form) num_wide_posteriors(sp, yv, MatView{nullptr, 0, 0, 0}, c, b, dv, MatView{nullptr, 0, 0, 0}, 0.f, false, s);
-  else
-    hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, MatView{nullptr, 0, 0, 0}, c.la, c.lb, b.num_lp, b.xent, dv,
-                       MatView{nullptr, 0, 0, 0}, 0.f, 2);
-  if (l2_regularize != 0.f) {
-    TDNNF_HIP(hipMemsetAsync(b.l2sum, 0, sizeof(double), s));
-    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for((long long)yv.rows * yv.cols, 256, 1024)), dim3(256), 0, s, yv, b.l2sum);
+  const MatView none{nullptr, 0, 0, 0};
+  int rc;
+  if (sp->kind == 1) {
+    if ((rc = num_e2e_posteriors(sp, yv, none, b.num_lp, b.xent, dv, none, 0.f, false, s))) return rc;
+  } else {
+    NumCall c;
+    if ((rc = num_call(sp, b, &c))) return rc;
+    if (c.wide_form) num_wide_posteriors(sp, yv, none, c, b, dv, none, 0.f, false, s);
+    else hipLaunchKernelGGL(numerator_kernel, dim3(B), dim3(64), 0, s, sup_dev(sp), yv, none, c.la, c.lb, b.num_lp, b.xent, dv, none, 0.f, 2);
+  }
+  if (l2_regularize != 0.f) {  // (as many threads as the atomic form had: kFinishL2Parts blocks of 1024 where it had 1024 of 256)
+    const int parts = grid_for((long long)yv.rows * yv.cols, 1024, kFinishL2Parts);
+    hipLaunchKernelGGL(sumsq_parts_kernel, dim3(parts), dim3(1024), 0, s, yv, sp->l2_part);
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(64), 0, s, sp->l2_part, parts, b.l2sum);
   }
   hipLaunchKernelGGL(chain_finalize_kernel, dim3(1), dim3(64), 0, s, b.num_lp, b.den_lp, b.xent, l2_regularize != 0.f ? b.l2sum : nullptr,
                      B, T, sp->weight, l2_regularize, results);
@@ -334,6 +332,7 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision
   TDNNF_REQUIRE(!xent_deriv || (mat_ok(xent_deriv) && same_dim(y, xent_deriv)), "chain_objf_and_deriv: bad xent_deriv");
   TDNNF_REQUIRE(!xent_output || (mat_ok(xent_output) && same_dim(y, xent_output)), "chain_objf_and_deriv: bad xent_output");
   TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_workspace_bytes(g, B, T), "chain_objf_and_deriv: workspace too small");
+  TDNNF_REQUIRE(sp->kind == 0 || sp->num_pdfs <= g->P, "chain_objf_and_deriv: the supervision's num_pdfs %d exceeds the denominator graph's %d", sp->num_pdfs, g->P);
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if ((rc = chain_den(g, sp, y, leaky, deriv, ws, s))) return rc;
@@ -348,10 +347,11 @@ int tdnnf_chain_objf(const tdnnf_den_graph *g, const tdnnf_supervision *sp, cons
   TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P, "chain_objf: nnet_output must be (B*T) x num_pdfs, t-major");
   TDNNF_REQUIRE(!xent_output || (mat_ok(xent_output) && same_dim(y, xent_output)), "chain_objf: bad xent_output");
   TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_objf_workspace_bytes(g, B, T), "chain_objf: workspace too small");
+  TDNNF_REQUIRE(sp->kind == 0 || sp->num_pdfs <= g->P, "chain_objf: the supervision's num_pdfs %d exceeds the denominator graph's %d", sp->num_pdfs, g->P);
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if ((rc = chain_objf_den(g, sp, y, leaky, ws, s))) return rc;
-  if ((rc = chain_objf_num_recursion(sp, g, y, ws, s))) return rc;
+  if ((rc = num_recursion(sp, y, chain_objf_bufs(g, B, T, ws), s, !xent_output))) return rc;
   if ((rc = chain_objf_num_xent(g, sp, y, xent_output, ws, s))) return rc;
   return chain_objf_finish(g, sp, y, l2_regularize, results, ws, s);
 }
@@ -360,6 +360,7 @@ int tdnnf_chain_numerator_part(const tdnnf_den_graph *g, const tdnnf_supervision
                                tdnnf_mat *xent_deriv, void *ws, size_t ws_bytes, tdnnf_stream stream) {
   TDNNF_REQUIRE(g && sp && mat_ok(y) && y->rows == sp->B * sp->T && y->cols == g->P, "chain_numerator_part: bad arguments");
   TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_workspace_bytes(g, sp->B, sp->T), "chain_numerator_part: workspace too small");
+  TDNNF_REQUIRE(sp->kind == 0 || sp->num_pdfs <= g->P, "chain_numerator_part: the supervision's num_pdfs %d exceeds the denominator graph's %d", sp->num_pdfs, g->P);
   hipStream_t s = (hipStream_t)stream;
   if (part == 1) return chain_num_recursion(sp, g, y, ws, s);
   if (part == 4) {

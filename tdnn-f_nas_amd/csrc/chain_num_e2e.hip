@@ -1,0 +1,163 @@
+// chain_num_e2e.hip -- the chain numerator on cyclic per-sequence graphs (flat-start / end-to-end LF-MMI): creates the second kind of
+// tdnnf_supervision (its graphs are a tdnnf_align_graphs, its scratch its own) and launches num_e2e_kernels.h for the host functions of
+// chain_num.hip, which dispatch on the supervision's kind.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "chain_plan.h"
+#include "num_e2e_kernels.h"
+
+namespace tdnnf {
+namespace {
+
+struct E2eArgs {
+  AlignDev dev;
+  AlignFbDev fb;
+};
+E2eArgs e2e_args(const tdnnf_supervision *sp) {
+  const tdnnf_align_graphs *g = sp->e2e_graphs;
+  return E2eArgs{AlignDev{g->graphs, g->slots, g->heavy, g->arcs, g->init, g->final},
+                 AlignFbDev{g->fb_graphs, AlignFbTable{g->src_slots, g->src_heavy, g->src_arcs}, AlignFbTable{g->pdf_slots, g->pdf_heavy, g->pdf_arcs}}};
+}
+
+template <int NT, bool LDS, bool YLDS, bool FULL>
+int e2e_launch_form(const tdnnf_supervision *sp, const MatView &y, double *num_lp, hipStream_t s) {
+  if (LDS)
+    TDNNF_HIP(hipFuncSetAttribute((const void *)num_e2e_recursion_kernel<NT, LDS, YLDS, FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->e2e_lds_bytes));
+  const E2eArgs a = e2e_args(sp);
+  hipLaunchKernelGGL((num_e2e_recursion_kernel<NT, LDS, YLDS, FULL>), dim3(sp->B), dim3(NT), sp->e2e_lds_bytes, s, a.dev, a.fb, y, sp->B, sp->T, sp->e2e_alpha,
+                     sp->e2e_beta, sp->e2e_vecs, num_lp, sp->max_states_per_seq, sp->num_pdfs);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+
+template <int NT, bool FULL>
+int e2e_launch(const tdnnf_supervision *sp, const MatView &y, double *num_lp, hipStream_t s) {
+  if (sp->e2e_row_lds) return e2e_launch_form<NT, true, true, FULL>(sp, y, num_lp, s);
+  if (sp->e2e_lds) return e2e_launch_form<NT, true, false, FULL>(sp, y, num_lp, s);
+  return e2e_launch_form<NT, false, false, FULL>(sp, y, num_lp, s);
+}
+
+template <bool FULL>
+int e2e_recursion(const tdnnf_supervision *sp, const MatView &y, double *num_lp, hipStream_t s) {
+  switch (sp->e2e_threads) {
+    case 64:
+      return e2e_launch<64, FULL>(sp, y, num_lp, s);
+    case 256:
+      return e2e_launch<256, FULL>(sp, y, num_lp, s);
+    default:
+      return e2e_launch<1024, FULL>(sp, y, num_lp, s);
+  }
+}
+
+// the posterior pass: 256 threads, 1024 where the largest graph has more than 1024 states; alpha_t / beta_t+1 staged in LDS where the
+// recursion's two vectors live there (the same 16 * Smax bytes)
+template <int NT, bool LDS>
+int e2e_posterior_form(const tdnnf_supervision *sp, int blocks, const MatView &y, const MatView &xent_out, const double *num_lp, const MatView &deriv,
+                       const MatView &xent_deriv, float xent_scale, bool do_xent, hipStream_t s) {
+  const size_t lds = LDS ? 2 * sizeof(double) * (size_t)sp->max_states_per_seq : 0;
+  if (LDS) TDNNF_HIP(hipFuncSetAttribute((const void *)num_e2e_posterior_kernel<NT, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const E2eArgs a = e2e_args(sp);
+  hipLaunchKernelGGL((num_e2e_posterior_kernel<NT, LDS>), dim3(blocks, sp->B), dim3(NT), lds, s, a.dev, a.fb, y, xent_out, sp->B, sp->T, sp->weight, sp->e2e_alpha,
+                     sp->e2e_beta, num_lp, deriv, xent_deriv, xent_scale, do_xent ? 1 : 0, sp->xent_part, sp->max_states_per_seq);
+  return TDNNF_OK;
+}
+
+}  // namespace
+
+int num_e2e_recursion(const tdnnf_supervision *sp, const MatView &y, double *num_lp, bool forward_only, hipStream_t s) {
+  TDNNF_REQUIRE(sp->num_pdfs <= y.cols, "chain numerator: the end-to-end supervision's num_pdfs %d exceeds nnet_output's %d columns", sp->num_pdfs, y.cols);
+  return forward_only ? e2e_recursion<false>(sp, y, num_lp, s) : e2e_recursion<true>(sp, y, num_lp, s);
+}
+
+int num_e2e_posteriors(const tdnnf_supervision *sp, const MatView &y, const MatView &xent_out, const double *num_lp, double *xent_objf, const MatView &deriv,
+                       const MatView &xent_deriv, float xent_scale, bool do_xent, hipStream_t s) {
+  TDNNF_REQUIRE(sp->num_pdfs <= y.cols, "chain numerator: the end-to-end supervision's num_pdfs %d exceeds nnet_output's %d columns", sp->num_pdfs, y.cols);
+  const int blocks = (sp->T + kNumE2eFrames - 1) / kNumE2eFrames;
+  int rc;
+  if (sp->max_states_per_seq > 1024)
+    rc = sp->e2e_lds ? e2e_posterior_form<1024, true>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s)
+                     : e2e_posterior_form<1024, false>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s);
+  else
+    rc = sp->e2e_lds ? e2e_posterior_form<256, true>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s)
+                     : e2e_posterior_form<256, false>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s);
+  if (rc) return rc;
+  if (do_xent) hipLaunchKernelGGL(num_e2e_xent_sum_kernel, dim3((sp->B + 63) / 64), dim3(64), 0, s, sp->xent_part, sp->B, blocks, xent_objf);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+
+}  // namespace tdnnf
+
+using namespace tdnnf;
+
+extern "C" {
+
+int tdnnf_supervision_create_e2e(int B, int T, int num_pdfs, const int *seq_state_begin, const int *seq_arc_begin, const int *arc_src, const int *arc_dst,
+                                 const int *arc_pdf, const float *arc_logprob, const float *initial_logprob, const float *final_logprob, float weight,
+                                 tdnnf_supervision **out) {
+  TDNNF_REQUIRE(out && B > 0 && T > 0 && num_pdfs > 0 && seq_state_begin && seq_arc_begin && arc_src && arc_dst && arc_pdf && arc_logprob && initial_logprob &&
+                    final_logprob,
+                "supervision_create_e2e: bad arguments");
+  const int form = options().align_form;
+  TDNNF_REQUIRE(form >= 0 && form <= 2, "supervision_create_e2e: option align_form must be 0, 1 or 2");
+  tdnnf_align_graphs *graphs = nullptr;
+  // (validates what tdnnf_align_graphs_create validates: pdfs in [0, num_pdfs), states inside their sequence, an initial and a final state)
+  int rc = tdnnf_align_graphs_create(B, num_pdfs, seq_state_begin, seq_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob, final_logprob, &graphs);
+  if (rc) return rc;
+  tdnnf_supervision *sp = new tdnnf_supervision();
+  memset(sp, 0, sizeof(*sp));
+  sp->kind = 1;
+  sp->B = B;
+  sp->T = T;
+  sp->weight = weight;
+  sp->num_pdfs = num_pdfs;
+  sp->e2e_graphs = graphs;
+  sp->num_states = seq_state_begin[B];
+  sp->num_arcs = seq_arc_begin[B];
+  for (int s = 0; s < B; s++) sp->max_states_per_seq = std::max(sp->max_states_per_seq, seq_state_begin[s + 1] - seq_state_begin[s]);
+  sp->max_states_per_frame = sp->max_states_per_seq;
+  // the alignment's plan (align.hip align_plan), fixed here: the scratch depends on it
+  const size_t vec_bytes = 2 * sizeof(double) * (size_t)sp->max_states_per_seq, rows_bytes = 2 * sizeof(float) * (size_t)num_pdfs;
+  const bool fits = vec_bytes <= kLdsBudget;
+  if (form == 1 && !fits) {
+    const int smax = sp->max_states_per_seq;
+    tdnnf_supervision_destroy(sp);
+    TDNNF_REQUIRE(false, "supervision_create_e2e: option align_form = 1, but two vectors of %d doubles do not fit the LDS", smax);
+  }
+  sp->e2e_lds = form == 1 || (form == 0 && fits);
+  sp->e2e_threads = sp->max_states_per_seq <= 64 ? 64 : sp->max_states_per_seq <= 1024 ? 256 : 1024;
+  sp->e2e_row_lds = sp->e2e_lds && num_pdfs <= kAlignRowRegs * sp->e2e_threads && vec_bytes + rows_bytes <= kLdsBudget;
+  sp->e2e_lds_bytes = sp->e2e_lds ? vec_bytes + (sp->e2e_row_lds ? rows_bytes : 0) : 0;
+  const size_t frames = sizeof(double) * ((size_t)T + 1) * (size_t)sp->num_states, parts = (size_t)B * ((T + kNumE2eFrames - 1) / kNumE2eFrames);
+  hipError_t e = hipSuccess;
+  if ((e = hipMalloc((void **)&sp->e2e_alpha, frames)) != hipSuccess || (e = hipMalloc((void **)&sp->e2e_beta, frames)) != hipSuccess ||
+      (e = hipMalloc((void **)&sp->xent_part, sizeof(double) * parts)) != hipSuccess ||
+      (e = hipMalloc((void **)&sp->l2_part, sizeof(double) * kFinishL2Parts)) != hipSuccess ||
+      (!sp->e2e_lds && (e = hipMalloc((void **)&sp->e2e_vecs, 2 * sizeof(double) * (size_t)sp->num_states)) != hipSuccess)) {
+    tdnnf_supervision_destroy(sp);
+    return hip_status(e, "supervision_create_e2e: hipMalloc");
+  }
+  *out = sp;
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_kind(const tdnnf_supervision *sp) {
+  if (!sp) {
+    set_error("supervision_kind: null supervision");
+    return -1;
+  }
+  return sp->kind;
+}
+
+int tdnnf_supervision_e2e_form(const tdnnf_supervision *sp, int *threads, int *vectors_in_lds, int *rows_in_lds) {
+  TDNNF_REQUIRE(sp && sp->kind == 1, "supervision_e2e_form: not an end-to-end supervision");
+  if (threads) *threads = sp->e2e_threads;
+  if (vectors_in_lds) *vectors_in_lds = sp->e2e_lds ? 1 : 0;
+  if (rows_in_lds) *rows_in_lds = sp->e2e_row_lds ? 1 : 0;
+  return TDNNF_OK;
+}
+
+}  // extern "C"

@@ -40,4 +40,12 @@ __attribute__((visibility("hidden"))) ChainBufs chain_bufs(const tdnnf_den_graph
 constexpr int kObjfL2Parts = 32;  // (few: with them and the alignment slack the layout still fits every workspace of tdnnf_chain_workspace_bytes)
 __attribute__((visibility("hidden"))) ChainBufs chain_objf_bufs(const tdnnf_den_graph *g, int B, int T, void *ws, size_t *bytes = nullptr);
 
+// The numerator of an end-to-end supervision (kind 1; chain_num_e2e.hip), for the host functions of chain_num.hip.  The recursion leaves
+// num_lp[B] and, unless forward_only, alpha / beta of every frame in the supervision's scratch; the posterior pass reads those and adds
+// weight * gamma into deriv and / or xent_scale times it into xent_deriv (either may be absent), do_xent: the xent objective -> xent_objf[B].
+__attribute__((visibility("hidden"))) int num_e2e_recursion(const tdnnf_supervision *sp, const MatView &y, double *num_lp, bool forward_only, hipStream_t s);
+__attribute__((visibility("hidden"))) int num_e2e_posteriors(const tdnnf_supervision *sp, const MatView &y, const MatView &xent_out, const double *num_lp,
+                                                             double *xent_objf, const MatView &deriv, const MatView &xent_deriv, float xent_scale, bool do_xent,
+                                                             hipStream_t s);
+
 }  // namespace tdnnf

@@ -64,6 +64,18 @@ struct tdnnf_supervision {
   int *pf_src, *pf_dst, *pf_pdf, *pf_t;
   float *pf_lp;
   double *xent_part;  // B * ceil(T / kNumWideFrames) partial xent objectives of the posterior pass
+  double *l2_part;    // kFinishL2Parts partial sums of squares of nnet_output (chain_finish's l2 term, summed in order); every supervision has it
+  // ---- kind 1 (tdnnf_supervision_create_e2e, chain_num_e2e.hip): one cyclic graph per sequence.  Of the members above it sets B, T, weight,
+  // num_states, num_arcs, max_states_per_seq, max_states_per_frame (both the largest graph's state count) and xent_part; wide stays false and
+  // the time-synchronous tables null.  All null / zero for kind 0.
+  int kind;       // 0 time-synchronous, 1 end-to-end
+  int num_pdfs;   // kind 1: the graphs' pdfs are in [0, num_pdfs)
+  struct tdnnf_align_graphs *e2e_graphs;  // the arcs by destination, by source and by pdf (align_graphs.h); graph s is sequence s's
+  double *e2e_alpha, *e2e_beta;           // (T + 1) * num_states doubles each: alpha_t / beta_t of every frame, sequence after sequence
+  double *e2e_vecs;                       // 2 * num_states doubles where the two state vectors do not live in LDS, else null
+  int e2e_threads;                        // the recursion's workgroup: 64 up to 64 states in the largest graph, 256 up to 1024, 1024 above
+  bool e2e_lds, e2e_row_lds;              // state vectors in LDS; two output rows staged behind them
+  size_t e2e_lds_bytes;
 };
 
 namespace tdnnf {
@@ -88,6 +100,7 @@ struct SupDev {
   const int *out_begin, *out_dst, *out_pdf;
   const float *out_lp;
 };
+constexpr int kFinishL2Parts = 256;  // workgroups (of 1024 threads) of chain_finish's sum of squares, one partial sum each
 // the posterior pass of the wide numerator: frames per workgroup
 constexpr int kNumWideFrames = 8;
 struct SupWideDev {

@@ -1,0 +1,222 @@
+// num_e2e_kernels.h -- the chain numerator on cyclic per-sequence graphs (flat-start / "end-to-end" LF-MMI: Kaldi's
+// GenericNumeratorComputation).  Included by chain_num_e2e.hip only.  The graphs are a tdnnf_align_graphs (align_graphs.h: the arcs by
+// destination, by source and by pdf), one graph per sequence; the arithmetic is align_fb_kernels.h's with acoustic_scale = 1, all in double:
+//     term(arc, t) = (double)arc_logprob + (double)y[t * B + s, arc_pdf]                        no clamp
+//     alpha_0 = initial_logprob;  alpha_t+1[d] = LSE over arcs into d of alpha_t[src] + term(arc, t)
+//     num_lp[s] = LSE over states of alpha_T + final_logprob
+//     beta_T = final_logprob;     beta_t[st] = LSE over arcs out of st of term(arc, t) + beta_t+1[dst]
+//     gamma[t, p] = sum over arcs with pdf p of exp(alpha_t[src] + term + beta_t+1[dst] - num_lp[s])
+//
+// Two kernels, where align_fb_kernel is one: that kernel forms row t of the posteriors inside its serial backward loop, which triples the
+// time its workgroup holds the critical path (docs/experiments.md r6-p).  Here
+//  * num_e2e_recursion_kernel: one workgroup per sequence, the alignment's schedule (thread counts, state vectors in LDS or in the
+//    supervision's scratch, the next frame's output row staged one frame ahead), workgroup barriers only, every loop bounded by T.  It
+//    keeps alpha_t and beta_t of EVERY frame in the supervision's scratch ((T + 1) * S doubles each) and needs the chain output only, so
+//    the trainer starts it beside the denominator.  !FULL: the forward half alone on its two alternating vectors, nothing kept per frame.
+//  * num_e2e_posterior_kernel: grid (ceil(T / kNumE2eFrames), B), alpha_t and beta_t+1 of the frame at hand staged in LDS where the
+//    recursion's vectors live there.  A (frame, pdf) element has one owner -- a lane per pdf from the by-pdf
+//    table's slices, a wave per pdf that more than kAlignHeavy arcs name -- which sums the pdf's arcs in the caller's order, recomputing
+//    term: no atomics, nothing kept per arc, the same bits on every call.  It ADDS (float)(weight * gamma) into deriv (behind the
+//    denominator's term) and / or xent_scale times it into xent_deriv, and forms the xent objective as one partial sum per workgroup,
+//    which num_e2e_xent_sum_kernel adds in ascending order.  Elements whose pdf no arc of the sequence names are not touched.  A sequence
+//    whose num_lp is not finite is skipped: the failure path of chain_finalize_kernel / chain_guard_kernel zeroes the matrices, and no
+//    NaN is formed to be overwritten.
+#pragma once
+#include "align_fb_kernels.h"
+
+namespace tdnnf {
+namespace {
+
+constexpr int kNumE2eFrames = 8;  // frames per workgroup of the posterior pass (the wide numerator's kNumWideFrames)
+
+// grid = sequences; sequence s walks graph s.  Dynamic LDS: [LDS: 2 * Smax doubles, the state vectors] [YLDS: 2 * P floats, two output rows].
+// alpha_all / beta_all: the (T + 1) * S doubles of the sequence whose first state is state0 start at (T + 1) * state0; vecs (!LDS): its two
+// vectors at 2 * state0.
+template <int NT, bool LDS, bool YLDS, bool FULL>
+__global__ __launch_bounds__(NT) void num_e2e_recursion_kernel(AlignDev g, AlignFbDev fb, MatView y, int B, int T, double *alpha_all, double *beta_all,
+                                                               double *vecs, double *num_lp, int Smax, int P) {
+  static_assert(LDS || !YLDS, "the rows behind the vectors need the LDS form");
+  extern __shared__ double num_e2e_smem[];
+  __shared__ double red_m[NT / 64], red_s[NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, seq = blockIdx.x;
+  const AlignGraphDev gr = g.graphs[seq];
+  const int S = gr.num_states, s0 = gr.state0;
+  double *cur = LDS ? num_e2e_smem : vecs + 2 * (size_t)s0, *nxt = cur + S;
+  float *ylds = reinterpret_cast<float *>(num_e2e_smem + 2 * (size_t)Smax);  // YLDS: two rows of P floats
+  double *alpha = FULL ? alpha_all + (size_t)(T + 1) * s0 : nullptr;
+  const size_t row_step = (size_t)B * y.stride;  // t-major: the next frame's row of this sequence lies B rows on
+  const float *row0 = y.data + (size_t)seq * y.stride;
+  float yreg[kAlignRowRegs];
+  auto row_of = [&](int t) { return row0 + (size_t)t * row_step; };
+  auto load_row = [&](int t) {  // (only [0, P) of a row: what the graphs' arcs can name)
+    if (!YLDS || t < 0 || t >= T) return;
+    const float *r = row_of(t);
+#pragma unroll
+    for (int c = 0; c < kAlignRowRegs; c++)
+      if (tid + c * NT < P) yreg[c] = r[tid + c * NT];
+  };
+  auto store_row = [&](int t) {
+    if (!YLDS || t < 0 || t >= T) return;
+#pragma unroll
+    for (int c = 0; c < kAlignRowRegs; c++)
+      if (tid + c * NT < P) ylds[(size_t)(t & 1) * P + tid + c * NT] = yreg[c];
+  };
+  for (int s = tid; s < S; s += NT) {
+    const double v = (double)g.init[s0 + s];
+    cur[s] = v;
+    if (FULL) alpha[s] = v;
+  }
+  load_row(0);
+  store_row(0);
+  load_row(1);
+  __syncthreads();
+  for (int t = 0; t < T; t++) {
+    // row t + 1 (loaded a frame ago) into the buffer whose last readers -- frame t - 1 -- are behind the previous barrier; row t + 2 on its way
+    store_row(t + 1);
+    load_row(t + 2);
+    const float *yrow = YLDS ? ylds + (size_t)(t & 1) * P : row_of(t);
+    fb_lse_step<NT>(g.slots + gr.slot0, gr.num_slots, g.heavy + gr.heavy0, gr.num_heavy, g.arcs, cur, yrow, 1.0, nxt,
+                    FULL ? alpha + (size_t)(t + 1) * S : nullptr, tid);
+    __syncthreads();
+    double *sw = cur;
+    cur = nxt;
+    nxt = sw;
+  }
+  // the total: a thread's states in ascending order, the lanes by butterfly, the waves in ascending order -- by every thread alike
+  double m = -INFINITY, sum = 0.0;
+  for (int s = tid; s < S; s += NT) fb_lse_add(m, sum, cur[s] + (double)g.final[s0 + s]);
+  fb_lse_wave(m, sum);
+  if (lane == 0) {
+    red_m[wave] = m;
+    red_s[wave] = sum;
+  }
+  __syncthreads();
+  m = red_m[0];
+  sum = red_s[0];
+  for (int w = 1; w < NT / 64; w++) fb_lse_merge(m, sum, red_m[w], red_s[w]);
+  const double logprob = fb_lse_value(m, sum);
+  if (tid == 0) num_lp[seq] = logprob;
+  if (!FULL) return;
+  if (!(logprob > -INFINITY && logprob < INFINITY)) return;  // (the posterior pass skips this sequence: its beta has no reader)
+  const AlignFbGraphDev fg = fb.graphs[seq];
+  double *beta = beta_all + (size_t)(T + 1) * s0;
+  // (alpha_T's last readers are behind the barrier above)
+  for (int s = tid; s < S; s += NT) {
+    const double v = (double)g.final[s0 + s];
+    cur[s] = v;
+    beta[(size_t)T * S + s] = v;
+  }
+  load_row(T - 1);
+  store_row(T - 1);
+  load_row(T - 2);
+  __syncthreads();
+  for (int t = T - 1; t >= 0; t--) {
+    // row t - 1 into the buffer whose last readers -- frame t + 1 -- are behind the previous barrier; row t - 2 on its way
+    store_row(t - 1);
+    load_row(t - 2);
+    const float *yrow = YLDS ? ylds + (size_t)(t & 1) * P : row_of(t);
+    fb_lse_step<NT>(fb.by_src.slots + fg.src_slot0, fg.src_num_slots, fb.by_src.heavy + fg.src_heavy0, fg.src_num_heavy, fb.by_src.arcs, cur, yrow, 1.0, nxt,
+                    beta + (size_t)t * S, tid);
+    __syncthreads();
+    double *sw = cur;
+    cur = nxt;
+    nxt = sw;
+  }
+}
+
+// grid (ceil(T / kNumE2eFrames), B).  deriv += (float)(weight * gamma), xent_deriv += xent_scale * that (either may be absent);
+// do_xent: the workgroup's share of the xent objective -> xent_part[s * gridDim.x + block] (0 for a skipped sequence).
+// LDS: alpha_t and beta_t+1 of the frame being worked on are staged in 2 * Smax doubles of dynamic LDS (coalesced loads, two barriers a
+// frame) and the arcs gather from there: a gather of 8 bytes from global memory moves a whole cache line, and on a 4 000-state graph those
+// lines were the pass's time (20.2 ms a pass at 128 x 150 frames against 12.0 ms for all of align_fb_kernel; docs/experiments.md r6-q).
+// NT: 256 threads, 1024 where the largest graph has more than 1024 states (two such workgroups still fit a CU beside their vectors).
+template <int NT, bool LDS>
+__global__ __launch_bounds__(NT) void num_e2e_posterior_kernel(AlignDev g, AlignFbDev fb, MatView y, MatView xent_out, int B, int T, float weight,
+                                                               const double *alpha_all, const double *beta_all, const double *num_lp, MatView deriv,
+                                                               MatView xent_deriv, float xent_scale, int do_xent, double *xent_part, int Smax) {
+  extern __shared__ double num_e2e_post_smem[];
+  __shared__ double red[NT / 64];
+  const int seq = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double logprob = num_lp[seq], w = (double)weight;
+  double xo = 0.0;
+  auto emit = [&](size_t row, int pdf, double sum) {
+    const float gam = (float)(w * sum);
+    if (deriv.data) deriv.data[row * deriv.stride + pdf] += gam;
+    if (xent_deriv.data) xent_deriv.data[row * xent_deriv.stride + pdf] += xent_scale * gam;
+    if (do_xent && xent_out.data) xo += (double)gam * (double)xent_out.data[row * xent_out.stride + pdf];
+  };
+  if (logprob > -INFINITY && logprob < INFINITY) {  // (the same for every thread of the workgroup: the barriers below are met by all or none)
+    const AlignGraphDev gr = g.graphs[seq];
+    const AlignFbGraphDev fg = fb.graphs[seq];
+    const int S = gr.num_states, t0 = blockIdx.x * kNumE2eFrames, t1 = min(T, t0 + kNumE2eFrames);
+    const double *alpha = alpha_all + (size_t)(T + 1) * gr.state0, *beta = beta_all + (size_t)(T + 1) * gr.state0;
+    const int4 *slots = fb.by_pdf.slots + fg.pdf_slot0, *heavy = fb.by_pdf.heavy + fg.pdf_heavy0, *arcs = fb.by_pdf.arcs;
+    for (int t = t0; t < t1; t++) {
+      const double *at = alpha + (size_t)t * S, *bt = beta + (size_t)(t + 1) * S;
+      if (LDS) {
+        double *al = num_e2e_post_smem, *bl = al + Smax;
+        if (t > t0) __syncthreads();  // the last frame's readers are done
+        for (int s = tid; s < S; s += NT) {
+          al[s] = at[s];
+          bl[s] = bt[s];
+        }
+        __syncthreads();
+        at = al;
+        bt = bl;
+      }
+      const size_t row = (size_t)t * B + seq;
+      const float *yrow = y.data + row * y.stride;
+      for (int slot = tid; slot < fg.pdf_num_slots; slot += NT) {  // light pdfs: a lane per pdf, slice by slice
+        const int4 r = slots[slot];
+        if (r.x < 0) continue;
+        const double yv = (double)yrow[r.x];
+        double sum = 0.0;
+        for (int j = 0; j < r.y; j += kAlignBatch) {
+          int4 arc[kAlignBatch];
+#pragma unroll
+          for (int k = 0; k < kAlignBatch; k++) arc[k] = arcs[r.z + 64 * min(j + k, r.y - 1)];
+#pragma unroll
+          for (int k = 0; k < kAlignBatch; k++) {
+            const double v = (at[arc[k].x] + ((double)__int_as_float(arc[k].z) + yv)) + bt[arc[k].y];
+            if (j + k < r.y && v > -INFINITY) sum += exp(v - logprob);
+          }
+        }
+        emit(row, r.x, sum);
+      }
+      for (int h = wave; h < fg.pdf_num_heavy; h += NT / 64) {  // heavy pdfs: a wave per pdf, the lanes' sums by butterfly
+        const int4 r = heavy[h];
+        const double yv = (double)yrow[r.x];
+        double sum = 0.0;
+        for (int a = r.y + lane; a < r.z; a += 64) {
+          const int4 arc = arcs[a];
+          const double v = (at[arc.x] + ((double)__int_as_float(arc.z) + yv)) + bt[arc.y];
+          if (v > -INFINITY) sum += exp(v - logprob);
+        }
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        if (lane == 0) emit(row, r.x, sum);
+      }
+    }
+  }
+  if (do_xent) {
+    for (int o = 32; o > 0; o >>= 1) xo += __shfl_xor(xo, o, 64);
+    if (lane == 0) red[wave] = xo;
+    __syncthreads();
+    if (tid == 0) {
+      double x = 0.0;
+      for (int k = 0; k < NT / 64; k++) x += red[k];
+      xent_part[(size_t)seq * gridDim.x + blockIdx.x] = x;
+    }
+  }
+}
+
+// xent_objf[s] = the sum of sequence s's partial sums, in ascending order
+__global__ void num_e2e_xent_sum_kernel(const double *part, int B, int blocks, double *xent_objf) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= B) return;
+  double x = 0.0;
+  for (int k = 0; k < blocks; k++) x += part[(size_t)s * blocks + k];
+  xent_objf[s] = x;
+}
+
+}  // namespace
+}  // namespace tdnnf

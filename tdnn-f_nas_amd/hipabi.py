@@ -205,18 +205,56 @@ class DenGraph:
 
 
 class Supervision:
+    """Device-resident numerator graphs of one minibatch (tdnnf_supervision).  `s`: a time-synchronous supervision dict
+    (synth.make_supervision ...), or -- with a "graphs" key -- an end-to-end one (synth.make_e2e_supervision: {B, T, P, weight, graphs}),
+    which goes through from_graphs.  .kind: 0 time-synchronous, 1 end-to-end."""
+
     def __init__(self, s):
         lib = load()
         self.h = C.c_void_p()
+        if "graphs" in s:
+            self._create_e2e(s["graphs"], int(s["T"]), float(s.get("weight", 1.0)), s.get("P"))
+            return
         k = [iarr(s["seq_state_begin"]), iarr(s["seq_arc_begin"]), iarr(s["state_time"]), farr(s["final_logprob"]),
              iarr(s["arc_src"]), iarr(s["arc_dst"]), iarr(s["arc_pdf"]), farr(s["arc_logprob"])]
         check(lib.tdnnf_supervision_create(int(s["B"]), int(s["T"]), k[0][1], k[1][1], k[2][1], k[3][1], k[4][1], k[5][1],
                                            k[6][1], k[7][1], float(s.get("weight", 1.0)), C.byref(self.h)))
         self.B, self.T = int(s["B"]), int(s["T"])
 
+    @classmethod
+    def from_graphs(cls, graphs, frames_per_sequence, weight=1.0, num_pdfs=None):
+        """End-to-end supervision (tdnnf_supervision_create_e2e): one cyclic pdf-labelled graph per sequence, each a dict {S, P, src, dst,
+        pdf, logprob, init, final} with states numbered from 0, stacked as AlignGraphs stacks them.  num_pdfs: default the graphs' largest P."""
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        self._create_e2e(graphs, int(frames_per_sequence), float(weight), num_pdfs)
+        return self
+
+    def _create_e2e(self, graphs, T, weight, num_pdfs):
+        import numpy as np
+        graphs = [graphs] if isinstance(graphs, dict) else list(graphs)
+        P = int(num_pdfs if num_pdfs is not None else max(int(g["P"]) for g in graphs))
+        sb = np.concatenate([[0], np.cumsum([int(g["S"]) for g in graphs])])
+        ab = np.concatenate([[0], np.cumsum([len(g["src"]) for g in graphs])])
+        cat = lambda key, off=None: np.concatenate([np.asarray(g[key]) + (0 if off is None else off[i]) for i, g in enumerate(graphs)])
+        k = [iarr(sb), iarr(ab), iarr(cat("src", sb)), iarr(cat("dst", sb)), iarr(cat("pdf")), farr(cat("logprob")), farr(cat("init")), farr(cat("final"))]
+        check(load().tdnnf_supervision_create_e2e(len(graphs), T, P, *[x[1] for x in k], weight, C.byref(self.h)))
+        self.B, self.T, self.P = len(graphs), T, P
+
+    @property
+    def kind(self):
+        return int(load().tdnnf_supervision_kind(self.h))
+
+    def e2e_form(self):
+        """{threads, vectors_in_lds, rows_in_lds}: the launch form of an end-to-end supervision's recursion (tdnnf_supervision_e2e_form)."""
+        v = [C.c_int() for _ in range(3)]
+        check(load().tdnnf_supervision_e2e_form(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("threads", "vectors_in_lds", "rows_in_lds"), (x.value for x in v)))
+
     def info(self):
         """{num_states, num_arcs, max_states_per_frame, wide} (tdnnf_supervision_info); wide: over 4 states per frame on average,
-        the supervision holds its own numerator scratch and takes the numerator's wide form."""
+        the supervision holds its own numerator scratch and takes the numerator's wide form.  End-to-end kind: the totals over its
+        graphs, max_states_per_frame the largest graph's state count, wide 0."""
         v = [C.c_int() for _ in range(4)]
         check(load().tdnnf_supervision_info(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("num_states", "num_arcs", "max_states_per_frame", "wide"), (x.value for x in v)))

@@ -306,3 +306,43 @@ def alignment_graphs_from_supervision(sup):
                     "logprob": np.asarray(sup["arc_logprob"][a0:a1], dtype=np.float32), "init": init,
                     "final": np.asarray(sup["final_logprob"][s0:s1], dtype=np.float32)})
     return out
+
+
+def _shortest_accepting_path(g):
+    """Fewest arcs on a path from an initial to a final state of a make_alignment_graph dict (inf: none)."""
+    dist = np.where(np.asarray(g["init"]) > -np.inf, 0.0, np.inf)
+    for _ in range(int(g["S"])):
+        nxt = dist.copy()
+        np.minimum.at(nxt, g["dst"], dist[g["src"]] + 1)
+        if np.array_equal(nxt, dist):
+            break
+        dist = nxt
+    return float(dist[np.asarray(g["final"]) > -np.inf].min())
+
+
+def make_e2e_supervision(B, T, P, units=(2, 6), seed=0, weight=1.0, **graph_kw):
+    """End-to-end (flat-start) supervision: per sequence one make_alignment_graph transcript -- lo..hi units (at most T) with random pdfs,
+    self-loops on, graph_kw (optional=..., alternatives=...) passed through -- whose shortest accepting path is at most T arcs, so that
+    with its self-loops it accepts exactly T frames.  Returns {B, T, P, weight, graphs: [...]}: what hipabi.Supervision takes."""
+    rng = np.random.default_rng(seed)
+    lo, hi = units
+    graphs = []
+    for s in range(B):
+        n = int(rng.integers(min(lo, T), min(hi, T) + 1))
+        n = max(n, 1)
+        kw = dict(graph_kw)
+        if "optional" in kw:
+            kw["optional"] = [k for k in kw["optional"] if k < n]
+        if "alternatives" in kw:
+            kw["alternatives"] = {k: v for k, v in kw["alternatives"].items() if k < n}
+        g = make_alignment_graph(rng.integers(0, P, size=n), self_loops=True, seed=int(rng.integers(1 << 30)), num_pdfs=P, **kw)
+        assert _shortest_accepting_path(g) <= T
+        graphs.append(g)
+    return {"B": int(B), "T": int(T), "P": int(P), "weight": float(weight), "graphs": graphs}
+
+
+def e2e_supervision_from_supervision(sup, P):
+    """The end-to-end form of a time-synchronous supervision dict: its sequences as graphs (alignment_graphs_from_supervision), same
+    weight.  Both forms have the same paths, so the chain objective and its derivatives agree."""
+    return {"B": int(sup["B"]), "T": int(sup["T"]), "P": int(P), "weight": float(sup.get("weight", 1.0)),
+            "graphs": alignment_graphs_from_supervision(sup)}

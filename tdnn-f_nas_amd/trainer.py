@@ -274,6 +274,8 @@ class ChainNet:
 
     # ------------------------------------------------------------------------ steps
     def forward_backward(self, feats, ivectors, den_graph, supervision, step=0):
+        """One training step's forward and backward pass (tdnnf_net_forward_backward).  `supervision`: a hipabi.Supervision of either
+        kind -- an end-to-end one (Supervision.from_graphs) needs nothing different here: the library dispatches on its kind."""
         hipabi.check(self.lib.tdnnf_net_forward_backward(self.h, hipabi.pmat(feats), hipabi.pmat(ivectors), den_graph.h,
                                                          supervision.h, hipabi.ptr(self.results), int(step), hipabi.stream()))
         return self.results
@@ -281,7 +283,8 @@ class ChainNet:
     def objective(self, feats, ivectors, den_graph, supervision, store_stats=False):
         """The objective of one minibatch without derivatives (tdnnf_net_objective): the forward pass and the chain objective only; the
         same 8 doubles as forward_backward.  Leaves no trace in the net, unless store_stats (training-mode BatchNorm only): then the
-        BatchNorm statistics accumulate as in forward_backward; the ReLU statistics never do."""
+        BatchNorm statistics accumulate as in forward_backward; the ReLU statistics never do.  `supervision` may be of either kind,
+        as for forward_backward (so outer_loop.compute_prob evaluates end-to-end minibatches unchanged)."""
         hipabi.check(self.lib.tdnnf_net_objective(self.h, hipabi.pmat(feats), hipabi.pmat(ivectors), den_graph.h, supervision.h,
                                                   hipabi.ptr(self.results), hipabi.OBJECTIVE_STORE_BATCHNORM_STATS if store_stats else 0,
                                                   hipabi.stream()))
@@ -563,7 +566,12 @@ def shard_sequences(num_sequences, rank, world_size):
 
 def shard_supervision(sup, begin, end):
     """The numerator graphs of sequences [begin, end) of a merged minibatch (the dict of synth.make_supervision /
-    egs.merge): what rank g of a strong-scaling step hands to tdnnf_supervision_create."""
+    egs.merge): what rank g of a strong-scaling step hands to tdnnf_supervision_create.  An end-to-end dict
+    (synth.make_e2e_supervision: a "graphs" list, one per sequence) keeps its graphs [begin, end), in order."""
+    if "graphs" in sup:
+        out = dict(sup)
+        out.update(B=end - begin, graphs=list(sup["graphs"][begin:end]))
+        return out
     sb, ab = np.asarray(sup["seq_state_begin"]), np.asarray(sup["seq_arc_begin"])
     s0, s1, a0, a1 = int(sb[begin]), int(sb[end]), int(ab[begin]), int(ab[end])
     out = dict(sup)
