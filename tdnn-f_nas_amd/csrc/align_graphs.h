@@ -1,45 +1,100 @@
-// align_graphs.h -- the device copy of a set of pdf-labelled graphs (tdnnf_align_graphs), shared by its two readers: align.hip (best path;
-// builds and reads the arcs by destination) and align_fb.hip (forward-backward; reads them too and adds the arcs by source and by pdf).
+// align_graphs.h -- the device copy of a set of pdf-labelled graphs (tdnnf_align_graphs) and what its three readers share on the host:
+// align.hip (best path), align_fb.hip (forward-backward) and chain_num_e2e.hip (the end-to-end numerator).  align_graphs.hip creates and
+// destroys the handle from the tables of align_tables.h; the kernels take its AlignDev by value.
 #pragma once
+#include <string>
 #include <vector>
 
-#include "align_kernels.h"
+#include "align_tables.h"
+#include "common.h"
 
 namespace tdnnf {
-namespace {
 
-// One more grouping of a set's arcs, laid out as align.hip lays out the arcs by destination (align_kernels.h): the rows of at most
-// kAlignHeavy arcs sorted by descending length and cut into slices of 64, the heavy rows one after the other; a row's arcs in the
-// caller's order.  What a row is and what an arc's int4 holds is the table's own (align_fb_kernels.h).
-struct AlignFbTable {
+struct AlignTable {   // one grouping of a set's arcs (align_tables.h), on the device
   const int4 *slots;  // (row LOCAL to its graph or -1 for an empty lane, length, position of the row's first arc: its j-th is 64 j further, 0)
   const int4 *heavy;  // (LOCAL row, first arc, one past the last arc, 0)
-  const int4 *arcs;
-};
-struct AlignFbGraphDev {  // one graph's share of the two tables
-  int src_slot0, src_num_slots, src_heavy0, src_num_heavy;
-  int pdf_slot0, pdf_num_slots, pdf_heavy0, pdf_num_heavy;
+  const int4 *arcs;   // a row's arcs in the caller's order
 };
 
-}  // namespace
+struct AlignDev {
+  const AlignGraphDev *graphs;
+  AlignTable by_dst;          // rows: states; arcs (source state, pdf, log-prob bits, caller's arc index)
+  AlignTable by_src;          // rows: states; arcs (destination state, pdf, log-prob bits, caller's arc index)
+  AlignTable by_pdf;          // rows: pdfs;   arcs (source state, destination state, log-prob bits, caller's arc index)
+  const float *init, *final;  // [total states]
+};
+
+struct AlignUtt {  // one utterance of a call (device table at the head of the workspace)
+  int graph, frames;
+  int row_begin;
+  int out_begin;          // best path: first element of pdf_out; state_out starts at out_begin + (index of the utterance).  Forward-backward: 0
+  long long frame_begin;  // first element of its per-frame region of the workspace: best path -- the back-pointers, frames * S ints padded to an
+                          // even count; forward-backward -- alpha of every frame, (frames + 1) * S doubles (posteriors)
+  long long vec_begin;    // first double of its two state vectors in the workspace's vector region (workspace form)
+};
+
+static_assert(sizeof(AlignUtt) == 32, "the workspace formula of include/tdnnf_hip.h counts 32 bytes an utterance");
+
 }  // namespace tdnnf
 
 struct tdnnf_align_graphs {
   int G, P;
   std::vector<int> state_begin, num_arcs, max_in_degree;  // host: [G + 1], [G], [G]
-  tdnnf::AlignGraphDev *graphs;
-  int4 *slots, *heavy, *arcs;
-  float *init, *final;
-  // forward-backward (align_fb.hip): by source -- rows are states, every state has one; by pdf -- rows are the pdfs that an arc of the graph names
-  tdnnf::AlignFbGraphDev *fb_graphs;
-  int4 *src_slots, *src_heavy, *src_arcs;
-  int4 *pdf_slots, *pdf_heavy, *pdf_arcs;
+  tdnnf::AlignDev dev;                                    // device arrays, owned
 };
 
 namespace tdnnf {
-// (align_fb.hip; not part of the library's symbol table)  Fills the fb_* / src_* / pdf_* members from the arrays tdnnf_align_graphs_create
-// has validated; align_fb_tables_free releases them (null members are fine).
-__attribute__((visibility("hidden"))) int align_fb_tables_create(tdnnf_align_graphs *g, const int *graph_state_begin, const int *graph_arc_begin,
-                                                                 const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob);
-__attribute__((visibility("hidden"))) void align_fb_tables_free(tdnnf_align_graphs *g);
+
+inline size_t align_round_up(size_t n, size_t m) { return (n + m - 1) / m * m; }
+
+// The utterances of one call, for tdnnf_align_best_path (best_path) and tdnnf_align_posteriors and their *_workspace_bytes.
+struct AlignCall {
+  std::vector<AlignUtt> utts;
+  int max_states;        // the largest graph an utterance of the call names
+  size_t frame_elems;    // the per-frame regions together (ints or doubles: AlignUtt::frame_begin)
+  size_t vec_doubles;    // the vector regions together: 2 * S doubles an utterance
+  size_t desc_bytes;     // AlignUtt x num_utts, padded to 256 bytes
+};
+
+// Checks and describes the utterances.  plan / call: the prefixes of the messages ("align: " and "align_best_path: ").  nnet_output (may be
+// null: the workspace question, no rows are named yet) and post_out (may be null) bound the rows an utterance reads and writes.
+inline int align_call(const tdnnf_align_graphs *g, bool best_path, const char *plan, const char *call, int num_utts, const int *utt_graph,
+                      const int *utt_frames, const int *utt_row_begin, int row_stride, const tdnnf_mat *nnet_output, const tdnnf_mat *post_out,
+                      AlignCall *c) {
+  TDNNF_REQUIRE(g && num_utts > 0 && utt_frames, "%snull graphs, no utterances or null utt_frames", plan);
+  TDNNF_REQUIRE(utt_graph || g->G == 1 || g->G == num_utts, "%sutt_graph may be null only for one graph or one graph per utterance", plan);
+  c->utts.resize(num_utts);
+  c->max_states = 0;
+  size_t per_frame = 0, vec = 0;
+  long long rows = 0;
+  for (int u = 0; u < num_utts; u++) {
+    const int gi = utt_graph ? utt_graph[u] : g->G == 1 ? 0 : u;
+    TDNNF_REQUIRE(gi >= 0 && gi < g->G, "%sutterance %d names graph %d of %d", plan, u, gi, g->G);
+    TDNNF_REQUIRE(utt_frames[u] >= 0, "%sutterance %d has %d frames", plan, u, utt_frames[u]);
+    const int S = g->state_begin[gi + 1] - g->state_begin[gi];
+    c->max_states = std::max(c->max_states, S);
+    AlignUtt &d = c->utts[u];
+    d.graph = gi;
+    d.frames = utt_frames[u];
+    d.row_begin = utt_row_begin ? utt_row_begin[u] : 0;
+    d.out_begin = best_path ? (int)rows : 0;
+    d.frame_begin = (long long)per_frame;
+    d.vec_begin = (long long)vec;
+    rows += utt_frames[u];
+    TDNNF_REQUIRE(rows + num_utts < (1ll << 31), "%smore than 2^31 frames in one call", plan);
+    per_frame += best_path ? align_round_up((size_t)utt_frames[u] * (size_t)S, 2) : ((size_t)utt_frames[u] + 1) * (size_t)S;
+    vec += 2 * (size_t)S;
+    if (!nnet_output) continue;
+    const long long last = (long long)d.row_begin + (long long)(utt_frames[u] - 1) * row_stride;
+    TDNNF_REQUIRE(d.row_begin >= 0 && (utt_frames[u] == 0 || last < nnet_output->rows), "%sutterance %d reads rows %d .. %lld of a matrix of %d rows",
+                  call, u, d.row_begin, last, nnet_output->rows);
+    TDNNF_REQUIRE(!post_out || utt_frames[u] == 0 || last < post_out->rows, "%sutterance %d writes rows %d .. %lld of a post_out of %d rows", call, u,
+                  d.row_begin, last, post_out ? post_out->rows : 0);
+  }
+  c->frame_elems = per_frame;
+  c->vec_doubles = vec;
+  c->desc_bytes = align_round_up(sizeof(AlignUtt) * (size_t)num_utts, 256);
+  return TDNNF_OK;
+}
+
 }  // namespace tdnnf

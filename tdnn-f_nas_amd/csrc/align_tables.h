@@ -1,0 +1,157 @@
+// align_tables.h -- host side of a tdnnf_align_graphs, free of HIP (g++ compiles it: tests/test_align_tables_cpu.py, as host_linalg.h): the
+// three arc tables of a set of pdf-labelled graphs and the launch form of the recursions that walk them.  align_graphs.hip uploads the
+// tables; align.hip, align_fb.hip and chain_num_e2e.hip ask align_form_plan; the kernels (align_kernels.h, align_fb_kernels.h,
+// num_e2e_kernels.h) read the tables through AlignDev (align_graphs.h).
+//
+// A table groups a set's arcs into ROWS, 16 bytes an arc: one load per arc.  The rows of at most kAlignHeavy arcs (light rows) are sorted by
+// descending length (stable) and cut into SLICES of 64, one lane each: the j-th arcs of a slice's 64 rows lie side by side, so a wave's
+// load of them is one contiguous KB (a thread per row over a CSR array touched 64 lines for the same KB: with batched loads 46 -> 24 us per
+// frame on the 4 000-state graph, docs/experiments.md r6-o).  Unlike the denominator's SELL-64 tables, whose sums may take a row's arcs in
+// any order, a row's arcs stay in the caller's order (j ascending), which is what the best path's tie rule and the sums' one order of
+// summation need; a row is walked to its own length, so the padding of a slice is never read.  HEAVY rows (the denominator graph of a real
+// system has states with hundreds of incoming arcs; a slice would pad 63 rows to that length) lie one after the other behind the slices
+// and are taken a wave per row.
+//   by_dst: rows are states (every state has one, empty or not); arc = (source state, pdf, log-prob bits, caller's arc index)
+//   by_src: rows are states (likewise);                           arc = (destination state, pdf, log-prob bits, caller's arc index)
+//   by_pdf: rows are the pdfs that an arc of the graph names;     arc = (source state, destination state, log-prob bits, caller's arc index)
+// States are LOCAL to their graph everywhere.
+#pragma once
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace tdnnf {
+
+constexpr int kAlignHeavy = 64;       // a row of more arcs than this is a heavy row
+constexpr int kAlignRowRegs = 8;      // floats of an output row a thread carries from one frame to the next (row_in_lds)
+constexpr int kAlignFbAlphaRegs = 7;  // doubles of alpha_t a thread carries into LDS (alpha_in_lds): 7 * 1024 covers every S whose three vectors fit
+
+struct AlignInt4 {  // the 16 bytes of a device int4
+  int x, y, z, w;
+};
+static_assert(sizeof(AlignInt4) == 16, "copied into int4 arrays");
+
+struct AlignRange {       // one graph's share of a table
+  int slot0, num_slots;   // its light rows: slots[slot0 .. slot0 + num_slots), a multiple of 64
+  int heavy0, num_heavy;  // its heavy rows: heavy[heavy0 .. heavy0 + num_heavy)
+};
+struct AlignGraphDev {     // one graph of a tdnnf_align_graphs (device table)
+  int state0, num_states;  // its states are [state0, state0 + num_states) of the per-state arrays
+  AlignRange by_dst, by_src, by_pdf;
+};
+
+struct AlignHostTable {
+  std::vector<AlignInt4> slots;  // (row or -1 for an empty lane, length, position of the row's first arc: its j-th is 64 j further, 0)
+  std::vector<AlignInt4> heavy;  // (row, first arc, one past the last arc, 0)
+  std::vector<AlignInt4> arcs;
+};
+
+// One graph's rows into a table: rows[r] lists the arcs of row r in the caller's order; an empty row gets a slot of length 0 unless skip_empty.
+template <class Pack>
+AlignRange align_add_graph(AlignHostTable &t, const std::vector<std::vector<int>> &rows, bool skip_empty, Pack packed) {
+  AlignRange g;
+  g.slot0 = (int)t.slots.size();
+  g.heavy0 = (int)t.heavy.size();
+  std::vector<int> light;
+  for (int r = 0; r < (int)rows.size(); r++)
+    if ((int)rows[r].size() <= kAlignHeavy && !(skip_empty && rows[r].empty())) light.push_back(r);
+  std::stable_sort(light.begin(), light.end(), [&](int a, int b) { return rows[a].size() > rows[b].size(); });
+  for (size_t first = 0; first < light.size(); first += 64) {
+    const size_t base = t.arcs.size(), width = rows[light[first]].size();
+    t.arcs.resize(base + 64 * width, AlignInt4{0, 0, 0, -1});  // (entries beyond a row's length are never read)
+    for (int lane = 0; lane < 64; lane++) {
+      if (first + lane >= light.size()) {
+        t.slots.push_back(AlignInt4{-1, 0, 0, 0});
+        continue;
+      }
+      const int r = light[first + lane];
+      t.slots.push_back(AlignInt4{r, (int)rows[r].size(), (int)base + lane, 0});
+      for (size_t j = 0; j < rows[r].size(); j++) t.arcs[base + 64 * j + lane] = packed(rows[r][j]);
+    }
+  }
+  g.num_slots = (int)t.slots.size() - g.slot0;
+  for (int r = 0; r < (int)rows.size(); r++) {
+    if ((int)rows[r].size() <= kAlignHeavy) continue;
+    t.heavy.push_back(AlignInt4{r, (int)t.arcs.size(), (int)(t.arcs.size() + rows[r].size()), 0});
+    for (int a : rows[r]) t.arcs.push_back(packed(a));
+  }
+  g.num_heavy = (int)t.heavy.size() - g.heavy0;
+  return g;
+}
+
+struct AlignHostTables {
+  std::vector<AlignGraphDev> graphs;
+  AlignHostTable by_dst, by_src, by_pdf;
+  std::vector<int> max_in_degree;  // per graph: the longest row by destination
+};
+
+// The three tables of a set of graphs whose arrays tdnnf_align_graphs_create has validated (global state numbers, as the caller gives them).
+inline void align_build_tables(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, AlignHostTables *t) {
+  t->graphs.resize(num_graphs);
+  for (int k = 0; k < num_graphs; k++) {
+    const int s0 = graph_state_begin[k], S = graph_state_begin[k + 1] - s0;
+    std::vector<std::vector<int>> in(S), out(S), of_pdf(num_pdfs);
+    for (int a = graph_arc_begin[k]; a < graph_arc_begin[k + 1]; a++) {
+      in[arc_dst[a] - s0].push_back(a);
+      out[arc_src[a] - s0].push_back(a);
+      of_pdf[arc_pdf[a]].push_back(a);
+    }
+    auto bits = [&](int a) {
+      int b;
+      memcpy(&b, &arc_logprob[a], 4);
+      return b;
+    };
+    AlignGraphDev &g = t->graphs[k];
+    g.state0 = s0;
+    g.num_states = S;
+    g.by_dst = align_add_graph(t->by_dst, in, false, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_pdf[a], bits(a), a}; });
+    g.by_src = align_add_graph(t->by_src, out, false, [&](int a) { return AlignInt4{arc_dst[a] - s0, arc_pdf[a], bits(a), a}; });
+    g.by_pdf = align_add_graph(t->by_pdf, of_pdf, true, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_dst[a] - s0, bits(a), a}; });
+    size_t deg = 0;
+    for (const std::vector<int> &row : in) deg = std::max(deg, row.size());
+    t->max_in_degree.push_back((int)deg);
+  }
+}
+
+// What a recursion over graphs of at most max_states states and num_pdfs pdfs runs as: one workgroup per utterance.
+struct AlignFormPlan {
+  int threads;        // 64 for graphs of at most 64 states, 256 up to 1024 states, 1024 above
+  bool lds;           // the two alternating state vectors in LDS (else in the caller's workspace / scratch)
+  bool alpha_in_lds;  // a third vector behind them: alpha_t of the frame whose posteriors are formed (align_fb_kernels.h, ALDS)
+  bool row_in_lds;    // behind the vectors two output rows of num_pdfs floats, staged one frame ahead (align_kernels.h, AlignRowStage)
+  size_t lds_bytes;   // dynamic LDS of the launch
+};
+
+// align_form (option): 0 the vectors in LDS where two of them fit lds_budget, 1 / 2 force LDS / workspace.  want_alpha: the caller forms
+// posteriors inside the recursion's kernel and would stage alpha_t.  False and *err (starting with prefix) for a form that cannot be had.
+inline bool align_form_plan(int max_states, int num_pdfs, int align_form, bool want_alpha, size_t lds_budget, const char *prefix, AlignFormPlan *p,
+                            std::string *err) {
+  const size_t S8 = sizeof(double) * (size_t)max_states, rows_bytes = 2 * sizeof(float) * (size_t)num_pdfs;
+  const bool fits = 2 * S8 <= lds_budget;
+  char msg[200];
+  if (align_form < 0 || align_form > 2) {
+    snprintf(msg, sizeof(msg), "%soption align_form must be 0, 1 or 2", prefix);
+    *err = msg;
+    return false;
+  }
+  if (align_form == 1 && !fits) {
+    snprintf(msg, sizeof(msg), "%soption align_form = 1, but two vectors of %d doubles do not fit the LDS", prefix, max_states);
+    *err = msg;
+    return false;
+  }
+  p->lds = align_form == 1 || (align_form == 0 && fits);
+  p->threads = max_states <= 64 ? 64 : max_states <= 1024 ? 256 : 1024;
+  p->alpha_in_lds = want_alpha && p->lds && 3 * S8 <= lds_budget && max_states <= kAlignFbAlphaRegs * p->threads;
+  const size_t vec_bytes = (p->alpha_in_lds ? 3 : 2) * S8;
+  // (with posteriors the rows are staged only behind a staged alpha_t: one launch form fewer, and a graph whose third vector does not fit has
+  // little room left for rows)
+  p->row_in_lds = p->lds && (!want_alpha || p->alpha_in_lds) && num_pdfs <= kAlignRowRegs * p->threads && vec_bytes + rows_bytes <= lds_budget;
+  p->lds_bytes = p->lds ? vec_bytes + (p->row_in_lds ? rows_bytes : 0) : 0;
+  return true;
+}
+
+}  // namespace tdnnf

@@ -12,22 +12,11 @@
 namespace tdnnf {
 namespace {
 
-struct E2eArgs {
-  AlignDev dev;
-  AlignFbDev fb;
-};
-E2eArgs e2e_args(const tdnnf_supervision *sp) {
-  const tdnnf_align_graphs *g = sp->e2e_graphs;
-  return E2eArgs{AlignDev{g->graphs, g->slots, g->heavy, g->arcs, g->init, g->final},
-                 AlignFbDev{g->fb_graphs, AlignFbTable{g->src_slots, g->src_heavy, g->src_arcs}, AlignFbTable{g->pdf_slots, g->pdf_heavy, g->pdf_arcs}}};
-}
-
 template <int NT, bool LDS, bool YLDS, bool FULL>
 int e2e_launch_form(const tdnnf_supervision *sp, const MatView &y, double *num_lp, hipStream_t s) {
   if (LDS)
-    TDNNF_HIP(hipFuncSetAttribute((const void *)num_e2e_recursion_kernel<NT, LDS, YLDS, FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->e2e_lds_bytes));
-  const E2eArgs a = e2e_args(sp);
-  hipLaunchKernelGGL((num_e2e_recursion_kernel<NT, LDS, YLDS, FULL>), dim3(sp->B), dim3(NT), sp->e2e_lds_bytes, s, a.dev, a.fb, y, sp->B, sp->T, sp->e2e_alpha,
+    TDNNF_HIP(hipFuncSetAttribute((const void *)num_e2e_recursion_kernel<NT, LDS, YLDS, FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->e2e_form.lds_bytes));
+  hipLaunchKernelGGL((num_e2e_recursion_kernel<NT, LDS, YLDS, FULL>), dim3(sp->B), dim3(NT), sp->e2e_form.lds_bytes, s, sp->e2e_graphs->dev, y, sp->B, sp->T, sp->e2e_alpha,
                      sp->e2e_beta, sp->e2e_vecs, num_lp, sp->max_states_per_seq, sp->num_pdfs);
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
@@ -35,14 +24,14 @@ int e2e_launch_form(const tdnnf_supervision *sp, const MatView &y, double *num_l
 
 template <int NT, bool FULL>
 int e2e_launch(const tdnnf_supervision *sp, const MatView &y, double *num_lp, hipStream_t s) {
-  if (sp->e2e_row_lds) return e2e_launch_form<NT, true, true, FULL>(sp, y, num_lp, s);
-  if (sp->e2e_lds) return e2e_launch_form<NT, true, false, FULL>(sp, y, num_lp, s);
+  if (sp->e2e_form.row_in_lds) return e2e_launch_form<NT, true, true, FULL>(sp, y, num_lp, s);
+  if (sp->e2e_form.lds) return e2e_launch_form<NT, true, false, FULL>(sp, y, num_lp, s);
   return e2e_launch_form<NT, false, false, FULL>(sp, y, num_lp, s);
 }
 
 template <bool FULL>
 int e2e_recursion(const tdnnf_supervision *sp, const MatView &y, double *num_lp, hipStream_t s) {
-  switch (sp->e2e_threads) {
+  switch (sp->e2e_form.threads) {
     case 64:
       return e2e_launch<64, FULL>(sp, y, num_lp, s);
     case 256:
@@ -59,8 +48,7 @@ int e2e_posterior_form(const tdnnf_supervision *sp, int blocks, const MatView &y
                        const MatView &xent_deriv, float xent_scale, bool do_xent, hipStream_t s) {
   const size_t lds = LDS ? 2 * sizeof(double) * (size_t)sp->max_states_per_seq : 0;
   if (LDS) TDNNF_HIP(hipFuncSetAttribute((const void *)num_e2e_posterior_kernel<NT, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const E2eArgs a = e2e_args(sp);
-  hipLaunchKernelGGL((num_e2e_posterior_kernel<NT, LDS>), dim3(blocks, sp->B), dim3(NT), lds, s, a.dev, a.fb, y, xent_out, sp->B, sp->T, sp->weight, sp->e2e_alpha,
+  hipLaunchKernelGGL((num_e2e_posterior_kernel<NT, LDS>), dim3(blocks, sp->B), dim3(NT), lds, s, sp->e2e_graphs->dev, y, xent_out, sp->B, sp->T, sp->weight, sp->e2e_alpha,
                      sp->e2e_beta, num_lp, deriv, xent_deriv, xent_scale, do_xent ? 1 : 0, sp->xent_part, sp->max_states_per_seq);
   return TDNNF_OK;
 }
@@ -78,10 +66,10 @@ int num_e2e_posteriors(const tdnnf_supervision *sp, const MatView &y, const MatV
   const int blocks = (sp->T + kNumE2eFrames - 1) / kNumE2eFrames;
   int rc;
   if (sp->max_states_per_seq > 1024)
-    rc = sp->e2e_lds ? e2e_posterior_form<1024, true>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s)
+    rc = sp->e2e_form.lds ? e2e_posterior_form<1024, true>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s)
                      : e2e_posterior_form<1024, false>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s);
   else
-    rc = sp->e2e_lds ? e2e_posterior_form<256, true>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s)
+    rc = sp->e2e_form.lds ? e2e_posterior_form<256, true>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s)
                      : e2e_posterior_form<256, false>(sp, blocks, y, xent_out, num_lp, deriv, xent_deriv, xent_scale, do_xent, s);
   if (rc) return rc;
   if (do_xent) hipLaunchKernelGGL(num_e2e_xent_sum_kernel, dim3((sp->B + 63) / 64), dim3(64), 0, s, sp->xent_part, sp->B, blocks, xent_objf);
@@ -101,8 +89,6 @@ int tdnnf_supervision_create_e2e(int B, int T, int num_pdfs, const int *seq_stat
   TDNNF_REQUIRE(out && B > 0 && T > 0 && num_pdfs > 0 && seq_state_begin && seq_arc_begin && arc_src && arc_dst && arc_pdf && arc_logprob && initial_logprob &&
                     final_logprob,
                 "supervision_create_e2e: bad arguments");
-  const int form = options().align_form;
-  TDNNF_REQUIRE(form >= 0 && form <= 2, "supervision_create_e2e: option align_form must be 0, 1 or 2");
   tdnnf_align_graphs *graphs = nullptr;
   // (validates what tdnnf_align_graphs_create validates: pdfs in [0, num_pdfs), states inside their sequence, an initial and a final state)
   int rc = tdnnf_align_graphs_create(B, num_pdfs, seq_state_begin, seq_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob, final_logprob, &graphs);
@@ -119,24 +105,18 @@ int tdnnf_supervision_create_e2e(int B, int T, int num_pdfs, const int *seq_stat
   sp->num_arcs = seq_arc_begin[B];
   for (int s = 0; s < B; s++) sp->max_states_per_seq = std::max(sp->max_states_per_seq, seq_state_begin[s + 1] - seq_state_begin[s]);
   sp->max_states_per_frame = sp->max_states_per_seq;
-  // the alignment's plan (align.hip align_plan), fixed here: the scratch depends on it
-  const size_t vec_bytes = 2 * sizeof(double) * (size_t)sp->max_states_per_seq, rows_bytes = 2 * sizeof(float) * (size_t)num_pdfs;
-  const bool fits = vec_bytes <= kLdsBudget;
-  if (form == 1 && !fits) {
-    const int smax = sp->max_states_per_seq;
+  // the recursion's launch form, fixed here: the scratch depends on it
+  std::string err;
+  if (!align_form_plan(sp->max_states_per_seq, num_pdfs, options().align_form, false, kLdsBudget, "supervision_create_e2e: ", &sp->e2e_form, &err)) {
     tdnnf_supervision_destroy(sp);
-    TDNNF_REQUIRE(false, "supervision_create_e2e: option align_form = 1, but two vectors of %d doubles do not fit the LDS", smax);
+    TDNNF_REQUIRE(false, "%s", err.c_str());
   }
-  sp->e2e_lds = form == 1 || (form == 0 && fits);
-  sp->e2e_threads = sp->max_states_per_seq <= 64 ? 64 : sp->max_states_per_seq <= 1024 ? 256 : 1024;
-  sp->e2e_row_lds = sp->e2e_lds && num_pdfs <= kAlignRowRegs * sp->e2e_threads && vec_bytes + rows_bytes <= kLdsBudget;
-  sp->e2e_lds_bytes = sp->e2e_lds ? vec_bytes + (sp->e2e_row_lds ? rows_bytes : 0) : 0;
   const size_t frames = sizeof(double) * ((size_t)T + 1) * (size_t)sp->num_states, parts = (size_t)B * ((T + kNumE2eFrames - 1) / kNumE2eFrames);
   hipError_t e = hipSuccess;
   if ((e = hipMalloc((void **)&sp->e2e_alpha, frames)) != hipSuccess || (e = hipMalloc((void **)&sp->e2e_beta, frames)) != hipSuccess ||
       (e = hipMalloc((void **)&sp->xent_part, sizeof(double) * parts)) != hipSuccess ||
       (e = hipMalloc((void **)&sp->l2_part, sizeof(double) * kFinishL2Parts)) != hipSuccess ||
-      (!sp->e2e_lds && (e = hipMalloc((void **)&sp->e2e_vecs, 2 * sizeof(double) * (size_t)sp->num_states)) != hipSuccess)) {
+      (!sp->e2e_form.lds && (e = hipMalloc((void **)&sp->e2e_vecs, 2 * sizeof(double) * (size_t)sp->num_states)) != hipSuccess)) {
     tdnnf_supervision_destroy(sp);
     return hip_status(e, "supervision_create_e2e: hipMalloc");
   }
@@ -154,9 +134,9 @@ int tdnnf_supervision_kind(const tdnnf_supervision *sp) {
 
 int tdnnf_supervision_e2e_form(const tdnnf_supervision *sp, int *threads, int *vectors_in_lds, int *rows_in_lds) {
   TDNNF_REQUIRE(sp && sp->kind == 1, "supervision_e2e_form: not an end-to-end supervision");
-  if (threads) *threads = sp->e2e_threads;
-  if (vectors_in_lds) *vectors_in_lds = sp->e2e_lds ? 1 : 0;
-  if (rows_in_lds) *rows_in_lds = sp->e2e_row_lds ? 1 : 0;
+  if (threads) *threads = sp->e2e_form.threads;
+  if (vectors_in_lds) *vectors_in_lds = sp->e2e_form.lds ? 1 : 0;
+  if (rows_in_lds) *rows_in_lds = sp->e2e_form.row_in_lds ? 1 : 0;
   return TDNNF_OK;
 }
 

@@ -19,6 +19,7 @@
 //    with a frame tolerance, any width) takes one workgroup per sequence with the frontier in LDS and a posterior pass spread over
 //    (sequence, block of frames) (num_wide_kernels.h); it owns its scratch, so the workspace does not grow with the supervision.
 #pragma once
+#include "align_tables.h"
 #include "common.h"
 
 struct tdnnf_den_graph {
@@ -70,12 +71,10 @@ struct tdnnf_supervision {
   // the time-synchronous tables null.  All null / zero for kind 0.
   int kind;       // 0 time-synchronous, 1 end-to-end
   int num_pdfs;   // kind 1: the graphs' pdfs are in [0, num_pdfs)
-  struct tdnnf_align_graphs *e2e_graphs;  // the arcs by destination, by source and by pdf (align_graphs.h); graph s is sequence s's
+  struct tdnnf_align_graphs *e2e_graphs;  // the arcs by destination, by source and by pdf (align_tables.h); graph s is sequence s's
   double *e2e_alpha, *e2e_beta;           // (T + 1) * num_states doubles each: alpha_t / beta_t of every frame, sequence after sequence
   double *e2e_vecs;                       // 2 * num_states doubles where the two state vectors do not live in LDS, else null
-  int e2e_threads;                        // the recursion's workgroup: 64 up to 64 states in the largest graph, 256 up to 1024, 1024 above
-  bool e2e_lds, e2e_row_lds;              // state vectors in LDS; two output rows staged behind them
-  size_t e2e_lds_bytes;
+  tdnnf::AlignFormPlan e2e_form;          // the recursion's launch form (align_tables.h), fixed at creation: e2e_vecs depends on it
 };
 
 namespace tdnnf {

@@ -1,6 +1,7 @@
 // num_e2e_kernels.h -- the chain numerator on cyclic per-sequence graphs (flat-start / "end-to-end" LF-MMI: Kaldi's
 // GenericNumeratorComputation).  Included by chain_num_e2e.hip only.  The graphs are a tdnnf_align_graphs (align_graphs.h: the arcs by
-// destination, by source and by pdf), one graph per sequence; the arithmetic is align_fb_kernels.h's with acoustic_scale = 1, all in double:
+// destination, by source and by pdf), one graph per sequence; the arithmetic is align_fb_kernels.h's with acoustic_scale = 1, all in double,
+// and so is the code: its forward pass (fb_forward), its step on the arcs by source (align_step with AlignLseAcc) and its per-pdf sum (fb_post_step):
 //     term(arc, t) = (double)arc_logprob + (double)y[t * B + s, arc_pdf]                        no clamp
 //     alpha_0 = initial_logprob;  alpha_t+1[d] = LSE over arcs into d of alpha_t[src] + term(arc, t)
 //     num_lp[s] = LSE over states of alpha_T + final_logprob
@@ -33,72 +34,20 @@ constexpr int kNumE2eFrames = 8;  // frames per workgroup of the posterior pass 
 // alpha_all / beta_all: the (T + 1) * S doubles of the sequence whose first state is state0 start at (T + 1) * state0; vecs (!LDS): its two
 // vectors at 2 * state0.
 template <int NT, bool LDS, bool YLDS, bool FULL>
-__global__ __launch_bounds__(NT) void num_e2e_recursion_kernel(AlignDev g, AlignFbDev fb, MatView y, int B, int T, double *alpha_all, double *beta_all,
-                                                               double *vecs, double *num_lp, int Smax, int P) {
+__global__ __launch_bounds__(NT) void num_e2e_recursion_kernel(AlignDev g, MatView y, int B, int T, double *alpha_all, double *beta_all, double *vecs,
+                                                               double *num_lp, int Smax, int P) {
   static_assert(LDS || !YLDS, "the rows behind the vectors need the LDS form");
   extern __shared__ double num_e2e_smem[];
-  __shared__ double red_m[NT / 64], red_s[NT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, seq = blockIdx.x;
+  const int tid = threadIdx.x, seq = blockIdx.x;
   const AlignGraphDev gr = g.graphs[seq];
   const int S = gr.num_states, s0 = gr.state0;
   double *cur = LDS ? num_e2e_smem : vecs + 2 * (size_t)s0, *nxt = cur + S;
-  float *ylds = reinterpret_cast<float *>(num_e2e_smem + 2 * (size_t)Smax);  // YLDS: two rows of P floats
-  double *alpha = FULL ? alpha_all + (size_t)(T + 1) * s0 : nullptr;
-  const size_t row_step = (size_t)B * y.stride;  // t-major: the next frame's row of this sequence lies B rows on
-  const float *row0 = y.data + (size_t)seq * y.stride;
-  float yreg[kAlignRowRegs];
-  auto row_of = [&](int t) { return row0 + (size_t)t * row_step; };
-  auto load_row = [&](int t) {  // (only [0, P) of a row: what the graphs' arcs can name)
-    if (!YLDS || t < 0 || t >= T) return;
-    const float *r = row_of(t);
-#pragma unroll
-    for (int c = 0; c < kAlignRowRegs; c++)
-      if (tid + c * NT < P) yreg[c] = r[tid + c * NT];
-  };
-  auto store_row = [&](int t) {
-    if (!YLDS || t < 0 || t >= T) return;
-#pragma unroll
-    for (int c = 0; c < kAlignRowRegs; c++)
-      if (tid + c * NT < P) ylds[(size_t)(t & 1) * P + tid + c * NT] = yreg[c];
-  };
-  for (int s = tid; s < S; s += NT) {
-    const double v = (double)g.init[s0 + s];
-    cur[s] = v;
-    if (FULL) alpha[s] = v;
-  }
-  load_row(0);
-  store_row(0);
-  load_row(1);
-  __syncthreads();
-  for (int t = 0; t < T; t++) {
-    // row t + 1 (loaded a frame ago) into the buffer whose last readers -- frame t - 1 -- are behind the previous barrier; row t + 2 on its way
-    store_row(t + 1);
-    load_row(t + 2);
-    const float *yrow = YLDS ? ylds + (size_t)(t & 1) * P : row_of(t);
-    fb_lse_step<NT>(g.slots + gr.slot0, gr.num_slots, g.heavy + gr.heavy0, gr.num_heavy, g.arcs, cur, yrow, 1.0, nxt,
-                    FULL ? alpha + (size_t)(t + 1) * S : nullptr, tid);
-    __syncthreads();
-    double *sw = cur;
-    cur = nxt;
-    nxt = sw;
-  }
-  // the total: a thread's states in ascending order, the lanes by butterfly, the waves in ascending order -- by every thread alike
-  double m = -INFINITY, sum = 0.0;
-  for (int s = tid; s < S; s += NT) fb_lse_add(m, sum, cur[s] + (double)g.final[s0 + s]);
-  fb_lse_wave(m, sum);
-  if (lane == 0) {
-    red_m[wave] = m;
-    red_s[wave] = sum;
-  }
-  __syncthreads();
-  m = red_m[0];
-  sum = red_s[0];
-  for (int w = 1; w < NT / 64; w++) fb_lse_merge(m, sum, red_m[w], red_s[w]);
-  const double logprob = fb_lse_value(m, sum);
+  // t-major: the next frame's row of this sequence lies B rows on
+  AlignRowStage<NT, YLDS> rows(y.data + (size_t)seq * y.stride, (size_t)B * y.stride, P, T, reinterpret_cast<float *>(num_e2e_smem + 2 * (size_t)Smax));
+  const double logprob = fb_forward<NT, YLDS, FULL>(g, gr, T, rows, 1.0, cur, nxt, FULL ? alpha_all + (size_t)(T + 1) * s0 : nullptr);
   if (tid == 0) num_lp[seq] = logprob;
   if (!FULL) return;
   if (!(logprob > -INFINITY && logprob < INFINITY)) return;  // (the posterior pass skips this sequence: its beta has no reader)
-  const AlignFbGraphDev fg = fb.graphs[seq];
   double *beta = beta_all + (size_t)(T + 1) * s0;
   // (alpha_T's last readers are behind the barrier above)
   for (int s = tid; s < S; s += NT) {
@@ -106,17 +55,15 @@ __global__ __launch_bounds__(NT) void num_e2e_recursion_kernel(AlignDev g, Align
     cur[s] = v;
     beta[(size_t)T * S + s] = v;
   }
-  load_row(T - 1);
-  store_row(T - 1);
-  load_row(T - 2);
+  rows.load(T - 1);
+  rows.store(T - 1);
+  rows.load(T - 2);
   __syncthreads();
   for (int t = T - 1; t >= 0; t--) {
     // row t - 1 into the buffer whose last readers -- frame t + 1 -- are behind the previous barrier; row t - 2 on its way
-    store_row(t - 1);
-    load_row(t - 2);
-    const float *yrow = YLDS ? ylds + (size_t)(t & 1) * P : row_of(t);
-    fb_lse_step<NT>(fb.by_src.slots + fg.src_slot0, fg.src_num_slots, fb.by_src.heavy + fg.src_heavy0, fg.src_num_heavy, fb.by_src.arcs, cur, yrow, 1.0, nxt,
-                    beta + (size_t)t * S, tid);
+    rows.store(t - 1);
+    rows.load(t - 2);
+    align_step<NT>(g.by_src, gr.by_src, cur, rows.row(t), 1.0, AlignLseAcc{nxt, beta + (size_t)t * S});
     __syncthreads();
     double *sw = cur;
     cur = nxt;
@@ -131,9 +78,9 @@ __global__ __launch_bounds__(NT) void num_e2e_recursion_kernel(AlignDev g, Align
 // lines were the pass's time (20.2 ms a pass at 128 x 150 frames against 12.0 ms for all of align_fb_kernel; docs/experiments.md r6-q).
 // NT: 256 threads, 1024 where the largest graph has more than 1024 states (two such workgroups still fit a CU beside their vectors).
 template <int NT, bool LDS>
-__global__ __launch_bounds__(NT) void num_e2e_posterior_kernel(AlignDev g, AlignFbDev fb, MatView y, MatView xent_out, int B, int T, float weight,
-                                                               const double *alpha_all, const double *beta_all, const double *num_lp, MatView deriv,
-                                                               MatView xent_deriv, float xent_scale, int do_xent, double *xent_part, int Smax) {
+__global__ __launch_bounds__(NT) void num_e2e_posterior_kernel(AlignDev g, MatView y, MatView xent_out, int B, int T, float weight, const double *alpha_all,
+                                                               const double *beta_all, const double *num_lp, MatView deriv, MatView xent_deriv,
+                                                               float xent_scale, int do_xent, double *xent_part, int Smax) {
   extern __shared__ double num_e2e_post_smem[];
   __shared__ double red[NT / 64];
   const int seq = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -147,10 +94,8 @@ __global__ __launch_bounds__(NT) void num_e2e_posterior_kernel(AlignDev g, Align
   };
   if (logprob > -INFINITY && logprob < INFINITY) {  // (the same for every thread of the workgroup: the barriers below are met by all or none)
     const AlignGraphDev gr = g.graphs[seq];
-    const AlignFbGraphDev fg = fb.graphs[seq];
     const int S = gr.num_states, t0 = blockIdx.x * kNumE2eFrames, t1 = min(T, t0 + kNumE2eFrames);
     const double *alpha = alpha_all + (size_t)(T + 1) * gr.state0, *beta = beta_all + (size_t)(T + 1) * gr.state0;
-    const int4 *slots = fb.by_pdf.slots + fg.pdf_slot0, *heavy = fb.by_pdf.heavy + fg.pdf_heavy0, *arcs = fb.by_pdf.arcs;
     for (int t = t0; t < t1; t++) {
       const double *at = alpha + (size_t)t * S, *bt = beta + (size_t)(t + 1) * S;
       if (LDS) {
@@ -165,36 +110,7 @@ __global__ __launch_bounds__(NT) void num_e2e_posterior_kernel(AlignDev g, Align
         bt = bl;
       }
       const size_t row = (size_t)t * B + seq;
-      const float *yrow = y.data + row * y.stride;
-      for (int slot = tid; slot < fg.pdf_num_slots; slot += NT) {  // light pdfs: a lane per pdf, slice by slice
-        const int4 r = slots[slot];
-        if (r.x < 0) continue;
-        const double yv = (double)yrow[r.x];
-        double sum = 0.0;
-        for (int j = 0; j < r.y; j += kAlignBatch) {
-          int4 arc[kAlignBatch];
-#pragma unroll
-          for (int k = 0; k < kAlignBatch; k++) arc[k] = arcs[r.z + 64 * min(j + k, r.y - 1)];
-#pragma unroll
-          for (int k = 0; k < kAlignBatch; k++) {
-            const double v = (at[arc[k].x] + ((double)__int_as_float(arc[k].z) + yv)) + bt[arc[k].y];
-            if (j + k < r.y && v > -INFINITY) sum += exp(v - logprob);
-          }
-        }
-        emit(row, r.x, sum);
-      }
-      for (int h = wave; h < fg.pdf_num_heavy; h += NT / 64) {  // heavy pdfs: a wave per pdf, the lanes' sums by butterfly
-        const int4 r = heavy[h];
-        const double yv = (double)yrow[r.x];
-        double sum = 0.0;
-        for (int a = r.y + lane; a < r.z; a += 64) {
-          const int4 arc = arcs[a];
-          const double v = (at[arc.x] + ((double)__int_as_float(arc.z) + yv)) + bt[arc.y];
-          if (v > -INFINITY) sum += exp(v - logprob);
-        }
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-        if (lane == 0) emit(row, r.x, sum);
-      }
+      fb_post_step<NT>(g.by_pdf, gr.by_pdf, at, bt, y.data + row * y.stride, 1.0, logprob, [&](int pdf, double sum) { emit(row, pdf, sum); });
     }
   }
   if (do_xent) {

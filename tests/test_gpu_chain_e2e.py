@@ -8,7 +8,8 @@ flat-start LF-MMI; csrc/chain_num_e2e.hip, csrc/num_e2e_kernels.h).
    output rows live; the posterior kernel's four forms, threads x LDS or scratch, are among them), on sub-matrix views, with canaries; bars: [3] 1e-9, [4] [6] 1e-6 relative, [0] 1e-6 (|num| + |den|), xent_deriv
    elementwise 2 float32 ulps at xent_regularize * weight, deriv rel_l2 < 1e-4 (tests/test_gpu_chain_hostile.py, tests/test_gpu_posteriors.py);
 3. the failure path (a sequence without a path of T arcs), and a good minibatch on the same workspace behind it;
-4. tdnnf_chain_objf on the same cases; 5. determinism and tdnnf_chain_numerator_part 1, 4, 2; 6. argument errors."""
+4. tdnnf_chain_objf on the same cases; 5. determinism and tdnnf_chain_numerator_part 1, 4, 2; 6. argument errors;
+7. the numerator and AlignGraphs.posteriors run the same device code on the same tables: log-probs and posteriors have the same bits."""
 import ctypes as C
 
 import numpy as np
@@ -444,3 +445,63 @@ def test_argument_errors(hip, pkg):
     short = torch.zeros(B * T - 1, P, device="cuda")
     assert lib.tdnnf_chain_objf_and_deriv(*args(ds, short, torch.zeros_like(short))) == 1 and b"nnet_output" in lib.tdnnf_last_error()
     assert lib.tdnnf_supervision_kind(None) == -1
+
+
+# ------------------------------------------------------------------------------------------------ 7. the bits of AlignGraphs.posteriors
+def _dense(S, P, seed, heavy_state=None, heavy_pdf=None):
+    """S states, all initial and final (every path of T arcs accepts), three arcs out of each (loop, next, seventh on) with pdfs below
+    P - 4, so the last four are free: heavy_state gets arcs from further states until 65 enter it, heavy_pdf is put on 65 arcs."""
+    rng = np.random.default_rng(seed)
+    st = np.arange(S)
+    src, dst = np.repeat(st, 3), np.stack([st, (st + 1) % S, (st + 7) % S], 1).reshape(-1)
+    if heavy_state is not None:
+        more = np.setdiff1d(st, src[dst == heavy_state])[:65 - int((dst == heavy_state).sum())]
+        src, dst = np.concatenate([src, more]), np.concatenate([dst, np.full(len(more), heavy_state)])
+    pdf = rng.integers(0, P - 4, size=len(src))
+    if heavy_pdf is not None:
+        pdf[rng.permutation(len(src))[:65]] = heavy_pdf
+    f32 = lambda a: a.astype(np.float32)
+    return {"S": S, "P": P, "src": src.astype(np.int32), "dst": dst.astype(np.int32), "pdf": pdf.astype(np.int32),
+            "logprob": f32(-rng.random(len(src))), "init": f32(-rng.random(S)), "final": f32(-rng.random(S))}
+
+
+@pytest.mark.parametrize("form", [1, 2], ids=["lds", "global"])
+def test_numerator_has_the_bits_of_align_posteriors(hip, pkg, form):
+    """Three graphs of 70 to 80 states (256 threads), T = 12, 40 pdfs, a state that 65 arcs enter and a pdf on 65 arcs (a heavy row by
+    destination and one by pdf, beside light ones), vectors in LDS and in the scratch.  The supervision's recursion and
+    AlignGraphs.posteriors(row_stride=B, acoustic_scale=1) walk the same tables with the same step in the same order, so
+      * results[3] = weight * (num_lp[0] + num_lp[1] + num_lp[2]) (chain_finalize_kernel: from 0, ascending, weight 1) is that sum of the
+        three logprobs, bit for bit;
+      * parts 1 and 2 on a zeroed matrix (weight 1, no l2 term) leave (float)gamma: the bits of post on every pdf the sequence names, zero elsewhere."""
+    B, T, P = 3, 12, 40
+    graphs = [_dense(70, P, 1), _dense(77, P, 2, heavy_state=5), _dense(80, P, 3, heavy_pdf=P - 1)]
+    assert np.bincount(graphs[1]["dst"]).max() == 65 and np.bincount(graphs[2]["pdf"]).max() == 65
+    assert max(np.bincount(g["dst"]).max() for g in (graphs[0], graphs[2])) <= 64 and max(np.bincount(g["pdf"]).max() for g in graphs[:2]) <= 64
+    named = _named(graphs, B, T, P)
+    assert named.any() and not named.all()
+    y = dev((1.5 * np.random.default_rng(7).standard_normal((T * B, P))).astype(np.float32))
+    _, dg = _den(pkg, 30, P)
+    with pkg.hipabi.option("align_form", form), _Mode(pkg, 4):
+        ds = pkg.hipabi.Supervision({"B": B, "T": T, "P": P, "weight": 1.0, "graphs": graphs})
+        f = ds.e2e_form()
+        assert (f["threads"], f["vectors_in_lds"]) == (256, 1 if form == 1 else 0)
+        post, res = pkg.hipabi.AlignGraphs(graphs, num_pdfs=P).posteriors(y, [T] * B, list(range(B)), row_stride=B, acoustic_scale=1.0)
+        post, res = host(post).copy(), host(res).copy()
+        nb = hip.chain_workspace_bytes(dg.h, B, T)
+        ws = hip.ws(nb)
+        ws.fill_(float("nan"))
+        d, xd = torch.full(y.shape, 5.0, device="cuda"), torch.full(y.shape, 5.0, device="cuda")
+        whole = _full(hip, dg, ds, y, None, 0.1, 0.0, d, xd, ws=ws)  # (leaves the denominator's log-probs, which part 2 reads, in ws)
+        d.zero_()
+        r = torch.zeros(8, dtype=torch.float64, device="cuda")
+        hip.chain_numerator_part(dg.h, ds.h, y, 1, hip.vec(r), None, None, hip.vec(ws), nb, hip.stream())
+        hip.chain_numerator_part(dg.h, ds.h, y, 2, hip.vec(r), d, None, hip.vec(ws), nb, hip.stream())
+        parts, gamma = host(r).copy(), host(d).copy()
+    lp = res[:, 0]
+    want = ((np.float64(0.0) + lp[0]) + lp[1]) + lp[2]
+    print("E2E bits of align_posteriors, align_form %d: form %r logprob %r sum %r results[3] %r / parts %r; posteriors differ in %d of %d named elements"
+          % (form, f, lp.tolist(), want, whole[3], parts[3], int((gamma[named].view(np.uint32) != post[named].view(np.uint32)).sum()), int(named.sum())))
+    assert np.all(res[:, 1] == 1.0) and whole[5] == 1.0 and parts[5] == 1.0
+    assert whole[3] == want and parts[3] == want
+    assert np.array_equal(gamma[named].view(np.uint32), post[named].view(np.uint32))
+    assert post[named].any() and not gamma[~named].any() and not post[~named].any()
