@@ -65,7 +65,7 @@ int tdnnf_abi_version(void);
                      supervision can take form 2 only if it was created while the option was 2 (tdnnf_supervision_create builds the tables then)
      "align_form"    0 (default) best-path alignment keeps its two state vectors in LDS where they fit, in the workspace otherwise; 1 / 2
                      force one (tests); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path, and in the same way by
-                     tdnnf_align_posteriors_workspace_bytes and tdnnf_align_posteriors
+                     tdnnf_align_posteriors_workspace_bytes, tdnnf_align_posteriors and tdnnf_align_posteriors_compact
      "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
      "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
                      kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
@@ -488,6 +488,29 @@ size_t tdnnf_align_posteriors_workspace_bytes(const tdnnf_align_graphs *, int nu
 int tdnnf_align_posteriors(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                            int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, tdnnf_mat *post_out /* may be NULL */,
                            double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
+
+/* ---- compact posteriors: the same pass writing only the columns a graph can fill.
+ * A transcript graph names a few hundred of the num_pdfs pdfs, and what consumes posteriors (a Posterior archive, soft targets) wants
+ * (pdf, value) pairs.  The COLUMN LIST of a graph is the ascending list of the distinct pdfs its arcs name, D_g of them
+ * (tdnnf_align_graphs_pdfs); the compact output of an utterance on graph g is frames x D_g floats, element [t, k] = post[t, pdfs_g[k]] of the
+ * dense call above -- the same arithmetic in the same order by the same owner, so the same bits -- and every pdf outside the list has
+ * posterior 0 by construction.  Every element of a block has an owner, so nothing is zeroed first and nothing outside the blocks is
+ * touched.  ok = 0: the utterance's whole block is 0.  The layout is a function of (utt_graph, utt_frames) alone. */
+/* distinct pdfs of one graph, ascending; pdfs_out (host, may be NULL) gets *num of them */
+int tdnnf_align_graphs_pdfs(const tdnnf_align_graphs *, int graph, int *num, int *pdfs_out);
+/* layout of a call's compact output: utterance u owns floats [utt_begin[u], utt_begin[u + 1]),
+   frames[u] rows of D_graph(u) floats, row t then column k.  utt_begin_out (host, num_utts + 1,
+   may be NULL); *elems_out = utt_begin[num_utts] (may be 0 for a call of zero-frame utterances) */
+int tdnnf_align_posteriors_compact_layout(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, long long *elems_out,
+                                          long long *utt_begin_out);
+/* as tdnnf_align_posteriors with a posterior matrix, but writing the compact layout.  Workspace:
+   tdnnf_align_posteriors_workspace_bytes(..., want_posteriors = 1), unchanged.
+   TDNNF_EINVAL as there, plus: null post_compact_dev with elems > 0, post_compact_elems smaller than the layout's, and a call in which an
+   utterance's block starts beyond float 2^31 - 1 of the output (8 GiB: split the call).  Everything runs on the caller's stream, nothing
+   waits for the device; option "align_form" is read as by the dense call. */
+int tdnnf_align_posteriors_compact(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                                   int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float *post_compact_dev,
+                                   size_t post_compact_elems, double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
 
 /* ========================================================================== A8
  * OnlineNaturalGradient::PreconditionDirections (UPSTREAM; call sites

@@ -412,6 +412,20 @@ inline void AlignPosteriors(const tdnnf_align_graphs *graphs, int num_utts, cons
                                post_out ? &vp : nullptr, results_dev, workspace_dev, workspace_bytes, stream));
 }
 
+// The same pass writing the compact layout (tdnnf_hip.h, "compact posteriors"): per utterance frames x D floats, D the distinct pdfs of its
+// graph (tdnnf_align_graphs_pdfs), at the offsets of tdnnf_align_posteriors_compact_layout -- the (pdf, posterior) pairs of a Posterior
+// without a num_pdfs-wide matrix.  post_compact_dev: device memory of post_compact_elems floats.  workspace:
+// tdnnf_align_posteriors_workspace_bytes(graphs, num_utts, utt_graph, utt_frames, 1).
+template <class CuMat>
+inline void AlignPosteriorsCompact(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames,
+                                   const int *utt_row_begin, int row_stride, const CuMat &nnet_output, float acoustic_scale, float weight,
+                                   float *post_compact_dev, size_t post_compact_elems, double *results_dev, void *workspace_dev,
+                                   size_t workspace_bytes, tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output);
+  Check(tdnnf_align_posteriors_compact(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, &vy, acoustic_scale, weight,
+                                       post_compact_dev, post_compact_elems, results_dev, workspace_dev, workspace_bytes, stream));
+}
+
 // ConstrainOrthonormalInternal nnet-utils.cc:914-1032 on a CuMatrixBase with rows <= cols (pass the transpose otherwise, :1068-1075)
 template <class CuMat>
 inline void ConstrainOrthonormal(float scale, CuMat *M, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {

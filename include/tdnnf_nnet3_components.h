@@ -2054,5 +2054,16 @@ inline void AlignPosteriors(const tdnnf_align_graphs *graphs, int32 num_utts, co
                                  workspace->Get(bytes), bytes, Hooks().stream);
 }
 
+// The same pass in the compact form: per utterance frames x D floats, D the distinct pdfs of its graph (tdnnf_align_graphs_pdfs), at the
+// offsets of tdnnf_align_posteriors_compact_layout in post_compact_dev (post_compact_elems floats of device memory) -- the pairs of a
+// Posterior without a num_pdfs-wide matrix.
+inline void AlignPosteriorsCompact(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames,
+                                   const int32 *utt_row_begin, const CuMatrixBase &nnet_output, float acoustic_scale, float weight,
+                                   float *post_compact_dev, size_t post_compact_elems, double *results_dev, Scratch *workspace) {
+  const size_t bytes = tdnnf_align_posteriors_workspace_bytes(graphs, num_utts, utt_graph, utt_frames, 1);
+  tdnnf_adapter::AlignPosteriorsCompact(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, 1, nnet_output, acoustic_scale, weight, post_compact_dev,
+                                        post_compact_elems, results_dev, workspace->Get(bytes), bytes, Hooks().stream);
+}
+
 }  // namespace tdnnf_nnet3
 #endif  // TDNNF_NNET3_COMPONENTS_H_

@@ -23,6 +23,9 @@
 //      order, so every element has one owner and one order of summation.  The row is first zeroed by coalesced stores, and behind the
 //      barrier that separates step 1 from step 2 the owners store their elements straight to global memory: no LDS row of num_pdfs
 //      floats, no atomics.  Step 2 recomputes term + beta_t+1[dst] per arc; step 1 leaves nothing per arc.
+//      The COMPACT form (align_fb_compact_kernel, FbCompactOut) runs the same steps, but an utterance's output is frames x D floats, D the
+//      distinct pdfs of its graph, and the owner of pdf p stores to the column of p (its rank among them, which comes with the by-pdf
+//      row): every column of a frame has an owner, so there is no zeroing loop in the frame, and the values are the dense form's bits.
 // alpha_t of every frame is kept in the workspace ((T + 1) * S doubles) by the forward pass when posteriors are wanted; without them the
 // forward pass runs alone on its two alternating vectors.
 //  * LDS: the two state vectors are 2 * Smax doubles of dynamic LDS, else they lie in the workspace;
@@ -132,9 +135,9 @@ __device__ __forceinline__ double fb_forward(const AlignDev &g, const AlignGraph
   return fb_lse_value(m, sum);
 }
 
-// One frame's posteriors from one graph's rows of the arcs by pdf: emit(p, sum over the arcs of pdf p of exp(alpha[src] + term + beta[dst] - logprob)),
-// by the element's one owner -- a lane per light pdf, lane 0 of the wave that walks a heavy one -- with the arcs in the caller's order.
-// Only the pdfs that an arc names have a row.
+// One frame's posteriors from one graph's rows of the arcs by pdf: emit(p, column of p, sum over the arcs of pdf p of exp(alpha[src] + term +
+// beta[dst] - logprob)), by the element's one owner -- a lane per light pdf, lane 0 of the wave that walks a heavy one -- with the arcs in
+// the caller's order.  Only the pdfs that an arc names have a row; a row's column (align_tables.h) comes with its slot or descriptor.
 template <int NT, class Emit>
 __device__ __forceinline__ void fb_post_step(const AlignTable &tb, const AlignRange &r, const double *alpha, const double *beta, const float *yrow,
                                              double scale, double logprob, Emit emit) {
@@ -155,7 +158,7 @@ __device__ __forceinline__ void fb_post_step(const AlignTable &tb, const AlignRa
         if (j + k < row.y && v > -INFINITY) sum += exp(v - logprob);
       }
     }
-    emit(row.x, sum);
+    emit(row.x, row.w, sum);
   }
   for (int h = wave; h < r.num_heavy; h += NT / 64) {
     const int4 row = heavy[h];
@@ -167,15 +170,51 @@ __device__ __forceinline__ void fb_post_step(const AlignTable &tb, const AlignRa
       if (v > -INFINITY) sum += exp(v - logprob);
     }
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if (lane == 0) emit(row.x, sum);
+    if (lane == 0) emit(row.x, row.w, sum);
   }
 }
 
-// grid = utterances.  Dynamic LDS: [LDS: 2 * Smax doubles, the state vectors] [ALDS: Smax doubles, alpha_t] [YLDS: 2 * P floats, two output rows].
-// POST: alpha_all / post are read and written; otherwise the kernel ends with the total.
-template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST>
-__global__ __launch_bounds__(NT) void align_fb_kernel(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight,
-                                                      MatView post, double *alpha_all, double *vecs, double *results, int Smax, int P) {
+// Where an utterance's posteriors go.  frame(t) before the owners of frame t emit(pdf, column, value), with a workgroup barrier in between;
+// fail(T): the utterance has no finite logprob, all it owns becomes 0.
+// Dense: row utt_row_begin + t * row_stride of a matrix of P columns, element [t, pdf]; the pdfs no arc names have no owner, so frame(t)
+// zeroes the row first.
+template <int NT>
+struct FbDenseOut {
+  MatView post;
+  int row_begin, row_stride, P;
+  float *prow;
+  __device__ __forceinline__ float *row(int t) const { return post.data + (size_t)(row_begin + (long long)t * row_stride) * post.stride; }
+  __device__ __forceinline__ void fail(int T) {
+    for (int t = 0; t < T; t++) {
+      prow = row(t);
+      for (int c = threadIdx.x; c < P; c += NT) prow[c] = 0.f;
+    }
+  }
+  __device__ __forceinline__ void frame(int t) {
+    prow = row(t);
+    for (int c = threadIdx.x; c < P; c += NT) prow[c] = 0.f;
+  }
+  __device__ __forceinline__ void emit(int pdf, int, float v) { prow[pdf] = v; }
+};
+// Compact: the utterance's block of T rows of D floats, D the distinct pdfs of its graph, element [t, column]: every column has an owner
+// in every frame, so nothing is zeroed.
+template <int NT>
+struct FbCompactOut {
+  float *block;
+  int D;
+  float *prow;
+  __device__ __forceinline__ void fail(int T) {
+    for (size_t i = threadIdx.x; i < (size_t)T * D; i += NT) block[i] = 0.f;
+  }
+  __device__ __forceinline__ void frame(int t) { prow = block + (size_t)t * D; }
+  __device__ __forceinline__ void emit(int, int column, float v) { prow[column] = v; }
+};
+
+// One utterance on its workgroup.  Dynamic LDS: [LDS: 2 * Smax doubles, the state vectors] [ALDS: Smax doubles, alpha_t] [YLDS: 2 * P floats, two output rows].
+// POST: alpha_all / out are read and written; otherwise it ends with the total.
+template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST, class MakeOut>
+__device__ __forceinline__ void fb_utterance(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight,
+                                             MakeOut make_out, double *alpha_all, double *vecs, double *results, int Smax, int P) {
   static_assert(LDS || !(YLDS || ALDS), "the rows behind the vectors need the LDS form");
   static_assert(POST || !ALDS, "alpha_t is staged for the posteriors only");
   extern __shared__ double fb_smem[];
@@ -196,12 +235,9 @@ __global__ __launch_bounds__(NT) void align_fb_kernel(AlignDev g, const AlignUtt
     results[2 * (size_t)blockIdx.x + 1] = ok ? 1.0 : 0.0;
   }
   if (!POST) return;
-  auto post_row = [&](int t) { return post.data + (size_t)(u.row_begin + (long long)t * row_stride) * post.stride; };
+  auto out = make_out(u);
   if (!ok) {
-    for (int t = 0; t < T; t++) {
-      float *prow = post_row(t);
-      for (int c = tid; c < P; c += NT) prow[c] = 0.f;
-    }
+    out.fail(T);
     return;
   }
   const double w = (double)weight;
@@ -216,8 +252,7 @@ __global__ __launch_bounds__(NT) void align_fb_kernel(AlignDev g, const AlignUtt
     rows.store(t - 1);
     rows.load(t - 2);
     const float *yrow = rows.row(t);
-    float *prow = post_row(t);
-    for (int c = tid; c < P; c += NT) prow[c] = 0.f;
+    out.frame(t);
     const double *at = alpha + (size_t)t * S;
     double areg[kAlignFbAlphaRegs];
     if (ALDS) {
@@ -232,14 +267,34 @@ __global__ __launch_bounds__(NT) void align_fb_kernel(AlignDev g, const AlignUtt
       for (int c = 0; c < kAlignFbAlphaRegs; c++)
         if (tid + c * NT < S) alds[tid + c * NT] = areg[c];
     }
-    __syncthreads();  // alpha_t is in place and the row's zeros are stored
+    __syncthreads();  // alpha_t is in place and the row's zeros (dense) are stored
     fb_post_step<NT>(g.by_pdf, gr.by_pdf, ALDS ? (const double *)alds : at, cur, yrow, scale, logprob,
-                     [&](int pdf, double sum) { prow[pdf] = (float)(w * sum); });
+                     [&](int pdf, int column, double sum) { out.emit(pdf, column, (float)(w * sum)); });
     __syncthreads();
     double *sw = cur;
     cur = nxt;
     nxt = sw;
   }
+}
+
+// grid = utterances.  The dense form: post is addressed like y.
+template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST>
+__global__ __launch_bounds__(NT) void align_fb_kernel(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight,
+                                                      MatView post, double *alpha_all, double *vecs, double *results, int Smax, int P) {
+  fb_utterance<NT, LDS, YLDS, ALDS, POST>(
+      g, utts, y, row_stride, acoustic_scale, weight, [&](const AlignUtt &u) { return FbDenseOut<NT>{post, u.row_begin, row_stride, P, nullptr}; }, alpha_all,
+      vecs, results, Smax, P);
+}
+
+// grid = utterances.  The compact form (always with posteriors): utterance u's block starts at compact + u.out_begin and has
+// graph_cols[u.graph] floats a frame.
+template <int NT, bool LDS, bool YLDS, bool ALDS>
+__global__ __launch_bounds__(NT) void align_fb_compact_kernel(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale,
+                                                              float weight, float *compact, const int *graph_cols, double *alpha_all, double *vecs,
+                                                              double *results, int Smax, int P) {
+  fb_utterance<NT, LDS, YLDS, ALDS, true>(
+      g, utts, y, row_stride, acoustic_scale, weight,
+      [&](const AlignUtt &u) { return FbCompactOut<NT>{compact + u.out_begin, graph_cols[u.graph], nullptr}; }, alpha_all, vecs, results, Smax, P);
 }
 
 }  // namespace

@@ -11,8 +11,9 @@
 namespace tdnnf {
 
 struct AlignTable {   // one grouping of a set's arcs (align_tables.h), on the device
-  const int4 *slots;  // (row LOCAL to its graph or -1 for an empty lane, length, position of the row's first arc: its j-th is 64 j further, 0)
-  const int4 *heavy;  // (LOCAL row, first arc, one past the last arc, 0)
+  const int4 *slots;  // (row LOCAL to its graph or -1 for an empty lane, length, position of the row's first arc: its j-th is 64 j further,
+                      // by_pdf: the row's column, else 0)
+  const int4 *heavy;  // (LOCAL row, first arc, one past the last arc, by_pdf: the row's column, else 0)
   const int4 *arcs;   // a row's arcs in the caller's order
 };
 
@@ -27,7 +28,8 @@ struct AlignDev {
 struct AlignUtt {  // one utterance of a call (device table at the head of the workspace)
   int graph, frames;
   int row_begin;
-  int out_begin;          // best path: first element of pdf_out; state_out starts at out_begin + (index of the utterance).  Forward-backward: 0
+  int out_begin;          // best path: first element of pdf_out; state_out starts at out_begin + (index of the utterance).  Forward-backward: 0,
+                          // compact posteriors: first float of the utterance's block
   long long frame_begin;  // first element of its per-frame region of the workspace: best path -- the back-pointers, frames * S ints padded to an
                           // even count; forward-backward -- alpha of every frame, (frames + 1) * S doubles (posteriors)
   long long vec_begin;    // first double of its two state vectors in the workspace's vector region (workspace form)
@@ -41,6 +43,8 @@ struct tdnnf_align_graphs {
   int G, P;
   std::vector<int> state_begin, num_arcs, max_in_degree;  // host: [G + 1], [G], [G]
   tdnnf::AlignDev dev;                                    // device arrays, owned
+  std::vector<int> col_begin, col_pdfs;                   // host: graph k's column list (align_tables.h) is col_pdfs[col_begin[k] .. col_begin[k + 1])
+  const int *num_cols_dev;                                // device, owned: [G] the lengths of the column lists (the compact posteriors' row widths)
 };
 
 namespace tdnnf {

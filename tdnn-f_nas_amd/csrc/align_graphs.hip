@@ -57,7 +57,7 @@ int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_sta
     }
   }
   AlignHostTables t;
-  align_build_tables(num_graphs, num_pdfs, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, &t);
+  align_build_tables(num_graphs, num_pdfs, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, &t, true);
   TDNNF_REQUIRE(t.by_dst.arcs.size() < (size_t)1 << 31, "align_graphs_create: the sliced arc table has more than 2^31 entries");
   TDNNF_REQUIRE(t.by_src.arcs.size() < (size_t)1 << 31 && t.by_pdf.arcs.size() < (size_t)1 << 31,
                 "align_graphs_create: a sliced arc table (by source, by pdf) has more than 2^31 entries");
@@ -68,11 +68,16 @@ int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_sta
   g->state_begin.assign(graph_state_begin, graph_state_begin + num_graphs + 1);
   for (int k = 0; k < num_graphs; k++) g->num_arcs.push_back(graph_arc_begin[k + 1] - graph_arc_begin[k]);
   g->max_in_degree = t.max_in_degree;
+  g->col_begin = t.col_begin;
+  g->col_pdfs = t.col_pdfs;
+  g->num_cols_dev = nullptr;
+  std::vector<int> num_cols;
+  for (int k = 0; k < num_graphs; k++) num_cols.push_back(t.col_begin[k + 1] - t.col_begin[k]);
   const std::vector<float> init(initial_logprob, initial_logprob + NS), fin(final_logprob, final_logprob + NS);
   int rc;
   if ((rc = align_to_device(t.graphs, &g->dev.graphs)) || (rc = align_table_to_device(t.by_dst, &g->dev.by_dst)) ||
       (rc = align_table_to_device(t.by_src, &g->dev.by_src)) || (rc = align_table_to_device(t.by_pdf, &g->dev.by_pdf)) ||
-      (rc = align_to_device(init, &g->dev.init)) || (rc = align_to_device(fin, &g->dev.final))) {
+      (rc = align_to_device(init, &g->dev.init)) || (rc = align_to_device(fin, &g->dev.final)) || (rc = align_to_device(num_cols, &g->num_cols_dev))) {
     tdnnf_align_graphs_destroy(g);
     return rc;
   }
@@ -84,7 +89,8 @@ void tdnnf_align_graphs_destroy(tdnnf_align_graphs *g) {
   if (!g) return;
   const AlignDev &d = g->dev;
   const void *ptrs[] = {d.graphs,      d.by_dst.slots, d.by_dst.heavy, d.by_dst.arcs, d.by_src.slots, d.by_src.heavy,
-                        d.by_src.arcs, d.by_pdf.slots, d.by_pdf.heavy, d.by_pdf.arcs, d.init,         d.final};
+                        d.by_src.arcs, d.by_pdf.slots, d.by_pdf.heavy, d.by_pdf.arcs, d.init,         d.final,
+                        g->num_cols_dev};
   for (const void *p : ptrs) (void)hipFree(const_cast<void *>(p));
   delete g;
 }
@@ -94,6 +100,14 @@ int tdnnf_align_graphs_info(const tdnnf_align_graphs *g, int graph, int *num_sta
   if (num_states) *num_states = g->state_begin[graph + 1] - g->state_begin[graph];
   if (num_arcs) *num_arcs = g->num_arcs[graph];
   if (max_in_degree) *max_in_degree = g->max_in_degree[graph];
+  return TDNNF_OK;
+}
+
+int tdnnf_align_graphs_pdfs(const tdnnf_align_graphs *g, int graph, int *num, int *pdfs_out) {
+  TDNNF_REQUIRE(g && graph >= 0 && graph < g->G, "align_graphs_pdfs: null graphs or graph %d out of range", graph);
+  const int c0 = g->col_begin[graph], c1 = g->col_begin[graph + 1];
+  if (num) *num = c1 - c0;
+  if (pdfs_out) std::copy(g->col_pdfs.begin() + c0, g->col_pdfs.begin() + c1, pdfs_out);
   return TDNNF_OK;
 }
 

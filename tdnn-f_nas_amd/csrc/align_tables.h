@@ -15,6 +15,9 @@
 //   by_src: rows are states (likewise);                           arc = (destination state, pdf, log-prob bits, caller's arc index)
 //   by_pdf: rows are the pdfs that an arc of the graph names;     arc = (source state, destination state, log-prob bits, caller's arc index)
 // States are LOCAL to their graph everywhere.
+// The pdfs that a graph's arcs name, ascending, are its COLUMN LIST (AlignHostTables::col_pdfs): a by_pdf row carries the rank of its pdf in
+// that list -- its column -- in the 4th int of its slot or heavy-row descriptor, where the other two tables have 0.  The compact posteriors
+// (align_fb_kernels.h) are addressed by it; the lists themselves stay on the host.
 #pragma once
 #include <stdio.h>
 #include <string.h>
@@ -44,14 +47,15 @@ struct AlignGraphDev {     // one graph of a tdnnf_align_graphs (device table)
 };
 
 struct AlignHostTable {
-  std::vector<AlignInt4> slots;  // (row or -1 for an empty lane, length, position of the row's first arc: its j-th is 64 j further, 0)
-  std::vector<AlignInt4> heavy;  // (row, first arc, one past the last arc, 0)
+  std::vector<AlignInt4> slots;  // (row or -1 for an empty lane, length, position of the row's first arc: its j-th is 64 j further, column or 0)
+  std::vector<AlignInt4> heavy;  // (row, first arc, one past the last arc, column or 0)
   std::vector<AlignInt4> arcs;
 };
 
 // One graph's rows into a table: rows[r] lists the arcs of row r in the caller's order; an empty row gets a slot of length 0 unless skip_empty.
+// row_col (may be null: 0): what the 4th int of row r's slot or heavy-row descriptor carries.
 template <class Pack>
-AlignRange align_add_graph(AlignHostTable &t, const std::vector<std::vector<int>> &rows, bool skip_empty, Pack packed) {
+AlignRange align_add_graph(AlignHostTable &t, const std::vector<std::vector<int>> &rows, bool skip_empty, const int *row_col, Pack packed) {
   AlignRange g;
   g.slot0 = (int)t.slots.size();
   g.heavy0 = (int)t.heavy.size();
@@ -68,14 +72,14 @@ AlignRange align_add_graph(AlignHostTable &t, const std::vector<std::vector<int>
         continue;
       }
       const int r = light[first + lane];
-      t.slots.push_back(AlignInt4{r, (int)rows[r].size(), (int)base + lane, 0});
+      t.slots.push_back(AlignInt4{r, (int)rows[r].size(), (int)base + lane, row_col ? row_col[r] : 0});
       for (size_t j = 0; j < rows[r].size(); j++) t.arcs[base + 64 * j + lane] = packed(rows[r][j]);
     }
   }
   g.num_slots = (int)t.slots.size() - g.slot0;
   for (int r = 0; r < (int)rows.size(); r++) {
     if ((int)rows[r].size() <= kAlignHeavy) continue;
-    t.heavy.push_back(AlignInt4{r, (int)t.arcs.size(), (int)(t.arcs.size() + rows[r].size()), 0});
+    t.heavy.push_back(AlignInt4{r, (int)t.arcs.size(), (int)(t.arcs.size() + rows[r].size()), row_col ? row_col[r] : 0});
     for (int a : rows[r]) t.arcs.push_back(packed(a));
   }
   g.num_heavy = (int)t.heavy.size() - g.heavy0;
@@ -86,12 +90,18 @@ struct AlignHostTables {
   std::vector<AlignGraphDev> graphs;
   AlignHostTable by_dst, by_src, by_pdf;
   std::vector<int> max_in_degree;  // per graph: the longest row by destination
+  std::vector<int> col_begin;      // [graphs + 1]: graph k's column list is col_pdfs[col_begin[k] .. col_begin[k + 1])
+  std::vector<int> col_pdfs;       // the distinct pdfs of a graph's arcs, ascending
 };
 
-// The three tables of a set of graphs whose arrays tdnnf_align_graphs_create has validated (global state numbers, as the caller gives them).
+// The three tables of a set of graphs whose arrays tdnnf_align_graphs_create has validated (global state numbers, as the caller gives them),
+// and the graphs' column lists.  columns: the by_pdf rows carry their columns, as tdnnf_align_graphs_create uploads them; without, the 4th
+// int of every slot and descriptor is 0 (the tables as they were before there were columns, which tests/test_align_tables_cpu.py decodes).
 inline void align_build_tables(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
-                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, AlignHostTables *t) {
+                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, AlignHostTables *t, bool columns = false) {
   t->graphs.resize(num_graphs);
+  t->col_begin.assign(1, 0);
+  std::vector<int> col(num_pdfs);
   for (int k = 0; k < num_graphs; k++) {
     const int s0 = graph_state_begin[k], S = graph_state_begin[k + 1] - s0;
     std::vector<std::vector<int>> in(S), out(S), of_pdf(num_pdfs);
@@ -108,9 +118,14 @@ inline void align_build_tables(int num_graphs, int num_pdfs, const int *graph_st
     AlignGraphDev &g = t->graphs[k];
     g.state0 = s0;
     g.num_states = S;
-    g.by_dst = align_add_graph(t->by_dst, in, false, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_pdf[a], bits(a), a}; });
-    g.by_src = align_add_graph(t->by_src, out, false, [&](int a) { return AlignInt4{arc_dst[a] - s0, arc_pdf[a], bits(a), a}; });
-    g.by_pdf = align_add_graph(t->by_pdf, of_pdf, true, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_dst[a] - s0, bits(a), a}; });
+    for (int p = 0; p < num_pdfs; p++) {
+      col[p] = (int)t->col_pdfs.size() - t->col_begin[k];  // (read for the pdfs with a row only)
+      if (!of_pdf[p].empty()) t->col_pdfs.push_back(p);
+    }
+    t->col_begin.push_back((int)t->col_pdfs.size());
+    g.by_dst = align_add_graph(t->by_dst, in, false, nullptr, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_pdf[a], bits(a), a}; });
+    g.by_src = align_add_graph(t->by_src, out, false, nullptr, [&](int a) { return AlignInt4{arc_dst[a] - s0, arc_pdf[a], bits(a), a}; });
+    g.by_pdf = align_add_graph(t->by_pdf, of_pdf, true, columns ? col.data() : nullptr, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_dst[a] - s0, bits(a), a}; });
     size_t deg = 0;
     for (const std::vector<int> &row : in) deg = std::max(deg, row.size());
     t->max_in_degree.push_back((int)deg);

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(NT) void num_e2e_posterior_kernel(AlignDev g, MatVi
         bt = bl;
       }
       const size_t row = (size_t)t * B + seq;
-      fb_post_step<NT>(g.by_pdf, gr.by_pdf, at, bt, y.data + row * y.stride, 1.0, logprob, [&](int pdf, double sum) { emit(row, pdf, sum); });
+      fb_post_step<NT>(g.by_pdf, gr.by_pdf, at, bt, y.data + row * y.stride, 1.0, logprob, [&](int pdf, int, double sum) { emit(row, pdf, sum); });
     }
   }
   if (do_xent) {

@@ -349,6 +349,47 @@ class AlignGraphs:
         post = out if out is not None else torch.zeros((nnet_output.shape[0], self.P), dtype=torch.float32, device="cuda")
         return post, self._forward_backward(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post)
 
+    def pdfs(self, graph=0):
+        """The column list of one graph (tdnnf_align_graphs_pdfs): the distinct pdfs its arcs name, ascending, as a numpy int32 array."""
+        import numpy as np
+        n = C.c_int()
+        check(load().tdnnf_align_graphs_pdfs(self.h, int(graph), C.byref(n), None))
+        out = np.zeros(n.value, np.int32)
+        check(load().tdnnf_align_graphs_pdfs(self.h, int(graph), None, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def posteriors_compact_layout(self, utt_frames, utt_graph=None):
+        """tdnnf_align_posteriors_compact_layout: utt_begin, numpy int64 [utterances + 1] -- utterance u owns floats
+        [utt_begin[u], utt_begin[u + 1]) of the compact output, utt_frames[u] rows of len(pdfs(its graph)) floats."""
+        import numpy as np
+        n = len(utt_frames)
+        ug = iarr(utt_graph) if utt_graph is not None else (None, None)
+        begin = np.zeros(n + 1, np.int64)
+        check(load().tdnnf_align_posteriors_compact_layout(self.h, n, ug[1], iarr(utt_frames)[1], None, begin.ctypes.data_as(C.c_void_p)))
+        return begin
+
+    def posteriors_compact(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+        """tdnnf_align_posteriors_compact on the current stream.  Returns (values, utt_begin, results): values float32 CUDA tensor of
+        utt_begin[-1] floats, of which utterance u owns [utt_begin[u], utt_begin[u + 1]) -- utt_frames[u] rows of one float per pdf of
+        pdfs(its graph), = weight x the posterior; utt_begin numpy int64; results float64 [utterances, 2] (logprob, ok) CUDA tensor.
+        Nothing is synchronised."""
+        import torch
+        n = len(utt_frames)
+        fr, frp = iarr(utt_frames)
+        rb, rbp = iarr(utt_row_begin)
+        ug = iarr(utt_graph) if utt_graph is not None else (None, None)
+        begin = self.posteriors_compact_layout(fr, utt_graph)
+        nbytes = int(load().tdnnf_align_posteriors_workspace_bytes(self.h, n, ug[1], frp, 1))
+        if nbytes == 0:
+            raise HipAbiError(f"tdnnf_align_posteriors_workspace_bytes: {load().tdnnf_last_error().decode()}")
+        ws = workspace(nbytes)
+        elems = int(begin[-1])
+        values = torch.empty(elems, dtype=torch.float32, device="cuda")
+        results = torch.empty((n, 2), dtype=torch.float64, device="cuda")
+        check(load().tdnnf_align_posteriors_compact(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale),
+                                                    float(weight), ptr(values) if elems else None, elems, ptr(results), ptr(ws), nbytes, stream()))
+        return values, begin, results
+
     def logprob(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0):
         """The same call without a posterior matrix: the forward recursion alone.  Returns results float64 [utterances, 2] (logprob, ok)."""
         return self._forward_backward(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, 1.0, None)

@@ -116,6 +116,12 @@ class AcousticModel:
         out, outs = self._compute_stacked(utterances, ivector_period)
         return _posteriors_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight) if outs else []
 
+    def posteriors_compact(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10):
+        """compute, then forward-backward of every utterance through its graph in the compact form (posteriors_compact below):
+        [(pdf_ids [D] int32, post [O_u, D] CUDA tensor, logprob, ok)]; the output stays on the device in between."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _posteriors_compact_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight) if outs else []
+
     def logprob(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
         """compute, then the total log-likelihood of every utterance through its graph (logprob below): [(logprob, ok)]."""
         out, outs = self._compute_stacked(utterances, ivector_period)
@@ -371,6 +377,18 @@ def posteriors(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0):
     return _posteriors_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight)
 
 
+def posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+    """posteriors in the compact form (include/tdnnf_hip.h, "compact posteriors"): only the columns an utterance's graph can fill.  Returns a
+    list of (pdf_ids numpy int32 [D] = graphs.pdfs(the utterance's graph), ascending; post float32 [O_u, D] CUDA tensor, a view of the
+    call's one output, with post[t, k] = what posteriors gives for [t, pdf_ids[k]], bit for bit; logprob; ok).  Every pdf outside pdf_ids
+    has posterior 0.  What write_posterior_archive takes as (key, pdf_ids, post)."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _posteriors_compact_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight)
+
+
 def logprob(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
     """The total log-likelihood alone (the forward recursion, no per-frame memory): a list of (logprob, ok)."""
     import torch
@@ -389,6 +407,20 @@ def _posteriors_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight):
     return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(post, frames))]
 
 
+def _posteriors_compact_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight):
+    rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    values, begin, results = graphs.posteriors_compact(y, frames, rows, 1, utt_graph, acoustic_scale, weight)
+    res = results.cpu().numpy()  # (waits for the stream)
+    lists, out = {}, []
+    for u, T in enumerate(frames):
+        gi = int(utt_graph[u]) if utt_graph is not None else (0 if graphs.G == 1 else u)
+        if gi not in lists:
+            lists[gi] = graphs.pdfs(gi)
+        post = values[int(begin[u]):int(begin[u + 1])].view(T, len(lists[gi]))
+        out.append((lists[gi], post, float(res[u, 0]), bool(res[u, 1] == 1.0)))
+    return out
+
+
 def _logprob_stacked(y, frames, graphs, utt_graph, acoustic_scale):
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
     res = graphs.logprob(y, frames, rows, 1, utt_graph, acoustic_scale).cpu().numpy()  # (waits for the stream)
@@ -400,20 +432,28 @@ def write_posterior_archive(path, items, min_post=0.0):
     frame the pair count and the (pdf-id, posterior) pairs -- every int32 and float as `\\4` + 4 little-endian bytes, the size-prefixed
     basic-type encoding include/tdnnf_kaldi_io.h restates; what ali-to-post writes and copy-post reads with ark:path.  The layout is
     written AS RECALLED (hmm/posterior.cc WritePosterior), not checked against a Kaldi build.  items: iterable of (key, post [frames,
-    num_pdfs]) with numpy or torch matrices; entries with post <= min_post are dropped, pdf-ids ascend within a frame."""
+    num_pdfs]) with numpy or torch matrices; entries with post <= min_post are dropped, pdf-ids ascend within a frame.  An item may also be
+    (key, pdf_ids [D], post [frames, D]), the compact form of posteriors_compact: column k holds pdf pdf_ids[k], ascending, and every other
+    pdf 0 -- the same bytes as the dense matrix gives, without forming it."""
     with open(path, "wb") as f:
-        for key, m in items:
+        for item in items:
+            key, m = item[0], item[-1]
             if hasattr(m, "detach"):
                 m = m.detach().cpu().numpy()
             m = np.asarray(m, dtype=np.float32)
             assert m.ndim == 2 and " " not in key and key
+            pdf_ids = None
+            if len(item) == 3:
+                pdf_ids = np.asarray(item[1].detach().cpu().numpy() if hasattr(item[1], "detach") else item[1], dtype=np.int32).reshape(-1)
+                assert len(pdf_ids) == m.shape[1] and (np.diff(pdf_ids) > 0).all()
+                assert min_post >= 0  # (below 0 the dense form writes the zeros of the pdfs outside the list)
             f.write(key.encode() + b" \0B")
             f.write(struct.pack("<bi", 4, m.shape[0]))
             for row in m:
                 ids = np.nonzero(row > min_post)[0]
                 f.write(struct.pack("<bi", 4, len(ids)))
                 pairs = np.zeros(len(ids), dtype=[("a", "i1"), ("pdf", "<i4"), ("b", "i1"), ("post", "<f4")])
-                pairs["a"], pairs["b"], pairs["pdf"], pairs["post"] = 4, 4, ids, row[ids]
+                pairs["a"], pairs["b"], pairs["pdf"], pairs["post"] = 4, 4, ids if pdf_ids is None else pdf_ids[ids], row[ids]
                 f.write(pairs.tobytes())
 
 

@@ -8,11 +8,16 @@ per-frame gather with a sum in float, no back-pointer) with the numerator's recu
 --posteriors: instead of the yardstick, forward-backward (tdnnf_align_posteriors) on the same two workloads and the same data, with the
 posterior matrix ("posteriors") and without ("logprob": the forward recursion alone), timed INTERLEAVED with the best path (one
 repeat of each after the other), and the two ratios to the best path.
-usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors]"""
+--posteriors --compact: the compact call (tdnnf_align_posteriors_compact) joins that interleaved round, and for both output forms the time
+from the finished device result to host-side per-frame (pdf-ids, posteriors) lists -- the copy and the sparsification ("to_lists_ms": the
+dense form copies frames x num_pdfs floats and searches every row, the compact form frames x D and maps columns to pdfs); the lists of the
+two forms are compared, ids and bits.
+usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors [--compact]]"""
 import argparse
 import json
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
@@ -38,7 +43,10 @@ def main():
     ap.add_argument("--pdfs", type=int, default=6034)
     ap.add_argument("--form", type=int, default=0, help="option align_form")
     ap.add_argument("--posteriors", action="store_true", help="time tdnnf_align_posteriors beside the best path")
+    ap.add_argument("--compact", action="store_true", help="with --posteriors: time tdnnf_align_posteriors_compact and the way to host-side lists as well")
     args = ap.parse_args()
+    if args.compact and not args.posteriors:
+        ap.error("--compact goes with --posteriors")
     pkg = ge.load_package()
     abi = pkg.hipabi
     lib = abi.load()
@@ -83,6 +91,17 @@ def main():
             abi.check(lib.tdnnf_align_posteriors(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, None, abi.ptr(out), abi.ptr(ws), nb[0], s))
 
         fns = dict(best_path=best_path, posteriors=full, logprob=forward)
+        if args.compact:
+            begin = ag.posteriors_compact_layout(frames[0], ug[0])
+            elems = int(begin[-1])
+            values = torch.zeros(elems, device="cuda")
+            out_c = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+
+            def compact():
+                abi.check(lib.tdnnf_align_posteriors_compact(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, abi.ptr(values), elems, abi.ptr(out_c),
+                                                             abi.ptr(ws), nb[1], s))
+
+            fns["posteriors_compact"] = compact
         for fn in fns.values():
             fn(), fn()
         torch.cuda.synchronize()
@@ -99,6 +118,40 @@ def main():
             d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v], us_per_frame=round(1e3 * float(np.median(v)) / T, 3))
         d["posteriors_over_best_path"] = round(d["posteriors"]["ms"] / d["best_path"]["ms"], 3)
         d["logprob_over_best_path"] = round(d["logprob"]["ms"] / d["best_path"]["ms"], 3)
+        if args.compact:
+            d["compact_over_posteriors"] = round(d["posteriors_compact"]["ms"] / d["posteriors"]["ms"], 3)
+            d["output_bytes"] = dict(posteriors=4 * post.numel(), posteriors_compact=4 * elems)
+            lists_of = [ag.pdfs(int(gi)) for gi in ug[0]]
+
+            def dense_lists():
+                m = post.cpu().numpy()
+                return [(ids, row[ids]) for row in m for ids in (np.nonzero(row > 0)[0],)]
+
+            def compact_lists():
+                v, res = values.cpu().numpy(), []
+                for u in range(B):
+                    m = v[begin[u]:begin[u + 1]].reshape(T, -1)
+                    res += [(lists_of[u][ids], row[ids]) for row in m for ids in (np.nonzero(row > 0)[0],)]
+                return res
+
+            compact()
+            torch.cuda.synchronize()
+            to_lists = dict(posteriors=[], posteriors_compact=[])
+            for _ in range(args.repeats):
+                for k, fn in (("posteriors", dense_lists), ("posteriors_compact", compact_lists)):
+                    t0 = time.perf_counter()
+                    got = fn()
+                    to_lists[k].append(1e3 * (time.perf_counter() - t0))
+                    if k == "posteriors":
+                        want = got
+                    else:
+                        assert len(got) == len(want) and all(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int32), b[1].view(np.int32))
+                                                             for a, b in zip(got, want)), "the two forms give different lists"
+            for k, v in to_lists.items():
+                d[k]["to_lists_ms"] = round(float(np.median(v)), 1)
+                d[k]["to_lists_ms_all"] = [round(x, 1) for x in v]
+            assert np.array_equal(out_c.cpu().numpy().view(np.int64), r.view(np.int64)), "logprob / ok differ between the forms"
+            d["pairs"] = int(sum(len(a[0]) for a in want))
         return d
 
     # forced alignment: transcripts of 120 units with optional units and alternative branches -- a few hundred states each
