@@ -6,9 +6,12 @@
 //   net_graph.hip   host only, no HIP call: config checks, time grids, TdnnComponent indexes, the component list with its draw plan,
 //                   cv-update factors, the "same model" check, gradient-bucket ranges, and the lists net_model.h declares
 //   net_arena.hip   the arena layout as a sequence of named parts (sizing pass and real pass run the same function), named activations
-//   net_create.hip  create (describe, allocate, name) / destroy, accessors and setters, the statistics get / set
+//   net_create.hip  create (describe, allocate, name) / destroy, the streams and events of the first step, accessors and setters, the
+//                   statistics get / set
 //   net_update.hip  the optimizer step (tdnnf_net_update) with transpose_kernel and scale_doubles_kernel
-//   net_step.hip    one minibatch: forward, chain objective, backward
+//   net_step.h      one minibatch (forward, chain objective, backward) as one object, Step, with the map of its units: net_step.hip the
+//                   schedule, net_step_planes.hip the plane operands, net_step_grad.hip gradients and natural-gradient scheduling,
+//                   net_supernet.hip the supernets' ops
 //   splice.hip      tdnnf_splice_input / tdnnf_reorder_rows with their kernels (no net object)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -285,6 +288,8 @@ struct Arena {
 // ng_grouped, planes_np); the table of named activations that tdnnf_net_get_activation serves
 void net_layout_arena(tdnnf_net *n, Arena &A);
 void net_name_activations(tdnnf_net *n);
+// net_create.hip: what the first step of a net creates (the chain workspace, the streams and events of the step, in a fixed order)
+int create_streams_and_events(tdnnf_net *n, const tdnnf_den_graph *den);
 // view of the rows of a t-major matrix (grid g, B sequences, `cols` wide) that lie on a coarser grid `sub`
 inline tdnnf_mat sub_grid_view(float *data, const Grid &g, const Grid &sub, int B, int cols) {
   const int stride = ldpad(cols);

@@ -1,6 +1,6 @@
 // net_create.hip -- the tdnnf_net object: creation (describe: net_graph.hip; allocate: the preconditioners, the bucket events and the
 // arena of net_arena.hip; name), destruction, the accessors and setters of the C-ABI, and the statistics get / set.  The streams and the
-// step's events are created by the first step (net_step.hip create_streams_and_events), not here.
+// step's events are created by create_streams_and_events, which the net's first step calls (net_step.hip), not by create.
 #include <string.h>
 
 #include <string>
@@ -88,7 +88,54 @@ bool name_matches(const char *name, const char *pat) {
   return *name == *pat && name_matches(name + 1, pat + 1);
 }
 
+// Few sequences leave most CUs idle while one workgroup per sequence walks the frames: there the backward recursion of the denominator runs beside
+// the forward one and the occupancies of all frames at once (the split form).  Measured (ms per step, one-kernel backward -> split): 1500 x 16
+// 37.3 -> 28.5, x 32 53.1 -> 45.3, x 64 80.9 -> 75.2, x 128 127.6 -> 128.2; 150 x 64 14.2 -> 13.8.  The second recursion runs on the
+// weight-gradient stream (or the natural-gradient side stream), idle until the backward pass (on a stream of its own -- a fifth in flight -- the
+// step at 150 x 64 took 20.0 ms: they then share hardware queues).
+// [r4] with the pre-split plane GEMMs (planes = true) the xent head no longer covers a 25 ms denominator at 128 sequences: side by side there too
+// (same box, ms per step: f16x3 103.8 / 105.2 -> 102.1 / 102.4; exact f32 124.4 / 124.6 -> 125.4 / 125.0, so f32 keeps the one-kernel backward pass)
+// [r4, later] with the recursions at 8.8 us per frame (den_persistent_kernels.h, FAST kernels) side by side wins for exact f32 at 128 sequences as well: 122.3 / 122.6 ms
+// against 122.7 / 122.9 on one box, and the GEMM launches beside it are stretched less (event-timed 128 x 128 class 0.642 of the peak against 0.617)
+bool den_uses_split() { return options().den_split >= 0 ? options().den_split != 0 : true; }
+
 }  // namespace
+
+// the first step of a net: the chain workspace and every stream and event of the step, in this order (HIP maps streams to hardware
+// queues in creation order); tdnnf_net_destroy below takes them apart
+int tdnnf::create_streams_and_events(tdnnf_net *n, const tdnnf_den_graph *den) {
+  n->den_split = den_uses_split();  // latched: option den_split read once per net (the workspace is sized for it)
+  n->chain_ws_bytes = tdnnf_chain_workspace_bytes(den, n->B, n->Tout) - (n->den_split ? 0 : chain_split_region_bytes(den, n->B, n->Tout));
+  TDNNF_HIP(hipMalloc(&n->chain_ws, n->chain_ws_bytes));
+  TDNNF_HIP(hipStreamCreateWithFlags(&n->s2, hipStreamNonBlocking));
+  TDNNF_HIP(hipEventCreateWithFlags(&n->ev_fork, hipEventDisableTiming));
+  TDNNF_HIP(hipEventCreateWithFlags(&n->ev_den, hipEventDisableTiming));
+  TDNNF_HIP(hipEventCreateWithFlags(&n->ev_num, hipEventDisableTiming));
+  // The side stream (natural-gradient statistics, the denominator's second recursion) at the default priority, as every stream of the
+  // library: rounds 2-3 gave it the lowest priority above 32 sequences, which is worth nothing measurable in the step any more
+  // (124.0 / 124.0 ms at 128 sequences, 22.9 / 23.0 at 16) and made a job's step time depend on what had run before it in the
+  // process -- once a stream of another priority has existed, HIP's hardware-queue pool maps the next net's streams differently (a
+  // 16-sequence step took 35 ms instead of 23 after a 128-sequence job, a 128-sequence step 142 ms after a 16-sequence one;
+  // docs/experiments.md r4-d).
+  TDNNF_HIP(hipStreamCreateWithFlags(&n->s3, hipStreamNonBlocking));
+  TDNNF_HIP(hipEventCreateWithFlags(&n->ev_s3, hipEventDisableTiming));
+  TDNNF_HIP(hipEventCreateWithFlags(&n->ev_fin0, hipEventDisableTiming));
+  TDNNF_HIP(hipEventCreateWithFlags(&n->ev_fin, hipEventDisableTiming));
+  if (n->early_on) {
+    TDNNF_HIP(hipEventCreateWithFlags(&n->ev_early_in, hipEventDisableTiming));
+    TDNNF_HIP(hipEventCreateWithFlags(&n->ev_early, hipEventDisableTiming));
+    n->early.assign(n->comps.size(), tdnnf_net::EarlyIn());
+  }
+  if (n->early_on && !n->wg_on) TDNNF_HIP(hipStreamCreateWithFlags(&n->s4, hipStreamNonBlocking));
+  if (n->wg_on) {
+    TDNNF_HIP(hipStreamCreateWithFlags(&n->s4, hipStreamNonBlocking));
+    if (n->ws5) TDNNF_HIP(hipStreamCreateWithFlags(&n->s5, hipStreamNonBlocking));
+    for (int i = 0; i < 4; i++) TDNNF_HIP(hipEventCreateWithFlags(&n->ev_pg[i], hipEventDisableTiming));
+    TDNNF_HIP(hipEventCreateWithFlags(&n->ev_pg_in, hipEventDisableTiming));
+  }
+  TDNNF_HIP(hipEventCreateWithFlags(&n->ev_ngc, hipEventDisableTiming));
+  return TDNNF_OK;
+}
 
 extern "C" {
 
