@@ -65,7 +65,8 @@ int tdnnf_abi_version(void);
                      supervision can take form 2 only if it was created while the option was 2 (tdnnf_supervision_create builds the tables then)
      "align_form"    0 (default) best-path alignment keeps its two state vectors in LDS where they fit, in the workspace otherwise; 1 / 2
                      force one (tests); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path, and in the same way by
-                     tdnnf_align_posteriors_workspace_bytes, tdnnf_align_posteriors and tdnnf_align_posteriors_compact
+                     tdnnf_align_posteriors_workspace_bytes, tdnnf_align_posteriors, tdnnf_align_posteriors_compact and the two
+                     tdnnf_align_posteriors_sparse entries
      "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
      "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
                      kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
@@ -511,6 +512,37 @@ int tdnnf_align_posteriors_compact_layout(const tdnnf_align_graphs *, int num_ut
 int tdnnf_align_posteriors_compact(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                                    int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float *post_compact_dev,
                                    size_t post_compact_elems, double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
+
+/* ---- sparse posteriors: per frame the at most K (pdf, value) pairs above a floor.
+ * What a Posterior archive, soft targets and data clean-up take: of the D_g floats of a frame a handful carry mass.  The compact pass above
+ * runs into a block of the workspace (the caller never sees it) and a selection pass (csrc/align_sparse_kernels.h) reads it; everything below
+ * is a function of the floats the compact call writes, v[k] = compact[t, k] for frame t of utterance u on graph g, with its column list pdfs_g:
+ *   candidates  the columns with v[k] > min_post -- strict; min_post is finite and >= 0, so a zero, a negative value and a NaN never are;
+ *               n of them;
+ *   kept        all candidates if n <= K = max_per_frame (1 <= K <= 64), else the K of greatest value, among equal values the lower pdf;
+ *   written     in ascending pdf order: frame f = frame_begin[u] + t, frame_begin the exclusive prefix sum of utt_frames (whatever
+ *               utt_row_begin and row_stride are), owns slots [f * K, (f + 1) * K) of pdf_out_dev and post_out_dev; count_out_dev[f] =
+ *               min(n, K); slots [0, count) hold the kept pairs (pdfs_g[k], v[k]) -- the compact call's bits, NOT renormalised -- and slots
+ *               [count, K) hold (-1, 0.f).  Every slot and count of the call is written, nothing is zeroed first, nothing else is touched.
+ * ok = 0: every count of the utterance 0, every slot (-1, 0.f).  results_dev: FOUR doubles per utterance -- logprob and ok as above, the
+ * number of its frames with n > K (truncated frames) and the greatest n over its frames (the K a retry needs), both exact integers.
+ * No atomics, one owner per slot: two calls on the same inputs give the same bits. */
+/* With W = tdnnf_align_posteriors_workspace_bytes(..., want_posteriors = 1) and elems that of tdnnf_align_posteriors_compact_layout:
+     bytes = 16 + roundup(W, 16) + 48 * num_utts + 8 * sum_u ceil(utt_frames[u] / 16) + 4 * elems
+   (alignment slack; the compact call's workspace; its results and the selection's table, 16 + 32 bytes an utterance; the selection's
+   (truncated frames, greatest n) per 16 frames; the compact block).  0 for bad arguments, max_per_frame outside [1, 64] among them. */
+size_t tdnnf_align_posteriors_sparse_workspace_bytes(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames,
+                                                     int max_per_frame);
+/* utt_graph .. weight as for tdnnf_align_posteriors_compact.  pdf_out_dev, post_out_dev: sum(utt_frames) * max_per_frame elements each,
+   count_out_dev: sum(utt_frames) ints (all three may be NULL for a call of zero-frame utterances, which writes results only).
+   TDNNF_EINVAL, with a message and nothing launched: all that tdnnf_align_posteriors_compact refuses (its limit of 8 GiB to the start of an
+   utterance's block included), max_per_frame outside [1, 64], min_post negative or not finite, a null output with frames to write, a
+   workspace smaller than tdnnf_align_posteriors_sparse_workspace_bytes.  Everything runs on the caller's stream, nothing waits for the
+   device; option "align_form" is read as by the dense call. */
+int tdnnf_align_posteriors_sparse(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                                  int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float min_post, int max_per_frame,
+                                  int *pdf_out_dev, float *post_out_dev, int *count_out_dev, double *results_dev, void *workspace_dev,
+                                  size_t workspace_bytes, tdnnf_stream);
 
 /* ========================================================================== A8
  * OnlineNaturalGradient::PreconditionDirections (UPSTREAM; call sites

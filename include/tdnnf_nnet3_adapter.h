@@ -426,6 +426,21 @@ inline void AlignPosteriorsCompact(const tdnnf_align_graphs *graphs, int num_utt
                                        post_compact_dev, post_compact_elems, results_dev, workspace_dev, workspace_bytes, stream));
 }
 
+// The same pass reduced to what a Posterior holds (tdnnf_hip.h, "sparse posteriors"): per frame the at most max_per_frame (pdf, value)
+// pairs with value > min_post, ascending by pdf, in slots [f * max_per_frame, ..) of pdf_out_dev / post_out_dev with their number in
+// count_out_dev[f]; frames are numbered utterance after utterance.  results_dev: 4 doubles per utterance (logprob, ok, frames that had more
+// candidates than slots, the greatest number of candidates).  workspace: tdnnf_align_posteriors_sparse_workspace_bytes(graphs, num_utts,
+// utt_graph, utt_frames, max_per_frame).
+template <class CuMat>
+inline void AlignPosteriorsSparse(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames,
+                                  const int *utt_row_begin, int row_stride, const CuMat &nnet_output, float acoustic_scale, float weight,
+                                  float min_post, int max_per_frame, int *pdf_out_dev, float *post_out_dev, int *count_out_dev, double *results_dev,
+                                  void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output);
+  Check(tdnnf_align_posteriors_sparse(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, &vy, acoustic_scale, weight, min_post,
+                                      max_per_frame, pdf_out_dev, post_out_dev, count_out_dev, results_dev, workspace_dev, workspace_bytes, stream));
+}
+
 // ConstrainOrthonormalInternal nnet-utils.cc:914-1032 on a CuMatrixBase with rows <= cols (pass the transpose otherwise, :1068-1075)
 template <class CuMat>
 inline void ConstrainOrthonormal(float scale, CuMat *M, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {

@@ -2065,5 +2065,18 @@ inline void AlignPosteriorsCompact(const tdnnf_align_graphs *graphs, int32 num_u
                                         post_compact_elems, results_dev, workspace->Get(bytes), bytes, Hooks().stream);
 }
 
+// The same pass reduced to the pairs of a Posterior: per frame the at most max_per_frame (pdf, value) pairs with value > min_post, ascending
+// by pdf, in slots [f * max_per_frame, ..) of pdf_out_dev / post_out_dev, their number in count_out_dev[f]; results_dev takes FOUR device
+// doubles per utterance (logprob, ok, truncated frames, the greatest number of candidates in a frame).  `workspace` grows to
+// tdnnf_align_posteriors_sparse_workspace_bytes, which holds the compact block.
+inline void AlignPosteriorsSparse(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames,
+                                  const int32 *utt_row_begin, const CuMatrixBase &nnet_output, float acoustic_scale, float weight, float min_post,
+                                  int32 max_per_frame, int32 *pdf_out_dev, float *post_out_dev, int32 *count_out_dev, double *results_dev,
+                                  Scratch *workspace) {
+  const size_t bytes = tdnnf_align_posteriors_sparse_workspace_bytes(graphs, num_utts, utt_graph, utt_frames, max_per_frame);
+  tdnnf_adapter::AlignPosteriorsSparse(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, 1, nnet_output, acoustic_scale, weight, min_post,
+                                       max_per_frame, pdf_out_dev, post_out_dev, count_out_dev, results_dev, workspace->Get(bytes), bytes, Hooks().stream);
+}
+
 }  // namespace tdnnf_nnet3
 #endif  // TDNNF_NNET3_COMPONENTS_H_

@@ -1,5 +1,5 @@
 // align_graphs.h -- the device copy of a set of pdf-labelled graphs (tdnnf_align_graphs) and what its three readers share on the host:
-// align.hip (best path), align_fb.hip (forward-backward) and chain_num_e2e.hip (the end-to-end numerator).  align_graphs.hip creates and
+// align.hip (best path), align_fb.hip (forward-backward), align_sparse.hip (its sparse output) and chain_num_e2e.hip (the end-to-end numerator).  align_graphs.hip creates and
 // destroys the handle from the tables of align_tables.h; the kernels take its AlignDev by value.
 #pragma once
 #include <string>
@@ -45,6 +45,7 @@ struct tdnnf_align_graphs {
   tdnnf::AlignDev dev;                                    // device arrays, owned
   std::vector<int> col_begin, col_pdfs;                   // host: graph k's column list (align_tables.h) is col_pdfs[col_begin[k] .. col_begin[k + 1])
   const int *num_cols_dev;                                // device, owned: [G] the lengths of the column lists (the compact posteriors' row widths)
+  const int *col_pdfs_dev;                                // device, owned: col_pdfs (the sparse posteriors' selection names a kept column's pdf)
 };
 
 namespace tdnnf {

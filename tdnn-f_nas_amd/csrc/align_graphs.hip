@@ -1,5 +1,5 @@
 // align_graphs.hip -- creates, describes and destroys a tdnnf_align_graphs (include/tdnnf_hip.h, "best-path alignment"): validates the caller's
-// arrays, builds the three arc tables on the host (align_tables.h) and uploads them.  Its readers: align.hip, align_fb.hip, chain_num_e2e.hip.
+// arrays, builds the three arc tables on the host (align_tables.h) and uploads them.  Its readers: align.hip, align_fb.hip, align_sparse.hip, chain_num_e2e.hip.
 #include <math.h>
 
 #include "align_graphs.h"
@@ -71,13 +71,15 @@ int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_sta
   g->col_begin = t.col_begin;
   g->col_pdfs = t.col_pdfs;
   g->num_cols_dev = nullptr;
+  g->col_pdfs_dev = nullptr;
   std::vector<int> num_cols;
   for (int k = 0; k < num_graphs; k++) num_cols.push_back(t.col_begin[k + 1] - t.col_begin[k]);
   const std::vector<float> init(initial_logprob, initial_logprob + NS), fin(final_logprob, final_logprob + NS);
   int rc;
   if ((rc = align_to_device(t.graphs, &g->dev.graphs)) || (rc = align_table_to_device(t.by_dst, &g->dev.by_dst)) ||
       (rc = align_table_to_device(t.by_src, &g->dev.by_src)) || (rc = align_table_to_device(t.by_pdf, &g->dev.by_pdf)) ||
-      (rc = align_to_device(init, &g->dev.init)) || (rc = align_to_device(fin, &g->dev.final)) || (rc = align_to_device(num_cols, &g->num_cols_dev))) {
+      (rc = align_to_device(init, &g->dev.init)) || (rc = align_to_device(fin, &g->dev.final)) || (rc = align_to_device(num_cols, &g->num_cols_dev)) ||
+      (rc = align_to_device(t.col_pdfs, &g->col_pdfs_dev))) {
     tdnnf_align_graphs_destroy(g);
     return rc;
   }
@@ -90,7 +92,7 @@ void tdnnf_align_graphs_destroy(tdnnf_align_graphs *g) {
   const AlignDev &d = g->dev;
   const void *ptrs[] = {d.graphs,      d.by_dst.slots, d.by_dst.heavy, d.by_dst.arcs, d.by_src.slots, d.by_src.heavy,
                         d.by_src.arcs, d.by_pdf.slots, d.by_pdf.heavy, d.by_pdf.arcs, d.init,         d.final,
-                        g->num_cols_dev};
+                        g->num_cols_dev, g->col_pdfs_dev};
   for (const void *p : ptrs) (void)hipFree(const_cast<void *>(p));
   delete g;
 }

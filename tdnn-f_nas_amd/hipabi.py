@@ -390,6 +390,33 @@ class AlignGraphs:
                                                     float(weight), ptr(values) if elems else None, elems, ptr(results), ptr(ws), nbytes, stream()))
         return values, begin, results
 
+    def posteriors_sparse(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01,
+                          max_per_frame=16):
+        """tdnnf_align_posteriors_sparse on the current stream: per frame the at most K = max_per_frame (pdf, value) pairs with value >
+        min_post, of the values posteriors_compact gives, in ascending pdf order.  Returns (pdf int32 [F, K], post float32 [F, K], count
+        int32 [F], results float64 [utterances, 4]) as CUDA tensors, F = sum(utt_frames), utterance after utterance: the first count[f]
+        slots of frame f hold its pairs, the others (-1, 0); results = (logprob, ok, frames with more than K candidates, the greatest
+        number of candidates in a frame).  Nothing is synchronised."""
+        import torch
+        n = len(utt_frames)
+        fr, frp = iarr(utt_frames)
+        rb, rbp = iarr(utt_row_begin)
+        ug = iarr(utt_graph) if utt_graph is not None else (None, None)
+        K = int(max_per_frame)
+        nbytes = int(load().tdnnf_align_posteriors_sparse_workspace_bytes(self.h, n, ug[1], frp, K))
+        if nbytes == 0:
+            raise HipAbiError(f"tdnnf_align_posteriors_sparse_workspace_bytes: {load().tdnnf_last_error().decode()}")
+        ws = workspace(nbytes)
+        F = int(fr.sum())
+        pdf = torch.empty((F, K), dtype=torch.int32, device="cuda")
+        post = torch.empty((F, K), dtype=torch.float32, device="cuda")
+        count = torch.empty(F, dtype=torch.int32, device="cuda")
+        results = torch.empty((n, 4), dtype=torch.float64, device="cuda")
+        check(load().tdnnf_align_posteriors_sparse(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), float(weight),
+                                                   float(min_post), K, ptr(pdf) if F else None, ptr(post) if F else None, ptr(count) if F else None,
+                                                   ptr(results), ptr(ws), nbytes, stream()))
+        return pdf, post, count, results
+
     def logprob(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0):
         """The same call without a posterior matrix: the forward recursion alone.  Returns results float64 [utterances, 2] (logprob, ok)."""
         return self._forward_backward(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, 1.0, None)

@@ -122,6 +122,13 @@ class AcousticModel:
         out, outs = self._compute_stacked(utterances, ivector_period)
         return _posteriors_compact_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight) if outs else []
 
+    def posteriors_sparse(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16, ivector_period=10):
+        """compute, then forward-backward of every utterance through its graph in the sparse form (posteriors_sparse below):
+        [(pdf [O_u, K] int32, post [O_u, K], count [O_u] int32 CUDA tensors, logprob, ok, truncated_frames)]; the output stays on the
+        device in between."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame) if outs else []
+
     def logprob(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
         """compute, then the total log-likelihood of every utterance through its graph (logprob below): [(logprob, ok)]."""
         out, outs = self._compute_stacked(utterances, ivector_period)
@@ -389,6 +396,19 @@ def posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weig
     return _posteriors_compact_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight)
 
 
+def posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16):
+    """posteriors in the sparse form (include/tdnnf_hip.h, "sparse posteriors"): per frame the at most K = max_per_frame pairs whose value
+    -- what posteriors_compact gives, bit for bit, not renormalised -- is above min_post; of more than K candidates the K greatest, among
+    equal values the lower pdf.  Returns a list of (pdf int32 [O_u, K], post float32 [O_u, K], count int32 [O_u], views of the call's three
+    CUDA outputs: the first count[t] slots of frame t hold its pairs in ascending pdf order, the others (-1, 0); logprob; ok;
+    truncated_frames, how many of its frames had more than K candidates).  What write_posterior_archive takes as (key, pdf, post, count)."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _posteriors_sparse_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame)
+
+
 def logprob(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
     """The total log-likelihood alone (the forward recursion, no per-frame memory): a list of (logprob, ok)."""
     import torch
@@ -421,6 +441,15 @@ def _posteriors_compact_stacked(y, frames, graphs, utt_graph, acoustic_scale, we
     return out
 
 
+def _posteriors_sparse_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame):
+    import torch
+    rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    pdf, post, count, results = graphs.posteriors_sparse(y, frames, rows, 1, utt_graph, acoustic_scale, weight, min_post, max_per_frame)
+    res = results.cpu().numpy()  # (waits for the stream)
+    return [(a, b, c, float(res[u, 0]), bool(res[u, 1] == 1.0), int(res[u, 2]))
+            for u, (a, b, c) in enumerate(zip(torch.split(pdf, frames), torch.split(post, frames), torch.split(count, frames)))]
+
+
 def _logprob_stacked(y, frames, graphs, utt_graph, acoustic_scale):
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
     res = graphs.logprob(y, frames, rows, 1, utt_graph, acoustic_scale).cpu().numpy()  # (waits for the stream)
@@ -434,9 +463,15 @@ def write_posterior_archive(path, items, min_post=0.0):
     written AS RECALLED (hmm/posterior.cc WritePosterior), not checked against a Kaldi build.  items: iterable of (key, post [frames,
     num_pdfs]) with numpy or torch matrices; entries with post <= min_post are dropped, pdf-ids ascend within a frame.  An item may also be
     (key, pdf_ids [D], post [frames, D]), the compact form of posteriors_compact: column k holds pdf pdf_ids[k], ascending, and every other
-    pdf 0 -- the same bytes as the dense matrix gives, without forming it."""
+    pdf 0 -- the same bytes as the dense matrix gives, without forming it.  Or (key, pdf [frames, K], post [frames, K], count [frames]), the
+    sparse form of posteriors_sparse: of frame t the first count[t] pairs with post > min_post are written, in their order (ascending pdf).
+    Where no frame was truncated and min_post is at least the call's, these are the dense matrix's bytes again."""
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else a
     with open(path, "wb") as f:
         for item in items:
+            if len(item) == 4:
+                _write_sparse_posterior(f, item[0], *[np.asarray(host(a)) for a in item[1:]], min_post)
+                continue
             key, m = item[0], item[-1]
             if hasattr(m, "detach"):
                 m = m.detach().cpu().numpy()
@@ -455,6 +490,24 @@ def write_posterior_archive(path, items, min_post=0.0):
                 pairs = np.zeros(len(ids), dtype=[("a", "i1"), ("pdf", "<i4"), ("b", "i1"), ("post", "<f4")])
                 pairs["a"], pairs["b"], pairs["pdf"], pairs["post"] = 4, 4, ids if pdf_ids is None else pdf_ids[ids], row[ids]
                 f.write(pairs.tobytes())
+
+
+def _write_sparse_posterior(f, key, pdf, post, count, min_post):
+    """one (key, pdf, post, count) item of write_posterior_archive: no row is searched -- one mask over frames x K slots"""
+    pdf, post, count = pdf.astype("<i4", copy=False), post.astype("<f4", copy=False), count.reshape(-1)
+    assert pdf.ndim == 2 and pdf.shape == post.shape and len(count) == len(pdf) and " " not in key and key
+    keep = (np.arange(pdf.shape[1])[None, :] < count[:, None]) & (post > min_post)
+    f.write(key.encode() + b" \0B")
+    f.write(struct.pack("<bi", 4, len(pdf)))
+    head = np.zeros(len(pdf), dtype=[("a", "i1"), ("n", "<i4")])
+    head["a"], head["n"] = 4, keep.sum(1)
+    pairs = np.zeros(int(head["n"].sum()), dtype=[("a", "i1"), ("pdf", "<i4"), ("b", "i1"), ("post", "<f4")])
+    pairs["a"], pairs["b"], pairs["pdf"], pairs["post"] = 4, 4, pdf[keep], post[keep]  # (row-major: frame after frame, slots ascending)
+    ends = np.cumsum(head["n"])
+    hb, pb = head.tobytes(), pairs.tobytes()
+    for t in range(len(pdf)):
+        f.write(hb[5 * t:5 * t + 5])
+        f.write(pb[10 * (ends[t] - head["n"][t]):10 * ends[t]])
 
 
 def read_posterior_archive(path):

@@ -12,7 +12,12 @@ repeat of each after the other), and the two ratios to the best path.
 from the finished device result to host-side per-frame (pdf-ids, posteriors) lists -- the copy and the sparsification ("to_lists_ms": the
 dense form copies frames x num_pdfs floats and searches every row, the compact form frames x D and maps columns to pdfs); the lists of the
 two forms are compared, ids and bits.
-usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors [--compact]]"""
+--posteriors --sparse [--min-post X --max-per-frame K]: the compact and the sparse call (tdnnf_align_posteriors_sparse: the compact pass
+into the workspace, then the selection of at most K pairs above X a frame) join the interleaved round, and for both the time from the
+finished device result to host-side per-frame (pdf-ids, posteriors) lists of the entries above X: the compact form copies frames x D
+floats and searches every row, the sparse form copies frames x K pairs and their counts and slices.  Where no frame was truncated the lists
+are compared, ids and bits.
+usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors [--compact | --sparse]]"""
 import argparse
 import json
 import os
@@ -44,9 +49,14 @@ def main():
     ap.add_argument("--form", type=int, default=0, help="option align_form")
     ap.add_argument("--posteriors", action="store_true", help="time tdnnf_align_posteriors beside the best path")
     ap.add_argument("--compact", action="store_true", help="with --posteriors: time tdnnf_align_posteriors_compact and the way to host-side lists as well")
+    ap.add_argument("--sparse", action="store_true", help="with --posteriors: time the compact and the sparse call and their ways to host-side lists")
+    ap.add_argument("--min-post", type=float, default=0.01, help="--sparse: the floor")
+    ap.add_argument("--max-per-frame", type=int, default=16, help="--sparse: pairs a frame")
     args = ap.parse_args()
-    if args.compact and not args.posteriors:
-        ap.error("--compact goes with --posteriors")
+    if (args.compact or args.sparse) and not args.posteriors:
+        ap.error("--compact and --sparse go with --posteriors")
+    if args.compact and args.sparse:
+        ap.error("--compact or --sparse")
     pkg = ge.load_package()
     abi = pkg.hipabi
     lib = abi.load()
@@ -91,6 +101,8 @@ def main():
             abi.check(lib.tdnnf_align_posteriors(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, None, abi.ptr(out), abi.ptr(ws), nb[0], s))
 
         fns = dict(best_path=best_path, posteriors=full, logprob=forward)
+        if args.sparse:
+            return sparse_case(ag, B, y, frames, rows, ug, ws, nb[1], fns)
         if args.compact:
             begin = ag.posteriors_compact_layout(frames[0], ug[0])
             elems = int(begin[-1])
@@ -152,6 +164,75 @@ def main():
                 d[k]["to_lists_ms_all"] = [round(x, 1) for x in v]
             assert np.array_equal(out_c.cpu().numpy().view(np.int64), r.view(np.int64)), "logprob / ok differ between the forms"
             d["pairs"] = int(sum(len(a[0]) for a in want))
+        return d
+
+    def sparse_case(ag, B, y, frames, rows, ug, ws, nb, fns):
+        K, floor = args.max_per_frame, np.float32(args.min_post)
+        begin = ag.posteriors_compact_layout(frames[0], ug[0])
+        elems = int(begin[-1])
+        values = torch.zeros(elems, device="cuda")
+        out_c = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+        nbs = int(lib.tdnnf_align_posteriors_sparse_workspace_bytes(ag.h, B, ug[1], frames[1], K))
+        wss = abi.workspace(nbs)
+        pdf = torch.zeros(B * T, K, dtype=torch.int32, device="cuda")
+        post = torch.zeros(B * T, K, device="cuda")
+        count = torch.zeros(B * T, dtype=torch.int32, device="cuda")
+        out_s = torch.zeros(B, 4, dtype=torch.float64, device="cuda")
+        s = abi.stream()
+
+        def compact():
+            abi.check(lib.tdnnf_align_posteriors_compact(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, abi.ptr(values), elems, abi.ptr(out_c),
+                                                         abi.ptr(ws), nb, s))
+
+        def sparse():
+            abi.check(lib.tdnnf_align_posteriors_sparse(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, float(floor), K, abi.ptr(pdf), abi.ptr(post),
+                                                        abi.ptr(count), abi.ptr(out_s), abi.ptr(wss), nbs, s))
+
+        fns = dict(best_path=fns["best_path"], posteriors_compact=compact, posteriors_sparse=sparse)
+        for fn in fns.values():
+            fn(), fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in fns}
+        for _ in range(args.repeats):
+            for k, fn in fns.items():
+                ms[k].append(timed(fn, args.calls))
+        rs = out_s.cpu().numpy()
+        d = dict(utterances=B, min_post=float(floor), max_per_frame=K, workspace_bytes=dict(posteriors_compact=nb, posteriors_sparse=nbs), ok=int(rs[:, 1].sum()),
+                 truncated_frames=int(rs[:, 2].sum()), most_candidates=int(rs[:, 3].max()))
+        for k, v in ms.items():
+            d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v], us_per_frame=round(1e3 * float(np.median(v)) / T, 3))
+        d["selection_ms"] = round(d["posteriors_sparse"]["ms"] - d["posteriors_compact"]["ms"], 3)
+        d["sparse_over_compact"] = round(d["posteriors_sparse"]["ms"] / d["posteriors_compact"]["ms"], 3)
+        d["output_bytes"] = dict(posteriors_compact=4 * elems, posteriors_sparse=B * T * (8 * K + 4))
+        lists_of = [ag.pdfs(int(gi)) for gi in ug[0]]
+
+        def compact_lists():
+            v, res = values.cpu().numpy(), []
+            for u in range(B):
+                m = v[begin[u]:begin[u + 1]].reshape(T, -1)
+                res += [(lists_of[u][ids], row[ids]) for row in m for ids in (np.nonzero(row > floor)[0],)]
+            return res
+
+        def sparse_lists():
+            p, v, c = pdf.cpu().numpy(), post.cpu().numpy(), count.cpu().numpy()
+            return [(p[f, :n], v[f, :n]) for f, n in enumerate(c.tolist())]
+
+        to_lists = dict(posteriors_compact=[], posteriors_sparse=[])
+        for _ in range(args.repeats):
+            for k, fn in (("posteriors_compact", compact_lists), ("posteriors_sparse", sparse_lists)):
+                t0 = time.perf_counter()
+                got = fn()
+                to_lists[k].append(1e3 * (time.perf_counter() - t0))
+                if k == "posteriors_compact":
+                    want = got
+                elif d["truncated_frames"] == 0:
+                    assert len(got) == len(want) and all(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int32), b[1].view(np.int32))
+                                                         for a, b in zip(got, want)), "the two forms give different lists"
+        for k, v in to_lists.items():
+            d[k]["to_lists_ms"] = round(float(np.median(v)), 1)
+            d[k]["to_lists_ms_all"] = [round(x, 1) for x in v]
+        assert np.array_equal(out_c.cpu().numpy().view(np.int64), np.ascontiguousarray(rs[:, :2]).view(np.int64)), "logprob / ok differ between the forms"
+        d["pairs"] = dict(posteriors_compact=int(sum(len(a[0]) for a in want)), posteriors_sparse=int(count.sum().item()))
         return d
 
     # forced alignment: transcripts of 120 units with optional units and alternative branches -- a few hundred states each
