@@ -65,8 +65,8 @@ int tdnnf_abi_version(void);
                      supervision can take form 2 only if it was created while the option was 2 (tdnnf_supervision_create builds the tables then)
      "align_form"    0 (default) best-path alignment keeps its two state vectors in LDS where they fit, in the workspace otherwise; 1 / 2
                      force one (tests); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path, and in the same way by
-                     tdnnf_align_posteriors_workspace_bytes, tdnnf_align_posteriors, tdnnf_align_posteriors_compact and the two
-                     tdnnf_align_posteriors_sparse entries
+                     tdnnf_align_posteriors_workspace_bytes, tdnnf_align_posteriors, tdnnf_align_posteriors_compact, the two
+                     tdnnf_align_posteriors_sparse entries and the label entries (tdnnf_align_best_path_labels, tdnnf_align_label_posteriors_*)
      "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
      "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
                      kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
@@ -398,7 +398,9 @@ int tdnnf_chain_numerator_part(const tdnnf_den_graph *, const tdnnf_supervision 
 /* ------------------------------------------------------------------ A7, best-path alignment
  * The best path (Viterbi) of a cyclic, epsilon-free acceptor with pdf-ids on its arcs, scored on rows of the model's output: forced
  * alignment on transcript graphs (what nnet3-align-compiled | ali-to-pdf prints) and the free best path through the denominator graph.
- * Not a decoder: no beam, no lattice, no word labels, no transition-ids; compiling graphs from transcripts stays the caller's job.
+ * Not a decoder: no beam, no lattice; compiling graphs from transcripts stays the caller's job.  Transition-ids, phones and word positions
+ * are the caller's: a second integer per arc, the arc's LABEL (tdnnf_align_graphs_create_labelled), which the labelled entries below report
+ * per frame (tdnnf_align_best_path_labels) and form posteriors over (tdnnf_align_label_posteriors_compact / _sparse).
  *
  *   term(arc, t)  = (double)arc_logprob + (double)acoustic_scale * (double)y[t, arc_pdf]
  *   alpha_0[s]    = (double)initial_logprob[s]
@@ -426,6 +428,15 @@ typedef struct tdnnf_align_graphs tdnnf_align_graphs; /* device-resident set of 
 int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
                               const float *final_logprob, tdnnf_align_graphs **out);
+/* The same with one caller-defined label per arc: arc_label has one int per arc in the caller's arc order, every value in [0, num_labels)
+   (else TDNNF_EINVAL, naming the arc) -- a transition-id, a phone, a word position, the arc's own index.  The handle serves every entry that
+   takes a tdnnf_align_graphs with the bits of an unlabelled handle of the same graphs, and the label entries, which refuse an unlabelled
+   handle with TDNNF_EINVAL.  Memory on top of the above: a fourth copy of the arcs, by label (16 bytes an arc plus the padding of the
+   slices; the entry carries the arc's pdf where the other tables carry its index), 4 bytes an arc for the labels themselves, and per graph
+   the ascending list of its distinct labels (4 bytes a label on the host and on the device) and 20 bytes of ranges and counts. */
+int tdnnf_align_graphs_create_labelled(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                                       const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
+                                       const float *final_logprob, const int *arc_label, int num_labels, tdnnf_align_graphs **out);
 void tdnnf_align_graphs_destroy(tdnnf_align_graphs *);
 /* states, arcs and largest in-degree of one graph; any out-pointer may be NULL */
 int tdnnf_align_graphs_info(const tdnnf_align_graphs *, int graph, int *num_states, int *num_arcs, int *max_in_degree);
@@ -445,12 +456,27 @@ int tdnnf_align_best_path(const tdnnf_align_graphs *, int num_utts, const int *u
                           int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,
                           double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
 
+/* The best path with the identity of its arcs.  pdf_out_dev, state_out_dev, results_dev and the workspace (tdnnf_align_workspace_bytes) are
+   tdnnf_align_best_path's, which runs unchanged; behind it on the same stream a second kernel reads the chosen arc of every frame from
+   where the trace-back left it and writes, laid out as pdf_out_dev (sum(utt_frames) ints each, utterance after utterance):
+     arc_out_dev[t]    (may be NULL) the caller's index of the arc taken at frame t -- the index into the arrays given at creation, global
+                       over the graphs (subtract graph_arc_begin[g] for the index within graph g);
+     label_out_dev[t]  arc_label of that arc.
+   Both are -1 for every frame of an utterance with ok = 0.  Ties are the best path's: of two parallel arcs that differ only in their label
+   the first in the caller's list is reported.  Every element of both outputs is written, by one thread each.  TDNNF_EINVAL: as
+   tdnnf_align_best_path, a handle without labels, a null label_out_dev. */
+int tdnnf_align_best_path_labels(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                                 int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,
+                                 int *label_out_dev, int *arc_out_dev /* may be NULL */, double *results_dev, void *workspace_dev,
+                                 size_t workspace_bytes, tdnnf_stream);
+
 /* ------------------------------------------------------------------ A7, forward-backward
  * The summing counterpart of the best path on the same graphs (a tdnnf_align_graphs holds its arcs three times: by destination, by source,
  * by pdf): the total log-likelihood of each utterance through its graph and, on request, the per-frame pdf posteriors -- the score of a
  * transcript graph to set against the free path, soft alignments (what ali-to-post and its relatives consume).  It is also the arithmetic of
  * the numerator of flat-start ("end-to-end") LF-MMI; to TRAIN on such graphs use tdnnf_supervision_create_e2e above, whose kernels run the
- * same recursion beside the denominator and add the posteriors into the chain derivative.  No beam, epsilon-free graphs, pdf level (no transition-ids), as above.  All in double; term is the best path's:
+ * same recursion beside the denominator and add the posteriors into the chain derivative.  No beam, epsilon-free graphs, as above; per pdf
+ * here, per caller-defined label (a transition-id, a phone) under "label posteriors" below.  All in double; term is the best path's:
  *
  *   term(arc, t)   = (double)arc_logprob + (double)acoustic_scale * (double)y[t, arc_pdf]
  *   alpha_0[s]     = (double)initial_logprob[s]
@@ -543,6 +569,39 @@ int tdnnf_align_posteriors_sparse(const tdnnf_align_graphs *, int num_utts, cons
                                   int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float min_post, int max_per_frame,
                                   int *pdf_out_dev, float *post_out_dev, int *count_out_dev, double *results_dev, void *workspace_dev,
                                   size_t workspace_bytes, tdnnf_stream);
+
+/* ---- label posteriors: the compact and the sparse form per caller-defined label instead of per pdf.
+ * For a handle of tdnnf_align_graphs_create_labelled.  The LABEL COLUMN LIST of a graph is the ascending list of the distinct labels its arcs
+ * carry, L_g of them (tdnnf_align_graphs_labels); an utterance on graph g gets frames x L_g floats,
+ *   element [t, k] = (float)(weight * sum over the arcs with label labels_g[k], in the caller's order, of
+ *                            exp(alpha_t[src] + term(arc, t) + beta_t+1[dst] - logprob))
+ * with alpha, beta, term (its y is that of the ARC's pdf) and logprob those of tdnnf_align_posteriors, formed in the compact call's
+ * association by the same walk on a fourth arc table, by label: with arc_label = arc_pdf the output is tdnnf_align_posteriors_compact's bit
+ * for bit.  One owner per (t, label), no zeroing pass, no atomics: two calls give the same bits.  ok = 0: the utterance's block is 0.
+ * Summed over the labels that share a pdf the values are the pdf posteriors up to rounding; the sum of a row is weight as there.
+ * No dense num_labels-wide form. */
+/* distinct labels of one graph, ascending; labels_out (host, may be NULL) gets *num of them.  TDNNF_EINVAL for a handle without labels */
+int tdnnf_align_graphs_labels(const tdnnf_align_graphs *, int graph, int *num, int *labels_out);
+/* as tdnnf_align_posteriors_compact_layout with L_graph(u) for D_graph(u) */
+int tdnnf_align_label_posteriors_compact_layout(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames,
+                                                long long *elems_out, long long *utt_begin_out);
+/* as tdnnf_align_posteriors_compact on the label layout.  Workspace: tdnnf_align_posteriors_workspace_bytes(..., want_posteriors = 1),
+   unchanged.  TDNNF_EINVAL as there (the 8 GiB limit to the start of an utterance's block included), and a handle without labels. */
+int tdnnf_align_label_posteriors_compact(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames,
+                                         const int *utt_row_begin, int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight,
+                                         float *post_compact_dev, size_t post_compact_elems, double *results_dev, void *workspace_dev,
+                                         size_t workspace_bytes, tdnnf_stream);
+/* the formula of tdnnf_align_posteriors_sparse_workspace_bytes with elems that of tdnnf_align_label_posteriors_compact_layout.  0 for bad
+   arguments, a handle without labels and max_per_frame outside [1, 64] among them. */
+size_t tdnnf_align_label_posteriors_sparse_workspace_bytes(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames,
+                                                           int max_per_frame);
+/* tdnnf_align_posteriors_sparse over the label block and the label column list: semantics, layout and the four result doubles are those of
+   "sparse posteriors" above with labels_g for pdfs_g ("the lower pdf" reads "the lower label"); label_out_dev takes the place of
+   pdf_out_dev.  The selection kernels are the same. */
+int tdnnf_align_label_posteriors_sparse(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames,
+                                        const int *utt_row_begin, int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight,
+                                        float min_post, int max_per_frame, int *label_out_dev, float *post_out_dev, int *count_out_dev,
+                                        double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
 
 /* ========================================================================== A8
  * OnlineNaturalGradient::PreconditionDirections (UPSTREAM; call sites

@@ -441,6 +441,44 @@ inline void AlignPosteriorsSparse(const tdnnf_align_graphs *graphs, int num_utts
                                       max_per_frame, pdf_out_dev, post_out_dev, count_out_dev, results_dev, workspace_dev, workspace_bytes, stream));
 }
 
+// The labelled entries (tdnnf_hip.h, "best-path alignment" and "label posteriors"), for graphs of tdnnf_align_graphs_create_labelled: a
+// caller-defined label per arc -- a transition-id, a phone, a word position.
+// AlignBestPath plus, per frame, the label of the arc taken (label_out_dev: sum(utt_frames) ints, with transition-ids as labels what
+// nnet3-align-compiled writes) and the caller's index of that arc (arc_out_dev, may be null).  Same workspace.
+template <class CuMat>
+inline void AlignBestPathLabels(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                                int row_stride, const CuMat &nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev, int *label_out_dev,
+                                int *arc_out_dev, double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output);
+  Check(tdnnf_align_best_path_labels(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, &vy, acoustic_scale, pdf_out_dev, state_out_dev,
+                                     label_out_dev, arc_out_dev, results_dev, workspace_dev, workspace_bytes, stream));
+}
+
+// AlignPosteriorsCompact per label: frames x L floats, L the distinct labels of the utterance's graph (tdnnf_align_graphs_labels), at the
+// offsets of tdnnf_align_label_posteriors_compact_layout.  Same workspace.
+template <class CuMat>
+inline void AlignLabelPosteriorsCompact(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames,
+                                        const int *utt_row_begin, int row_stride, const CuMat &nnet_output, float acoustic_scale, float weight,
+                                        float *post_compact_dev, size_t post_compact_elems, double *results_dev, void *workspace_dev,
+                                        size_t workspace_bytes, tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output);
+  Check(tdnnf_align_label_posteriors_compact(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, &vy, acoustic_scale, weight,
+                                             post_compact_dev, post_compact_elems, results_dev, workspace_dev, workspace_bytes, stream));
+}
+
+// AlignPosteriorsSparse per label: (label, value) pairs -- with transition-ids as labels the pairs of the Posterior that ali-to-post writes.
+// workspace: tdnnf_align_label_posteriors_sparse_workspace_bytes(graphs, num_utts, utt_graph, utt_frames, max_per_frame).
+template <class CuMat>
+inline void AlignLabelPosteriorsSparse(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames,
+                                       const int *utt_row_begin, int row_stride, const CuMat &nnet_output, float acoustic_scale, float weight,
+                                       float min_post, int max_per_frame, int *label_out_dev, float *post_out_dev, int *count_out_dev,
+                                       double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
+  tdnnf_mat vy = View(nnet_output);
+  Check(tdnnf_align_label_posteriors_sparse(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, &vy, acoustic_scale, weight, min_post,
+                                            max_per_frame, label_out_dev, post_out_dev, count_out_dev, results_dev, workspace_dev, workspace_bytes,
+                                            stream));
+}
+
 // ConstrainOrthonormalInternal nnet-utils.cc:914-1032 on a CuMatrixBase with rows <= cols (pass the transpose otherwise, :1068-1075)
 template <class CuMat>
 inline void ConstrainOrthonormal(float scale, CuMat *M, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {

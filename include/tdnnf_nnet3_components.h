@@ -2078,5 +2078,39 @@ inline void AlignPosteriorsSparse(const tdnnf_align_graphs *graphs, int32 num_ut
                                        max_per_frame, pdf_out_dev, post_out_dev, count_out_dev, results_dev, workspace->Get(bytes), bytes, Hooks().stream);
 }
 
+// ------------------------------------------------------------------------------------------------ labelled graphs
+// The same three on graphs of tdnnf_align_graphs_create_labelled, whose arcs carry a label of the caller's beside the pdf (a transition-id,
+// a phone, a word position).  AlignBestPath plus the label of the arc taken at every frame into label_out_dev and the caller's index of
+// that arc into arc_out_dev (may be null), sum of utt_frames ints each: with transition-ids as labels, the alignment nnet3-align-compiled
+// writes and ali-to-phones, ali-to-post and steps/get_train_ctm.sh read.
+inline void AlignBestPathLabels(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames,
+                                const int32 *utt_row_begin, const CuMatrixBase &nnet_output, float acoustic_scale, int32 *pdf_out_dev,
+                                int32 *label_out_dev, int32 *arc_out_dev, double *results_dev, Scratch *workspace) {
+  const size_t bytes = tdnnf_align_workspace_bytes(graphs, num_utts, utt_graph, utt_frames);
+  tdnnf_adapter::AlignBestPathLabels(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, 1, nnet_output, acoustic_scale, pdf_out_dev, nullptr,
+                                     label_out_dev, arc_out_dev, results_dev, workspace->Get(bytes), bytes, Hooks().stream);
+}
+
+// AlignPosteriorsCompact per label: frames x L floats per utterance, L the distinct labels of its graph (tdnnf_align_graphs_labels), at the
+// offsets of tdnnf_align_label_posteriors_compact_layout.
+inline void AlignLabelPosteriorsCompact(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames,
+                                        const int32 *utt_row_begin, const CuMatrixBase &nnet_output, float acoustic_scale, float weight,
+                                        float *post_compact_dev, size_t post_compact_elems, double *results_dev, Scratch *workspace) {
+  const size_t bytes = tdnnf_align_posteriors_workspace_bytes(graphs, num_utts, utt_graph, utt_frames, 1);
+  tdnnf_adapter::AlignLabelPosteriorsCompact(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, 1, nnet_output, acoustic_scale, weight,
+                                             post_compact_dev, post_compact_elems, results_dev, workspace->Get(bytes), bytes, Hooks().stream);
+}
+
+// AlignPosteriorsSparse per label: per frame the at most max_per_frame (label, value) pairs with value > min_post, ascending by label.
+inline void AlignLabelPosteriorsSparse(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames,
+                                       const int32 *utt_row_begin, const CuMatrixBase &nnet_output, float acoustic_scale, float weight, float min_post,
+                                       int32 max_per_frame, int32 *label_out_dev, float *post_out_dev, int32 *count_out_dev, double *results_dev,
+                                       Scratch *workspace) {
+  const size_t bytes = tdnnf_align_label_posteriors_sparse_workspace_bytes(graphs, num_utts, utt_graph, utt_frames, max_per_frame);
+  tdnnf_adapter::AlignLabelPosteriorsSparse(graphs, num_utts, utt_graph, utt_frames, utt_row_begin, 1, nnet_output, acoustic_scale, weight, min_post,
+                                            max_per_frame, label_out_dev, post_out_dev, count_out_dev, results_dev, workspace->Get(bytes), bytes,
+                                            Hooks().stream);
+}
+
 }  // namespace tdnnf_nnet3
 #endif  // TDNNF_NNET3_COMPONENTS_H_

@@ -1,5 +1,5 @@
 // align.hip -- best-path alignment (include/tdnnf_hip.h, "best-path alignment") through a tdnnf_align_graphs (align_graphs.hip): sizes and lays
-// out the workspace, launches align_best_path_kernel (align_kernels.h).
+// out the workspace, launches align_best_path_kernel and, for the labelled call, align_path_labels_kernel behind it (align_kernels.h).
 #include "align_kernels.h"
 #include "chain_plan.h"
 
@@ -13,9 +13,10 @@ struct AlignPlan : AlignCall, AlignFormPlan {
   size_t bytes;
 };
 
-int align_plan(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin, int row_stride,
-               const tdnnf_mat *nnet_output, AlignPlan *p) {
-  int rc = align_call(g, true, "align: ", "align_best_path: ", num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, nullptr, p);
+// call: the prefix of the messages about the call's rows, the call's name
+int align_plan(const tdnnf_align_graphs *g, const char *call, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+               int row_stride, const tdnnf_mat *nnet_output, AlignPlan *p) {
+  int rc = align_call(g, true, "align: ", call, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, nullptr, p);
   if (rc) return rc;
   std::string err;
   TDNNF_REQUIRE(align_form_plan(p->max_states, g->P, options().align_form, false, kLdsBudget, "align: ", p, &err), "%s", err.c_str());
@@ -42,30 +43,19 @@ int align_launch(const AlignPlan &p, int P, const AlignDev &dev, const AlignUtt 
   return align_launch_form<NT, false, false>(p, P, dev, utts, y, row_stride, acoustic_scale, bp, vecs, pdf_out, state_out, results, s);
 }
 
-}  // namespace
-}  // namespace tdnnf
+constexpr int kAlignLabelThreads = 256;
 
-using namespace tdnnf;
-
-extern "C" {
-
-size_t tdnnf_align_workspace_bytes(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames) {
+// tdnnf_align_best_path (label_out_dev null) and tdnnf_align_best_path_labels.  who: the prefix of the messages, the call's name.
+int align_best_path(const tdnnf_align_graphs *g, const char *who, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                    int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev, int *label_out_dev,
+                    int *arc_out_dev, double *results_dev, void *workspace_dev, size_t workspace_bytes, hipStream_t s) {
+  TDNNF_REQUIRE(g && utt_row_begin && mat_ok(nnet_output) && pdf_out_dev && results_dev && workspace_dev, "%sbad arguments", who);
+  TDNNF_REQUIRE(row_stride >= 1, "%srow_stride %d", who, row_stride);
+  TDNNF_REQUIRE(nnet_output->cols >= g->P, "%snnet_output has %d columns, the graphs %d pdfs", who, nnet_output->cols, g->P);
   AlignPlan p;
-  if (align_plan(g, num_utts, utt_graph, utt_frames, nullptr, 1, nullptr, &p) != TDNNF_OK) return 0;
-  return p.bytes;
-}
-
-int tdnnf_align_best_path(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
-                          int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,
-                          double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
-  TDNNF_REQUIRE(g && utt_row_begin && mat_ok(nnet_output) && pdf_out_dev && results_dev && workspace_dev, "align_best_path: bad arguments");
-  TDNNF_REQUIRE(row_stride >= 1, "align_best_path: row_stride %d", row_stride);
-  TDNNF_REQUIRE(nnet_output->cols >= g->P, "align_best_path: nnet_output has %d columns, the graphs %d pdfs", nnet_output->cols, g->P);
-  AlignPlan p;
-  int rc = align_plan(g, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, &p);
+  int rc = align_plan(g, who, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, &p);
   if (rc) return rc;
-  TDNNF_REQUIRE(workspace_bytes >= p.bytes, "align_best_path: workspace of %zu bytes, %zu needed (tdnnf_align_workspace_bytes)", workspace_bytes, p.bytes);
-  hipStream_t s = (hipStream_t)stream;
+  TDNNF_REQUIRE(workspace_bytes >= p.bytes, "%sworkspace of %zu bytes, %zu needed (tdnnf_align_workspace_bytes)", who, workspace_bytes, p.bytes);
   char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace_dev) + 15) & ~(uintptr_t)15);
   AlignUtt *utts = reinterpret_cast<AlignUtt *>(base);
   int *bp = reinterpret_cast<int *>(base + p.desc_bytes);
@@ -76,12 +66,56 @@ int tdnnf_align_best_path(const tdnnf_align_graphs *g, int num_utts, const int *
   const MatView y = view(nnet_output);
   switch (p.threads) {
     case 64:
-      return align_launch<64>(p, g->P, dev, utts, y, row_stride, acoustic_scale, bp, vecs, pdf_out_dev, state_out_dev, results_dev, s);
+      rc = align_launch<64>(p, g->P, dev, utts, y, row_stride, acoustic_scale, bp, vecs, pdf_out_dev, state_out_dev, results_dev, s);
+      break;
     case 256:
-      return align_launch<256>(p, g->P, dev, utts, y, row_stride, acoustic_scale, bp, vecs, pdf_out_dev, state_out_dev, results_dev, s);
+      rc = align_launch<256>(p, g->P, dev, utts, y, row_stride, acoustic_scale, bp, vecs, pdf_out_dev, state_out_dev, results_dev, s);
+      break;
     default:
-      return align_launch<1024>(p, g->P, dev, utts, y, row_stride, acoustic_scale, bp, vecs, pdf_out_dev, state_out_dev, results_dev, s);
+      rc = align_launch<1024>(p, g->P, dev, utts, y, row_stride, acoustic_scale, bp, vecs, pdf_out_dev, state_out_dev, results_dev, s);
   }
+  if (rc || !label_out_dev) return rc;
+  int max_frames = 0;
+  for (int u = 0; u < num_utts; u++) max_frames = std::max(max_frames, utt_frames[u]);
+  const int blocks = (max_frames + kAlignLabelThreads - 1) / kAlignLabelThreads;
+  for (int u0 = 0; blocks > 0 && u0 < num_utts; u0 += 65535) {  // (a grid's second dimension ends at 65 535)
+    hipLaunchKernelGGL(align_path_labels_kernel<kAlignLabelThreads>, dim3(blocks, std::min(num_utts - u0, 65535)), dim3(kAlignLabelThreads), 0, s, dev,
+                       utts + u0, bp, results_dev + 2 * (size_t)u0, g->arc_label_dev, label_out_dev, arc_out_dev);
+    TDNNF_LAUNCH_CHECK();
+  }
+  return TDNNF_OK;
+}
+
+}  // namespace
+}  // namespace tdnnf
+
+using namespace tdnnf;
+
+extern "C" {
+
+size_t tdnnf_align_workspace_bytes(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames) {
+  AlignPlan p;
+  if (align_plan(g, "align_best_path: ", num_utts, utt_graph, utt_frames, nullptr, 1, nullptr, &p) != TDNNF_OK) return 0;
+  return p.bytes;
+}
+
+int tdnnf_align_best_path(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                          int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,
+                          double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
+  return align_best_path(g, "align_best_path: ", num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale, pdf_out_dev,
+                         state_out_dev, nullptr, nullptr, results_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+int tdnnf_align_best_path_labels(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
+                                 int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,
+                                 int *label_out_dev, int *arc_out_dev, double *results_dev, void *workspace_dev, size_t workspace_bytes,
+                                 tdnnf_stream stream) {
+  const char *who = "align_best_path_labels: ";
+  int rc = align_need_labels(g, who);
+  if (rc) return rc;
+  TDNNF_REQUIRE(label_out_dev, "%snull label_out_dev", who);
+  return align_best_path(g, who, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale, pdf_out_dev, state_out_dev,
+                         label_out_dev, arc_out_dev, results_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

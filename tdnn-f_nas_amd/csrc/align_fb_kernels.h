@@ -1,5 +1,5 @@
 // align_fb_kernels.h -- forward-backward through the graphs of align_graphs.h: total log-likelihood (log-sum over all paths) and per-frame
-// pdf posteriors.  Included by align_fb.hip and, for the shared parts (AlignLseAcc, fb_forward, fb_post_step), by num_e2e_kernels.h.
+// pdf (or label) posteriors.  Included by align_fb.hip and, for the shared parts (AlignLseAcc, fb_forward, fb_post_step), by num_e2e_kernels.h.
 //
 // Arithmetic (include/tdnnf_hip.h, "forward-backward"; held to a tolerance by tests/test_gpu_posteriors.py against tests/posteriors_ref64.py):
 //     term(arc, t) = (double)arc_logprob + (double)acoustic_scale * (double)y[t, arc_pdf]          (align_kernels.h's, rounded once either way)
@@ -26,6 +26,10 @@
 //      The COMPACT form (align_fb_compact_kernel, FbCompactOut) runs the same steps, but an utterance's output is frames x D floats, D the
 //      distinct pdfs of its graph, and the owner of pdf p stores to the column of p (its rank among them, which comes with the by-pdf
 //      row): every column of a frame has an owner, so there is no zeroing loop in the frame, and the values are the dense form's bits.
+//      The LABEL form (align_fb_label_kernel, FbLabelStep) is the compact form on the fourth table: step 2 walks the arcs by LABEL (the
+//      caller's second integer per arc: a transition-id, a phone, the arc's index) with fb_label_step, the same row walk, which reads
+//      y[t, pdf of the arc] per arc where fb_post_step reads y[t, pdf of the row] once; the output is frames x L floats, L the distinct
+//      labels of the graph.  With label = pdf both steps form the same sums in the same order: the same bits (tests/test_gpu_align_labels.py).
 // alpha_t of every frame is kept in the workspace ((T + 1) * S doubles) by the forward pass when posteriors are wanted; without them the
 // forward pass runs alone on its two alternating vectors.
 //  * LDS: the two state vectors are 2 * Smax doubles of dynamic LDS, else they lie in the workspace;
@@ -174,6 +178,65 @@ __device__ __forceinline__ void fb_post_step(const AlignTable &tb, const AlignRa
   }
 }
 
+// The same walk over one graph's rows of the arcs by label: emit(row, column of the label, sum over the arcs with that label of
+// exp(alpha[src] + term + beta[dst] - logprob)).  A label's arcs name different pdfs, so the arc carries its pdf (arc.w) and y[t, pdf] is
+// read per arc -- from the staged row in LDS or, where rows are not staged, from global memory behind the arc's own load, as align_step
+// gathers -- where fb_post_step reads it once per row.  The sum is formed in fb_post_step's association.
+template <int NT, class Emit>
+__device__ __forceinline__ void fb_label_step(const AlignTable &tb, const AlignRange &r, const double *alpha, const double *beta, const float *yrow,
+                                              double scale, double logprob, Emit emit) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int4 *slots = tb.slots + r.slot0, *heavy = tb.heavy + r.heavy0;
+  for (int slot = tid; slot < r.num_slots; slot += NT) {
+    const int4 row = slots[slot];
+    if (row.x < 0) continue;
+    double sum = 0.0;
+    for (int j = 0; j < row.y; j += kAlignBatch) {
+      int4 arc[kAlignBatch];
+      float yv[kAlignBatch];
+#pragma unroll
+      for (int k = 0; k < kAlignBatch; k++) arc[k] = tb.arcs[row.z + 64 * min(j + k, row.y - 1)];
+#pragma unroll
+      for (int k = 0; k < kAlignBatch; k++) yv[k] = yrow[arc[k].w];
+#pragma unroll
+      for (int k = 0; k < kAlignBatch; k++) {
+        const double v = (alpha[arc[k].x] + ((double)__int_as_float(arc[k].z) + scale * (double)yv[k])) + beta[arc[k].y];
+        if (j + k < row.y && v > -INFINITY) sum += exp(v - logprob);
+      }
+    }
+    emit(row.x, row.w, sum);
+  }
+  for (int h = wave; h < r.num_heavy; h += NT / 64) {
+    const int4 row = heavy[h];
+    double sum = 0.0;
+    for (int a = row.y + lane; a < row.z; a += 64) {
+      const int4 arc = tb.arcs[a];
+      const double v = (alpha[arc.x] + ((double)__int_as_float(arc.z) + scale * (double)yrow[arc.w])) + beta[arc.y];
+      if (v > -INFINITY) sum += exp(v - logprob);
+    }
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0) emit(row.x, row.w, sum);
+  }
+}
+
+// Step 2 of a frame as fb_utterance takes it: which table is walked, and by which step.
+struct FbPdfStep {
+  template <int NT, class Emit>
+  __device__ __forceinline__ void run(const AlignDev &g, const AlignGraphDev &gr, int, const double *alpha, const double *beta, const float *yrow,
+                                      double scale, double logprob, Emit emit) const {
+    fb_post_step<NT>(g.by_pdf, gr.by_pdf, alpha, beta, yrow, scale, logprob, emit);
+  }
+};
+struct FbLabelStep {
+  AlignTable by_label;       // tdnnf_align_graphs::by_label
+  const AlignRange *ranges;  // [graphs]: the graphs' shares of it (tdnnf_align_graphs::label_range_dev)
+  template <int NT, class Emit>
+  __device__ __forceinline__ void run(const AlignDev &, const AlignGraphDev &, int graph, const double *alpha, const double *beta, const float *yrow,
+                                      double scale, double logprob, Emit emit) const {
+    fb_label_step<NT>(by_label, ranges[graph], alpha, beta, yrow, scale, logprob, emit);
+  }
+};
+
 // Where an utterance's posteriors go.  frame(t) before the owners of frame t emit(pdf, column, value), with a workgroup barrier in between;
 // fail(T): the utterance has no finite logprob, all it owns becomes 0.
 // Dense: row utt_row_begin + t * row_stride of a matrix of P columns, element [t, pdf]; the pdfs no arc names have no owner, so frame(t)
@@ -211,9 +274,9 @@ struct FbCompactOut {
 };
 
 // One utterance on its workgroup.  Dynamic LDS: [LDS: 2 * Smax doubles, the state vectors] [ALDS: Smax doubles, alpha_t] [YLDS: 2 * P floats, two output rows].
-// POST: alpha_all / out are read and written; otherwise it ends with the total.
-template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST, class MakeOut>
-__device__ __forceinline__ void fb_utterance(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight,
+// POST: alpha_all / out are read and written; otherwise it ends with the total.  step: FbPdfStep or FbLabelStep.
+template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST, class Step, class MakeOut>
+__device__ __forceinline__ void fb_utterance(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight, Step step,
                                              MakeOut make_out, double *alpha_all, double *vecs, double *results, int Smax, int P) {
   static_assert(LDS || !(YLDS || ALDS), "the rows behind the vectors need the LDS form");
   static_assert(POST || !ALDS, "alpha_t is staged for the posteriors only");
@@ -268,8 +331,8 @@ __device__ __forceinline__ void fb_utterance(AlignDev g, const AlignUtt *utts, M
         if (tid + c * NT < S) alds[tid + c * NT] = areg[c];
     }
     __syncthreads();  // alpha_t is in place and the row's zeros (dense) are stored
-    fb_post_step<NT>(g.by_pdf, gr.by_pdf, ALDS ? (const double *)alds : at, cur, yrow, scale, logprob,
-                     [&](int pdf, int column, double sum) { out.emit(pdf, column, (float)(w * sum)); });
+    step.template run<NT>(g, gr, u.graph, ALDS ? (const double *)alds : at, cur, yrow, scale, logprob,
+                          [&](int row, int column, double sum) { out.emit(row, column, (float)(w * sum)); });
     __syncthreads();
     double *sw = cur;
     cur = nxt;
@@ -282,8 +345,8 @@ template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST>
 __global__ __launch_bounds__(NT) void align_fb_kernel(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight,
                                                       MatView post, double *alpha_all, double *vecs, double *results, int Smax, int P) {
   fb_utterance<NT, LDS, YLDS, ALDS, POST>(
-      g, utts, y, row_stride, acoustic_scale, weight, [&](const AlignUtt &u) { return FbDenseOut<NT>{post, u.row_begin, row_stride, P, nullptr}; }, alpha_all,
-      vecs, results, Smax, P);
+      g, utts, y, row_stride, acoustic_scale, weight, FbPdfStep{},
+      [&](const AlignUtt &u) { return FbDenseOut<NT>{post, u.row_begin, row_stride, P, nullptr}; }, alpha_all, vecs, results, Smax, P);
 }
 
 // grid = utterances.  The compact form (always with posteriors): utterance u's block starts at compact + u.out_begin and has
@@ -293,7 +356,18 @@ __global__ __launch_bounds__(NT) void align_fb_compact_kernel(AlignDev g, const 
                                                               float weight, float *compact, const int *graph_cols, double *alpha_all, double *vecs,
                                                               double *results, int Smax, int P) {
   fb_utterance<NT, LDS, YLDS, ALDS, true>(
-      g, utts, y, row_stride, acoustic_scale, weight,
+      g, utts, y, row_stride, acoustic_scale, weight, FbPdfStep{},
+      [&](const AlignUtt &u) { return FbCompactOut<NT>{compact + u.out_begin, graph_cols[u.graph], nullptr}; }, alpha_all, vecs, results, Smax, P);
+}
+
+// grid = utterances.  The label form: the compact form with step 2 on the arcs by label; graph_cols[u.graph] is the number of distinct
+// labels of the utterance's graph, label_ranges[u.graph] its share of by_label.
+template <int NT, bool LDS, bool YLDS, bool ALDS>
+__global__ __launch_bounds__(NT) void align_fb_label_kernel(AlignDev g, AlignTable by_label, const AlignRange *label_ranges, const AlignUtt *utts, MatView y,
+                                                            int row_stride, float acoustic_scale, float weight, float *compact, const int *graph_cols,
+                                                            double *alpha_all, double *vecs, double *results, int Smax, int P) {
+  fb_utterance<NT, LDS, YLDS, ALDS, true>(
+      g, utts, y, row_stride, acoustic_scale, weight, FbLabelStep{by_label, label_ranges},
       [&](const AlignUtt &u) { return FbCompactOut<NT>{compact + u.out_begin, graph_cols[u.graph], nullptr}; }, alpha_all, vecs, results, Smax, P);
 }
 

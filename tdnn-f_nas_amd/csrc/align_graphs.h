@@ -12,8 +12,8 @@ namespace tdnnf {
 
 struct AlignTable {   // one grouping of a set's arcs (align_tables.h), on the device
   const int4 *slots;  // (row LOCAL to its graph or -1 for an empty lane, length, position of the row's first arc: its j-th is 64 j further,
-                      // by_pdf: the row's column, else 0)
-  const int4 *heavy;  // (LOCAL row, first arc, one past the last arc, by_pdf: the row's column, else 0)
+                      // by_pdf and by_label: the row's column, else 0)
+  const int4 *heavy;  // (LOCAL row, first arc, one past the last arc, by_pdf and by_label: the row's column, else 0)
   const int4 *arcs;   // a row's arcs in the caller's order
 };
 
@@ -46,9 +46,25 @@ struct tdnnf_align_graphs {
   std::vector<int> col_begin, col_pdfs;                   // host: graph k's column list (align_tables.h) is col_pdfs[col_begin[k] .. col_begin[k + 1])
   const int *num_cols_dev;                                // device, owned: [G] the lengths of the column lists (the compact posteriors' row widths)
   const int *col_pdfs_dev;                                // device, owned: col_pdfs (the sparse posteriors' selection names a kept column's pdf)
+  // labelled graphs (tdnnf_align_graphs_create_labelled) only; L = 0 and null pointers otherwise
+  int L;                                     // num_labels
+  std::vector<int> lcol_begin, col_labels;   // host: graph k's label column list (align_tables.h) is col_labels[lcol_begin[k] .. lcol_begin[k + 1])
+  tdnnf::AlignTable by_label;                // device, owned: rows: labels; arcs (source state, destination state, log-prob bits, pdf).  Beside
+                                             // AlignDev, which every kernel takes by value: the kernels without labels are what they were
+  const tdnnf::AlignRange *label_range_dev;  // device, owned: [G] the graphs' shares of by_label (beside AlignGraphDev, which does not grow)
+  const int *num_lcols_dev;                  // device, owned: [G] the lengths of the label column lists
+  const int *col_labels_dev;                 // device, owned: col_labels
+  const int *arc_label_dev;                  // device, owned: [arcs] the caller's labels in the caller's arc order (the labelled best path)
 };
 
 namespace tdnnf {
+
+// The refusal every label entry gives a handle that tdnnf_align_graphs_create made.  who: the prefix of the message, the call's name.
+inline int align_need_labels(const tdnnf_align_graphs *g, const char *who) {
+  TDNNF_REQUIRE(g, "%snull graphs", who);
+  TDNNF_REQUIRE(g->L > 0, "%sthe graphs carry no labels (tdnnf_align_graphs_create_labelled makes the handle this call takes)", who);
+  return TDNNF_OK;
+}
 
 inline size_t align_round_up(size_t n, size_t m) { return (n + m - 1) / m * m; }
 

@@ -29,6 +29,8 @@
 //  * back-pointers: bp[t * S + d] = position (in the arc table) of the arc chosen for state d at frame t + 1, or -1.
 //  * trace-back: one thread walks the back-pointers from the best final state and leaves the chosen arc of frame t in bp[t * S];
 //    behind a barrier the workgroup writes pdf-ids (and states) coalesced.
+//  * labels (align_path_labels_kernel, behind the best path on its stream): bp[t * S] still holds the chosen arc of frame t, whose 4th
+//    int is the caller's arc index; a thread per (utterance, frame) writes that index and the caller's label of the arc.
 #pragma once
 #include "align_graphs.h"
 
@@ -222,6 +224,28 @@ __global__ __launch_bounds__(NT) void align_best_path_kernel(AlignDev g, const A
     if (states) states[t] = arc.x;
   }
   if (states && tid == 0) states[T] = bs;
+}
+
+// grid = (frames of the longest utterance / NT, utterances), behind align_best_path_kernel on the same stream: what the trace-back left in
+// bp_all (the chosen arc of frame t at bp[t * S]) becomes arc_out[t], the caller's arc index (global over the graphs), and label_out[t],
+// arc_label of that arc; -1 both for an utterance the best path gave ok = 0.  arc_out may be null.  Consecutive threads write consecutive
+// elements; every element of the utterance's share of both outputs is written.
+template <int NT>
+__global__ __launch_bounds__(NT) void align_path_labels_kernel(AlignDev g, const AlignUtt *utts, const int *bp_all, const double *results,
+                                                               const int *arc_label, int *label_out, int *arc_out) {
+  const AlignUtt u = utts[blockIdx.y];
+  const int t = blockIdx.x * NT + threadIdx.x;
+  if (t >= u.frames) return;
+  int arc = -1, label = -1;
+  if (results[2 * (size_t)blockIdx.y + 1] != 0.0) {
+    const int a = bp_all[u.frame_begin + (long long)t * g.graphs[u.graph].num_states];
+    if (a >= 0) {  // (guarded as the trace-back guards it)
+      arc = g.by_dst.arcs[a].w;
+      label = arc_label[arc];
+    }
+  }
+  label_out[u.out_begin + t] = label;
+  if (arc_out) arc_out[u.out_begin + t] = arc;
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // align_sparse.hip -- the sparse posteriors (include/tdnnf_hip.h, "sparse posteriors"): per frame the at most K (pdf, value) pairs above a
-// floor.  Runs the compact call (align_fb.hip) into a block of the workspace, then the selection pass over it (align_sparse_kernels.h) and
+// floor -- or (label, value) pairs: the pdf and the label form share one plan and one body.  Runs the compact call (align_fb.hip) into a block of the workspace, then the selection pass over it (align_sparse_kernels.h) and
 // the fold of its per-workgroup counts into the results.
 #include <limits.h>
 #include <math.h>
@@ -28,12 +28,18 @@ int sparse_refused(const char *who) {
   return TDNNF_EINVAL;
 }
 
-int sparse_plan(const tdnnf_align_graphs *g, const char *who, int num_utts, const int *utt_graph, const int *utt_frames, int max_per_frame, SparsePlan *p) {
+// labels: the block is the label compact call's and the columns are the graphs' label column lists
+int sparse_plan(const tdnnf_align_graphs *g, bool labels, const char *who, int num_utts, const int *utt_graph, const int *utt_frames, int max_per_frame,
+                SparsePlan *p) {
+  int rc;
+  if (labels && (rc = align_need_labels(g, who))) return rc;
   TDNNF_REQUIRE(max_per_frame >= 1 && max_per_frame <= kAlignSparseMaxK, "%smax_per_frame %d outside [1, %d]", who, max_per_frame, kAlignSparseMaxK);
   p->fb_bytes = tdnnf_align_posteriors_workspace_bytes(g, num_utts, utt_graph, utt_frames, 1);
   if (p->fb_bytes == 0) return sparse_refused(who);
   std::vector<long long> begin((size_t)num_utts + 1);
-  if (tdnnf_align_posteriors_compact_layout(g, num_utts, utt_graph, utt_frames, &p->elems, begin.data()) != TDNNF_OK) return sparse_refused(who);
+  const auto layout = labels ? tdnnf_align_label_posteriors_compact_layout : tdnnf_align_posteriors_compact_layout;
+  if (layout(g, num_utts, utt_graph, utt_frames, &p->elems, begin.data()) != TDNNF_OK) return sparse_refused(who);
+  const std::vector<int> &cb = labels ? g->lcol_begin : g->col_begin;
   p->utts.resize(num_utts);
   p->frames = p->parts = 0;
   p->max_frames = 0;
@@ -46,8 +52,8 @@ int sparse_plan(const tdnnf_align_graphs *g, const char *who, int num_utts, cons
     d.block_begin = begin[u];
     d.frames = utt_frames[u];
     d.frame_begin = (int)p->frames;  // (below 2^31: the compact call's plan has checked the sum)
-    d.D = g->col_begin[gi + 1] - g->col_begin[gi];
-    d.col_begin = g->col_begin[gi];
+    d.D = cb[gi + 1] - cb[gi];
+    d.col_begin = cb[gi];
     d.part_begin = (int)p->parts;
     d.pad = 0;
     p->frames += utt_frames[u];
@@ -62,6 +68,45 @@ int sparse_plan(const tdnnf_align_graphs *g, const char *who, int num_utts, cons
   return TDNNF_OK;
 }
 
+// tdnnf_align_posteriors_sparse and tdnnf_align_label_posteriors_sparse.  who: the prefix of the messages, the call's name.  The selection
+// kernels take a block, a column-list array and per-utterance (D, col_begin): they do not know which of the two they select from.
+int sparse_call(const tdnnf_align_graphs *g, bool labels, const char *who, int num_utts, const int *utt_graph, const int *utt_frames,
+                const int *utt_row_begin, int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float min_post,
+                int max_per_frame, int *pdf_out_dev, float *post_out_dev, int *count_out_dev, double *results_dev, void *workspace_dev,
+                size_t workspace_bytes, tdnnf_stream stream) {
+  TDNNF_REQUIRE(g && utt_row_begin && mat_ok(nnet_output) && results_dev && workspace_dev, "%sbad arguments", who);
+  TDNNF_REQUIRE(isfinite(min_post) && min_post >= 0.f, "%smin_post %g must be finite and not negative", who, (double)min_post);
+  SparsePlan p;
+  int rc = sparse_plan(g, labels, who, num_utts, utt_graph, utt_frames, max_per_frame, &p);
+  if (rc) return rc;
+  TDNNF_REQUIRE(p.frames == 0 || (pdf_out_dev && post_out_dev && count_out_dev), "%snull pdf_out_dev, post_out_dev or count_out_dev for %lld frames", who,
+                p.frames);
+  TDNNF_REQUIRE(workspace_bytes >= p.bytes, "%sworkspace of %zu bytes, %zu needed (tdnnf_align_%sposteriors_sparse_workspace_bytes)", who, workspace_bytes,
+                p.bytes, labels ? "label_" : "");
+  char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace_dev) + 15) & ~(uintptr_t)15);
+  double *fb_results = reinterpret_cast<double *>(base + p.results_at);
+  AlignSparseUtt *utts = reinterpret_cast<AlignSparseUtt *>(base + p.utts_at);
+  int2 *parts = reinterpret_cast<int2 *>(base + p.parts_at);
+  float *block = reinterpret_cast<float *>(base + p.block_at);
+  // the recursions: everything else the compact call refuses it refuses here, before anything is launched
+  const auto compact = labels ? tdnnf_align_label_posteriors_compact : tdnnf_align_posteriors_compact;
+  rc = compact(g, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale, weight, block, (size_t)p.elems, fb_results, base,
+               p.fb_bytes, stream);
+  if (rc) return rc == TDNNF_EINVAL ? sparse_refused(who) : rc;
+  hipStream_t s = (hipStream_t)stream;
+  // (pageable source: the runtime has taken the table by the time the call returns)
+  TDNNF_HIP(hipMemcpyAsync(utts, p.utts.data(), sizeof(AlignSparseUtt) * p.utts.size(), hipMemcpyHostToDevice, s));
+  const int groups = (p.max_frames + kAlignSparseGroup - 1) / kAlignSparseGroup;
+  for (int u0 = 0; groups > 0 && u0 < num_utts; u0 += 65535) {  // (a grid's second dimension ends at 65 535)
+    hipLaunchKernelGGL(align_sparse_select_kernel, dim3(groups, std::min(num_utts - u0, 65535)), dim3(kAlignSparseWaves * 64), 0, s, utts + u0, block,
+                       labels ? g->col_labels_dev : g->col_pdfs_dev, min_post, max_per_frame, pdf_out_dev, post_out_dev, count_out_dev, parts);
+    TDNNF_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(align_sparse_results_kernel, dim3(num_utts), dim3(64), 0, s, utts, fb_results, parts, results_dev);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+
 }  // namespace
 }  // namespace tdnnf
 
@@ -72,7 +117,7 @@ extern "C" {
 size_t tdnnf_align_posteriors_sparse_workspace_bytes(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames,
                                                      int max_per_frame) {
   SparsePlan p;
-  if (sparse_plan(g, "align_posteriors_sparse: ", num_utts, utt_graph, utt_frames, max_per_frame, &p) != TDNNF_OK) return 0;
+  if (sparse_plan(g, false, "align_posteriors_sparse: ", num_utts, utt_graph, utt_frames, max_per_frame, &p) != TDNNF_OK) return 0;
   return p.bytes;
 }
 
@@ -80,37 +125,23 @@ int tdnnf_align_posteriors_sparse(const tdnnf_align_graphs *g, int num_utts, con
                                   int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float min_post, int max_per_frame,
                                   int *pdf_out_dev, float *post_out_dev, int *count_out_dev, double *results_dev, void *workspace_dev,
                                   size_t workspace_bytes, tdnnf_stream stream) {
-  const char *who = "align_posteriors_sparse: ";
-  TDNNF_REQUIRE(g && utt_row_begin && mat_ok(nnet_output) && results_dev && workspace_dev, "%sbad arguments", who);
-  TDNNF_REQUIRE(isfinite(min_post) && min_post >= 0.f, "%smin_post %g must be finite and not negative", who, (double)min_post);
+  return sparse_call(g, false, "align_posteriors_sparse: ", num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale, weight,
+                     min_post, max_per_frame, pdf_out_dev, post_out_dev, count_out_dev, results_dev, workspace_dev, workspace_bytes, stream);
+}
+
+size_t tdnnf_align_label_posteriors_sparse_workspace_bytes(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames,
+                                                           int max_per_frame) {
   SparsePlan p;
-  int rc = sparse_plan(g, who, num_utts, utt_graph, utt_frames, max_per_frame, &p);
-  if (rc) return rc;
-  TDNNF_REQUIRE(p.frames == 0 || (pdf_out_dev && post_out_dev && count_out_dev), "%snull pdf_out_dev, post_out_dev or count_out_dev for %lld frames", who,
-                p.frames);
-  TDNNF_REQUIRE(workspace_bytes >= p.bytes, "%sworkspace of %zu bytes, %zu needed (tdnnf_align_posteriors_sparse_workspace_bytes)", who, workspace_bytes,
-                p.bytes);
-  char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace_dev) + 15) & ~(uintptr_t)15);
-  double *fb_results = reinterpret_cast<double *>(base + p.results_at);
-  AlignSparseUtt *utts = reinterpret_cast<AlignSparseUtt *>(base + p.utts_at);
-  int2 *parts = reinterpret_cast<int2 *>(base + p.parts_at);
-  float *block = reinterpret_cast<float *>(base + p.block_at);
-  // the recursions: everything else the compact call refuses it refuses here, before anything is launched
-  rc = tdnnf_align_posteriors_compact(g, num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale, weight, block,
-                                      (size_t)p.elems, fb_results, base, p.fb_bytes, stream);
-  if (rc) return rc == TDNNF_EINVAL ? sparse_refused(who) : rc;
-  hipStream_t s = (hipStream_t)stream;
-  // (pageable source: the runtime has taken the table by the time the call returns)
-  TDNNF_HIP(hipMemcpyAsync(utts, p.utts.data(), sizeof(AlignSparseUtt) * p.utts.size(), hipMemcpyHostToDevice, s));
-  const int groups = (p.max_frames + kAlignSparseGroup - 1) / kAlignSparseGroup;
-  for (int u0 = 0; groups > 0 && u0 < num_utts; u0 += 65535) {  // (a grid's second dimension ends at 65 535)
-    hipLaunchKernelGGL(align_sparse_select_kernel, dim3(groups, std::min(num_utts - u0, 65535)), dim3(kAlignSparseWaves * 64), 0, s, utts + u0, block,
-                       g->col_pdfs_dev, min_post, max_per_frame, pdf_out_dev, post_out_dev, count_out_dev, parts);
-    TDNNF_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(align_sparse_results_kernel, dim3(num_utts), dim3(64), 0, s, utts, fb_results, parts, results_dev);
-  TDNNF_LAUNCH_CHECK();
-  return TDNNF_OK;
+  if (sparse_plan(g, true, "align_label_posteriors_sparse: ", num_utts, utt_graph, utt_frames, max_per_frame, &p) != TDNNF_OK) return 0;
+  return p.bytes;
+}
+
+int tdnnf_align_label_posteriors_sparse(const tdnnf_align_graphs *g, int num_utts, const int *utt_graph, const int *utt_frames,
+                                        const int *utt_row_begin, int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight,
+                                        float min_post, int max_per_frame, int *label_out_dev, float *post_out_dev, int *count_out_dev,
+                                        double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream stream) {
+  return sparse_call(g, true, "align_label_posteriors_sparse: ", num_utts, utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale,
+                     weight, min_post, max_per_frame, label_out_dev, post_out_dev, count_out_dev, results_dev, workspace_dev, workspace_bytes, stream);
 }
 
 }  // extern "C"

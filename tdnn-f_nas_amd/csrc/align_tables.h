@@ -1,6 +1,6 @@
 // align_tables.h -- host side of a tdnnf_align_graphs, free of HIP (g++ compiles it: tests/test_align_tables_cpu.py, as host_linalg.h): the
-// three arc tables of a set of pdf-labelled graphs and the launch form of the recursions that walk them.  align_graphs.hip uploads the
-// tables; align.hip, align_fb.hip and chain_num_e2e.hip ask align_form_plan; the kernels (align_kernels.h, align_fb_kernels.h,
+// three arc tables of a set of pdf-labelled graphs (four when the caller labels the arcs) and the launch form of the recursions that walk them.
+// align_graphs.hip uploads the tables; align.hip, align_fb.hip and chain_num_e2e.hip ask align_form_plan; the kernels (align_kernels.h, align_fb_kernels.h,
 // num_e2e_kernels.h) read the tables through AlignDev (align_graphs.h).
 //
 // A table groups a set's arcs into ROWS, 16 bytes an arc: one load per arc.  The rows of at most kAlignHeavy arcs (light rows) are sorted by
@@ -14,10 +14,13 @@
 //   by_dst: rows are states (every state has one, empty or not); arc = (source state, pdf, log-prob bits, caller's arc index)
 //   by_src: rows are states (likewise);                           arc = (destination state, pdf, log-prob bits, caller's arc index)
 //   by_pdf: rows are the pdfs that an arc of the graph names;     arc = (source state, destination state, log-prob bits, caller's arc index)
+//   by_label (labelled graphs only): rows are the labels that an arc of the graph carries, row r the r-th of them ascending; arc = (source state, destination state, log-prob bits, pdf)
+//             -- the pdf where by_pdf has the caller's arc index, because a label's arcs name different pdfs.
 // States are LOCAL to their graph everywhere.
 // The pdfs that a graph's arcs name, ascending, are its COLUMN LIST (AlignHostTables::col_pdfs): a by_pdf row carries the rank of its pdf in
 // that list -- its column -- in the 4th int of its slot or heavy-row descriptor, where the other two tables have 0.  The compact posteriors
-// (align_fb_kernels.h) are addressed by it; the lists themselves stay on the host.
+// (align_fb_kernels.h) are addressed by it; the lists themselves stay on the host.  The labels of a graph's arcs, ascending, are its LABEL
+// COLUMN LIST (col_labels) in the same way: a by_label row carries the rank of its label, and the label posteriors are addressed by it.
 #pragma once
 #include <stdio.h>
 #include <string.h>
@@ -92,15 +95,24 @@ struct AlignHostTables {
   std::vector<int> max_in_degree;  // per graph: the longest row by destination
   std::vector<int> col_begin;      // [graphs + 1]: graph k's column list is col_pdfs[col_begin[k] .. col_begin[k + 1])
   std::vector<int> col_pdfs;       // the distinct pdfs of a graph's arcs, ascending
+  // labelled graphs only (align_build_tables with arc_label); AlignGraphDev does not grow, so the by_label ranges lie beside it
+  AlignHostTable by_label;
+  std::vector<AlignRange> label_range;  // [graphs]: graph k's share of by_label
+  std::vector<int> lcol_begin;          // [graphs + 1]: graph k's label column list is col_labels[lcol_begin[k] .. lcol_begin[k + 1])
+  std::vector<int> col_labels;          // the distinct labels of a graph's arcs, ascending
 };
 
 // The three tables of a set of graphs whose arrays tdnnf_align_graphs_create has validated (global state numbers, as the caller gives them),
 // and the graphs' column lists.  columns: the by_pdf rows carry their columns, as tdnnf_align_graphs_create uploads them; without, the 4th
 // int of every slot and descriptor is 0 (the tables as they were before there were columns, which tests/test_align_tables_cpu.py decodes).
+// arc_label (may be null: no fourth table), one int per arc: the by_label table, whose rows always carry their columns, and
+// the label column lists; the other three tables are what they are without labels.
 inline void align_build_tables(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
-                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, AlignHostTables *t, bool columns = false) {
+                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, AlignHostTables *t, bool columns = false,
+                               const int *arc_label = nullptr) {
   t->graphs.resize(num_graphs);
   t->col_begin.assign(1, 0);
+  t->lcol_begin.assign(1, 0);
   std::vector<int> col(num_pdfs);
   for (int k = 0; k < num_graphs; k++) {
     const int s0 = graph_state_begin[k], S = graph_state_begin[k + 1] - s0;
@@ -126,6 +138,22 @@ inline void align_build_tables(int num_graphs, int num_pdfs, const int *graph_st
     g.by_dst = align_add_graph(t->by_dst, in, false, nullptr, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_pdf[a], bits(a), a}; });
     g.by_src = align_add_graph(t->by_src, out, false, nullptr, [&](int a) { return AlignInt4{arc_dst[a] - s0, arc_pdf[a], bits(a), a}; });
     g.by_pdf = align_add_graph(t->by_pdf, of_pdf, true, columns ? col.data() : nullptr, [&](int a) { return AlignInt4{arc_src[a] - s0, arc_dst[a] - s0, bits(a), a}; });
+    if (arc_label) {
+      // (rows by rank, not by label: with the arc's own index as its label num_labels is the arcs of ALL graphs, and a row per label
+      // per graph would be quadratic in the graphs)
+      std::vector<int> list(arc_label + graph_arc_begin[k], arc_label + graph_arc_begin[k + 1]);
+      std::sort(list.begin(), list.end());
+      list.erase(std::unique(list.begin(), list.end()), list.end());
+      std::vector<std::vector<int>> of_label(list.size());
+      std::vector<int> rank(list.size());
+      for (size_t r = 0; r < list.size(); r++) rank[r] = (int)r;
+      for (int a = graph_arc_begin[k]; a < graph_arc_begin[k + 1]; a++)
+        of_label[std::lower_bound(list.begin(), list.end(), arc_label[a]) - list.begin()].push_back(a);
+      t->col_labels.insert(t->col_labels.end(), list.begin(), list.end());
+      t->lcol_begin.push_back((int)t->col_labels.size());
+      t->label_range.push_back(
+          align_add_graph(t->by_label, of_label, true, rank.data(), [&](int a) { return AlignInt4{arc_src[a] - s0, arc_dst[a] - s0, bits(a), arc_pdf[a]}; }));
+    }
     size_t deg = 0;
     for (const std::vector<int> &row : in) deg = std::max(deg, row.size());
     t->max_in_degree.push_back((int)deg);

@@ -268,9 +268,11 @@ class Supervision:
 class AlignGraphs:
     """Device-resident set of pdf-labelled graphs for best-path alignment and forward-backward (tdnnf_align_graphs).  `graphs`: one graph or a list of graphs,
     each a dict {S, P, src, dst, pdf, logprob, init, final} with states numbered from 0 (synth.make_alignment_graph,
-    synth.alignment_graph_from_den); they are stacked with the state numbering of tdnnf_align_graphs_create."""
+    synth.alignment_graph_from_den); they are stacked with the state numbering of tdnnf_align_graphs_create.  A graph dict may carry
+    "label", one int per arc in [0, num_labels) -- all graphs or none: with labels the handle is tdnnf_align_graphs_create_labelled's and
+    serves the label methods (labels, best_path_labels, label_posteriors_*) as well.  num_labels: default the largest label + 1."""
 
-    def __init__(self, graphs, num_pdfs=None):
+    def __init__(self, graphs, num_pdfs=None, num_labels=None):
         import numpy as np
         lib = load()
         graphs = [graphs] if isinstance(graphs, dict) else list(graphs)
@@ -282,7 +284,21 @@ class AlignGraphs:
         cat = lambda key, off=None: np.concatenate([np.asarray(g[key]) + (0 if off is None else off[i]) for i, g in enumerate(graphs)])
         self._keep = [iarr(sb), iarr(ab), iarr(cat("src", sb)), iarr(cat("dst", sb)), iarr(cat("pdf")), farr(cat("logprob")),
                       farr(cat("init")), farr(cat("final"))]
-        check(lib.tdnnf_align_graphs_create(self.G, self.P, *[k[1] for k in self._keep], C.byref(self.h)))
+        with_label = ["label" in g for g in graphs]
+        if any(with_label) != all(with_label):
+            raise HipAbiError("AlignGraphs: every graph carries a \"label\" array, or none does")
+        self.labelled = all(with_label)
+        self.arc_begin = ab.astype(np.int64)
+        if self.labelled:
+            lab = iarr(cat("label"))
+            self._keep.append(lab)
+            self.L = int(num_labels if num_labels is not None else (int(lab[0].max()) + 1 if len(lab[0]) else 1))
+            check(lib.tdnnf_align_graphs_create_labelled(self.G, self.P, *[k[1] for k in self._keep], self.L, C.byref(self.h)))
+        else:
+            if num_labels is not None:
+                raise HipAbiError("AlignGraphs: num_labels without a \"label\" array in the graphs")
+            self.L = 0
+            check(lib.tdnnf_align_graphs_create(self.G, self.P, *[k[1] for k in self._keep], C.byref(self.h)))
         self.num_states = [int(g["S"]) for g in graphs]
 
     @classmethod
@@ -305,6 +321,17 @@ class AlignGraphs:
     def best_path(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, states=False):
         """tdnnf_align_best_path on the current stream.  Returns (pdf_out int32 [sum frames], state_out int32 [sum frames + utterances]
         or None, results float64 [utterances, 2]) as CUDA tensors; nothing is synchronised."""
+        return self._best_path(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, False)[:3]
+
+    def best_path_labels(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, states=False):
+        """tdnnf_align_best_path_labels on the current stream.  Returns (pdf_out, state_out or None, results, label_out int32 [sum frames],
+        arc_out int32 [sum frames]) as CUDA tensors: best_path's three, the label of the arc taken at every frame and that arc's index
+        LOCAL to the utterance's graph dict (the C call's global index minus the graph's first arc); -1 both where ok is 0.  Nothing is
+        synchronised."""
+        return self._best_path(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, True)
+
+    def _best_path(self, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, labels):
+        import numpy as np
         import torch
         n = len(utt_frames)
         fr, frp = iarr(utt_frames)
@@ -318,9 +345,20 @@ class AlignGraphs:
         pdf_out = torch.empty(max(total, 1), dtype=torch.int32, device="cuda")
         state_out = torch.empty(total + n, dtype=torch.int32, device="cuda") if states else None
         results = torch.empty((n, 2), dtype=torch.float64, device="cuda")
-        check(load().tdnnf_align_best_path(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), ptr(pdf_out),
-                                           ptr(state_out), ptr(results), ptr(ws), nbytes, stream()))
-        return pdf_out[:total], state_out, results
+        if not labels:
+            check(load().tdnnf_align_best_path(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), ptr(pdf_out),
+                                               ptr(state_out), ptr(results), ptr(ws), nbytes, stream()))
+            return pdf_out[:total], state_out, results
+        label_out = torch.empty(max(total, 1), dtype=torch.int32, device="cuda")
+        arc_out = torch.empty(max(total, 1), dtype=torch.int32, device="cuda")
+        check(load().tdnnf_align_best_path_labels(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), ptr(pdf_out),
+                                                  ptr(state_out), ptr(label_out), ptr(arc_out), ptr(results), ptr(ws), nbytes, stream()))
+        # the arcs local to each utterance's graph dict: minus the graph's first arc, where there is an arc
+        first = np.asarray([self.arc_begin[int(ug[0][u]) if ug[0] is not None else (0 if self.G == 1 else u)] for u in range(n)], dtype=np.int64)
+        shift = torch.from_numpy(np.repeat(first, fr).astype(np.int32)).to("cuda")
+        arc_out = arc_out[:total]
+        arc_out = torch.where(arc_out >= 0, arc_out - shift, arc_out)
+        return pdf_out[:total], state_out, results, label_out[:total], arc_out
 
     def posteriors_workspace_bytes(self, utt_graph, utt_frames, want_posteriors=True):
         ug = iarr(utt_graph)[1] if utt_graph is not None else None
@@ -358,14 +396,30 @@ class AlignGraphs:
         check(load().tdnnf_align_graphs_pdfs(self.h, int(graph), None, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def labels(self, graph=0):
+        """The label column list of one graph (tdnnf_align_graphs_labels): the distinct labels its arcs carry, ascending, numpy int32."""
+        import numpy as np
+        n = C.c_int()
+        check(load().tdnnf_align_graphs_labels(self.h, int(graph), C.byref(n), None))
+        out = np.zeros(n.value, np.int32)
+        check(load().tdnnf_align_graphs_labels(self.h, int(graph), None, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def posteriors_compact_layout(self, utt_frames, utt_graph=None):
         """tdnnf_align_posteriors_compact_layout: utt_begin, numpy int64 [utterances + 1] -- utterance u owns floats
         [utt_begin[u], utt_begin[u + 1]) of the compact output, utt_frames[u] rows of len(pdfs(its graph)) floats."""
+        return self._compact_layout("tdnnf_align_posteriors_compact_layout", utt_frames, utt_graph)
+
+    def label_posteriors_compact_layout(self, utt_frames, utt_graph=None):
+        """tdnnf_align_label_posteriors_compact_layout: as posteriors_compact_layout with rows of len(labels(its graph)) floats."""
+        return self._compact_layout("tdnnf_align_label_posteriors_compact_layout", utt_frames, utt_graph)
+
+    def _compact_layout(self, entry, utt_frames, utt_graph):
         import numpy as np
         n = len(utt_frames)
         ug = iarr(utt_graph) if utt_graph is not None else (None, None)
         begin = np.zeros(n + 1, np.int64)
-        check(load().tdnnf_align_posteriors_compact_layout(self.h, n, ug[1], iarr(utt_frames)[1], None, begin.ctypes.data_as(C.c_void_p)))
+        check(getattr(load(), entry)(self.h, n, ug[1], iarr(utt_frames)[1], None, begin.ctypes.data_as(C.c_void_p)))
         return begin
 
     def posteriors_compact(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0):
@@ -373,12 +427,22 @@ class AlignGraphs:
         utt_begin[-1] floats, of which utterance u owns [utt_begin[u], utt_begin[u + 1]) -- utt_frames[u] rows of one float per pdf of
         pdfs(its graph), = weight x the posterior; utt_begin numpy int64; results float64 [utterances, 2] (logprob, ok) CUDA tensor.
         Nothing is synchronised."""
+        return self._compact("tdnnf_align_posteriors_compact", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight)
+
+    def label_posteriors_compact(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+        """tdnnf_align_label_posteriors_compact on the current stream: posteriors_compact per label -- utterance u owns utt_frames[u] rows of
+        one float per label of labels(its graph), = weight x the summed posterior of the arcs that carry the label.  Returns (values,
+        utt_begin, results) as posteriors_compact does.  Nothing is synchronised."""
+        return self._compact("tdnnf_align_label_posteriors_compact", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale,
+                             weight)
+
+    def _compact(self, entry, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight):
         import torch
         n = len(utt_frames)
         fr, frp = iarr(utt_frames)
         rb, rbp = iarr(utt_row_begin)
         ug = iarr(utt_graph) if utt_graph is not None else (None, None)
-        begin = self.posteriors_compact_layout(fr, utt_graph)
+        begin = self._compact_layout(entry + "_layout", fr, utt_graph)
         nbytes = int(load().tdnnf_align_posteriors_workspace_bytes(self.h, n, ug[1], frp, 1))
         if nbytes == 0:
             raise HipAbiError(f"tdnnf_align_posteriors_workspace_bytes: {load().tdnnf_last_error().decode()}")
@@ -386,8 +450,8 @@ class AlignGraphs:
         elems = int(begin[-1])
         values = torch.empty(elems, dtype=torch.float32, device="cuda")
         results = torch.empty((n, 2), dtype=torch.float64, device="cuda")
-        check(load().tdnnf_align_posteriors_compact(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale),
-                                                    float(weight), ptr(values) if elems else None, elems, ptr(results), ptr(ws), nbytes, stream()))
+        check(getattr(load(), entry)(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), float(weight),
+                                     ptr(values) if elems else None, elems, ptr(results), ptr(ws), nbytes, stream()))
         return values, begin, results
 
     def posteriors_sparse(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01,
@@ -397,24 +461,36 @@ class AlignGraphs:
         int32 [F], results float64 [utterances, 4]) as CUDA tensors, F = sum(utt_frames), utterance after utterance: the first count[f]
         slots of frame f hold its pairs, the others (-1, 0); results = (logprob, ok, frames with more than K candidates, the greatest
         number of candidates in a frame).  Nothing is synchronised."""
+        return self._sparse("tdnnf_align_posteriors_sparse", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight,
+                            min_post, max_per_frame)
+
+    def label_posteriors_sparse(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0,
+                                min_post=0.01, max_per_frame=16):
+        """tdnnf_align_label_posteriors_sparse on the current stream: posteriors_sparse over label_posteriors_compact's values and the
+        graphs' label lists.  Returns (label int32 [F, K], post float32 [F, K], count int32 [F], results float64 [utterances, 4]) as
+        posteriors_sparse does.  Nothing is synchronised."""
+        return self._sparse("tdnnf_align_label_posteriors_sparse", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale,
+                            weight, min_post, max_per_frame)
+
+    def _sparse(self, entry, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, min_post, max_per_frame):
         import torch
         n = len(utt_frames)
         fr, frp = iarr(utt_frames)
         rb, rbp = iarr(utt_row_begin)
         ug = iarr(utt_graph) if utt_graph is not None else (None, None)
         K = int(max_per_frame)
-        nbytes = int(load().tdnnf_align_posteriors_sparse_workspace_bytes(self.h, n, ug[1], frp, K))
+        nbytes = int(getattr(load(), entry + "_workspace_bytes")(self.h, n, ug[1], frp, K))
         if nbytes == 0:
-            raise HipAbiError(f"tdnnf_align_posteriors_sparse_workspace_bytes: {load().tdnnf_last_error().decode()}")
+            raise HipAbiError(f"{entry}_workspace_bytes: {load().tdnnf_last_error().decode()}")
         ws = workspace(nbytes)
         F = int(fr.sum())
         pdf = torch.empty((F, K), dtype=torch.int32, device="cuda")
         post = torch.empty((F, K), dtype=torch.float32, device="cuda")
         count = torch.empty(F, dtype=torch.int32, device="cuda")
         results = torch.empty((n, 4), dtype=torch.float64, device="cuda")
-        check(load().tdnnf_align_posteriors_sparse(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), float(weight),
-                                                   float(min_post), K, ptr(pdf) if F else None, ptr(post) if F else None, ptr(count) if F else None,
-                                                   ptr(results), ptr(ws), nbytes, stream()))
+        check(getattr(load(), entry)(self.h, n, ug[1], frp, rbp, int(row_stride), pmat(nnet_output), float(acoustic_scale), float(weight),
+                                     float(min_post), K, ptr(pdf) if F else None, ptr(post) if F else None, ptr(count) if F else None, ptr(results),
+                                     ptr(ws), nbytes, stream()))
         return pdf, post, count, results
 
     def logprob(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0):

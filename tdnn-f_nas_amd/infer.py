@@ -129,6 +129,24 @@ class AcousticModel:
         out, outs = self._compute_stacked(utterances, ivector_period)
         return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame) if outs else []
 
+    def align_labels(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
+        """compute, then the labelled best path of every utterance through its graph (align_labels below)."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale, labels=True) if outs else []
+
+    def label_posteriors_compact(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10):
+        """compute, then the compact posteriors per label (label_posteriors_compact below): [(labels [L] int32, post [O_u, L] CUDA tensor,
+        logprob, ok)]."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _posteriors_compact_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, labels=True) if outs else []
+
+    def label_posteriors_sparse(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16,
+                                ivector_period=10):
+        """compute, then the sparse posteriors per label (label_posteriors_sparse below): [(label [O_u, K] int32, post [O_u, K], count [O_u]
+        int32 CUDA tensors, logprob, ok, truncated_frames)]."""
+        out, outs = self._compute_stacked(utterances, ivector_period)
+        return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, labels=True) if outs else []
+
     def logprob(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
         """compute, then the total log-likelihood of every utterance through its graph (logprob below): [(logprob, ok)]."""
         out, outs = self._compute_stacked(utterances, ivector_period)
@@ -347,10 +365,28 @@ def align(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
     return _align_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale)
 
 
-def _align_stacked(y, frames, graphs, utt_graph, acoustic_scale):
+def align_labels(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
+    """align with the identity of the path's arcs, through labelled graphs (hipabi.AlignGraphs of graph dicts with "label": a transition-id,
+    a phone, a word position per arc).  Returns a list of (pdf-ids, labels, arcs, score, ok): three torch int32 CUDA tensors of O_u
+    elements -- per frame the pdf, the label and the index (in the utterance's graph dict) of the arc taken -- all -1 without an accepting
+    path.  With transition-ids as labels `labels` is what nnet3-align-compiled writes (write_int_vector_archive), with phones what
+    ali-to-phones --per-frame prints."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _align_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, labels=True)
+
+
+def _align_stacked(y, frames, graphs, utt_graph, acoustic_scale, labels=False):
     """align on the utterances' rows stacked in one matrix (what tdnnf_infer_compute writes): row_stride 1"""
     import torch
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    if labels:
+        pdfs, _, results, lab, arcs = graphs.best_path_labels(y, frames, rows, 1, utt_graph, acoustic_scale)
+        res = results.cpu().numpy()  # (waits for the stream)
+        return [(p, l, a, float(res[u, 0]), bool(res[u, 1] == 1.0))
+                for u, (p, l, a) in enumerate(zip(torch.split(pdfs, frames), torch.split(lab, frames), torch.split(arcs, frames)))]
     pdfs, _, results = graphs.best_path(y, frames, rows, 1, utt_graph, acoustic_scale)
     res = results.cpu().numpy()  # (waits for the stream)
     return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(pdfs, frames))]
@@ -409,6 +445,30 @@ def posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weigh
     return _posteriors_sparse_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame)
 
 
+def label_posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+    """posteriors_compact per label (include/tdnnf_hip.h, "label posteriors"), through labelled graphs.  Returns a list of (labels numpy
+    int32 [L] = graphs.labels(the utterance's graph), ascending; post float32 [O_u, L] CUDA tensor with post[t, k] = weight x the summed
+    posterior of the arcs that carry labels[k]; logprob; ok).  What write_posterior_archive takes as (key, labels, post): with
+    transition-ids as labels, the Posterior archive ali-to-post and its relatives exchange."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _posteriors_compact_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, labels=True)
+
+
+def label_posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16):
+    """posteriors_sparse per label: the selection over label_posteriors_compact's values and the graphs' label lists.  Returns a list of
+    (label int32 [O_u, K], post float32 [O_u, K], count int32 [O_u], logprob, ok, truncated_frames) as posteriors_sparse does.  What
+    write_posterior_archive takes as (key, label, post, count)."""
+    import torch
+    if not outputs:
+        return []
+    frames = [int(o.shape[0]) for o in outputs]
+    return _posteriors_sparse_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame,
+                                      labels=True)
+
+
 def logprob(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
     """The total log-likelihood alone (the forward recursion, no per-frame memory): a list of (logprob, ok)."""
     import torch
@@ -427,24 +487,25 @@ def _posteriors_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight):
     return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(post, frames))]
 
 
-def _posteriors_compact_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight):
+def _posteriors_compact_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, labels=False):
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
-    values, begin, results = graphs.posteriors_compact(y, frames, rows, 1, utt_graph, acoustic_scale, weight)
+    call, column_list = (graphs.label_posteriors_compact, graphs.labels) if labels else (graphs.posteriors_compact, graphs.pdfs)
+    values, begin, results = call(y, frames, rows, 1, utt_graph, acoustic_scale, weight)
     res = results.cpu().numpy()  # (waits for the stream)
     lists, out = {}, []
     for u, T in enumerate(frames):
         gi = int(utt_graph[u]) if utt_graph is not None else (0 if graphs.G == 1 else u)
         if gi not in lists:
-            lists[gi] = graphs.pdfs(gi)
+            lists[gi] = column_list(gi)
         post = values[int(begin[u]):int(begin[u + 1])].view(T, len(lists[gi]))
         out.append((lists[gi], post, float(res[u, 0]), bool(res[u, 1] == 1.0)))
     return out
 
 
-def _posteriors_sparse_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame):
+def _posteriors_sparse_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, labels=False):
     import torch
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
-    pdf, post, count, results = graphs.posteriors_sparse(y, frames, rows, 1, utt_graph, acoustic_scale, weight, min_post, max_per_frame)
+    pdf, post, count, results = (graphs.label_posteriors_sparse if labels else graphs.posteriors_sparse)(y, frames, rows, 1, utt_graph, acoustic_scale, weight, min_post, max_per_frame)
     res = results.cpu().numpy()  # (waits for the stream)
     return [(a, b, c, float(res[u, 0]), bool(res[u, 1] == 1.0), int(res[u, 2]))
             for u, (a, b, c) in enumerate(zip(torch.split(pdf, frames), torch.split(post, frames), torch.split(count, frames)))]

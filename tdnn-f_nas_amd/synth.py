@@ -232,7 +232,7 @@ def make_supervision_lattice(B, T, P, tolerance=2, alternatives=1, mean_dur=3.0,
             "arc_logprob": a_lp, "weight": float(weight)}
 
 
-def make_alignment_graph(pdf_sequence, self_loops=True, optional=(), alternatives=None, seed=0, num_pdfs=None):
+def make_alignment_graph(pdf_sequence, self_loops=True, optional=(), alternatives=None, seed=0, num_pdfs=None, labels=None):
     """Left-to-right transcript graph for best-path alignment: the shape of a compile-train-graphs output reduced to pdf labels.
     Epsilon-free, so a state is "inside a unit": state 0 is the start, unit k is one state, every arc INTO it carries its pdf --
     the entering arc and, with self_loops, its loop.  The main chain is one unit per entry of pdf_sequence.
@@ -241,7 +241,12 @@ def make_alignment_graph(pdf_sequence, self_loops=True, optional=(), alternative
       optional      main units that may be skipped: their predecessors also enter their successors (one unit per skip; with
                     the last unit optional its predecessors are final, with the first the start enters unit 1).
     Arcs are ordered by (source, destination) and carry small random log-weights (seed).  Returns {S, P, src, dst, pdf, logprob,
-    init, final} with states numbered from 0: init is 0 at the start state, final 0 at the last units, -inf elsewhere."""
+    init, final} with states numbered from 0: init is 0 at the start state, final 0 at the last units, -inf elsewhere.
+      labels        None: no labels.  "unit": the dict also has "label", per arc the index of the unit it enters (main units first, then
+                    the alternatives' in ascending k) -- phone-like, shared by the entering arcs and the self-loop -- and "L", the number
+                    of units; "arc": "label" is the arc's index and "L" the number of arcs -- transition-id-like.  For
+                    hipabi.AlignGraphs(..., num_labels=...)."""
+    assert labels in (None, "unit", "arc")
     rng = np.random.default_rng(seed)
     pdfs = [int(p) for p in pdf_sequence]
     n = len(pdfs)
@@ -277,8 +282,13 @@ def make_alignment_graph(pdf_sequence, self_loops=True, optional=(), alternative
     final = np.full(S, -np.inf, dtype=np.float32)
     final[[f + 1 for f in finals]] = 0.0
     P = int(num_pdfs if num_pdfs is not None else max(pdfs) + 1)
-    return {"S": S, "P": P, "src": src, "dst": dst, "pdf": np.asarray(pdfs, dtype=np.int32)[dst - 1],
-            "logprob": (-rng.random(len(arcs)) * 0.5).astype(np.float32), "init": init, "final": final}
+    g = {"S": S, "P": P, "src": src, "dst": dst, "pdf": np.asarray(pdfs, dtype=np.int32)[dst - 1],
+         "logprob": (-rng.random(len(arcs)) * 0.5).astype(np.float32), "init": init, "final": final}
+    if labels == "unit":
+        g["label"], g["L"] = (dst - 1).astype(np.int32), len(pdfs)
+    elif labels == "arc":
+        g["label"], g["L"] = np.arange(len(arcs), dtype=np.int32), len(arcs)
+    return g
 
 
 def alignment_graph_from_den(den):

@@ -17,7 +17,13 @@ into the workspace, then the selection of at most K pairs above X a frame) join 
 finished device result to host-side per-frame (pdf-ids, posteriors) lists of the entries above X: the compact form copies frames x D
 floats and searches every row, the sparse form copies frames x K pairs and their counts and slices.  Where no frame was truncated the lists
 are compared, ids and bits.
-usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors [--compact | --sparse]]"""
+--labels unit|arc: the graphs carry labels (synth.make_alignment_graph's: the unit an arc enters, or the arc's index; on the denominator
+graph the state an arc enters, or the arc's index) and the labelled call joins the interleaved round beside its pdf counterpart, with the
+ratio to it: tdnnf_align_best_path_labels beside the best path (without --posteriors), tdnnf_align_label_posteriors_compact beside the
+compact call (--posteriors --compact), tdnnf_align_label_posteriors_sparse beside the sparse call (--posteriors --sparse).  With
+--labels arc the free workload has 64 utterances, not 128: the label block of 128 would pass the compact call's 8 GiB limit.
+usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors [--compact | --sparse]]
+                                             [--labels unit|arc]"""
 import argparse
 import json
 import os
@@ -52,7 +58,10 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="with --posteriors: time the compact and the sparse call and their ways to host-side lists")
     ap.add_argument("--min-post", type=float, default=0.01, help="--sparse: the floor")
     ap.add_argument("--max-per-frame", type=int, default=16, help="--sparse: pairs a frame")
+    ap.add_argument("--labels", choices=["unit", "arc"], help="labelled graphs: time the labelled call beside its pdf counterpart")
     args = ap.parse_args()
+    if args.labels and args.posteriors and not (args.compact or args.sparse):
+        ap.error("--labels goes with the best path, with --posteriors --compact or with --posteriors --sparse")
     if (args.compact or args.sparse) and not args.posteriors:
         ap.error("--compact and --sparse go with --posteriors")
     if args.compact and args.sparse:
@@ -82,10 +91,29 @@ def main():
         torch.cuda.synchronize()
         if args.posteriors:
             return y, posteriors_case(ag, B, y, frames, rows, ug, run, out)
-        ms = [timed(run, args.calls) for _ in range(args.repeats)]
+        if args.labels:
+            labels = torch.zeros(B * T, dtype=torch.int32, device="cuda")
+            arcs = torch.zeros(B * T, dtype=torch.int32, device="cuda")
+
+            def run_labels():
+                abi.check(lib.tdnnf_align_best_path_labels(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, abi.ptr(pdfs), None, abi.ptr(labels),
+                                                           abi.ptr(arcs), abi.ptr(out), abi.ptr(ws), nb, s))
+
+            run_labels(), run_labels()
+            torch.cuda.synchronize()
+            ms, ms_l = [], []
+            for _ in range(args.repeats):
+                ms.append(timed(run, args.calls))
+                ms_l.append(timed(run_labels, args.calls))
+        else:
+            ms = [timed(run, args.calls) for _ in range(args.repeats)]
         r = out.cpu().numpy()
-        return y, dict(utterances=B, workspace_bytes=nb, ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms],
-                       us_per_frame=round(1e3 * float(np.median(ms)) / T, 3), ok=int(r[:, 1].sum()))
+        d = dict(utterances=B, workspace_bytes=nb, ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms],
+                 us_per_frame=round(1e3 * float(np.median(ms)) / T, 3), ok=int(r[:, 1].sum()))
+        if args.labels:
+            d["best_path_labels"] = dict(ms=round(float(np.median(ms_l)), 3), ms_all=[round(v, 3) for v in ms_l])
+            d["labels_over_best_path"] = round(d["best_path_labels"]["ms"] / d["ms"], 3)
+        return y, d
 
     def posteriors_case(ag, B, y, frames, rows, ug, best_path, bp_out):
         nb = [int(lib.tdnnf_align_posteriors_workspace_bytes(ag.h, B, ug[1], frames[1], want)) for want in (0, 1)]
@@ -114,6 +142,17 @@ def main():
                                                              abi.ptr(ws), nb[1], s))
 
             fns["posteriors_compact"] = compact
+            if args.labels:
+                lbegin = ag.label_posteriors_compact_layout(frames[0], ug[0])
+                lelems = int(lbegin[-1])
+                lvalues = torch.zeros(lelems, device="cuda")
+                out_l = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+
+                def label_compact():
+                    abi.check(lib.tdnnf_align_label_posteriors_compact(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, abi.ptr(lvalues), lelems,
+                                                                       abi.ptr(out_l), abi.ptr(ws), nb[1], s))
+
+                fns["label_posteriors_compact"] = label_compact
         for fn in fns.values():
             fn(), fn()
         torch.cuda.synchronize()
@@ -133,6 +172,12 @@ def main():
         if args.compact:
             d["compact_over_posteriors"] = round(d["posteriors_compact"]["ms"] / d["posteriors"]["ms"], 3)
             d["output_bytes"] = dict(posteriors=4 * post.numel(), posteriors_compact=4 * elems)
+            if args.labels:
+                d["label_over_compact"] = round(d["label_posteriors_compact"]["ms"] / d["posteriors_compact"]["ms"], 3)
+                d["output_bytes"]["label_posteriors_compact"] = 4 * lelems
+                d["label_row_sum_err"] = float(max((lvalues[int(lbegin[u]):int(lbegin[u + 1])].view(T, -1).sum(1, dtype=torch.float64) - 1.0).abs().max()
+                                                   for u in range(B)))
+                assert np.array_equal(out_l.cpu().numpy().view(np.int64), out_c.cpu().numpy().view(np.int64)), "logprob / ok differ between pdfs and labels"
             lists_of = [ag.pdfs(int(gi)) for gi in ug[0]]
 
             def dense_lists():
@@ -189,6 +234,17 @@ def main():
                                                         abi.ptr(count), abi.ptr(out_s), abi.ptr(wss), nbs, s))
 
         fns = dict(best_path=fns["best_path"], posteriors_compact=compact, posteriors_sparse=sparse)
+        if args.labels:
+            nbl = int(lib.tdnnf_align_label_posteriors_sparse_workspace_bytes(ag.h, B, ug[1], frames[1], K))
+            wsl = abi.workspace(nbl)
+            lab, lpost = torch.zeros(B * T, K, dtype=torch.int32, device="cuda"), torch.zeros(B * T, K, device="cuda")
+            lcount, out_l = torch.zeros(B * T, dtype=torch.int32, device="cuda"), torch.zeros(B, 4, dtype=torch.float64, device="cuda")
+
+            def label_sparse():
+                abi.check(lib.tdnnf_align_label_posteriors_sparse(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, float(floor), K, abi.ptr(lab),
+                                                                  abi.ptr(lpost), abi.ptr(lcount), abi.ptr(out_l), abi.ptr(wsl), nbl, s))
+
+            fns["label_posteriors_sparse"] = label_sparse
         for fn in fns.values():
             fn(), fn()
         torch.cuda.synchronize()
@@ -203,6 +259,10 @@ def main():
             d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v], us_per_frame=round(1e3 * float(np.median(v)) / T, 3))
         d["selection_ms"] = round(d["posteriors_sparse"]["ms"] - d["posteriors_compact"]["ms"], 3)
         d["sparse_over_compact"] = round(d["posteriors_sparse"]["ms"] / d["posteriors_compact"]["ms"], 3)
+        if args.labels:
+            rl = out_l.cpu().numpy()
+            d["label_sparse_over_sparse"] = round(d["label_posteriors_sparse"]["ms"] / d["posteriors_sparse"]["ms"], 3)
+            d["label_sparse"] = dict(workspace_bytes=nbl, truncated_frames=int(rl[:, 2].sum()), most_candidates=int(rl[:, 3].max()), pairs=int(lcount.sum().item()))
         d["output_bytes"] = dict(posteriors_compact=4 * elems, posteriors_sparse=B * T * (8 * K + 4))
         lists_of = [ag.pdfs(int(gi)) for gi in ug[0]]
 
@@ -237,16 +297,25 @@ def main():
 
     # forced alignment: transcripts of 120 units with optional units and alternative branches -- a few hundred states each
     graphs = [pkg.synth.make_alignment_graph(rng.integers(0, P, size=120).tolist(), optional=list(range(5, 120, 10)),
-                                             alternatives={k: rng.integers(0, P, size=12).tolist() for k in range(3, 120, 8)}, num_pdfs=P, seed=u)
+                                             alternatives={k: rng.integers(0, P, size=12).tolist() for k in range(3, 120, 8)}, num_pdfs=P, seed=u,
+                                             labels=args.labels)
               for u in range(64)]
-    ag = abi.AlignGraphs(graphs, num_pdfs=P)
+    ag = abi.AlignGraphs(graphs, num_pdfs=P, num_labels=max(g["L"] for g in graphs) if args.labels else None)
+    if args.labels:
+        res["labels"] = args.labels
     _, res["forced"] = case(ag, 64, np.arange(64))
     res["forced"]["states_per_graph"] = int(np.mean(ag.num_states))
     del ag
     # free decode on the bench's denominator graph
     den = pkg.synth.make_den_graph(4000, P, mean_out_degree=12.0, seed=1)
-    ag = abi.AlignGraphs.from_den_graph(den)
-    B = 128
+    if args.labels:
+        g = pkg.synth.alignment_graph_from_den(den)
+        g["label"] = g["dst"] if args.labels == "unit" else np.arange(len(g["src"]), dtype=np.int32)
+        ag = abi.AlignGraphs(g, num_labels=int(g["label"].max()) + 1)
+    else:
+        ag = abi.AlignGraphs.from_den_graph(den)
+    # (one column per arc: 48 k floats a frame, and an utterance's block must start below float 2^31 of the output -- 64 utterances do)
+    B = 64 if args.labels == "arc" else 128
     y, res["free"] = case(ag, B, np.zeros(B, np.int32))
     res["free"].update(ag.info())
     if args.posteriors:
