@@ -81,9 +81,12 @@ __global__ __launch_bounds__(256) void upd_factors_kernel(const double *partial,
   }
   const float param_delta = sqrtf(param_delta_squared);
   float ok = 1.f, scale = 1.f;
-  if (tb.max_param_change != 0.f && param_delta > tb.max_param_change) {
-    if (param_delta - param_delta != 0.f) ok = 0.f;  // infinite change: do not apply (:2144-2147)
-    else scale = tb.max_param_change / param_delta;
+  if (tb.max_param_change != 0.f) {
+    // infinite change: do not apply (:2144-2147).  Looked for BEFORE the comparison, not inside it as the reference has it: a clipped
+    // component with an infinite dot product has f = 0 and 0 * 0 * inf = NaN, NaN > max_param_change is false, and the other
+    // components' deltas of the same broken minibatch would be applied.  No difference for a finite param_delta.
+    if (param_delta - param_delta != 0.f) ok = 0.f;
+    else if (param_delta > tb.max_param_change) scale = tb.max_param_change / param_delta;
   }
   for (int i = 0; i < tb.nc; i++) factors[i] = ok != 0.f ? factors[i] * scale : 0.f;
   factors[tb.nc] = ok;

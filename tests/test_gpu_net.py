@@ -200,7 +200,8 @@ def test_net_step_matches_oracle(pkg, name, kw, H):
             # come from differences of posteriors, which amplify the ~1e-5 error of the logits
             ctol = max(3e-2, 2 * gtol) if x3 else 2 * gtol
             assert rel_l2(g[sl], g_ref[sl]) < ctol, (c["name"], rel_l2(g[sl], g_ref[sl]))
-        # optimizer step: L2 + max-change + scheduled orthonormal constraint
+        # optimizer step: L2 + max-change + scheduled orthonormal constraint (an aggregate bar over the whole vector; per component and
+        # per element, with clipping on and every orthonormal regime: tests/test_gpu_net_update.py)
         p_ref = ref.update(params, g_ref, 1e-3, float(cfg.num_sequences), step)
         net.update(1e-3, step=step)
         p = host(net.params)
