@@ -67,6 +67,12 @@ int tdnnf_abi_version(void);
                      force one (tests); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path, and in the same way by
                      tdnnf_align_posteriors_workspace_bytes, tdnnf_align_posteriors, tdnnf_align_posteriors_compact, the two
                      tdnnf_align_posteriors_sparse entries and the label entries (tdnnf_align_best_path_labels, tdnnf_align_label_posteriors_*)
+     "align_checkpoint"  0 (default) forward-backward keeps alpha of every frame in the workspace; C >= 1: alpha of every C-th frame only, and
+                     the backward pass recomputes each segment of C frames from its checkpoint -- the same bits, about one forward sweep more;
+                     -1: C = ceil(sqrt(frames of the call's longest utterance)).  Anything else: TDNNF_EINVAL from the calls, 0 from the
+                     workspace questions.  Read by tdnnf_align_posteriors_workspace_bytes (want_posteriors != 0) and by tdnnf_align_posteriors
+                     (post_out != NULL), tdnnf_align_posteriors_compact, the sparse and the label posterior entries and their workspace
+                     questions alike: set it before both.  Ignored where no alpha is kept (want_posteriors = 0, post_out == NULL)
      "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
      "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
                      kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
@@ -496,12 +502,25 @@ int tdnnf_align_best_path_labels(const tdnnf_align_graphs *, int num_utts, const
  *
  * One workgroup per utterance with the best path's thread counts and option "align_form" for where the two state vectors live (read by
  * both functions below: set it before both).  Where they fit, a third vector (alpha_t) and two output rows are staged in LDS beside
- * them; otherwise those gathers read global memory.  Same results either way. */
-/* With S_u the states of utterance u's graph:
-     bytes = 16 + roundup(32 * num_utts, 256)  [+ 8 * sum_u (utt_frames[u] + 1) * S_u with want_posteriors]
+ * them; otherwise those gathers read global memory.  Same results either way.
+ *
+ * Alpha checkpointing (option "align_checkpoint", default 0 = off; read by the workspace question and by the calls: set it before both).
+ * With posteriors the forward pass keeps alpha_t of every frame, 8 * (T + 1) * S bytes an utterance.  With an interval C >= 1 (or -1: one C
+ * for the call, ceil(sqrt(its longest utterance's frames)), at least 1; a C above the longest utterance counts as that length) it keeps
+ * alpha_kC only -- one CHECKPOINT per segment [kC, min(kC + C, T)) -- and the backward pass, segment by segment from the last, first
+ * recomputes alpha_kC+1 .. of the segment from its checkpoint into a buffer of min(C, T) - 1 vectors, then walks the segment's frames.  The
+ * recomputation is the forward pass's own step in its own order: every output, logprob and ok flag has the bits it has with the option
+ * off, in every form (tests/test_gpu_posteriors_checkpoint.py).  Vectors of alpha per utterance of T frames:
+ *     V(T, C) = ceil(T / C) + min(C, T) - 1   for T >= 1,   V(0, C) = 1,   V(T, 0) = T + 1;      V(T, C) <= T for C >= 1, T >= 1
+ * -- 500 frames: 501 vectors off, 44 at C = 23 (automatic); 20 000 frames: 20 001 off, 282 at C = 142.  The cost is one more sweep over the
+ * arcs by destination for every frame that is not a checkpoint (about 4 sweeps with an exp per arc where there are 3).  The option does not
+ * touch the call without a posterior matrix, the best path or the end-to-end numerator. */
+/* With S_u the states of utterance u's graph and V the vectors of alpha above (V = utt_frames[u] + 1 unless option "align_checkpoint" is set):
+     bytes = 16 + roundup(32 * num_utts, 256)  [+ 8 * sum_u V(utt_frames[u], C) * S_u with want_posteriors]
                                                [+ 16 * sum_u S_u in the workspace form]
-   (alignment slack; the per-utterance table; alpha of every frame; the two state vectors).  The alpha region is twice the best path's
-   back-pointers: about 2 GB for 128 x 500 frames on 4 000 states.  0 for bad arguments. */
+   (alignment slack; the per-utterance table; alpha; the two state vectors).  With every frame kept the alpha region is twice the best
+   path's back-pointers: about 2 GB for 128 x 500 frames on 4 000 states, 180 MB at C = 23.  0 for bad arguments, an
+   "align_checkpoint" below -1 with want_posteriors among them. */
 size_t tdnnf_align_posteriors_workspace_bytes(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames,
                                               int want_posteriors);
 /* utt_graph, utt_frames, utt_row_begin, row_stride, nnet_output, acoustic_scale as for tdnnf_align_best_path.  results_dev: two doubles per
@@ -534,7 +553,7 @@ int tdnnf_align_posteriors_compact_layout(const tdnnf_align_graphs *, int num_ut
    tdnnf_align_posteriors_workspace_bytes(..., want_posteriors = 1), unchanged.
    TDNNF_EINVAL as there, plus: null post_compact_dev with elems > 0, post_compact_elems smaller than the layout's, and a call in which an
    utterance's block starts beyond float 2^31 - 1 of the output (8 GiB: split the call).  Everything runs on the caller's stream, nothing
-   waits for the device; option "align_form" is read as by the dense call. */
+   waits for the device; options "align_form" and "align_checkpoint" are read as by the dense call. */
 int tdnnf_align_posteriors_compact(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                                    int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float *post_compact_dev,
                                    size_t post_compact_elems, double *results_dev, void *workspace_dev, size_t workspace_bytes, tdnnf_stream);
@@ -564,7 +583,7 @@ size_t tdnnf_align_posteriors_sparse_workspace_bytes(const tdnnf_align_graphs *,
    TDNNF_EINVAL, with a message and nothing launched: all that tdnnf_align_posteriors_compact refuses (its limit of 8 GiB to the start of an
    utterance's block included), max_per_frame outside [1, 64], min_post negative or not finite, a null output with frames to write, a
    workspace smaller than tdnnf_align_posteriors_sparse_workspace_bytes.  Everything runs on the caller's stream, nothing waits for the
-   device; option "align_form" is read as by the dense call. */
+   device; options "align_form" and "align_checkpoint" are read as by the dense call (and by the workspace question above, through W). */
 int tdnnf_align_posteriors_sparse(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                                   int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, float weight, float min_post, int max_per_frame,
                                   int *pdf_out_dev, float *post_out_dev, int *count_out_dev, double *results_dev, void *workspace_dev,

@@ -401,7 +401,9 @@ inline void AlignBestPath(const tdnnf_align_graphs *graphs, int num_utts, const 
 // per utterance) and, with post_out, weight x the per-frame pdf posteriors into columns [0, num_pdfs) of post_out's rows utt_row_begin[u] +
 // t * row_stride -- soft alignments, or the flat-start numerator's derivative (GenericNumeratorComputation: deriv = weight * posterior).
 // post_out null: the forward recursion alone.  workspace: tdnnf_align_posteriors_workspace_bytes(graphs, num_utts, utt_graph, utt_frames,
-// post_out != null).
+// post_out != null).  Option "align_checkpoint" (tdnnf_set_option; alpha of every C-th frame only, the same bits) governs AlignPosteriors,
+// AlignPosteriorsCompact, AlignPosteriorsSparse and the label forms below as "align_form" does: the workspace question and the call read
+// it, so set it before both.
 template <class CuMat>
 inline void AlignPosteriors(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                             int row_stride, const CuMat &nnet_output, float acoustic_scale, float weight, CuMat *post_out, double *results_dev,

@@ -2045,7 +2045,10 @@ inline void AlignBestPath(const tdnnf_align_graphs *graphs, int32 num_utts, cons
 // results_dev (two device doubles per utterance) and, with post_out, weight x the per-frame pdf posteriors into the same rows of post_out
 // (columns [0, num_pdfs) overwritten) -- what ali-to-post consumers read.  (Training on such graphs, flat-start LF-MMI, goes through
 // tdnnf_adapter::SupervisionCreateE2e and the chain entries instead.)  post_out null: the forward recursion alone, no per-frame memory.
-// `workspace` grows to tdnnf_align_posteriors_workspace_bytes -- with post_out one double per (frame, state).
+// `workspace` grows to tdnnf_align_posteriors_workspace_bytes -- with post_out one double per (frame, state), or, under option
+// "align_checkpoint" (tdnnf_set_option), per (checkpointed frame, state): the option governs AlignPosteriors, AlignPosteriorsCompact,
+// AlignPosteriorsSparse and the label forms below as "align_form" does, and each of them asks for its workspace and calls under the
+// option as it stands, so it may be set at any time between two of these calls.
 inline void AlignPosteriors(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames, const int32 *utt_row_begin,
                             const CuMatrixBase &nnet_output, float acoustic_scale, float weight, CuMatrixBase *post_out, double *results_dev,
                             Scratch *workspace) {

@@ -1,6 +1,7 @@
 // align_fb.hip -- forward-backward over pdf-labelled graphs (include/tdnnf_hip.h, "forward-backward") through a tdnnf_align_graphs
 // (align_graphs.hip): sizes and lays out the workspace, launches align_fb_kernel or, for the compact posteriors, align_fb_compact_kernel
-// (per pdf) or align_fb_label_kernel (per label; align_fb_kernels.h).
+// (per pdf) or align_fb_label_kernel (per label; align_fb_kernels.h) -- under option align_checkpoint their *_ckpt_kernel twins, which keep
+// alpha of every C-th frame only.
 #include <limits.h>
 
 #include "align_fb_kernels.h"
@@ -10,9 +11,11 @@ namespace tdnnf {
 namespace {
 
 // What a call runs as and where its arrays lie behind the (16-byte aligned) start of the workspace:
-//   [AlignUtt x num_utts, padded to 256 bytes] [posteriors: per utterance (frames + 1) * S doubles, alpha of every frame]
+//   [AlignUtt x num_utts, padded to 256 bytes] [posteriors: per utterance V * S doubles of alpha -- V = frames + 1, alpha of every frame,
+//   or under option align_checkpoint the checkpoints and the segment buffer of AlignCheckpointPlan (align_tables.h)]
 //   [workspace form only: per utterance 2 * S doubles]
 struct FbPlan : AlignCall, AlignFormPlan {
+  AlignCheckpointPlan ckpt;  // (C = 0 without posteriors: there is no alpha region to shorten)
   size_t alpha_doubles, bytes;
 };
 
@@ -23,7 +26,16 @@ int fb_plan(const tdnnf_align_graphs *g, const char *who, int num_utts, const in
   if (rc) return rc;
   std::string err;
   TDNNF_REQUIRE(align_form_plan(p->max_states, g->P, options().align_form, post, kLdsBudget, who, p, &err), "%s", err.c_str());
-  p->alpha_doubles = post ? p->frame_elems : 0;
+  int longest = 0;
+  for (const AlignUtt &u : p->utts) longest = std::max(longest, u.frames);
+  TDNNF_REQUIRE(align_checkpoint_plan(post ? options().align_checkpoint : 0, longest, who, &p->ckpt, &err), "%s", err.c_str());
+  p->alpha_doubles = 0;
+  if (post) {
+    for (AlignUtt &u : p->utts) {
+      u.frame_begin = (long long)p->alpha_doubles;
+      p->alpha_doubles += p->ckpt.vectors(u.frames) * (size_t)(g->state_begin[u.graph + 1] - g->state_begin[u.graph]);
+    }
+  }
   if (p->lds) p->vec_doubles = 0;
   p->bytes = 16 + p->desc_bytes + sizeof(double) * (p->alpha_doubles + p->vec_doubles);
   return TDNNF_OK;
@@ -68,14 +80,25 @@ int fb_args(const tdnnf_align_graphs *g, const FbPlan &p, int row_stride, const 
   return TDNNF_OK;
 }
 
-template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST>
-int fb_launch_form(const FbPlan &p, const FbArgs &a, hipStream_t s) {
-  if (LDS)
-    TDNNF_HIP(hipFuncSetAttribute((const void *)align_fb_kernel<NT, LDS, YLDS, ALDS, POST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-  hipLaunchKernelGGL((align_fb_kernel<NT, LDS, YLDS, ALDS, POST>), dim3((int)p.utts.size()), dim3(NT), p.lds_bytes, s, a.dev, a.utts, a.y, a.row_stride,
-                     a.acoustic_scale, a.weight, a.post, a.alpha, a.vecs, a.results, p.max_states, a.P);
+// One kernel of any form on the call's grid -- a workgroup of p.threads threads per utterance -- with the call's dynamic LDS.
+template <class... P, class... A>
+int fb_launch_kernel(void (*kernel)(P...), const FbPlan &p, hipStream_t s, A... args) {
+  if (p.lds) TDNNF_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+  hipLaunchKernelGGL(kernel, dim3((int)p.utts.size()), dim3(p.threads), p.lds_bytes, s, args...);
   TDNNF_LAUNCH_CHECK();
   return TDNNF_OK;
+}
+
+// (under option align_checkpoint -- p.ckpt.C > 0 -- the *_ckpt_kernel of the same form, which takes the interval behind the other arguments)
+template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST>
+int fb_launch_form(const FbPlan &p, const FbArgs &a, hipStream_t s) {
+  if constexpr (POST) {  // (the forward-only forms keep no alpha and have no checkpointed twin)
+    if (p.ckpt.C > 0)
+      return fb_launch_kernel(align_fb_ckpt_kernel<NT, LDS, YLDS, ALDS>, p, s, a.dev, a.utts, a.y, a.row_stride, a.acoustic_scale, a.weight, a.post, a.alpha,
+                              a.vecs, a.results, p.max_states, a.P, p.ckpt.C);
+  }
+  return fb_launch_kernel(align_fb_kernel<NT, LDS, YLDS, ALDS, POST>, p, s, a.dev, a.utts, a.y, a.row_stride, a.acoustic_scale, a.weight, a.post, a.alpha,
+                          a.vecs, a.results, p.max_states, a.P);
 }
 
 template <int NT>
@@ -93,12 +116,11 @@ int fb_launch(const FbPlan &p, bool post, const FbArgs &a, hipStream_t s) {
 
 template <int NT, bool LDS, bool YLDS, bool ALDS>
 int fb_compact_launch_form(const FbPlan &p, const FbArgs &a, hipStream_t s) {
-  if (LDS)
-    TDNNF_HIP(hipFuncSetAttribute((const void *)align_fb_compact_kernel<NT, LDS, YLDS, ALDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-  hipLaunchKernelGGL((align_fb_compact_kernel<NT, LDS, YLDS, ALDS>), dim3((int)p.utts.size()), dim3(NT), p.lds_bytes, s, a.dev, a.utts, a.y, a.row_stride,
-                     a.acoustic_scale, a.weight, a.compact, a.cols, a.alpha, a.vecs, a.results, p.max_states, a.P);
-  TDNNF_LAUNCH_CHECK();
-  return TDNNF_OK;
+  if (p.ckpt.C > 0)
+    return fb_launch_kernel(align_fb_compact_ckpt_kernel<NT, LDS, YLDS, ALDS>, p, s, a.dev, a.utts, a.y, a.row_stride, a.acoustic_scale, a.weight, a.compact,
+                            a.cols, a.alpha, a.vecs, a.results, p.max_states, a.P, p.ckpt.C);
+  return fb_launch_kernel(align_fb_compact_kernel<NT, LDS, YLDS, ALDS>, p, s, a.dev, a.utts, a.y, a.row_stride, a.acoustic_scale, a.weight, a.compact, a.cols,
+                          a.alpha, a.vecs, a.results, p.max_states, a.P);
 }
 
 template <int NT>
@@ -111,12 +133,11 @@ int fb_compact_launch(const FbPlan &p, const FbArgs &a, hipStream_t s) {
 
 template <int NT, bool LDS, bool YLDS, bool ALDS>
 int fb_label_launch_form(const FbPlan &p, const FbArgs &a, hipStream_t s) {
-  if (LDS)
-    TDNNF_HIP(hipFuncSetAttribute((const void *)align_fb_label_kernel<NT, LDS, YLDS, ALDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-  hipLaunchKernelGGL((align_fb_label_kernel<NT, LDS, YLDS, ALDS>), dim3((int)p.utts.size()), dim3(NT), p.lds_bytes, s, a.dev, a.by_label, a.label_ranges, a.utts,
-                     a.y, a.row_stride, a.acoustic_scale, a.weight, a.compact, a.cols, a.alpha, a.vecs, a.results, p.max_states, a.P);
-  TDNNF_LAUNCH_CHECK();
-  return TDNNF_OK;
+  if (p.ckpt.C > 0)
+    return fb_launch_kernel(align_fb_label_ckpt_kernel<NT, LDS, YLDS, ALDS>, p, s, a.dev, a.by_label, a.label_ranges, a.utts, a.y, a.row_stride,
+                            a.acoustic_scale, a.weight, a.compact, a.cols, a.alpha, a.vecs, a.results, p.max_states, a.P, p.ckpt.C);
+  return fb_launch_kernel(align_fb_label_kernel<NT, LDS, YLDS, ALDS>, p, s, a.dev, a.by_label, a.label_ranges, a.utts, a.y, a.row_stride, a.acoustic_scale,
+                          a.weight, a.compact, a.cols, a.alpha, a.vecs, a.results, p.max_states, a.P);
 }
 
 template <int NT>

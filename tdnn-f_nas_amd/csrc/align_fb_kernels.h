@@ -31,7 +31,8 @@
 //      y[t, pdf of the arc] per arc where fb_post_step reads y[t, pdf of the row] once; the output is frames x L floats, L the distinct
 //      labels of the graph.  With label = pdf both steps form the same sums in the same order: the same bits (tests/test_gpu_align_labels.py).
 // alpha_t of every frame is kept in the workspace ((T + 1) * S doubles) by the forward pass when posteriors are wanted; without them the
-// forward pass runs alone on its two alternating vectors.
+// forward pass runs alone on its two alternating vectors.  Under option align_checkpoint (the *_ckpt_kernel forms; fb_utterance, CKPT) the
+// forward pass keeps alpha of every C-th frame only and the backward pass recomputes a segment's alphas before it walks the segment.
 //  * LDS: the two state vectors are 2 * Smax doubles of dynamic LDS, else they lie in the workspace;
 //  * ALDS (LDS, posteriors): a third vector holds alpha_t: loaded from the workspace into kAlignFbAlphaRegs registers before step 1, stored
 //    to LDS behind it, so the loads' latency hides behind step 1; else step 2 gathers alpha_t from the workspace;
@@ -100,9 +101,11 @@ struct AlignLseAcc {
 // (T + 1) * S doubles.  (A compile-time choice: with a test of the pointer in every frame, and the step indexing its slots from the table's
 // start, the numerator's recursion on transcripts took 0.399 ms where it takes 0.384: docs/experiments.md r6-r.)
 // Returns the log-sum, the same in every thread.
-template <int NT, bool YLDS, bool KEEP>
+// KEEP = kFbKeepEvery (CKPT below): alpha_t only of the frames t = kC < T, k = 0, 1 .. -- the checkpoints, vector k of alpha.
+constexpr int kFbKeepEvery = 2;
+template <int NT, bool YLDS, int KEEP>
 __device__ __forceinline__ double fb_forward(const AlignDev &g, const AlignGraphDev &gr, int T, AlignRowStage<NT, YLDS> &rows, double scale, double *&cur,
-                                             double *&nxt, double *alpha) {
+                                             double *&nxt, double *alpha, int C = 0) {
   __shared__ double red_m[NT / 64], red_s[NT / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, S = gr.num_states, s0 = gr.state0;
   for (int s = tid; s < S; s += NT) {
@@ -118,7 +121,11 @@ __device__ __forceinline__ double fb_forward(const AlignDev &g, const AlignGraph
     // row t + 1 (loaded a frame ago) into the buffer whose last readers -- frame t - 1 -- are behind the previous barrier; row t + 2 on its way
     rows.store(t + 1);
     rows.load(t + 2);
-    align_step<NT>(g.by_dst, gr.by_dst, cur, rows.row(t), scale, AlignLseAcc{nxt, KEEP ? alpha + (size_t)(t + 1) * S : nullptr});
+    // (KEEP = kFbKeepEvery, t + 1 < T: a checkpoint at T would be vector ceil(T / C), the first of the segment buffer)
+    align_step<NT>(g.by_dst, gr.by_dst, cur, rows.row(t), scale,
+                   AlignLseAcc{nxt, KEEP == kFbKeepEvery ? (t + 1 < T && (t + 1) % C == 0 ? alpha + (size_t)((t + 1) / C) * S : nullptr)
+                                    : KEEP             ? alpha + (size_t)(t + 1) * S
+                                                       : nullptr});
     __syncthreads();
     double *sw = cur;
     cur = nxt;
@@ -273,13 +280,93 @@ struct FbCompactOut {
   __device__ __forceinline__ void emit(int, int column, float v) { prow[column] = v; }
 };
 
+// The backward pass of fb_utterance over an alpha region with checkpoints (CKPT there; C >= 1 the interval, the layout is AlignCheckpointPlan's,
+// align_tables.h): the forward pass has kept alpha_kC, the checkpoint of segment k = [kC, min(kC + C, T)); cur holds beta_T.  The segments
+// are taken from the last to the first:
+//   a. alpha_kC+1 .. alpha_end-1 again, from the checkpoint into the segment buffer, by the forward pass's own step on the arcs by destination:
+//      the same candidates in the same order through the same accumulator, so the bits of the first pass.  beta_end (cur) is live meanwhile.
+//      ALDS: nxt and the third vector are free then, and the recursion runs on them (its first step reads the checkpoint from the workspace),
+//      the buffer getting the accumulator's second copy; otherwise (LDS without a third vector, the workspace form) each step gathers
+//      alpha_t from the buffer in the workspace and writes alpha_t+1 there.
+//   b. the frames end - 1 .. kC as fb_utterance takes them -- its frame, word for word, in a function of its own so that the kernels without
+//      checkpoints compile to what they were -- with alpha_t from the checkpoint (t = kC) or the buffer.
+// The row stage is primed for one direction: it is primed again before a. (forward from kC) and before b. (backward from end - 1), behind the
+// barrier that ends the frame before.  A one-frame segment has no a., and its b. goes on with the rows the segment before it staged.
+template <int NT, bool YLDS, bool ALDS, class Step, class Out>
+__device__ __forceinline__ void fb_backward_ckpt(const AlignDev &g, const AlignGraphDev &gr, int graph, int T, int C, AlignRowStage<NT, YLDS> &rows,
+                                                 double scale, double w, double logprob, double *cur, double *nxt, double *alds, double *alpha,
+                                                 Step &step, Out &out) {
+  const int tid = threadIdx.x, S = gr.num_states;
+  const int segments = T > 0 ? (T - 1) / C + 1 : 0;
+  double *buffer = alpha + (size_t)segments * S;  // slot j is alpha_begin+1+j of the segment at hand
+  for (int k = segments - 1; k >= 0; k--) {
+    const int begin = k * C, end = begin + min(C, T - begin);
+    const double *checkpoint = alpha + (size_t)k * S;
+    if (end - begin > 1) {
+      // (the rows' and the vectors' last readers -- frame end, or the total -- are behind a barrier)
+      rows.load(begin);
+      rows.store(begin);
+      rows.load(begin + 1);
+      __syncthreads();
+      const double *from = checkpoint;
+      double *to = nxt, *spare = alds;
+      for (int t = begin; t < end - 1; t++) {
+        rows.store(t + 1);
+        rows.load(t + 2);
+        double *slot = buffer + (size_t)(t - begin) * S;
+        align_step<NT>(g.by_dst, gr.by_dst, from, rows.row(t), scale, ALDS ? AlignLseAcc{to, slot} : AlignLseAcc{slot, nullptr});
+        __syncthreads();
+        from = ALDS ? to : slot;
+        double *sw = to;
+        to = spare;
+        spare = sw;
+      }
+    }
+    if (k == segments - 1 || end - begin > 1) {
+      rows.load(end - 1);
+      rows.store(end - 1);
+      rows.load(end - 2);
+      __syncthreads();
+    }
+    for (int t = end - 1; t >= begin; t--) {
+      rows.store(t - 1);
+      rows.load(t - 2);
+      const float *yrow = rows.row(t);
+      out.frame(t);
+      const double *at = t == begin ? checkpoint : buffer + (size_t)(t - begin - 1) * S;
+      double areg[kAlignFbAlphaRegs];
+      if (ALDS) {
+#pragma unroll
+        for (int c = 0; c < kAlignFbAlphaRegs; c++)
+          if (tid + c * NT < S) areg[c] = at[tid + c * NT];
+      }
+      if (t > 0)  // (beta_0 has no reader)
+        align_step<NT>(g.by_src, gr.by_src, cur, yrow, scale, AlignLseAcc{nxt, nullptr});
+      if (ALDS) {
+#pragma unroll
+        for (int c = 0; c < kAlignFbAlphaRegs; c++)
+          if (tid + c * NT < S) alds[tid + c * NT] = areg[c];
+      }
+      __syncthreads();  // alpha_t is in place and the row's zeros (dense) are stored
+      step.template run<NT>(g, gr, graph, ALDS ? (const double *)alds : at, cur, yrow, scale, logprob,
+                            [&](int row, int column, double sum) { out.emit(row, column, (float)(w * sum)); });
+      __syncthreads();
+      double *sw = cur;
+      cur = nxt;
+      nxt = sw;
+    }
+  }
+}
+
 // One utterance on its workgroup.  Dynamic LDS: [LDS: 2 * Smax doubles, the state vectors] [ALDS: Smax doubles, alpha_t] [YLDS: 2 * P floats, two output rows].
 // POST: alpha_all / out are read and written; otherwise it ends with the total.  step: FbPdfStep or FbLabelStep.
-template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST, class Step, class MakeOut>
+// CKPT (POST; C >= 1 the interval): the forward pass keeps alpha of every C-th frame only and fb_backward_ckpt walks the frames.
+template <int NT, bool LDS, bool YLDS, bool ALDS, bool POST, bool CKPT = false, class Step, class MakeOut>
 __device__ __forceinline__ void fb_utterance(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight, Step step,
-                                             MakeOut make_out, double *alpha_all, double *vecs, double *results, int Smax, int P) {
+                                             MakeOut make_out, double *alpha_all, double *vecs, double *results, int Smax, int P, int C = 0) {
   static_assert(LDS || !(YLDS || ALDS), "the rows behind the vectors need the LDS form");
   static_assert(POST || !ALDS, "alpha_t is staged for the posteriors only");
+  static_assert(POST || !CKPT, "checkpoints are of the alpha kept for the posteriors");
   extern __shared__ double fb_smem[];
   const int tid = threadIdx.x;
   const AlignUtt u = utts[blockIdx.x];
@@ -291,7 +378,7 @@ __device__ __forceinline__ void fb_utterance(AlignDev g, const AlignUtt *utts, M
   const double scale = (double)acoustic_scale;
   AlignRowStage<NT, YLDS> rows(y.data + (size_t)u.row_begin * y.stride, (size_t)row_stride * y.stride, P, T,
                                reinterpret_cast<float *>(fb_smem + (ALDS ? 3 : 2) * (size_t)Smax));
-  const double logprob = fb_forward<NT, YLDS, POST>(g, gr, T, rows, scale, cur, nxt, alpha);
+  const double logprob = fb_forward<NT, YLDS, CKPT ? kFbKeepEvery : POST>(g, gr, T, rows, scale, cur, nxt, alpha, C);
   const bool ok = logprob > -INFINITY && logprob < INFINITY;
   if (tid == 0) {
     results[2 * (size_t)blockIdx.x] = logprob;
@@ -306,6 +393,10 @@ __device__ __forceinline__ void fb_utterance(AlignDev g, const AlignUtt *utts, M
   const double w = (double)weight;
   // (alpha_T's last readers are behind the barrier above)
   for (int s = tid; s < S; s += NT) cur[s] = (double)g.final[s0 + s];
+  if constexpr (CKPT) {
+    fb_backward_ckpt<NT, YLDS, ALDS>(g, gr, u.graph, T, C, rows, scale, w, logprob, cur, nxt, alds, alpha, step, out);
+    return;
+  }
   rows.load(T - 1);
   rows.store(T - 1);
   rows.load(T - 2);
@@ -369,6 +460,35 @@ __global__ __launch_bounds__(NT) void align_fb_label_kernel(AlignDev g, AlignTab
   fb_utterance<NT, LDS, YLDS, ALDS, true>(
       g, utts, y, row_stride, acoustic_scale, weight, FbLabelStep{by_label, label_ranges},
       [&](const AlignUtt &u) { return FbCompactOut<NT>{compact + u.out_begin, graph_cols[u.graph], nullptr}; }, alpha_all, vecs, results, Smax, P);
+}
+
+// The three kernels above with alpha checkpoints (fb_utterance, CKPT): the same arguments and C >= 1, the call's interval, behind them.
+// Kernels of their own, so that a call without checkpoints launches what it launched before there were any.
+template <int NT, bool LDS, bool YLDS, bool ALDS>
+__global__ __launch_bounds__(NT) void align_fb_ckpt_kernel(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale, float weight,
+                                                           MatView post, double *alpha_all, double *vecs, double *results, int Smax, int P, int C) {
+  fb_utterance<NT, LDS, YLDS, ALDS, true, true>(
+      g, utts, y, row_stride, acoustic_scale, weight, FbPdfStep{},
+      [&](const AlignUtt &u) { return FbDenseOut<NT>{post, u.row_begin, row_stride, P, nullptr}; }, alpha_all, vecs, results, Smax, P, C);
+}
+
+template <int NT, bool LDS, bool YLDS, bool ALDS>
+__global__ __launch_bounds__(NT) void align_fb_compact_ckpt_kernel(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale,
+                                                                   float weight, float *compact, const int *graph_cols, double *alpha_all, double *vecs,
+                                                                   double *results, int Smax, int P, int C) {
+  fb_utterance<NT, LDS, YLDS, ALDS, true, true>(
+      g, utts, y, row_stride, acoustic_scale, weight, FbPdfStep{},
+      [&](const AlignUtt &u) { return FbCompactOut<NT>{compact + u.out_begin, graph_cols[u.graph], nullptr}; }, alpha_all, vecs, results, Smax, P, C);
+}
+
+template <int NT, bool LDS, bool YLDS, bool ALDS>
+__global__ __launch_bounds__(NT) void align_fb_label_ckpt_kernel(AlignDev g, AlignTable by_label, const AlignRange *label_ranges, const AlignUtt *utts,
+                                                                 MatView y, int row_stride, float acoustic_scale, float weight, float *compact,
+                                                                 const int *graph_cols, double *alpha_all, double *vecs, double *results, int Smax, int P,
+                                                                 int C) {
+  fb_utterance<NT, LDS, YLDS, ALDS, true, true>(
+      g, utts, y, row_stride, acoustic_scale, weight, FbLabelStep{by_label, label_ranges},
+      [&](const AlignUtt &u) { return FbCompactOut<NT>{compact + u.out_begin, graph_cols[u.graph], nullptr}; }, alpha_all, vecs, results, Smax, P, C);
 }
 
 }  // namespace

@@ -197,4 +197,37 @@ inline bool align_form_plan(int max_states, int num_pdfs, int align_form, bool w
   return true;
 }
 
+// Alpha checkpointing of the forward-backward pass (option align_checkpoint; align_fb_kernels.h, CKPT).  With an interval C >= 1 an utterance
+// of T frames is cut into the SEGMENTS [kC, min(kC + C, T)), k = 0 .. ceil(T / C) - 1; its alpha region holds, in this order,
+//   the CHECKPOINTS   alpha_kC, one per segment (alpha_0 alone for T = 0: the forward pass always writes it), then
+//   the SEGMENT BUFFER of min(C, T) - 1 vectors: slot j is alpha_(kC + 1 + j) of the segment k the backward pass is walking.
+// alpha_T has no place: no frame's posteriors read it.  C = 0: alpha of every frame, T + 1 vectors, vector t is alpha_t.
+struct AlignCheckpointPlan {
+  int C;  // 0: off; else the interval, at most the call's longest utterance (a longer one cuts no utterance differently) and at least 1
+  size_t checkpoints(int T) const { return C == 0 ? (size_t)T + 1 : T > 0 ? ((size_t)T - 1) / C + 1 : 1; }  // (C > 0: the segments of T >= 1 frames)
+  size_t buffer(int T) const { return C == 0 || T < 1 ? 0 : (size_t)std::min(C, T) - 1; }
+  size_t vectors(int T) const { return checkpoints(T) + buffer(T); }  // V(T, C), never more than T + 1
+  int segments(int T) const { return C == 0 || T < 1 ? 0 : (T - 1) / C + 1; }
+  int segment_begin(int k) const { return k * C; }
+  int segment_end(int T, int k) const { return k * C + std::min(C, T - k * C); }
+};
+
+// align_checkpoint (option): 0 off, C >= 1 the interval, -1 automatic: the least C with C * C >= max_frames, the call's longest utterance --
+// ceil(sqrt(max_frames)) -- and at least 1.  False and *err (starting with prefix) for any other value.
+inline bool align_checkpoint_plan(int align_checkpoint, int max_frames, const char *prefix, AlignCheckpointPlan *p, std::string *err) {
+  if (align_checkpoint < -1) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%soption align_checkpoint must be 0 (off), an interval >= 1 or -1 (automatic), not %d", prefix, align_checkpoint);
+    *err = msg;
+    return false;
+  }
+  const int longest = std::max(max_frames, 1);
+  long long c = align_checkpoint;
+  if (align_checkpoint == -1)
+    for (c = 1; c * c < longest; c++) {
+    }
+  p->C = (int)std::min<long long>(c, longest);
+  return true;
+}
+
 }  // namespace tdnnf

@@ -81,6 +81,7 @@ struct Options {
   int gemm_arith_test = 0;   // tests: 1 / 3 = the stand-alone GEMM entries (no GemmPrecisionScope around them) run the in-kernel split-bf16 kernels bf16x3 / bf16x6 where exact f32 is the default; the exact-f32 scopes (natural gradient, orthonormal constraint) keep f32
   int num_frontier_cap = 0;  // tests: the wide numerator keeps its frontier in global memory for supervisions with a frame of more states than this (0: what the LDS holds)
   int align_form = 0;       // best-path alignment (align.hip; the rules: align_tables.h align_form_plan): 0 the two state vectors in LDS where 2 * S doubles fit kLdsBudget, in the workspace otherwise; 1 / 2 force LDS / workspace (tests/test_gpu_align.py runs both); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path, and alike by forward-backward (align_fb.hip; tests/test_gpu_posteriors.py runs both)
+  int align_checkpoint = 0;  // forward-backward with posteriors (align_fb.hip; the rules: align_tables.h align_checkpoint_plan): 0 alpha of every frame stays in the workspace; C >= 1 alpha of every C-th frame, the backward pass recomputes each segment's from its checkpoint (the same bits; tests/test_gpu_posteriors_checkpoint.py); -1 C = ceil(sqrt(the call's longest utterance)); read by tdnnf_align_posteriors_workspace_bytes and by every posterior call alike
   int den_gamma_pairs = 0;  // the split form's occupancy pass: 1 one (frame, sequence) per workgroup (den_gamma_kernel), 0 two frames per workgroup where their vectors fit the LDS (den_gamma2_kernel)
 };
 Options &options();

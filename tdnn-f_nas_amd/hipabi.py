@@ -174,6 +174,12 @@ class option:
         return False
 
 
+def _checkpoint(value):
+    """The scope of a `checkpoint=` keyword (AlignGraphs): None leaves option align_checkpoint as it is, an int sets it for the block."""
+    import contextlib
+    return contextlib.nullcontext() if value is None else option("align_checkpoint", value)
+
+
 def launch_forms(reset=False):
     """{name: value} of the non-zero GEMM launch-form counters (tdnnf_gemm_launch_forms); reset: clear them all afterwards."""
     lib = load()
@@ -360,11 +366,32 @@ class AlignGraphs:
         arc_out = torch.where(arc_out >= 0, arc_out - shift, arc_out)
         return pdf_out[:total], state_out, results, label_out[:total], arc_out
 
-    def posteriors_workspace_bytes(self, utt_graph, utt_frames, want_posteriors=True):
+    def posteriors_workspace_bytes(self, utt_graph, utt_frames, want_posteriors=True, checkpoint=None):
+        """tdnnf_align_posteriors_workspace_bytes.  checkpoint (here and on every posterior call below): None reads option
+        align_checkpoint as it stands; an int (0 off, C >= 1 an interval, -1 automatic) sets it around the workspace question and the call
+        and restores it afterwards -- alpha of every C-th frame only, the same bits."""
         ug = iarr(utt_graph)[1] if utt_graph is not None else None
-        return int(load().tdnnf_align_posteriors_workspace_bytes(self.h, len(utt_frames), ug, iarr(utt_frames)[1], 1 if want_posteriors else 0))
+        with _checkpoint(checkpoint):
+            return int(load().tdnnf_align_posteriors_workspace_bytes(self.h, len(utt_frames), ug, iarr(utt_frames)[1], 1 if want_posteriors else 0))
 
-    def _forward_backward(self, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post):
+    def posteriors_sparse_workspace_bytes(self, utt_graph, utt_frames, max_per_frame=16, checkpoint=None):
+        """tdnnf_align_posteriors_sparse_workspace_bytes (0 for a call it refuses)."""
+        return self._sparse_workspace_bytes("tdnnf_align_posteriors_sparse", utt_graph, utt_frames, max_per_frame, checkpoint)
+
+    def label_posteriors_sparse_workspace_bytes(self, utt_graph, utt_frames, max_per_frame=16, checkpoint=None):
+        """tdnnf_align_label_posteriors_sparse_workspace_bytes (0 for a call it refuses)."""
+        return self._sparse_workspace_bytes("tdnnf_align_label_posteriors_sparse", utt_graph, utt_frames, max_per_frame, checkpoint)
+
+    def _sparse_workspace_bytes(self, entry, utt_graph, utt_frames, max_per_frame, checkpoint):
+        ug = iarr(utt_graph)[1] if utt_graph is not None else None
+        with _checkpoint(checkpoint):
+            return int(getattr(load(), entry + "_workspace_bytes")(self.h, len(utt_frames), ug, iarr(utt_frames)[1], int(max_per_frame)))
+
+    def _forward_backward(self, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post, checkpoint=None):
+        with _checkpoint(checkpoint):
+            return self._forward_backward_call(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post)
+
+    def _forward_backward_call(self, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post):
         import torch
         n = len(utt_frames)
         fr, frp = iarr(utt_frames)
@@ -379,13 +406,13 @@ class AlignGraphs:
                                             pmat(post), ptr(results), ptr(ws), nbytes, stream()))
         return results
 
-    def posteriors(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0, out=None):
+    def posteriors(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0, out=None, checkpoint=None):
         """tdnnf_align_posteriors on the current stream.  Returns (post, results): post float32, addressed like nnet_output (row
         utt_row_begin[u] + t * row_stride) -- `out` if given, else a new zeroed [rows of nnet_output, num_pdfs] matrix; results float64
         [utterances, 2] (logprob, ok).  CUDA tensors; nothing is synchronised."""
         import torch
         post = out if out is not None else torch.zeros((nnet_output.shape[0], self.P), dtype=torch.float32, device="cuda")
-        return post, self._forward_backward(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post)
+        return post, self._forward_backward(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, post, checkpoint)
 
     def pdfs(self, graph=0):
         """The column list of one graph (tdnnf_align_graphs_pdfs): the distinct pdfs its arcs name, ascending, as a numpy int32 array."""
@@ -422,19 +449,22 @@ class AlignGraphs:
         check(getattr(load(), entry)(self.h, n, ug[1], iarr(utt_frames)[1], None, begin.ctypes.data_as(C.c_void_p)))
         return begin
 
-    def posteriors_compact(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+    def posteriors_compact(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0, checkpoint=None):
         """tdnnf_align_posteriors_compact on the current stream.  Returns (values, utt_begin, results): values float32 CUDA tensor of
         utt_begin[-1] floats, of which utterance u owns [utt_begin[u], utt_begin[u + 1]) -- utt_frames[u] rows of one float per pdf of
         pdfs(its graph), = weight x the posterior; utt_begin numpy int64; results float64 [utterances, 2] (logprob, ok) CUDA tensor.
         Nothing is synchronised."""
-        return self._compact("tdnnf_align_posteriors_compact", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight)
+        with _checkpoint(checkpoint):
+            return self._compact("tdnnf_align_posteriors_compact", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight)
 
-    def label_posteriors_compact(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+    def label_posteriors_compact(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0,
+                                 checkpoint=None):
         """tdnnf_align_label_posteriors_compact on the current stream: posteriors_compact per label -- utterance u owns utt_frames[u] rows of
         one float per label of labels(its graph), = weight x the summed posterior of the arcs that carry the label.  Returns (values,
         utt_begin, results) as posteriors_compact does.  Nothing is synchronised."""
-        return self._compact("tdnnf_align_label_posteriors_compact", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale,
-                             weight)
+        with _checkpoint(checkpoint):
+            return self._compact("tdnnf_align_label_posteriors_compact", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale,
+                                 weight)
 
     def _compact(self, entry, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight):
         import torch
@@ -455,22 +485,24 @@ class AlignGraphs:
         return values, begin, results
 
     def posteriors_sparse(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01,
-                          max_per_frame=16):
+                          max_per_frame=16, checkpoint=None):
         """tdnnf_align_posteriors_sparse on the current stream: per frame the at most K = max_per_frame (pdf, value) pairs with value >
         min_post, of the values posteriors_compact gives, in ascending pdf order.  Returns (pdf int32 [F, K], post float32 [F, K], count
         int32 [F], results float64 [utterances, 4]) as CUDA tensors, F = sum(utt_frames), utterance after utterance: the first count[f]
         slots of frame f hold its pairs, the others (-1, 0); results = (logprob, ok, frames with more than K candidates, the greatest
         number of candidates in a frame).  Nothing is synchronised."""
-        return self._sparse("tdnnf_align_posteriors_sparse", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight,
-                            min_post, max_per_frame)
+        with _checkpoint(checkpoint):
+            return self._sparse("tdnnf_align_posteriors_sparse", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight,
+                                min_post, max_per_frame)
 
     def label_posteriors_sparse(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, weight=1.0,
-                                min_post=0.01, max_per_frame=16):
+                                min_post=0.01, max_per_frame=16, checkpoint=None):
         """tdnnf_align_label_posteriors_sparse on the current stream: posteriors_sparse over label_posteriors_compact's values and the
         graphs' label lists.  Returns (label int32 [F, K], post float32 [F, K], count int32 [F], results float64 [utterances, 4]) as
         posteriors_sparse does.  Nothing is synchronised."""
-        return self._sparse("tdnnf_align_label_posteriors_sparse", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale,
-                            weight, min_post, max_per_frame)
+        with _checkpoint(checkpoint):
+            return self._sparse("tdnnf_align_label_posteriors_sparse", nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale,
+                                weight, min_post, max_per_frame)
 
     def _sparse(self, entry, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, weight, min_post, max_per_frame):
         import torch

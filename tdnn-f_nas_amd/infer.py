@@ -110,42 +110,43 @@ class AcousticModel:
         out, outs = self._compute_stacked(utterances, ivector_period)
         return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale) if outs else []
 
-    def posteriors(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10):
+    def posteriors(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10, checkpoint=None):
         """compute, then forward-backward of every utterance through its graph (posteriors below): [(post [O_u, num_pdfs] CUDA tensor,
         logprob, ok)]; the output stays on the device in between."""
         out, outs = self._compute_stacked(utterances, ivector_period)
-        return _posteriors_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight) if outs else []
+        return _posteriors_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, checkpoint=checkpoint) if outs else []
 
-    def posteriors_compact(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10):
+    def posteriors_compact(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10, checkpoint=None):
         """compute, then forward-backward of every utterance through its graph in the compact form (posteriors_compact below):
         [(pdf_ids [D] int32, post [O_u, D] CUDA tensor, logprob, ok)]; the output stays on the device in between."""
         out, outs = self._compute_stacked(utterances, ivector_period)
-        return _posteriors_compact_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight) if outs else []
+        return _posteriors_compact_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, checkpoint=checkpoint) if outs else []
 
-    def posteriors_sparse(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16, ivector_period=10):
+    def posteriors_sparse(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16,
+                          ivector_period=10, checkpoint=None):
         """compute, then forward-backward of every utterance through its graph in the sparse form (posteriors_sparse below):
         [(pdf [O_u, K] int32, post [O_u, K], count [O_u] int32 CUDA tensors, logprob, ok, truncated_frames)]; the output stays on the
         device in between."""
         out, outs = self._compute_stacked(utterances, ivector_period)
-        return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame) if outs else []
+        return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, checkpoint=checkpoint) if outs else []
 
     def align_labels(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
         """compute, then the labelled best path of every utterance through its graph (align_labels below)."""
         out, outs = self._compute_stacked(utterances, ivector_period)
         return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale, labels=True) if outs else []
 
-    def label_posteriors_compact(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10):
+    def label_posteriors_compact(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10, checkpoint=None):
         """compute, then the compact posteriors per label (label_posteriors_compact below): [(labels [L] int32, post [O_u, L] CUDA tensor,
         logprob, ok)]."""
         out, outs = self._compute_stacked(utterances, ivector_period)
-        return _posteriors_compact_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, labels=True) if outs else []
+        return _posteriors_compact_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, labels=True, checkpoint=checkpoint) if outs else []
 
     def label_posteriors_sparse(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16,
-                                ivector_period=10):
+                                ivector_period=10, checkpoint=None):
         """compute, then the sparse posteriors per label (label_posteriors_sparse below): [(label [O_u, K] int32, post [O_u, K], count [O_u]
         int32 CUDA tensors, logprob, ok, truncated_frames)]."""
         out, outs = self._compute_stacked(utterances, ivector_period)
-        return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, labels=True) if outs else []
+        return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, labels=True, checkpoint=checkpoint) if outs else []
 
     def logprob(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
         """compute, then the total log-likelihood of every utterance through its graph (logprob below): [(logprob, ok)]."""
@@ -407,20 +408,22 @@ def write_int_vector_archive(path, items):
             f.write(v.tobytes())
 
 
-def posteriors(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+def posteriors(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, checkpoint=None):
     """Forward-backward (include/tdnnf_hip.h, "forward-backward") of the model's outputs, a list of O_u x num_pdfs CUDA tensors as
     AcousticModel.compute returns them, through `graphs` (hipabi.AlignGraphs; utt_graph as for align).  Returns a list of (post float32
     [O_u, num_pdfs] CUDA tensor = weight x the per-frame pdf posteriors, logprob, ok): logprob is the log-sum over all paths of the
     utterance's length; without a finite one ok is False and post all zeros.  Soft alignments and the flat-start numerator's derivative;
-    no beam, pdf level."""
+    no beam, pdf level.  checkpoint (here and on the other posterior functions and AcousticModel methods): AlignGraphs' keyword -- None
+    leaves option align_checkpoint as it stands, an int sets it for the call (alpha of every C-th frame only, -1 automatic: a workspace
+    of O(sqrt(frames)) vectors, the same bits)."""
     import torch
     if not outputs:
         return []
     frames = [int(o.shape[0]) for o in outputs]
-    return _posteriors_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight)
+    return _posteriors_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, checkpoint=checkpoint)
 
 
-def posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+def posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, checkpoint=None):
     """posteriors in the compact form (include/tdnnf_hip.h, "compact posteriors"): only the columns an utterance's graph can fill.  Returns a
     list of (pdf_ids numpy int32 [D] = graphs.pdfs(the utterance's graph), ascending; post float32 [O_u, D] CUDA tensor, a view of the
     call's one output, with post[t, k] = what posteriors gives for [t, pdf_ids[k]], bit for bit; logprob; ok).  Every pdf outside pdf_ids
@@ -429,10 +432,10 @@ def posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weig
     if not outputs:
         return []
     frames = [int(o.shape[0]) for o in outputs]
-    return _posteriors_compact_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight)
+    return _posteriors_compact_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, checkpoint=checkpoint)
 
 
-def posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16):
+def posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16, checkpoint=None):
     """posteriors in the sparse form (include/tdnnf_hip.h, "sparse posteriors"): per frame the at most K = max_per_frame pairs whose value
     -- what posteriors_compact gives, bit for bit, not renormalised -- is above min_post; of more than K candidates the K greatest, among
     equal values the lower pdf.  Returns a list of (pdf int32 [O_u, K], post float32 [O_u, K], count int32 [O_u], views of the call's three
@@ -442,10 +445,10 @@ def posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weigh
     if not outputs:
         return []
     frames = [int(o.shape[0]) for o in outputs]
-    return _posteriors_sparse_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame)
+    return _posteriors_sparse_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, checkpoint=checkpoint)
 
 
-def label_posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0):
+def label_posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, checkpoint=None):
     """posteriors_compact per label (include/tdnnf_hip.h, "label posteriors"), through labelled graphs.  Returns a list of (labels numpy
     int32 [L] = graphs.labels(the utterance's graph), ascending; post float32 [O_u, L] CUDA tensor with post[t, k] = weight x the summed
     posterior of the arcs that carry labels[k]; logprob; ok).  What write_posterior_archive takes as (key, labels, post): with
@@ -454,10 +457,10 @@ def label_posteriors_compact(outputs, graphs, utt_graph=None, acoustic_scale=1.0
     if not outputs:
         return []
     frames = [int(o.shape[0]) for o in outputs]
-    return _posteriors_compact_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, labels=True)
+    return _posteriors_compact_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, labels=True, checkpoint=checkpoint)
 
 
-def label_posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16):
+def label_posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, min_post=0.01, max_per_frame=16, checkpoint=None):
     """posteriors_sparse per label: the selection over label_posteriors_compact's values and the graphs' label lists.  Returns a list of
     (label int32 [O_u, K], post float32 [O_u, K], count int32 [O_u], logprob, ok, truncated_frames) as posteriors_sparse does.  What
     write_posterior_archive takes as (key, label, post, count)."""
@@ -466,7 +469,7 @@ def label_posteriors_sparse(outputs, graphs, utt_graph=None, acoustic_scale=1.0,
         return []
     frames = [int(o.shape[0]) for o in outputs]
     return _posteriors_sparse_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame,
-                                      labels=True)
+                                      labels=True, checkpoint=checkpoint)
 
 
 def logprob(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
@@ -478,19 +481,19 @@ def logprob(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
     return _logprob_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale)
 
 
-def _posteriors_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight):
+def _posteriors_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, checkpoint=None):
     """posteriors on the utterances' rows stacked in one matrix (what tdnnf_infer_compute writes): row_stride 1"""
     import torch
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
-    post, results = graphs.posteriors(y, frames, rows, 1, utt_graph, acoustic_scale, weight)
+    post, results = graphs.posteriors(y, frames, rows, 1, utt_graph, acoustic_scale, weight, checkpoint=checkpoint)
     res = results.cpu().numpy()  # (waits for the stream)
     return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(post, frames))]
 
 
-def _posteriors_compact_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, labels=False):
+def _posteriors_compact_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, labels=False, checkpoint=None):
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
     call, column_list = (graphs.label_posteriors_compact, graphs.labels) if labels else (graphs.posteriors_compact, graphs.pdfs)
-    values, begin, results = call(y, frames, rows, 1, utt_graph, acoustic_scale, weight)
+    values, begin, results = call(y, frames, rows, 1, utt_graph, acoustic_scale, weight, checkpoint=checkpoint)
     res = results.cpu().numpy()  # (waits for the stream)
     lists, out = {}, []
     for u, T in enumerate(frames):
@@ -502,10 +505,11 @@ def _posteriors_compact_stacked(y, frames, graphs, utt_graph, acoustic_scale, we
     return out
 
 
-def _posteriors_sparse_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, labels=False):
+def _posteriors_sparse_stacked(y, frames, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, labels=False, checkpoint=None):
     import torch
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
-    pdf, post, count, results = (graphs.label_posteriors_sparse if labels else graphs.posteriors_sparse)(y, frames, rows, 1, utt_graph, acoustic_scale, weight, min_post, max_per_frame)
+    pdf, post, count, results = (graphs.label_posteriors_sparse if labels else graphs.posteriors_sparse)(y, frames, rows, 1, utt_graph, acoustic_scale, weight, min_post,
+                                                                                                       max_per_frame, checkpoint=checkpoint)
     res = results.cpu().numpy()  # (waits for the stream)
     return [(a, b, c, float(res[u, 0]), bool(res[u, 1] == 1.0), int(res[u, 2]))
             for u, (a, b, c) in enumerate(zip(torch.split(pdf, frames), torch.split(post, frames), torch.split(count, frames)))]

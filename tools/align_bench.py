@@ -22,8 +22,13 @@ graph the state an arc enters, or the arc's index) and the labelled call joins t
 ratio to it: tdnnf_align_best_path_labels beside the best path (without --posteriors), tdnnf_align_label_posteriors_compact beside the
 compact call (--posteriors --compact), tdnnf_align_label_posteriors_sparse beside the sparse call (--posteriors --sparse).  With
 --labels arc the free workload has 64 utterances, not 128: the label block of 128 would pass the compact call's 8 GiB limit.
+--checkpoint C (with --posteriors --compact or --posteriors --sparse): the compact (sparse) call under option align_checkpoint = C -- alpha of
+every C-th frame only, -1 for ceil(sqrt(frames)) -- joins the interleaved round beside the full call, in the workspace the option asks for;
+the JSON gains both workspace sizes, the time ratio and whether the bits agree.  A third workload, "long": 4 utterances of 20 000 frames,
+each on its own transcript graph of some 3 000 states, through the compact call.  Without --checkpoint (or with 0) it reports the bytes it
+would need and is skipped; with it, it runs in the checkpointed workspace.
 usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors [--compact | --sparse]]
-                                             [--labels unit|arc]"""
+                                             [--labels unit|arc] [--checkpoint C]"""
 import argparse
 import json
 import os
@@ -59,7 +64,10 @@ def main():
     ap.add_argument("--min-post", type=float, default=0.01, help="--sparse: the floor")
     ap.add_argument("--max-per-frame", type=int, default=16, help="--sparse: pairs a frame")
     ap.add_argument("--labels", choices=["unit", "arc"], help="labelled graphs: time the labelled call beside its pdf counterpart")
+    ap.add_argument("--checkpoint", type=int, help="with --posteriors --compact | --sparse: option align_checkpoint for a second compact (sparse) call")
     args = ap.parse_args()
+    if args.checkpoint is not None and not (args.compact or args.sparse):
+        ap.error("--checkpoint goes with --posteriors --compact or --posteriors --sparse")
     if args.labels and args.posteriors and not (args.compact or args.sparse):
         ap.error("--labels goes with the best path, with --posteriors --compact or with --posteriors --sparse")
     if (args.compact or args.sparse) and not args.posteriors:
@@ -142,6 +150,18 @@ def main():
                                                              abi.ptr(ws), nb[1], s))
 
             fns["posteriors_compact"] = compact
+            if args.checkpoint is not None:
+                with abi.option("align_checkpoint", args.checkpoint):
+                    nb_k = int(lib.tdnnf_align_posteriors_workspace_bytes(ag.h, B, ug[1], frames[1], 1))
+                values_k = torch.zeros(elems, device="cuda")
+                out_k = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+
+                def compact_checkpoint():
+                    with abi.option("align_checkpoint", args.checkpoint):
+                        abi.check(lib.tdnnf_align_posteriors_compact(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, abi.ptr(values_k), elems,
+                                                                     abi.ptr(out_k), abi.ptr(ws), nb_k, s))
+
+                fns["posteriors_compact_checkpoint"] = compact_checkpoint
             if args.labels:
                 lbegin = ag.label_posteriors_compact_layout(frames[0], ug[0])
                 lelems = int(lbegin[-1])
@@ -172,6 +192,12 @@ def main():
         if args.compact:
             d["compact_over_posteriors"] = round(d["posteriors_compact"]["ms"] / d["posteriors"]["ms"], 3)
             d["output_bytes"] = dict(posteriors=4 * post.numel(), posteriors_compact=4 * elems)
+            if args.checkpoint is not None:
+                d["checkpoint"] = args.checkpoint
+                d["workspace_bytes_checkpoint"] = nb_k
+                d["checkpoint_over_compact"] = round(d["posteriors_compact_checkpoint"]["ms"] / d["posteriors_compact"]["ms"], 3)
+                d["checkpoint_same_bits"] = bool(torch.equal(values_k.view(torch.int32), values.view(torch.int32))
+                                                 and torch.equal(out_k.view(torch.int64), out_c.view(torch.int64)))
             if args.labels:
                 d["label_over_compact"] = round(d["label_posteriors_compact"]["ms"] / d["posteriors_compact"]["ms"], 3)
                 d["output_bytes"]["label_posteriors_compact"] = 4 * lelems
@@ -234,6 +260,18 @@ def main():
                                                         abi.ptr(count), abi.ptr(out_s), abi.ptr(wss), nbs, s))
 
         fns = dict(best_path=fns["best_path"], posteriors_compact=compact, posteriors_sparse=sparse)
+        if args.checkpoint is not None:
+            with abi.option("align_checkpoint", args.checkpoint):
+                nbs_k = int(lib.tdnnf_align_posteriors_sparse_workspace_bytes(ag.h, B, ug[1], frames[1], K))
+            pdf_k, post_k = torch.zeros(B * T, K, dtype=torch.int32, device="cuda"), torch.zeros(B * T, K, device="cuda")
+            count_k, out_k = torch.zeros(B * T, dtype=torch.int32, device="cuda"), torch.zeros(B, 4, dtype=torch.float64, device="cuda")
+
+            def sparse_checkpoint():
+                with abi.option("align_checkpoint", args.checkpoint):
+                    abi.check(lib.tdnnf_align_posteriors_sparse(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, float(floor), K, abi.ptr(pdf_k),
+                                                                abi.ptr(post_k), abi.ptr(count_k), abi.ptr(out_k), abi.ptr(wss), nbs_k, s))
+
+            fns["posteriors_sparse_checkpoint"] = sparse_checkpoint
         if args.labels:
             nbl = int(lib.tdnnf_align_label_posteriors_sparse_workspace_bytes(ag.h, B, ug[1], frames[1], K))
             wsl = abi.workspace(nbl)
@@ -257,6 +295,12 @@ def main():
                  truncated_frames=int(rs[:, 2].sum()), most_candidates=int(rs[:, 3].max()))
         for k, v in ms.items():
             d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v], us_per_frame=round(1e3 * float(np.median(v)) / T, 3))
+        if args.checkpoint is not None:
+            d["checkpoint"] = args.checkpoint
+            d["workspace_bytes"]["posteriors_sparse_checkpoint"] = nbs_k
+            d["checkpoint_over_sparse"] = round(d["posteriors_sparse_checkpoint"]["ms"] / d["posteriors_sparse"]["ms"], 3)
+            d["checkpoint_same_bits"] = bool(torch.equal(pdf_k, pdf) and torch.equal(post_k.view(torch.int32), post.view(torch.int32))
+                                             and torch.equal(count_k, count) and torch.equal(out_k.view(torch.int64), out_s.view(torch.int64)))
         d["selection_ms"] = round(d["posteriors_sparse"]["ms"] - d["posteriors_compact"]["ms"], 3)
         d["sparse_over_compact"] = round(d["posteriors_sparse"]["ms"] / d["posteriors_compact"]["ms"], 3)
         if args.labels:
@@ -295,6 +339,45 @@ def main():
         d["pairs"] = dict(posteriors_compact=int(sum(len(a[0]) for a in want)), posteriors_sparse=int(count.sum().item()))
         return d
 
+    def long_case():
+        """4 utterances of 20 000 frames, each on its own transcript graph of 1 200 units, through the compact call: what alpha of every frame
+        would need, and -- under --checkpoint -- the call in the checkpointed workspace"""
+        B, TL = 4, 20000
+        lrng = np.random.default_rng(1)
+        lgraphs = [pkg.synth.make_alignment_graph(lrng.integers(0, P, size=1200).tolist(), optional=list(range(5, 1200, 10)),
+                                                  alternatives={k: lrng.integers(0, P, size=12).tolist() for k in range(3, 1200, 8)}, num_pdfs=P, seed=u)
+                   for u in range(B)]
+        lag = abi.AlignGraphs(lgraphs, num_pdfs=P)
+        frames, rows, ug = abi.iarr([TL] * B), abi.iarr(np.arange(B) * TL), abi.iarr(np.arange(B))
+        nb0 = int(lib.tdnnf_align_posteriors_workspace_bytes(lag.h, B, ug[1], frames[1], 1))
+        d = dict(utterances=B, frames=TL, states_per_graph=int(np.mean(lag.num_states)), workspace_bytes=nb0)
+        if not args.checkpoint:
+            d["skipped"] = "alpha of every frame: %d bytes of workspace; run with --checkpoint" % nb0
+            return d
+        with abi.option("align_checkpoint", args.checkpoint):
+            nb_k = int(lib.tdnnf_align_posteriors_workspace_bytes(lag.h, B, ug[1], frames[1], 1))
+        y = torch.randn(B * TL, P, device="cuda")
+        ws = abi.workspace(nb_k)
+        elems = int(lag.posteriors_compact_layout(frames[0], ug[0])[-1])
+        values = torch.zeros(elems, device="cuda")
+        out = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+        s = abi.stream()
+
+        def compact_checkpoint():
+            with abi.option("align_checkpoint", args.checkpoint):
+                abi.check(lib.tdnnf_align_posteriors_compact(lag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, abi.ptr(values), elems, abi.ptr(out),
+                                                             abi.ptr(ws), nb_k, s))
+
+        compact_checkpoint()
+        torch.cuda.synchronize()
+        ms = [timed(compact_checkpoint, args.calls) for _ in range(args.repeats)]
+        r = out.cpu().numpy()
+        d.update(checkpoint=args.checkpoint, workspace_bytes_checkpoint=nb_k, ok=int(r[:, 1].sum()), output_bytes=4 * elems,
+                 posteriors_compact_checkpoint=dict(ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms],
+                                                    us_per_frame=round(1e3 * float(np.median(ms)) / TL, 3)),
+                 mass_per_frame=round(float(values.sum(dtype=torch.float64).item()) / (B * TL), 9))
+        return d
+
     # forced alignment: transcripts of 120 units with optional units and alternative branches -- a few hundred states each
     graphs = [pkg.synth.make_alignment_graph(rng.integers(0, P, size=120).tolist(), optional=list(range(5, 120, 10)),
                                              alternatives={k: rng.integers(0, P, size=12).tolist() for k in range(3, 120, 8)}, num_pdfs=P, seed=u,
@@ -320,6 +403,10 @@ def main():
     res["free"].update(ag.info())
     if args.posteriors:
         res["metric"] = "align_posteriors"
+        if args.compact:
+            del y, ag
+            torch.cuda.empty_cache()
+            res["long"] = long_case()
         print(json.dumps(res))
         return
     # the yardstick: the objective-only chain computation (forward recursions only) on the same graph and shape, rows read as a t-major minibatch
