@@ -98,6 +98,19 @@ int tdnnf_get_option(const char *name, int *value_out);
    Counting never changes a decision and never synchronises. */
 int tdnnf_gemm_launch_forms(long long *counts, int capacity, int reset);
 const char *tdnnf_gemm_launch_form_name(int index);
+/* the same for the trainer's fused BatchNorm / ReLU sweeps (one count per call of the sweep, none per kernel thread):
+     "apply_bypass.<vec4|scalar|planes>[.super][.mask][.rev]"  the forward pass out = BN(x) * mask + bypass * prev: the kernel instance (16-byte
+         accesses, float by float, vec4 with the f16 plane stores), whether the view was a super row, a dropout mask was given, the walk reversed;
+     "bwd.reduce.<vec4|scalar>.<stats|nostats>"  the backward sweep's reduction, with or without the ReLU statistics;
+     "bwd.finalize.<train|test>"  its finalize launch (test: the BatchNorm is in test mode);
+     "bwd.apply.<vec4|scalar|planes>[.mask][.rev]"  its apply launch; "bwd.apply.rows_unrolled" / "bwd.apply.rows_tail": those apply launches in
+         which some row lane runs the 16-row unrolled loop / the 4-row tail loop; "bwd.apply.short_last_chunk": whose last row chunk is short;
+     "bwd.apply_ng.nt<1|2|3>[.mask][.planes][.rev]"  the apply launch that carries the natural-gradient statistic, by the output rank's class
+         (up to 32, 64, 96); "bwd.apply_ng.partial_block" / "bwd.apply_ng.full_blocks": its last 128-row block was partial / every block whole;
+     "bwd.repair"  backward sweeps called with the self-repair term on.
+   Arguments and return value as tdnnf_gemm_launch_forms. */
+int tdnnf_fused_launch_forms(long long *counts, int capacity, int reset);
+const char *tdnnf_fused_launch_form_name(int index);
 
 /* ---- TdnnDARTSV3Component coefficient flags (nnet-tdnn-component.cc:150-163) */
 #define TDNNF_DARTS_USE_GUMBEL 1
@@ -983,7 +996,7 @@ int tdnnf_net_phase_times(tdnnf_net *, double *ms_out, int capacity, int *count)
 /* debugging / parity: on != 0 makes the following forward_backward calls keep copies of the backward pass's derivative
    matrices (which otherwise live in recycled scratch): "<layer>.noop.deriv" (w.r.t. the layer output), "<layer>.affine.deriv",
    "<layer>.linear.deriv" (w.r.t. those components' outputs), "prefinal-l.deriv", "prefinal-{chain,xent}.{batchnorm2,linear,
-   batchnorm1,affine}.deriv", "output-xent.deriv"; served by tdnnf_net_get_activation.  Costs memory and copies: tests only. */
+   batchnorm1,affine}.deriv", "output-xent.deriv", "tdnn1.batchnorm.deriv", "tdnn1.affine.deriv"; served by tdnnf_net_get_activation.  Costs memory and copies: tests only. */
 int tdnnf_net_set_capture(tdnnf_net *, int on);
 /* debugging / parity: copy an internal activation by name ("tdnnf2.linear", "output", ...) into out */
 int tdnnf_net_get_activation(const tdnnf_net *, const char *name, tdnnf_mat *out, tdnnf_stream);

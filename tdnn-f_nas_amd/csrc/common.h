@@ -49,7 +49,8 @@ inline bool vec4_ok(const MatView &m) {
 // the test hooks by the tests that name them; den_split and xent_behind_den at 0 and 1 by the trainer test that names them
 // (tests/test_gpu_net.py: a small net under den_split x xent_behind_den x wgrad_stream), and den_split 0's kernels stand-alone as
 // denominator mode 4 (tests/test_gpu_chain_hostile.py, tests/test_gpu_parity.py).  The trainer's other scheduling options (ng_early_fork,
-// wgrad_lag, wgrad_on_caller, reverse_passes, ng_pform, ng_early_in, ng_grouped) are tested at their defaults only.  The optimizer step
+// wgrad_lag, wgrad_on_caller, ng_pform, ng_early_in, ng_grouped) are tested at their defaults only; reverse_passes at 0 and 3, bit for bit
+// against each other with the sweeps' own form counters as the witness (tests/test_gpu_backward_layers.py).  The optimizer step
 // behind them (tdnnf_net_update: optim_group.hip, net_update.hip) has no option; tests/test_gpu_net_update.py holds it per component and
 // per element to float64: max-change regimes, the orthonormal step's regimes and tile / split-K edges, the tall-matrix path.
 struct Options {

@@ -18,6 +18,7 @@
 #include "ew_dev.h"
 #include "fused.h"
 #include "gemm_f32.h"
+#include "launch_forms.h"
 #include "planes_gemm.h"
 
 namespace tdnnf {
@@ -467,8 +468,11 @@ hipError_t bn_apply_bypass(MatView x, const float *memo, int D, int period, MatV
   if (planes && !(vec && x.cols == D && D % 32 == 0 && planes->P && planes->rec)) return hipErrorInvalidValue;
   ProfHbmRange prof(4, 4.0 * x.rows * x.cols * ((prev.data ? 3.0 : 2.0) + (planes ? 1.0 : 0.0)), s);  // reads x [and the bypass rows], writes out [and its planes]
   const PlanesSink none{nullptr, 0, nullptr};
+  const int rev = vec && !planes ? options().reverse_passes & 1 : 0;
+  count_fused(kFusedBypassFirst + (planes ? kFusedPlanes : vec ? kFusedVec4 : kFusedScalar) * 8 + (x.cols > D ? kFusedFlagSuper : 0) + (mask ? kFusedFlagMask : 0) +
+              (rev ? kFusedFlagRev : 0));
   if (planes) hipLaunchKernelGGL((bn_apply_bypass_kernel<4, true>), dim3(grid_for((long long)((x.rows + 7) / 8) * 8 * (x.cols / 4), 256)), dim3(256), 0, s, x, memo, memo + 2 * D, D, period, prev, bypass, out, mask, B, *planes, 0);
-  else if (vec) hipLaunchKernelGGL((bn_apply_bypass_kernel<4, false>), dim3(grid_for(work, 256)), dim3(256), 0, s, x, memo, memo + 2 * D, D, period, prev, bypass, out, mask, B, none, options().reverse_passes & 1);
+  else if (vec) hipLaunchKernelGGL((bn_apply_bypass_kernel<4, false>), dim3(grid_for(work, 256)), dim3(256), 0, s, x, memo, memo + 2 * D, D, period, prev, bypass, out, mask, B, none, rev);
   else hipLaunchKernelGGL((bn_apply_bypass_kernel<1, false>), dim3(grid_for(work, 256)), dim3(256), 0, s, x, memo, memo + 2 * D, D, period, prev, bypass, out, mask, B, none, 0);
   return hipGetLastError();
 }
@@ -511,6 +515,9 @@ hipError_t bn_relu_bwd(MatView x, MatView dz, float *memo, float target_rms, boo
   float *bias_partial = partial + 5 * (size_t)pl.chunks * D;     // column sums of d_aff
   // Order as in the reference: StoreStats runs with the forward pass, RepairGradients in Backprop sees the
   // statistics including this minibatch (when it was stored).
+  count_fused(kFusedReduceFirst + (vec ? 0 : 2) + (store_relu_stats ? 1 : 0));
+  count_fused(bn_test_mode ? kFusedFinalizeTest : kFusedFinalizeTrain);
+  if (self_repair) count_fused(kFusedRepair);
   if (store_relu_stats) {
     if (vec) hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<4, true>), grid, block, 0, s, x, dz, memo, memo + 2 * D, pl.rows_per_chunk, pl.chunks, partial, mask, B);
     else hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<1, true>), grid, block, 0, s, x, dz, memo, memo + 2 * D, pl.rows_per_chunk, pl.chunks, partial, mask, B);
@@ -539,14 +546,18 @@ hipError_t bn_relu_bwd(MatView x, MatView dz, float *memo, float target_rms, boo
     pk = PlanesSink{planes->P, planes->R, planes->rec};
     pk_lead = planes->lead;
   }
+  const int rev = (options().reverse_passes >> 1) & 1;
   if (ng) {
     const int blocks = (x.rows + 127) / 128;
+    count_fused(kFusedNgFirst + (ng->Rp <= 32 ? 0 : ng->Rp <= 64 ? 1 : 2) * 8 + (mask ? kFusedNgFlagMask : 0) + (pk.P ? kFusedNgFlagPlanes : 0) +
+                (rev ? kFusedNgFlagRev : 0));
+    count_fused(x.rows % 128 ? kFusedNgPartialBlock : kFusedNgFullBlocks);
 #define APPLY_NG(NT)                                                                                                                                     \
   do {                                                                                                                                               \
-    if (pk.P && mask) hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, true, true>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, (options().reverse_passes >> 1) & 1); \
-    else if (pk.P) hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, false, true>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, (options().reverse_passes >> 1) & 1); \
-    else if (mask) hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, true, false>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, (options().reverse_passes >> 1) & 1); \
-    else hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, false, false>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, (options().reverse_passes >> 1) & 1);    \
+    if (pk.P && mask) hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, true, true>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, rev); \
+    else if (pk.P) hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, false, true>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, rev); \
+    else if (mask) hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, true, false>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, rev); \
+    else hipLaunchKernelGGL((bn_relu_bwd_apply_ng_kernel<NT, false, false>), dim3(blocks), block, 0, s, x, dz, memo, D, rep, self_repair_scale, d_aff, bias_partial, mask, B, *ng, pk, pk_lead, rev);    \
   } while (0)
     if (ng->Rp <= 32) APPLY_NG(1);
     else if (ng->Rp <= 64) APPLY_NG(2);
@@ -554,9 +565,23 @@ hipError_t bn_relu_bwd(MatView x, MatView dz, float *memo, float target_rms, boo
 #undef APPLY_NG
     return bias_acc ? colsum_finalize(bias_partial, blocks, D, bias_scale, bias_acc, s) : hipGetLastError();
   }
-  if (pk.P) hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<4, true>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, (options().reverse_passes >> 1) & 1);
-  else if (vec) hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<4, false>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, (options().reverse_passes >> 1) & 1);
-  else hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<1, false>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, (options().reverse_passes >> 1) & 1);
+  count_fused(kFusedApplyFirst + (pk.P ? kFusedPlanes : vec ? kFusedVec4 : kFusedScalar) * 4 + (mask ? 1 : 0) + (rev ? 2 : 0));
+  {  // which of the apply kernel's two row loops some lane of some chunk runs: lane tr of a chunk of n rows has ceil((n - tr) / 4) rows
+    const int last = x.rows - (pl.chunks - 1) * pl.rows_per_chunk;
+    bool unrolled = false, tail = false;
+    for (int n : {pl.chunks > 1 ? pl.rows_per_chunk : last, last})
+      for (int tr = 0; tr < 4 && tr < n; tr++) {
+        const int m = (n - tr + 3) / 4;
+        unrolled |= m >= 4;
+        tail |= m % 4 != 0;
+      }
+    if (unrolled) count_fused(kFusedApplyUnrolled);
+    if (tail) count_fused(kFusedApplyTail);
+    if (pl.chunks > 1 && last < pl.rows_per_chunk) count_fused(kFusedApplyShortChunk);
+  }
+  if (pk.P) hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<4, true>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, rev);
+  else if (vec) hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<4, false>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, rev);
+  else hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<1, false>), grid, block, 0, s, x, dz, memo, D, rep, self_repair_scale, pl.rows_per_chunk, pl.chunks, d_aff, bias_partial, mask, B, pk, pk_lead, rev);
   return bias_acc ? colsum_finalize(bias_partial, pl.chunks, D, bias_scale, bias_acc, s) : hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // launch_forms.h -- process-wide counters of the kernel and launch form the GEMM planners chose (tdnnf_gemm_launch_forms,
-// include/tdnnf_hip.h).  Observation only: nothing reads them back into a decision, counting is one relaxed atomic add on the host.
+// include/tdnnf_hip.h) and of the forms of the fused BatchNorm / ReLU sweeps (tdnnf_fused_launch_forms).  Observation only: nothing reads them back into a decision, counting is one relaxed atomic add on the host.
 #pragma once
 #include <atomic>
 
@@ -52,5 +52,28 @@ std::atomic<long long> *launch_form_counters();  // kLaunchFormCounters of them
 inline void count_form(int index) { launch_form_counters()[index].fetch_add(1, std::memory_order_relaxed); }
 inline void note_rows_slices(int ksplit) { launch_form_counters()[kRowsLastSlices].store(ksplit, std::memory_order_relaxed); }
 inline void note_wgrad_slabs(int splits) { launch_form_counters()[kWgradLastSlabs].store(splits, std::memory_order_relaxed); }
+
+// ---- the fused BatchNorm / ReLU sweeps (fused.hip): counters of their own (tdnnf_fused_launch_forms), one add per call of the host
+// functions bn_apply_bypass / bn_relu_bwd for every property of the launch below
+enum { kFusedVec4, kFusedScalar, kFusedPlanes, kFusedKinds };  // the kernel instance: 16-byte accesses, float by float, or vec4 with the f16 plane stores
+constexpr int kFusedFlagSuper = 1, kFusedFlagMask = 2, kFusedFlagRev = 4;  // bn_apply_bypass: super-row view, dropout mask given, reversed walk
+constexpr int kFusedNgFlagMask = 1, kFusedNgFlagPlanes = 2, kFusedNgFlagRev = 4;
+enum FusedForm {
+  kFusedBypassFirst,                                      // + kind * 8 + flags (kFusedFlag*)
+  kFusedReduceFirst = kFusedBypassFirst + kFusedKinds * 8,  // + (scalar ? 2 : 0) + (ReLU statistics ? 1 : 0)
+  kFusedFinalizeTrain = kFusedReduceFirst + 4,
+  kFusedFinalizeTest,
+  kFusedApplyFirst,                                       // + kind * 4 + (mask ? 1 : 0) + (reversed ? 2 : 0)
+  kFusedApplyUnrolled = kFusedApplyFirst + kFusedKinds * 4,  // apply launches in which some row lane runs the 16-row unrolled loop ...
+  kFusedApplyTail,                                        // ... and the 4-row tail loop
+  kFusedApplyShortChunk,                                  // ... whose last chunk of rows is shorter than the others
+  kFusedNgFirst,                                          // + (NT - 1) * 8 + flags (kFusedNgFlag*)
+  kFusedNgPartialBlock = kFusedNgFirst + 3 * 8,           // apply-ng launches whose last 128-row block is partial / that have none
+  kFusedNgFullBlocks,
+  kFusedRepair,                                           // bn_relu_bwd calls with the self-repair term switched on
+  kFusedFormCounters
+};
+std::atomic<long long> *fused_form_counters();  // kFusedFormCounters of them
+inline void count_fused(int index) { fused_form_counters()[index].fetch_add(1, std::memory_order_relaxed); }
 
 }  // namespace tdnnf

@@ -428,7 +428,9 @@ int Step::backward_trunk() {
     FroBound fb_d;
     PlanesOperand po_d;
     tdnnf_mat d_aff = M(d_cur, N0, Hd);
+    CK(capture("tdnn1.batchnorm.deriv", d_aff));
     CK(bn_relu_backward(n->t1_relu, d_aff, d_aff, 0, n->t1_bn_memo, n->t1_relu_stats, bias_target(n->tdnn1.comp), n->tdnn1.comp, 0, mask_of(0), &fb_d, &po_d));
+    CK(capture("tdnn1.affine.deriv", d_aff));
     if (!po_d.base) CK(split(d_aff, 0, kT, &po_d, s, fb_d));
     CK(affine_grad(n->tdnn1.comp, po_d, po_lda, &lda_out, &d_aff, true));
   }

@@ -189,6 +189,16 @@ def launch_forms(reset=False):
     return {lib.tdnnf_gemm_launch_form_name(i).decode(): int(counts[i]) for i in range(n) if counts[i]}
 
 
+def fused_forms(reset=False):
+    """{name: count} of the non-zero counters of the fused BatchNorm / ReLU sweeps' forms (tdnnf_fused_launch_forms); reset: clear them
+    all afterwards."""
+    lib = load()
+    n = lib.tdnnf_fused_launch_forms(None, 0, 0)
+    counts = (C.c_longlong * n)()
+    lib.tdnnf_fused_launch_forms(counts, n, 1 if reset else 0)
+    return {lib.tdnnf_fused_launch_form_name(i).decode(): int(counts[i]) for i in range(n) if counts[i]}
+
+
 def chain_split_region_bytes(den_graph, num_sequences, frames_per_sequence):
     """Diagnostics (tdnnf_chain_split_region_bytes): the bytes at the end of the chain workspace that only the denominator's side-by-side
     recursions and their occupancy pass touch -- what a trainer under option den_split 0 leaves out.  Follows tdnnf_chain_set_denominator_mode."""

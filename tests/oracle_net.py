@@ -376,6 +376,7 @@ class OracleNet:
         grads = np.zeros_like(p)
         acts = {}
         self.relu_ties = {}
+        self.relu_near_zero = {}
 
         def relu_of(name, a):
             """ReLU.  relu_like (optional): {name: another implementation's ReLU output of the same matrix}.  A pre-activation
@@ -384,6 +385,9 @@ class OracleNet:
             (1e-3 at 10^6 elements).  Such ties are not a difference in arithmetic: they are taken over from relu_like
             (only where this side's pre-activation is itself within rounding of zero) and counted in self.relu_ties."""
             r = np.maximum(a, 0)
+            # (this side's own count of pre-activations a tie could be handed over at: what tests/test_backward_ref64.py caps per seed)
+            tie_tol = getattr(self, "relu_tie_tol", 1e-4) * float(np.sqrt((a.astype(np.float64) ** 2).mean()))
+            self.relu_near_zero[name] = (int((np.abs(a) <= tie_tol).sum()), a.size)
             if relu_like is not None and name in relu_like:
                 other = relu_like[name]
                 mism = (r > 0) != (other > 0)
@@ -607,6 +611,8 @@ class OracleNet:
         d_bn = d_cur if masks is None else (d_cur * self._mask_rows(masks[0], N0)).astype(F)
         d_relu = self._bn_bwd(t1_bn_pre, d_bn, t1_memo)
         d_aff = relu_bwd("tdnn1", t1_relu, d_relu)
+        # (as .noop.deriv above: the derivative in front of the sweep is the one w.r.t. the masked BatchNorm output, the mask is the sweep's)
+        acts["tdnn1.batchnorm.deriv"], acts["tdnn1.affine.deriv"] = d_cur, d_aff
         affine_bwd(lda, d_aff, W1, "tdnn1.affine", want_dx=False)
         res = dict(objf=objf.value, l2_term=l2t.value, weight=w.value, ok=ok, xent_objf=xent_objf)
         return res, grads, acts

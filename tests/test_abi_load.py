@@ -14,7 +14,20 @@ def test_library_exports_every_declared_symbol(pkg):
     out = subprocess.run(["nm", "-D", "--defined-only", pkg.hipabi.LIB_PATH], capture_output=True, text=True).stdout
     exported = {l.split()[-1] for l in out.splitlines() if l.strip()}
     assert set(names) <= exported, sorted(set(names) - exported)
+    assert {"tdnnf_gemm_launch_forms", "tdnnf_gemm_launch_form_name", "tdnnf_fused_launch_forms", "tdnnf_fused_launch_form_name"} <= set(names)
     assert lib.tdnnf_abi_version() == 1
+
+
+def test_fused_form_counters_are_named_and_start_at_zero(pkg):
+    """tdnnf_fused_launch_forms needs no GPU: every counter has a name of its own, none outside the range, and nothing has counted."""
+    lib = pkg.hipabi.load()
+    n = lib.tdnnf_fused_launch_forms(None, 0, 1)
+    names = [lib.tdnnf_fused_launch_form_name(i).decode() for i in range(n)]
+    assert n > 0 and len(set(names)) == n and lib.tdnnf_fused_launch_form_name(n) is None and lib.tdnnf_fused_launch_form_name(-1) is None
+    for want in ("apply_bypass.vec4.super.mask.rev", "apply_bypass.planes", "bwd.reduce.scalar.nostats", "bwd.finalize.test", "bwd.apply.planes.mask.rev",
+                 "bwd.apply.rows_tail", "bwd.apply_ng.nt3.mask.planes.rev", "bwd.apply_ng.partial_block", "bwd.repair"):
+        assert want in names, want
+    assert pkg.hipabi.fused_forms() == {}
 
 
 def test_one_hip_runtime_per_process():
