@@ -73,6 +73,12 @@ int tdnnf_abi_version(void);
                      workspace questions.  Read by tdnnf_align_posteriors_workspace_bytes (want_posteriors != 0) and by tdnnf_align_posteriors
                      (post_out != NULL), tdnnf_align_posteriors_compact, the sparse and the label posterior entries and their workspace
                      questions alike: set it before both.  Ignored where no alpha is kept (want_posteriors = 0, post_out == NULL)
+     "align_path_checkpoint"  0 (default) best-path alignment keeps one back-pointer per (frame, state) in the workspace; C >= 1: the state
+                     scores of every C-th frame and the back-pointers of C frames at a time, and the trace-back recomputes each earlier segment
+                     of C frames from its checkpoint -- the same path, score and ok flag, up to one more sweep over the arcs; -1: C =
+                     ceil(sqrt(frames of the call's longest utterance)).  Anything else: TDNNF_EINVAL from the calls, 0 from the workspace
+                     question.  Read by tdnnf_align_workspace_bytes, tdnnf_align_best_path and tdnnf_align_best_path_labels alike: set it
+                     before both.  Not read by the posterior entries, as "align_checkpoint" is not read by the best path
      "num_frontier_cap": test hook (0 = off): frames of more states than this keep the wide form's frontier in global memory
      "gemm_arith_test": test hook (0 = off): 1 / 3 = the stand-alone GEMM entries (tdnnf_tdnn_*, tdnnf_affine_*) run the in-kernel split-bf16
                      kernels (bf16x3 / bf16x6) wherever exact f32 would be their default; the natural-gradient statistics and the orthonormal
@@ -435,7 +441,19 @@ int tdnnf_chain_numerator_part(const tdnnf_den_graph *, const tdnnf_supervision 
  * tdnnf_align_workspace_bytes and tdnnf_align_best_path alike: set it before both).  The workgroup has 64 threads when the largest graph
  * that an utterance of the call names has at most 64 states, 256 up to 1024 states, 1024 above.  In the LDS form the output row of the
  * next frame is loaded coalesced one frame ahead and gathered from LDS where two rows of num_pdfs floats fit beside the vectors and
- * num_pdfs <= 8 * threads; otherwise y[t, pdf] is gathered from global memory.  Same results either way. */
+ * num_pdfs <= 8 * threads; otherwise y[t, pdf] is gathered from global memory.  Same results either way.
+ *
+ * Back-pointer checkpointing (option "align_path_checkpoint", default 0 = off; read by the workspace question and by both calls: set it
+ * before both).  The back-pointers are 4 * T * S bytes an utterance.  With an interval C >= 1 (or -1: one C for the call,
+ * ceil(sqrt(its longest utterance's frames)), at least 1; a C above the longest utterance counts as that length) an utterance is cut into
+ * the segments [kC, min(kC + C, T)); the forward pass stores alpha_kC of every segment start -- one CHECKPOINT of S doubles -- and keeps
+ * back-pointers only in a buffer of min(C, T) frames, each segment over the one before.  The trace-back walks the last segment as the
+ * forward pass left it, then for every earlier segment, from the last to the first, reloads its checkpoint, reruns its C frames into the
+ * buffer and walks on; the chosen arc of every frame goes to a path of T ints.  The rerun is the forward pass's own step on the same
+ * doubles in the same order: pdfs, states, labels, arcs, score and ok flag are those of option 0, in every form
+ * (tests/test_gpu_align_checkpoint.py).  T <= C is one segment and recomputes nothing.  The arcs are swept 2 - 1/ceil(T / C) times where
+ * option 0 sweeps them once; measured 1.7 x (64 x 500 frames on 301-state transcript graphs) and 1.9 x (128 x 500 on the 4 000-state
+ * graph) the option-0 time at -1.  At C = 1 the region is LARGER than option 0's (8 S T against 4 S T bytes): the caller chooses. */
 typedef struct tdnnf_align_graphs tdnnf_align_graphs; /* device-resident set of graphs */
 
 /* host arrays in, device copy out.  States are numbered as tdnnf_supervision_create numbers a sequence's: graph g owns the states
@@ -462,7 +480,12 @@ int tdnnf_align_graphs_info(const tdnnf_align_graphs *, int graph, int *num_stat
 /* utt_graph[u] (host) names the graph of utterance u -- many utterances may share one; NULL: graph 0 if there is one graph, else graph u
    (then num_utts must be num_graphs).  utt_frames[u] >= 0.  With S_u the states of utterance u's graph:
      bytes = 16 + roundup(32 * num_utts, 256) + 4 * sum_u roundup(utt_frames[u] * S_u, 2)  [+ 16 * sum_u S_u in the workspace form]
-   (alignment slack; the per-utterance table; one back-pointer per (frame, state); the two state vectors).  0 for bad arguments. */
+   (alignment slack; the per-utterance table; one back-pointer per (frame, state); the two state vectors).  0 for bad arguments.
+   Under option "align_path_checkpoint" with the interval C, K_u = ceil(utt_frames[u] / C) (0 for no frames) and B_u = min(C, utt_frames[u]):
+     bytes = 16 + roundup(32 * num_utts, 256) + sum_u [ 8 * K_u * S_u + 4 * roundup(B_u * S_u, 2) + 4 * roundup(utt_frames[u], 2) ]
+                                              [+ 16 * sum_u S_u in the workspace form]
+   (the checkpoints; the segment buffer; the path) -- 20 000 frames on 3 001 states at -1 (C = 142): 5.2 MB against 240 MB; 128 x 500 frames
+   on 4 000 states at -1 (C = 23): 137 MB against 1 GB.  0 for an option below -1 as well. */
 size_t tdnnf_align_workspace_bytes(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames);
 /* Frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output (which may be a sub-matrix view): row_stride 1 reads the
    concatenated utterances tdnnf_infer_compute writes, row_stride B a t-major minibatch of B sequences (utt_row_begin[u] = u).
@@ -482,7 +505,8 @@ int tdnnf_align_best_path(const tdnnf_align_graphs *, int num_utts, const int *u
                        over the graphs (subtract graph_arc_begin[g] for the index within graph g);
      label_out_dev[t]  arc_label of that arc.
    Both are -1 for every frame of an utterance with ok = 0.  Ties are the best path's: of two parallel arcs that differ only in their label
-   the first in the caller's list is reported.  Every element of both outputs is written, by one thread each.  TDNNF_EINVAL: as
+   the first in the caller's list is reported.  Every element of both outputs is written, by one thread each.  Under option
+   "align_path_checkpoint" the second kernel reads the path the checkpointed trace-back left: the same outputs.  TDNNF_EINVAL: as
    tdnnf_align_best_path, a handle without labels, a null label_out_dev. */
 int tdnnf_align_best_path_labels(const tdnnf_align_graphs *, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                                  int row_stride, const tdnnf_mat *nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev,

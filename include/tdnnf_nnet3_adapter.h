@@ -387,7 +387,9 @@ inline tdnnf_supervision *SupervisionCreateE2e(int num_sequences, int frames_per
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance
-// (score, ok).  workspace: tdnnf_align_workspace_bytes(graphs, num_utts, utt_graph, utt_frames).
+// (score, ok).  workspace: tdnnf_align_workspace_bytes(graphs, num_utts, utt_graph, utt_frames).  Option "align_path_checkpoint"
+// (tdnnf_set_option; back-pointers of C frames at a time, the same path) governs AlignBestPath and AlignBestPathLabels as "align_form" does:
+// the workspace question and the call read it alike.
 template <class CuMat>
 inline void AlignBestPath(const tdnnf_align_graphs *graphs, int num_utts, const int *utt_graph, const int *utt_frames, const int *utt_row_begin,
                           int row_stride, const CuMat &nnet_output, float acoustic_scale, int *pdf_out_dev, int *state_out_dev, double *results_dev,

@@ -2032,7 +2032,9 @@ inline tdnnf_supervision *CreateEnd2EndSupervision(int32 num_sequences, int32 fr
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames
 // ints), score and ok flag into results_dev (two device doubles per utterance), on the hooks' stream.  `workspace` grows to
-// tdnnf_align_workspace_bytes -- one back-pointer per (frame, state) -- and is reused from call to call.
+// tdnnf_align_workspace_bytes -- one back-pointer per (frame, state) -- and is reused from call to call.  Option "align_path_checkpoint"
+// (tdnnf_set_option) governs AlignBestPath and AlignBestPathLabels: each asks for its workspace and calls under the same global option, so
+// with it set the workspace holds the back-pointers of one segment of frames at a time.
 inline void AlignBestPath(const tdnnf_align_graphs *graphs, int32 num_utts, const int32 *utt_graph, const int32 *utt_frames, const int32 *utt_row_begin,
                           const CuMatrixBase &nnet_output, float acoustic_scale, int32 *pdf_out_dev, double *results_dev, Scratch *workspace) {
   const size_t bytes = tdnnf_align_workspace_bytes(graphs, num_utts, utt_graph, utt_frames);

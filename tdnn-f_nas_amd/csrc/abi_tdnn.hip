@@ -87,14 +87,14 @@ static int *option_slot(const char *name) {
   Options &o = options();
   if (!name) return nullptr;
   const struct { const char *n; int *p; } table[] = {{"ng_grouped", &o.ng_grouped}, {"ng_fuse", &o.ng_fuse}, {"ng_early_in", &o.ng_early_in},
-                                                     {"wgrad_stream", &o.wgrad_stream}, {"gemm_ring", &o.gemm_ring}, {"planes", &o.planes}, {"den_split", &o.den_split}, {"phase_events", &o.phase_events}, {"wgrad_lag", &o.wgrad_lag}, {"ng_bk", &o.ng_bk}, {"ng_valu", &o.ng_valu}, {"ng_pform", &o.ng_pform}, {"planes_group", &o.planes_group}, {"xent_behind_den", &o.xent_behind_den}, {"ng_early_fork", &o.ng_early_fork}, {"ng_diag_skip", &o.ng_diag_skip}, {"wgrad_small", &o.wgrad_small}, {"splitk_per_cu", &o.splitk_per_cu}, {"gemm_alt_taps", &o.gemm_alt_taps}, {"reverse_passes", &o.reverse_passes}, {"splitk_partial_round", &o.splitk_partial_round}, {"wgrad_on_caller", &o.wgrad_on_caller}, {"den_mw_test_abort", &o.den_mw_test_abort}, {"planes_check_bound", &o.planes_check_bound}, {"den_gamma_pairs", &o.den_gamma_pairs}, {"num_form", &o.num_form}, {"align_form", &o.align_form}, {"align_checkpoint", &o.align_checkpoint}, {"num_frontier_cap", &o.num_frontier_cap}, {"gemm_arith_test", &o.gemm_arith_test}};
+                                                     {"wgrad_stream", &o.wgrad_stream}, {"gemm_ring", &o.gemm_ring}, {"planes", &o.planes}, {"den_split", &o.den_split}, {"phase_events", &o.phase_events}, {"wgrad_lag", &o.wgrad_lag}, {"ng_bk", &o.ng_bk}, {"ng_valu", &o.ng_valu}, {"ng_pform", &o.ng_pform}, {"planes_group", &o.planes_group}, {"xent_behind_den", &o.xent_behind_den}, {"ng_early_fork", &o.ng_early_fork}, {"ng_diag_skip", &o.ng_diag_skip}, {"wgrad_small", &o.wgrad_small}, {"splitk_per_cu", &o.splitk_per_cu}, {"gemm_alt_taps", &o.gemm_alt_taps}, {"reverse_passes", &o.reverse_passes}, {"splitk_partial_round", &o.splitk_partial_round}, {"wgrad_on_caller", &o.wgrad_on_caller}, {"den_mw_test_abort", &o.den_mw_test_abort}, {"planes_check_bound", &o.planes_check_bound}, {"den_gamma_pairs", &o.den_gamma_pairs}, {"num_form", &o.num_form}, {"align_form", &o.align_form}, {"align_checkpoint", &o.align_checkpoint}, {"align_path_checkpoint", &o.align_path_checkpoint}, {"num_frontier_cap", &o.num_frontier_cap}, {"gemm_arith_test", &o.gemm_arith_test}};
   for (auto &e : table)
     if (strcmp(e.n, name) == 0) return e.p;
   return nullptr;
 }
 int tdnnf_set_option(const char *name, int value) {
   int *p = option_slot(name);
-  TDNNF_REQUIRE(p, "set_option: unknown option '%s' (ng_grouped, ng_fuse, ng_early_in, wgrad_stream, gemm_ring, planes, den_split, align_checkpoint)", name ? name : "(null)");
+  TDNNF_REQUIRE(p, "set_option: unknown option '%s' (ng_grouped, ng_fuse, ng_early_in, wgrad_stream, gemm_ring, planes, den_split, align_checkpoint, align_path_checkpoint)", name ? name : "(null)");
   *p = value;
   return TDNNF_OK;
 }

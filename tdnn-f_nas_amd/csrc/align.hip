@@ -1,5 +1,6 @@
 // align.hip -- best-path alignment (include/tdnnf_hip.h, "best-path alignment") through a tdnnf_align_graphs (align_graphs.hip): sizes and lays
-// out the workspace, launches align_best_path_kernel and, for the labelled call, align_path_labels_kernel behind it (align_kernels.h).
+// out the workspace, launches align_best_path_kernel and, for the labelled call, align_path_labels_kernel behind it (align_kernels.h) -- under
+// option align_path_checkpoint their *_ckpt_kernel twins, which keep the back-pointers of one segment of frames at a time.
 #include "align_kernels.h"
 #include "chain_plan.h"
 
@@ -9,7 +10,10 @@ namespace {
 // What a call runs as and where its arrays lie behind the (16-byte aligned) start of the workspace:
 //   [AlignUtt x num_utts, padded to 256 bytes] [back-pointers: per utterance frames * S ints, padded to an even count]
 //   [global form only: per utterance 2 * S doubles]
+// Under option align_path_checkpoint the second region holds per utterance the checkpoints, the segment buffer and the path of
+// AlignPathCheckpointPlan (align_tables.h) instead, counted in ints as the back-pointers are.
 struct AlignPlan : AlignCall, AlignFormPlan {
+  AlignPathCheckpointPlan ckpt;
   size_t bytes;
 };
 
@@ -20,6 +24,16 @@ int align_plan(const tdnnf_align_graphs *g, const char *call, int num_utts, cons
   if (rc) return rc;
   std::string err;
   TDNNF_REQUIRE(align_form_plan(p->max_states, g->P, options().align_form, false, kLdsBudget, "align: ", p, &err), "%s", err.c_str());
+  int longest = 0;
+  for (const AlignUtt &u : p->utts) longest = std::max(longest, u.frames);
+  TDNNF_REQUIRE(align_path_checkpoint_plan(options().align_path_checkpoint, longest, call, &p->ckpt, &err), "%s", err.c_str());
+  if (p->ckpt.C > 0) {
+    p->frame_elems = 0;
+    for (AlignUtt &u : p->utts) {
+      u.frame_begin = (long long)p->frame_elems;
+      p->frame_elems += p->ckpt.ints(u.frames, g->state_begin[u.graph + 1] - g->state_begin[u.graph]);
+    }
+  }
   if (p->lds) p->vec_doubles = 0;
   p->bytes = 16 + p->desc_bytes + sizeof(int) * p->frame_elems + sizeof(double) * p->vec_doubles;
   return TDNNF_OK;
@@ -28,6 +42,14 @@ int align_plan(const tdnnf_align_graphs *g, const char *call, int num_utts, cons
 template <int NT, bool LDS, bool YLDS>
 int align_launch_form(const AlignPlan &p, int P, const AlignDev &dev, const AlignUtt *utts, const MatView &y, int row_stride, float acoustic_scale, int *bp,
                       double *vecs, int *pdf_out, int *state_out, double *results, hipStream_t s) {
+  if (p.ckpt.C > 0) {  // (the same launch; the interval behind the other arguments)
+    if (LDS)
+      TDNNF_HIP(hipFuncSetAttribute((const void *)align_best_path_ckpt_kernel<NT, LDS, YLDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    hipLaunchKernelGGL((align_best_path_ckpt_kernel<NT, LDS, YLDS>), dim3((int)p.utts.size()), dim3(NT), p.lds_bytes, s, dev, utts, y, row_stride,
+                       acoustic_scale, bp, vecs, pdf_out, state_out, results, p.max_states, P, p.ckpt.C);
+    TDNNF_LAUNCH_CHECK();
+    return TDNNF_OK;
+  }
   if (LDS) TDNNF_HIP(hipFuncSetAttribute((const void *)align_best_path_kernel<NT, LDS, YLDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
   hipLaunchKernelGGL((align_best_path_kernel<NT, LDS, YLDS>), dim3((int)p.utts.size()), dim3(NT), p.lds_bytes, s, dev, utts, y, row_stride, acoustic_scale,
                      bp, vecs, pdf_out, state_out, results, p.max_states, P);
@@ -79,8 +101,12 @@ int align_best_path(const tdnnf_align_graphs *g, const char *who, int num_utts, 
   for (int u = 0; u < num_utts; u++) max_frames = std::max(max_frames, utt_frames[u]);
   const int blocks = (max_frames + kAlignLabelThreads - 1) / kAlignLabelThreads;
   for (int u0 = 0; blocks > 0 && u0 < num_utts; u0 += 65535) {  // (a grid's second dimension ends at 65 535)
-    hipLaunchKernelGGL(align_path_labels_kernel<kAlignLabelThreads>, dim3(blocks, std::min(num_utts - u0, 65535)), dim3(kAlignLabelThreads), 0, s, dev,
-                       utts + u0, bp, results_dev + 2 * (size_t)u0, g->arc_label_dev, label_out_dev, arc_out_dev);
+    if (p.ckpt.C > 0)
+      hipLaunchKernelGGL(align_path_labels_ckpt_kernel<kAlignLabelThreads>, dim3(blocks, std::min(num_utts - u0, 65535)), dim3(kAlignLabelThreads), 0, s,
+                         dev, utts + u0, bp, results_dev + 2 * (size_t)u0, g->arc_label_dev, label_out_dev, arc_out_dev, p.ckpt.C);
+    else
+      hipLaunchKernelGGL(align_path_labels_kernel<kAlignLabelThreads>, dim3(blocks, std::min(num_utts - u0, 65535)), dim3(kAlignLabelThreads), 0, s, dev,
+                         utts + u0, bp, results_dev + 2 * (size_t)u0, g->arc_label_dev, label_out_dev, arc_out_dev);
     TDNNF_LAUNCH_CHECK();
   }
   return TDNNF_OK;

@@ -31,7 +31,8 @@ struct AlignUtt {  // one utterance of a call (device table at the head of the w
   int out_begin;          // best path: first element of pdf_out; state_out starts at out_begin + (index of the utterance).  Forward-backward: 0,
                           // compact posteriors: first float of the utterance's block
   long long frame_begin;  // first element of its per-frame region of the workspace: best path -- the back-pointers, frames * S ints padded to an
-                          // even count; forward-backward -- alpha of every frame, (frames + 1) * S doubles (posteriors), or under option
+                          // even count, or under option align_path_checkpoint the checkpoints, the segment buffer and the path
+                          // (AlignPathCheckpointPlan; align.hip align_plan lays it out, still counted in ints); forward-backward -- alpha of every frame, (frames + 1) * S doubles (posteriors), or under option
                           // align_checkpoint the checkpoints and the segment buffer (AlignCheckpointPlan; align_fb.hip fb_plan lays it out)
   long long vec_begin;    // first double of its two state vectors in the workspace's vector region (workspace form)
 };

@@ -31,6 +31,8 @@
 //    behind a barrier the workgroup writes pdf-ids (and states) coalesced.
 //  * labels (align_path_labels_kernel, behind the best path on its stream): bp[t * S] still holds the chosen arc of frame t, whose 4th
 //    int is the caller's arc index; a thread per (utterance, frame) writes that index and the caller's label of the arc.
+//  * option align_path_checkpoint (align_best_path_ckpt_kernel, align_path_labels_ckpt_kernel, at the end): the state scores of every C-th
+//    frame and the back-pointers of C frames at a time; the trace-back recomputes each earlier segment's back-pointers from its checkpoint.
 #pragma once
 #include "align_graphs.h"
 
@@ -239,6 +241,160 @@ __global__ __launch_bounds__(NT) void align_path_labels_kernel(AlignDev g, const
   int arc = -1, label = -1;
   if (results[2 * (size_t)blockIdx.y + 1] != 0.0) {
     const int a = bp_all[u.frame_begin + (long long)t * g.graphs[u.graph].num_states];
+    if (a >= 0) {  // (guarded as the trace-back guards it)
+      arc = g.by_dst.arcs[a].w;
+      label = arc_label[arc];
+    }
+  }
+  label_out[u.out_begin + t] = label;
+  if (arc_out) arc_out[u.out_begin + t] = arc;
+}
+
+// ---- option align_path_checkpoint: back-pointers of one segment of C frames at a time (the layout: align_tables.h AlignPathCheckpointPlan)
+// An utterance's region starts at ints + u.frame_begin (an even count of ints: 8-byte aligned): K = ceil(T / C) checkpoints of S doubles, the
+// segment buffer of min(C, T) * S ints and the path of T ints, buffer and path padded to an even count.
+struct AlignPathRegions {
+  double *ck;  // alpha_kC at ck + k * S
+  int *buf;    // the back-pointers of frame kC + j of the segment last swept at buf + j * S
+  int *path;   // the chosen arc of frame t
+};
+__device__ __forceinline__ AlignPathRegions align_path_regions(int *ints, const AlignUtt &u, int S, int C) {
+  const size_t K = u.frames > 0 ? (size_t)(u.frames - 1) / C + 1 : 0, B = (size_t)min(C, u.frames);
+  AlignPathRegions r;
+  int *base = ints + u.frame_begin;
+  r.ck = reinterpret_cast<double *>(base);
+  r.buf = base + 2 * K * (size_t)S;
+  r.path = r.buf + (B * (size_t)S + 1) / 2 * 2;
+  return r;
+}
+
+// align_best_path_kernel under the option, C >= 1 the interval (at most the call's longest utterance): the same launch, the same arguments
+// and C; bp_all is the per-frame region of the workspace.  The forward pass is the recursion above; at every segment start kC it also
+// stores alpha_kC (the vector it is about to read) to the utterance's checkpoints, coalesced, and its back-pointers go to the segment buffer,
+// each segment over the one before: at the end the buffer holds the last segment's.  The trace-back walks that segment, then for k = K - 2
+// .. 0 the workgroup reloads alpha_kC, reruns the segment's C frames by the forward pass's own step -- max and + in double on the same
+// operands in the same order: the same back-pointers -- and thread 0 walks on from the state it had reached.  The rows of AlignRowStage are
+// primed again at every segment start.  The chosen arcs go to the path region, which the coalesced write of the outputs (and
+// align_path_labels_ckpt_kernel) reads.  T <= C is one segment: nothing is recomputed.  An utterance with ok = 0 writes its -1s and is done.
+// The frame body is written here a second time (and a third, for the rerun) so that align_best_path_kernel's device code is what it was.
+template <int NT, bool LDS, bool YLDS>
+__global__ __launch_bounds__(NT) void align_best_path_ckpt_kernel(AlignDev g, const AlignUtt *utts, MatView y, int row_stride, float acoustic_scale,
+                                                                  int *bp_all, double *vecs, int *pdf_out, int *state_out, double *results, int Smax, int P,
+                                                                  int C) {
+  extern __shared__ double align_smem[];
+  __shared__ double red_v[NT / 64];
+  __shared__ int red_p[NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const AlignUtt u = utts[blockIdx.x];
+  const AlignGraphDev gr = g.graphs[u.graph];
+  const int S = gr.num_states, T = u.frames, s0 = gr.state0;
+  double *cur = LDS ? align_smem : vecs + u.vec_begin, *nxt = cur + S;
+  const AlignPathRegions rg = align_path_regions(bp_all, u, S, C);
+  const double scale = (double)acoustic_scale;
+  AlignRowStage<NT, YLDS> rows(y.data + (size_t)u.row_begin * y.stride, (size_t)row_stride * y.stride, P, T,
+                               reinterpret_cast<float *>(align_smem + 2 * (size_t)Smax));
+  for (int s = tid; s < S; s += NT) cur[s] = (double)g.init[s0 + s];
+  rows.load(0);
+  rows.store(0);
+  rows.load(1);
+  __syncthreads();
+  int last = 0;  // the first frame of the segment whose back-pointers the buffer holds
+  for (int t = 0, j = 0; t < T; t++, j++) {
+    if (j == C) j = 0;
+    if (j == 0) {  // a segment starts: alpha_t (complete behind the last barrier, read-only in this frame) is its checkpoint
+      last = t;
+      double *ck = rg.ck + (size_t)(t / C) * S;
+      for (int s = tid; s < S; s += NT) ck[s] = cur[s];
+    }
+    rows.store(t + 1);
+    rows.load(t + 2);
+    align_step<NT>(g.by_dst, gr.by_dst, cur, rows.row(t), scale, AlignBestAcc{nxt, rg.buf + (size_t)j * S});
+    __syncthreads();
+    double *sw = cur;
+    cur = nxt;
+    nxt = sw;
+  }
+  // the best final state: the lowest state among equal scores
+  double best = -INFINITY;
+  int bs = -1;
+  for (int s = tid; s < S; s += NT) {
+    const double v = cur[s] + (double)g.final[s0 + s];
+    if (v > best) {
+      best = v;
+      bs = s;
+    }
+  }
+  align_wave_best(best, bs);
+  if (lane == 0) {
+    red_v[wave] = best;
+    red_p[wave] = bs;
+  }
+  __syncthreads();
+  best = red_v[0];  // (every thread merges the waves' results alike: what follows branches on them workgroup-wide)
+  bs = red_p[0];
+  for (int w = 1; w < NT / 64; w++) align_merge(best, bs, red_v[w], red_p[w]);
+  const bool ok = bs >= 0 && best < INFINITY;
+  if (tid == 0) {
+    results[2 * (size_t)blockIdx.x] = best;
+    results[2 * (size_t)blockIdx.x + 1] = ok ? 1.0 : 0.0;
+  }
+  int *pdfs = pdf_out + u.out_begin, *states = state_out ? state_out + u.out_begin + blockIdx.x : nullptr;
+  if (!ok) {
+    for (int t = tid; t < T; t += NT) pdfs[t] = -1;
+    if (states)
+      for (int t = tid; t <= T; t += NT) states[t] = -1;
+    return;
+  }
+  const int4 *arcs = g.by_dst.arcs;
+  int st = bs;  // (thread 0's: the state the trace-back has reached)
+  for (int b = last, e = T; e > 0; e = b, b -= C) {  // the segments [b, e) from the last to the first; every b is a multiple of C
+    if (e < T) {
+      // (behind this barrier thread 0 has walked the buffer, and every reader of the state vectors and of the staged rows is done)
+      __syncthreads();
+      const double *ck = rg.ck + (size_t)(b / C) * S;
+      for (int s = tid; s < S; s += NT) cur[s] = ck[s];
+      rows.load(b);
+      rows.store(b);
+      rows.load(b + 1);
+      __syncthreads();
+      for (int t = b; t < e; t++) {
+        rows.store(t + 1);
+        rows.load(t + 2);
+        align_step<NT>(g.by_dst, gr.by_dst, cur, rows.row(t), scale, AlignBestAcc{nxt, rg.buf + (size_t)(t - b) * S});
+        __syncthreads();
+        double *sw = cur;
+        cur = nxt;
+        nxt = sw;
+      }
+    }
+    if (tid == 0) {  // (as in align_best_path_kernel: no -1 on this walk; guarded all the same)
+      for (int t = e - 1; t >= b; t--) {
+        const int a = rg.buf[(size_t)(t - b) * S + st];
+        if (a >= 0) st = arcs[a].x;
+        rg.path[t] = a;
+      }
+    }
+  }
+  __syncthreads();
+  for (int t = tid; t < T; t += NT) {
+    const int a = rg.path[t];
+    const int4 arc = a >= 0 ? arcs[a] : make_int4(-1, -1, 0, -1);
+    pdfs[t] = arc.y;
+    if (states) states[t] = arc.x;
+  }
+  if (states && tid == 0) states[T] = bs;
+}
+
+// align_path_labels_kernel behind align_best_path_ckpt_kernel: the chosen arc of frame t is path[t] of the utterance's region.
+template <int NT>
+__global__ __launch_bounds__(NT) void align_path_labels_ckpt_kernel(AlignDev g, const AlignUtt *utts, int *bp_all, const double *results,
+                                                                    const int *arc_label, int *label_out, int *arc_out, int C) {
+  const AlignUtt u = utts[blockIdx.y];
+  const int t = blockIdx.x * NT + threadIdx.x;
+  if (t >= u.frames) return;
+  int arc = -1, label = -1;
+  if (results[2 * (size_t)blockIdx.y + 1] != 0.0) {
+    const int a = align_path_regions(bp_all, u, g.graphs[u.graph].num_states, C).path[t];
     if (a >= 0) {  // (guarded as the trace-back guards it)
       arc = g.by_dst.arcs[a].w;
       label = arc_label[arc];

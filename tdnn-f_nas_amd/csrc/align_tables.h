@@ -197,6 +197,25 @@ inline bool align_form_plan(int max_states, int num_pdfs, int align_form, bool w
   return true;
 }
 
+// The interval of a checkpointing option (align_checkpoint, align_path_checkpoint: `name`) of value `value`: 0 off, C >= 1 the interval, -1
+// automatic -- the least C with C * C >= max_frames, the call's longest utterance: ceil(sqrt(max_frames)).  An interval is at most that
+// utterance (a longer one cuts no utterance differently) and at least 1.  False and *err (starting with prefix) for any other value.
+inline bool align_checkpoint_interval(const char *name, int value, int max_frames, const char *prefix, int *C, std::string *err) {
+  if (value < -1) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%soption %s must be 0 (off), an interval >= 1 or -1 (automatic), not %d", prefix, name, value);
+    *err = msg;
+    return false;
+  }
+  const int longest = std::max(max_frames, 1);
+  long long c = value;
+  if (value == -1)
+    for (c = 1; c * c < longest; c++) {
+    }
+  *C = (int)std::min<long long>(c, longest);
+  return true;
+}
+
 // Alpha checkpointing of the forward-backward pass (option align_checkpoint; align_fb_kernels.h, CKPT).  With an interval C >= 1 an utterance
 // of T frames is cut into the SEGMENTS [kC, min(kC + C, T)), k = 0 .. ceil(T / C) - 1; its alpha region holds, in this order,
 //   the CHECKPOINTS   alpha_kC, one per segment (alpha_0 alone for T = 0: the forward pass always writes it), then
@@ -215,19 +234,35 @@ struct AlignCheckpointPlan {
 // align_checkpoint (option): 0 off, C >= 1 the interval, -1 automatic: the least C with C * C >= max_frames, the call's longest utterance --
 // ceil(sqrt(max_frames)) -- and at least 1.  False and *err (starting with prefix) for any other value.
 inline bool align_checkpoint_plan(int align_checkpoint, int max_frames, const char *prefix, AlignCheckpointPlan *p, std::string *err) {
-  if (align_checkpoint < -1) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "%soption align_checkpoint must be 0 (off), an interval >= 1 or -1 (automatic), not %d", prefix, align_checkpoint);
-    *err = msg;
-    return false;
+  return align_checkpoint_interval("align_checkpoint", align_checkpoint, max_frames, prefix, &p->C, err);
+}
+
+// Back-pointer checkpointing of the best path (option align_path_checkpoint; align_kernels.h align_best_path_ckpt_kernel).  With an interval
+// C >= 1 an utterance of T frames on a graph of S states is cut into the segments of AlignCheckpointPlan; its region of the workspace holds,
+// in this order,
+//   the CHECKPOINTS    alpha_kC, one vector of S doubles per segment (none for T = 0), written by the forward pass;
+//   the SEGMENT BUFFER of min(C, T) frames of S back-pointers: frame j is the back-pointers of frame kC + j of the segment k that was last
+//                      swept -- after the forward pass the last segment's, then those of the segment the trace-back has recomputed;
+//   the PATH           T ints, the arc chosen for frame t (what option 0 leaves at bp[t * S]).
+// Buffer and path are padded to an even count of ints each, so every region starts on 8 bytes.  C = 0: off, T * S back-pointers (align_call).
+// align_kernels.h (align_path_regions) derives the same three offsets on the device from AlignUtt::frame_begin, T, S and C.
+struct AlignPathCheckpointPlan {
+  int C;  // 0: off; else the interval, at most the call's longest utterance and at least 1
+  int segments(int T) const { return C == 0 || T < 1 ? 0 : (T - 1) / C + 1; }
+  size_t checkpoints(int T) const { return (size_t)segments(T); }
+  size_t buffer_frames(int T) const { return C == 0 ? (size_t)T : (size_t)std::min(C, T); }
+  int segment_begin(int k) const { return k * C; }
+  int segment_end(int T, int k) const { return k * C + std::min(C, T - k * C); }
+  // the utterance's region in ints (4 bytes): 2 per double of a checkpoint
+  size_t ints(int T, int S) const {
+    if (C == 0) return ((size_t)T * (size_t)S + 1) / 2 * 2;
+    return 2 * checkpoints(T) * (size_t)S + (buffer_frames(T) * (size_t)S + 1) / 2 * 2 + ((size_t)T + 1) / 2 * 2;
   }
-  const int longest = std::max(max_frames, 1);
-  long long c = align_checkpoint;
-  if (align_checkpoint == -1)
-    for (c = 1; c * c < longest; c++) {
-    }
-  p->C = (int)std::min<long long>(c, longest);
-  return true;
+};
+
+// align_path_checkpoint (option): the values of align_checkpoint.  False and *err (starting with prefix) for any other value.
+inline bool align_path_checkpoint_plan(int align_path_checkpoint, int max_frames, const char *prefix, AlignPathCheckpointPlan *p, std::string *err) {
+  return align_checkpoint_interval("align_path_checkpoint", align_path_checkpoint, max_frames, prefix, &p->C, err);
 }
 
 }  // namespace tdnnf

@@ -83,6 +83,7 @@ struct Options {
   int num_frontier_cap = 0;  // tests: the wide numerator keeps its frontier in global memory for supervisions with a frame of more states than this (0: what the LDS holds)
   int align_form = 0;       // best-path alignment (align.hip; the rules: align_tables.h align_form_plan): 0 the two state vectors in LDS where 2 * S doubles fit kLdsBudget, in the workspace otherwise; 1 / 2 force LDS / workspace (tests/test_gpu_align.py runs both); read by tdnnf_align_workspace_bytes and tdnnf_align_best_path, and alike by forward-backward (align_fb.hip; tests/test_gpu_posteriors.py runs both)
   int align_checkpoint = 0;  // forward-backward with posteriors (align_fb.hip; the rules: align_tables.h align_checkpoint_plan): 0 alpha of every frame stays in the workspace; C >= 1 alpha of every C-th frame, the backward pass recomputes each segment's from its checkpoint (the same bits; tests/test_gpu_posteriors_checkpoint.py); -1 C = ceil(sqrt(the call's longest utterance)); read by tdnnf_align_posteriors_workspace_bytes and by every posterior call alike
+  int align_path_checkpoint = 0;  // best-path alignment (align.hip; the rules: align_tables.h align_path_checkpoint_plan): 0 one back-pointer per (frame, state) stays in the workspace; C >= 1 the state scores of every C-th frame and the back-pointers of one segment of C frames, the trace-back recomputes each earlier segment's from its checkpoint (the same path; tests/test_gpu_align_checkpoint.py); -1 C = ceil(sqrt(the call's longest utterance)); read by tdnnf_align_workspace_bytes, tdnnf_align_best_path and tdnnf_align_best_path_labels alike
   int den_gamma_pairs = 0;  // the split form's occupancy pass: 1 one (frame, sequence) per workgroup (den_gamma_kernel), 0 two frames per workgroup where their vectors fit the LDS (den_gamma2_kernel)
 };
 Options &options();

@@ -180,6 +180,12 @@ def _checkpoint(value):
     return contextlib.nullcontext() if value is None else option("align_checkpoint", value)
 
 
+def _path_checkpoint(value):
+    """The same for the best-path methods' `checkpoint=` keyword and option align_path_checkpoint."""
+    import contextlib
+    return contextlib.nullcontext() if value is None else option("align_path_checkpoint", value)
+
+
 def launch_forms(reset=False):
     """{name: value} of the non-zero GEMM launch-form counters (tdnnf_gemm_launch_forms); reset: clear them all afterwards."""
     lib = load()
@@ -330,21 +336,28 @@ class AlignGraphs:
         check(load().tdnnf_align_graphs_info(self.h, int(graph), *[C.byref(x) for x in v]))
         return dict(zip(("num_states", "num_arcs", "max_in_degree"), (x.value for x in v)))
 
-    def workspace_bytes(self, utt_graph, utt_frames):
+    def workspace_bytes(self, utt_graph, utt_frames, checkpoint=None):
+        """tdnnf_align_workspace_bytes (0 for a call it refuses).  checkpoint (here and on best_path / best_path_labels): None reads option
+        align_path_checkpoint as it stands; an int (0 off, C >= 1 an interval, -1 automatic) sets it around the workspace question and the
+        call and restores it afterwards -- back-pointers of one segment of C frames at a time, the same path."""
         ug = iarr(utt_graph)[1] if utt_graph is not None else None
-        return int(load().tdnnf_align_workspace_bytes(self.h, len(utt_frames), ug, iarr(utt_frames)[1]))
+        with _path_checkpoint(checkpoint):
+            return int(load().tdnnf_align_workspace_bytes(self.h, len(utt_frames), ug, iarr(utt_frames)[1]))
 
-    def best_path(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, states=False):
+    def best_path(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, states=False, checkpoint=None):
         """tdnnf_align_best_path on the current stream.  Returns (pdf_out int32 [sum frames], state_out int32 [sum frames + utterances]
         or None, results float64 [utterances, 2]) as CUDA tensors; nothing is synchronised."""
-        return self._best_path(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, False)[:3]
+        with _path_checkpoint(checkpoint):
+            return self._best_path(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, False)[:3]
 
-    def best_path_labels(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, states=False):
+    def best_path_labels(self, nnet_output, utt_frames, utt_row_begin, row_stride=1, utt_graph=None, acoustic_scale=1.0, states=False,
+                         checkpoint=None):
         """tdnnf_align_best_path_labels on the current stream.  Returns (pdf_out, state_out or None, results, label_out int32 [sum frames],
         arc_out int32 [sum frames]) as CUDA tensors: best_path's three, the label of the arc taken at every frame and that arc's index
         LOCAL to the utterance's graph dict (the C call's global index minus the graph's first arc); -1 both where ok is 0.  Nothing is
         synchronised."""
-        return self._best_path(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, True)
+        with _path_checkpoint(checkpoint):
+            return self._best_path(nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, True)
 
     def _best_path(self, nnet_output, utt_frames, utt_row_begin, row_stride, utt_graph, acoustic_scale, states, labels):
         import numpy as np

@@ -105,10 +105,10 @@ class AcousticModel:
                                                   hipabi.pmat(out), hipabi.stream()))
         return out, outs
 
-    def align(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
+    def align(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10, checkpoint=None):
         """compute, then the best path of every utterance through its graph (align below); the output stays on the device in between."""
         out, outs = self._compute_stacked(utterances, ivector_period)
-        return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale) if outs else []
+        return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale, checkpoint=checkpoint) if outs else []
 
     def posteriors(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10, checkpoint=None):
         """compute, then forward-backward of every utterance through its graph (posteriors below): [(post [O_u, num_pdfs] CUDA tensor,
@@ -130,10 +130,10 @@ class AcousticModel:
         out, outs = self._compute_stacked(utterances, ivector_period)
         return _posteriors_sparse_stacked(out, outs, graphs, utt_graph, acoustic_scale, weight, min_post, max_per_frame, checkpoint=checkpoint) if outs else []
 
-    def align_labels(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10):
+    def align_labels(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, ivector_period=10, checkpoint=None):
         """compute, then the labelled best path of every utterance through its graph (align_labels below)."""
         out, outs = self._compute_stacked(utterances, ivector_period)
-        return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale, labels=True) if outs else []
+        return _align_stacked(out, outs, graphs, utt_graph, acoustic_scale, labels=True, checkpoint=checkpoint) if outs else []
 
     def label_posteriors_compact(self, utterances, graphs, utt_graph=None, acoustic_scale=1.0, weight=1.0, ivector_period=10, checkpoint=None):
         """compute, then the compact posteriors per label (label_posteriors_compact below): [(labels [L] int32, post [O_u, L] CUDA tensor,
@@ -354,19 +354,22 @@ def write_matrix_archive(path, items):
             f.write(m.tobytes())
 
 
-def align(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
+def align(outputs, graphs, utt_graph=None, acoustic_scale=1.0, checkpoint=None):
     """Best-path alignment (include/tdnnf_hip.h, "best-path alignment") of the model's outputs, a list of O_u x num_pdfs CUDA tensors as
     AcousticModel.compute returns them, through `graphs` (hipabi.AlignGraphs): utterance u takes graph utt_graph[u] -- None: the one
     graph there is, or graph u.  Returns a list of (pdf-ids as torch int32 CUDA tensor, score, ok); an utterance without an accepting
-    path of its length has score -inf, ok False and pdf-ids of -1.  What ali-to-pdf would print; no beam, no lattice."""
+    path of its length has score -inf, ok False and pdf-ids of -1.  What ali-to-pdf would print; no beam, no lattice.  checkpoint (here,
+    on align_labels and on the AcousticModel methods): AlignGraphs.best_path's keyword -- None leaves option align_path_checkpoint as it
+    stands, an int sets it for the call (back-pointers of C frames at a time, -1 automatic: a workspace of O(sqrt(frames)) vectors for
+    whole recordings, the same path)."""
     import torch
     if not outputs:
         return []
     frames = [int(o.shape[0]) for o in outputs]
-    return _align_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale)
+    return _align_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, checkpoint=checkpoint)
 
 
-def align_labels(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
+def align_labels(outputs, graphs, utt_graph=None, acoustic_scale=1.0, checkpoint=None):
     """align with the identity of the path's arcs, through labelled graphs (hipabi.AlignGraphs of graph dicts with "label": a transition-id,
     a phone, a word position per arc).  Returns a list of (pdf-ids, labels, arcs, score, ok): three torch int32 CUDA tensors of O_u
     elements -- per frame the pdf, the label and the index (in the utterance's graph dict) of the arc taken -- all -1 without an accepting
@@ -376,19 +379,19 @@ def align_labels(outputs, graphs, utt_graph=None, acoustic_scale=1.0):
     if not outputs:
         return []
     frames = [int(o.shape[0]) for o in outputs]
-    return _align_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, labels=True)
+    return _align_stacked(torch.cat(list(outputs)).contiguous(), frames, graphs, utt_graph, acoustic_scale, labels=True, checkpoint=checkpoint)
 
 
-def _align_stacked(y, frames, graphs, utt_graph, acoustic_scale, labels=False):
+def _align_stacked(y, frames, graphs, utt_graph, acoustic_scale, labels=False, checkpoint=None):
     """align on the utterances' rows stacked in one matrix (what tdnnf_infer_compute writes): row_stride 1"""
     import torch
     rows = np.concatenate([[0], np.cumsum(frames)[:-1]])
     if labels:
-        pdfs, _, results, lab, arcs = graphs.best_path_labels(y, frames, rows, 1, utt_graph, acoustic_scale)
+        pdfs, _, results, lab, arcs = graphs.best_path_labels(y, frames, rows, 1, utt_graph, acoustic_scale, checkpoint=checkpoint)
         res = results.cpu().numpy()  # (waits for the stream)
         return [(p, l, a, float(res[u, 0]), bool(res[u, 1] == 1.0))
                 for u, (p, l, a) in enumerate(zip(torch.split(pdfs, frames), torch.split(lab, frames), torch.split(arcs, frames)))]
-    pdfs, _, results = graphs.best_path(y, frames, rows, 1, utt_graph, acoustic_scale)
+    pdfs, _, results = graphs.best_path(y, frames, rows, 1, utt_graph, acoustic_scale, checkpoint=checkpoint)
     res = results.cpu().numpy()  # (waits for the stream)
     return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(pdfs, frames))]
 

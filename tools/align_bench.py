@@ -27,8 +27,14 @@ every C-th frame only, -1 for ceil(sqrt(frames)) -- joins the interleaved round 
 the JSON gains both workspace sizes, the time ratio and whether the bits agree.  A third workload, "long": 4 utterances of 20 000 frames,
 each on its own transcript graph of some 3 000 states, through the compact call.  Without --checkpoint (or with 0) it reports the bytes it
 would need and is skipped; with it, it runs in the checkpointed workspace.
+--path-checkpoint C (the best path alone: without --posteriors and --labels): both workloads also run under option
+align_path_checkpoint = C -- back-pointers of C frames at a time, -1 for ceil(sqrt(frames)) -- INTERLEAVED with the option-0 call in one
+process (one repeat of each after the other, medians of --repeats), in the workspace the option asks for; the JSON gains both workspace
+sizes, the time ratio and whether pdf_out and the results are equal.  A third workload, "long": the 4 utterances of 20 000 frames of
+--checkpoint's long case through the best path.  Without --path-checkpoint (or with 0) it reports the bytes it would need and is skipped;
+with it, it runs in the checkpointed workspace and reports ms and us per frame.
 usage (GPU box): python tools/align_bench.py [--repeats R] [--calls K] [--pdfs P] [--form 0|1|2] [--posteriors [--compact | --sparse]]
-                                             [--labels unit|arc] [--checkpoint C]"""
+                                             [--labels unit|arc] [--checkpoint C] [--path-checkpoint C]"""
 import argparse
 import json
 import os
@@ -65,7 +71,10 @@ def main():
     ap.add_argument("--max-per-frame", type=int, default=16, help="--sparse: pairs a frame")
     ap.add_argument("--labels", choices=["unit", "arc"], help="labelled graphs: time the labelled call beside its pdf counterpart")
     ap.add_argument("--checkpoint", type=int, help="with --posteriors --compact | --sparse: option align_checkpoint for a second compact (sparse) call")
+    ap.add_argument("--path-checkpoint", type=int, help="the best path alone: option align_path_checkpoint for a second best-path call, and the long workload")
     args = ap.parse_args()
+    if args.path_checkpoint is not None and (args.posteriors or args.labels):
+        ap.error("--path-checkpoint goes with the best path alone")
     if args.checkpoint is not None and not (args.compact or args.sparse):
         ap.error("--checkpoint goes with --posteriors --compact or --posteriors --sparse")
     if args.labels and args.posteriors and not (args.compact or args.sparse):
@@ -99,6 +108,33 @@ def main():
         torch.cuda.synchronize()
         if args.posteriors:
             return y, posteriors_case(ag, B, y, frames, rows, ug, run, out)
+        if args.path_checkpoint is not None:
+            with abi.option("align_path_checkpoint", args.path_checkpoint):
+                nb_k = int(lib.tdnnf_align_workspace_bytes(ag.h, B, ug[1], frames[1]))
+            ws_k = abi.workspace(nb_k)
+            pdfs_k = torch.zeros(B * T, dtype=torch.int32, device="cuda")
+            out_k = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+
+            def run_checkpoint():
+                with abi.option("align_path_checkpoint", args.path_checkpoint):
+                    abi.check(lib.tdnnf_align_best_path(ag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, abi.ptr(pdfs_k), None, abi.ptr(out_k),
+                                                        abi.ptr(ws_k), nb_k, s))
+
+            run_checkpoint(), run_checkpoint()
+            torch.cuda.synchronize()
+            ms, ms_k = [], []
+            for _ in range(args.repeats):
+                ms.append(timed(run, args.calls))
+                ms_k.append(timed(run_checkpoint, args.calls))
+            r = out.cpu().numpy()
+            d = dict(utterances=B, workspace_bytes=nb, ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms],
+                     us_per_frame=round(1e3 * float(np.median(ms)) / T, 3), ok=int(r[:, 1].sum()), path_checkpoint=args.path_checkpoint,
+                     workspace_bytes_checkpoint=nb_k,
+                     best_path_checkpoint=dict(ms=round(float(np.median(ms_k)), 3), ms_all=[round(v, 3) for v in ms_k],
+                                               us_per_frame=round(1e3 * float(np.median(ms_k)) / T, 3)))
+            d["checkpoint_over_best_path"] = round(d["best_path_checkpoint"]["ms"] / d["ms"], 3)
+            d["checkpoint_equal"] = bool(torch.equal(pdfs_k, pdfs) and torch.equal(out_k.view(torch.int64), out.view(torch.int64)))
+            return y, d
         if args.labels:
             labels = torch.zeros(B * T, dtype=torch.int32, device="cuda")
             arcs = torch.zeros(B * T, dtype=torch.int32, device="cuda")
@@ -339,15 +375,52 @@ def main():
         d["pairs"] = dict(posteriors_compact=int(sum(len(a[0]) for a in want)), posteriors_sparse=int(count.sum().item()))
         return d
 
-    def long_case():
-        """4 utterances of 20 000 frames, each on its own transcript graph of 1 200 units, through the compact call: what alpha of every frame
-        would need, and -- under --checkpoint -- the call in the checkpointed workspace"""
-        B, TL = 4, 20000
+    def long_graphs(B):
+        """B transcript graphs of 1 200 units with optional units and alternative branches: some 3 000 states each"""
         lrng = np.random.default_rng(1)
         lgraphs = [pkg.synth.make_alignment_graph(lrng.integers(0, P, size=1200).tolist(), optional=list(range(5, 1200, 10)),
                                                   alternatives={k: lrng.integers(0, P, size=12).tolist() for k in range(3, 1200, 8)}, num_pdfs=P, seed=u)
                    for u in range(B)]
-        lag = abi.AlignGraphs(lgraphs, num_pdfs=P)
+        return abi.AlignGraphs(lgraphs, num_pdfs=P)
+
+    def long_path_case():
+        """4 utterances of 20 000 frames, each on its own graph of long_graphs, through the best path: what a back-pointer per (frame,
+        state) would need, and -- under --path-checkpoint -- the call in the checkpointed workspace"""
+        B, TL = 4, 20000
+        lag = long_graphs(B)
+        frames, rows, ug = abi.iarr([TL] * B), abi.iarr(np.arange(B) * TL), abi.iarr(np.arange(B))
+        nb0 = int(lib.tdnnf_align_workspace_bytes(lag.h, B, ug[1], frames[1]))
+        d = dict(utterances=B, frames=TL, states_per_graph=int(np.mean(lag.num_states)), workspace_bytes=nb0)
+        if not args.path_checkpoint:
+            d["skipped"] = "a back-pointer per (frame, state): %d bytes of workspace; run with --path-checkpoint" % nb0
+            return d
+        with abi.option("align_path_checkpoint", args.path_checkpoint):
+            nb_k = int(lib.tdnnf_align_workspace_bytes(lag.h, B, ug[1], frames[1]))
+        y = torch.randn(B * TL, P, device="cuda")
+        ws = abi.workspace(nb_k)
+        pdfs = torch.zeros(B * TL, dtype=torch.int32, device="cuda")
+        out = torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+        s = abi.stream()
+
+        def run_checkpoint():
+            with abi.option("align_path_checkpoint", args.path_checkpoint):
+                abi.check(lib.tdnnf_align_best_path(lag.h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, abi.ptr(pdfs), None, abi.ptr(out), abi.ptr(ws),
+                                                    nb_k, s))
+
+        run_checkpoint()
+        torch.cuda.synchronize()
+        ms = [timed(run_checkpoint, args.calls) for _ in range(args.repeats)]
+        r = out.cpu().numpy()
+        d.update(path_checkpoint=args.path_checkpoint, workspace_bytes_checkpoint=nb_k, ok=int(r[:, 1].sum()),
+                 best_path_checkpoint=dict(ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms],
+                                           us_per_frame=round(1e3 * float(np.median(ms)) / TL, 3)))
+        return d
+
+    def long_case():
+        """4 utterances of 20 000 frames, each on its own graph of long_graphs, through the compact call: what alpha of every frame
+        would need, and -- under --checkpoint -- the call in the checkpointed workspace"""
+        B, TL = 4, 20000
+        lag = long_graphs(B)
         frames, rows, ug = abi.iarr([TL] * B), abi.iarr(np.arange(B) * TL), abi.iarr(np.arange(B))
         nb0 = int(lib.tdnnf_align_posteriors_workspace_bytes(lag.h, B, ug[1], frames[1], 1))
         d = dict(utterances=B, frames=TL, states_per_graph=int(np.mean(lag.num_states)), workspace_bytes=nb0)
@@ -425,6 +498,9 @@ def main():
     ms = [timed(objf, args.calls) for _ in range(args.repeats)]
     res["chain_objf"] = dict(ms=round(float(np.median(ms)), 3), ms_all=[round(v, 3) for v in ms], us_per_frame=round(1e3 * float(np.median(ms)) / T, 3))
     res["free_over_chain_objf"] = round(res["free"]["ms"] / res["chain_objf"]["ms"], 3)
+    del y, ag, dg, ds, ws
+    torch.cuda.empty_cache()
+    res["long"] = long_path_case()
     print(json.dumps(res))
 
 
