@@ -360,6 +360,21 @@ int tdnnf_supervision_info(const tdnnf_supervision *, int *num_states, int *num_
 int tdnnf_supervision_create_e2e(int num_sequences, int frames_per_sequence, int num_pdfs, const int *seq_state_begin, const int *seq_arc_begin,
                                  const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
                                  const float *initial_logprob, const float *final_logprob, float weight, tdnnf_supervision **out);
+/* The same kind, REUSABLE: flat-start training has new transcripts in every minibatch, and tdnnf_supervision_create_e2e allocates, copies
+   synchronously and (at destroy) waits for the whole device every time.  tdnnf_supervision_reserve_e2e makes every allocation once -- a
+   reserved graph set (tdnnf_align_graphs_reserve below: max_sequences graphs, max_states states and max_arcs arcs between them) and the
+   numerator's scratch at the capacities, 16 * (max_frames + 1) * max_states bytes, plus the two state vectors (16 * max_states, always:
+   the launch form now follows the minibatch).  tdnnf_supervision_assign_e2e gives it the next minibatch in stream order, with the arrays of
+   tdnnf_supervision_create_e2e: num_sequences, frames_per_sequence, weight and the graphs may all change, within the capacities
+   (TDNNF_EINVAL naming the capacity and the excess: max_sequences, max_frames here, max_states and max_arcs from tdnnf_align_graphs_assign,
+   which also validates the arrays; a refused assign leaves the supervision on its previous minibatch).  The launch form of the recursion is
+   planned here from the minibatch's largest graph (option "align_form" is read HERE).  No allocation, no free, no device-wide wait; stream
+   order as tdnnf_align_graphs_assign documents.  Every function that takes a supervision runs what it runs for a created one and gives the
+   same bits; before the first assign they refuse it. */
+int tdnnf_supervision_reserve_e2e(int max_sequences, int max_frames, int num_pdfs, int max_states, int max_arcs, tdnnf_supervision **out);
+int tdnnf_supervision_assign_e2e(tdnnf_supervision *, int num_sequences, int frames_per_sequence, const int *seq_state_begin,
+                                 const int *seq_arc_begin, const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
+                                 const float *initial_logprob, const float *final_logprob, float weight, tdnnf_stream stream);
 /* 0 time-synchronous (tdnnf_supervision_create), 1 end-to-end (tdnnf_supervision_create_e2e); -1 for NULL */
 int tdnnf_supervision_kind(const tdnnf_supervision *);
 /* diagnostics, end-to-end kind only: the launch form of its recursion -- threads per workgroup (64 up to 64 states in the largest graph,
@@ -475,6 +490,42 @@ int tdnnf_align_graphs_create_labelled(int num_graphs, int num_pdfs, const int *
                                        const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
                                        const float *final_logprob, const int *arc_label, int num_labels, tdnnf_align_graphs **out);
 void tdnnf_align_graphs_destroy(tdnnf_align_graphs *);
+/* A REUSABLE graph set: allocated once for a capacity, then assigned a new batch of graphs per call in stream order -- forced alignment of a
+   corpus has new transcript graphs for every batch of utterances, and tdnnf_align_graphs_create allocates, copies synchronously and (at
+   destroy) waits for the whole device every time.
+   tdnnf_align_graphs_reserve makes every allocation the handle will ever need: max_graphs graphs with max_states states and max_arcs arcs
+   BETWEEN them (totals over a batch); num_labels 0 reserves an unlabelled handle, > 0 one whose every batch carries labels.  ONE device
+   allocation holds the per-state and per-arc arrays, the tables at their bounds (per table and graph at most 63 empty slots and 63 * 64
+   padding entries on top of the rows and arcs: csrc/align_tables.h align_table_bound), the column lists, the build's scratch and the device
+   staging -- about 75 bytes a state, 125 bytes an arc (185 with labels) and 197 KB a graph of capacity (262 KB with labels: the padding bound
+   of three or four tables); two pinned host buffers of 28 bytes an arc and 8 a state stage the batches.  The device pointers never change afterwards.  Until the first assign the handle holds no graphs, and every
+   entry that takes it refuses with TDNNF_EINVAL and says so.
+   tdnnf_align_graphs_assign takes the eight host arrays of tdnnf_align_graphs_create and arc_label (non-NULL exactly when the handle was
+   reserved with labels), validates what create validates with the same messages under its own name, and refuses a batch beyond one of the
+   three capacities with TDNNF_EINVAL, naming the capacity and the excess.  All checks run before anything is written: a refused assign
+   leaves the handle serving its previous batch.  It then copies the arrays into pinned staging, enqueues asynchronous copies and three
+   kernels on `stream` that build the tables on the device -- the bytes tdnnf_align_graphs_create uploads for the same arrays, so every
+   entry gives the same bits -- and returns.  No allocation, no free, no device-wide or stream-wide wait; the one host wait there can be is
+   for the staging copy of the assign BEFORE LAST (the two staging buffers take turns).  The host arrays may be reused when it returns.
+   Calls enqueued on `stream` before the assign still see the previous batch, calls enqueued on it afterwards the new one; a call on another
+   stream must be ordered against the assign by the caller (an event), in both directions.  The host-side answers (tdnnf_align_graphs_info,
+   _pdfs, _labels, workspace and layout questions) follow the new batch at once.  A handle of tdnnf_align_graphs_create* is refused.  Not
+   capturable into a HIP graph (host validation and staging). */
+int tdnnf_align_graphs_reserve(int max_graphs, int num_pdfs, int num_labels /* 0: unlabelled */, int max_states, int max_arcs,
+                               tdnnf_align_graphs **out);
+int tdnnf_align_graphs_assign(tdnnf_align_graphs *, int num_graphs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                              const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
+                              const float *final_logprob, const int *arc_label /* NULL iff unlabelled */, tdnnf_stream stream);
+/* reserved handles only: the three capacities, the bytes of the handle's device allocation, the number of device allocations made for it
+   since it exists (the witness that assign makes none) and the assigns that succeeded.  Any out-pointer may be NULL. */
+int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *, int *max_graphs, int *max_states, int *max_arcs, long long *device_bytes,
+                                int *device_allocs, int *assigns);
+/* diagnostics (tests): a copy-out of the device arrays of a created or an assigned handle, as ints, after waiting for the stream of the last
+   assign.  table 0 by destination, 1 by source, 2 by pdf, 3 by label (labelled handles): which 0 the slots, 1 the heavy-row descriptors,
+   2 the arc entries, 4 ints each.  table 4: which 0 the graph descriptors (14 ints a graph), 1 the by-label ranges (4 ints a graph), 2 the
+   lengths of the pdf column lists and the lists, 3 the same for labels, 4 / 5 the bits of initial_logprob / final_logprob, 6 the labels.
+   *count: the ints of the answer; out may be NULL to ask for it, else capacity (ints) must cover it. */
+int tdnnf_align_graphs_dump(const tdnnf_align_graphs *, int table, int which, int *out, long long capacity, long long *count);
 /* states, arcs and largest in-degree of one graph; any out-pointer may be NULL */
 int tdnnf_align_graphs_info(const tdnnf_align_graphs *, int graph, int *num_states, int *num_arcs, int *max_in_degree);
 /* utt_graph[u] (host) names the graph of utterance u -- many utterances may share one; NULL: graph 0 if there is one graph, else graph u

@@ -384,6 +384,37 @@ inline tdnnf_supervision *SupervisionCreateE2e(int num_sequences, int frames_per
   return sup;
 }
 
+// The same supervision, reusable (tdnnf_hip.h, tdnnf_supervision_reserve_e2e): reserved once for the largest minibatch of the run, then
+// assigned every minibatch's graphs on the trainer's stream -- no allocation, no device-wide wait per step.  Calls enqueued on `stream`
+// before the assign still see the previous minibatch.  Throws on the argument errors and on a minibatch beyond a capacity (the supervision
+// then still holds the previous minibatch); release with tdnnf_supervision_destroy.
+inline tdnnf_supervision *SupervisionReserveE2e(int max_sequences, int max_frames, int num_pdfs, int max_states, int max_arcs) {
+  tdnnf_supervision *sup = nullptr;
+  Check(tdnnf_supervision_reserve_e2e(max_sequences, max_frames, num_pdfs, max_states, max_arcs, &sup));
+  return sup;
+}
+inline void SupervisionAssignE2e(tdnnf_supervision *sup, int num_sequences, int frames_per_sequence, const int *seq_state_begin,
+                                 const int *seq_arc_begin, const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
+                                 const float *initial_logprob, const float *final_logprob, float weight, tdnnf_stream stream) {
+  Check(tdnnf_supervision_assign_e2e(sup, num_sequences, frames_per_sequence, seq_state_begin, seq_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob,
+                                     initial_logprob, final_logprob, weight, stream));
+}
+
+// A reusable graph set for the Align* calls below (tdnnf_hip.h, tdnnf_align_graphs_reserve): reserved once for the largest batch -- max_states
+// and max_arcs are totals over a batch; num_labels 0: no labels -- then assigned each batch of transcript graphs on `stream`, where the
+// tables are built on the device.  arc_label: null exactly for a handle reserved without labels.  Release with tdnnf_align_graphs_destroy.
+inline tdnnf_align_graphs *AlignGraphsReserve(int max_graphs, int num_pdfs, int num_labels, int max_states, int max_arcs) {
+  tdnnf_align_graphs *graphs = nullptr;
+  Check(tdnnf_align_graphs_reserve(max_graphs, num_pdfs, num_labels, max_states, max_arcs, &graphs));
+  return graphs;
+}
+inline void AlignGraphsAssign(tdnnf_align_graphs *graphs, int num_graphs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                              const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
+                              const float *final_logprob, const int *arc_label, tdnnf_stream stream) {
+  Check(tdnnf_align_graphs_assign(graphs, num_graphs, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob,
+                                  final_logprob, arc_label, stream));
+}
+
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance

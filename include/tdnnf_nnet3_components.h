@@ -2028,6 +2028,35 @@ inline tdnnf_supervision *CreateEnd2EndSupervision(int32 num_sequences, int32 fr
                                              arc_dst.data(), arc_pdf.data(), arc_logprob.data(), initial_logprob.data(), final_logprob.data(), weight);
 }
 
+// The same supervision for a training run, whose every minibatch has other transcripts: reserved once for the largest minibatch (max_states
+// and max_arcs are totals over a minibatch), then assigned each minibatch's graphs on the hooks' stream -- nothing is allocated and the
+// device is not waited for; the chain calls enqueued before an assign still see the minibatch before.  Release with
+// tdnnf_supervision_destroy.
+inline tdnnf_supervision *ReserveEnd2EndSupervision(int32 max_sequences, int32 max_frames, int32 num_pdfs, int32 max_states, int32 max_arcs) {
+  return tdnnf_adapter::SupervisionReserveE2e(max_sequences, max_frames, num_pdfs, max_states, max_arcs);
+}
+inline void AssignEnd2EndSupervision(tdnnf_supervision *supervision, int32 num_sequences, int32 frames_per_sequence, const std::vector<int32> &seq_state_begin,
+                                     const std::vector<int32> &seq_arc_begin, const std::vector<int32> &arc_src, const std::vector<int32> &arc_dst,
+                                     const std::vector<int32> &arc_pdf, const std::vector<float> &arc_logprob, const std::vector<float> &initial_logprob,
+                                     const std::vector<float> &final_logprob, float weight) {
+  tdnnf_adapter::SupervisionAssignE2e(supervision, num_sequences, frames_per_sequence, seq_state_begin.data(), seq_arc_begin.data(), arc_src.data(),
+                                      arc_dst.data(), arc_pdf.data(), arc_logprob.data(), initial_logprob.data(), final_logprob.data(), weight, Hooks().stream);
+}
+
+// A graph set for the Align* calls below that is reserved once and assigned each batch of utterances' transcript graphs on the hooks' stream
+// (tdnnf_align_graphs_reserve / _assign: the tables are built on the device, nothing is allocated per batch).  arc_label: empty for a set
+// reserved with num_labels 0, else one label per arc.  Release with tdnnf_align_graphs_destroy.
+inline tdnnf_align_graphs *ReserveAlignGraphs(int32 max_graphs, int32 num_pdfs, int32 num_labels, int32 max_states, int32 max_arcs) {
+  return tdnnf_adapter::AlignGraphsReserve(max_graphs, num_pdfs, num_labels, max_states, max_arcs);
+}
+inline void AssignAlignGraphs(tdnnf_align_graphs *graphs, int32 num_graphs, const std::vector<int32> &graph_state_begin, const std::vector<int32> &graph_arc_begin,
+                              const std::vector<int32> &arc_src, const std::vector<int32> &arc_dst, const std::vector<int32> &arc_pdf,
+                              const std::vector<float> &arc_logprob, const std::vector<float> &initial_logprob, const std::vector<float> &final_logprob,
+                              const std::vector<int32> &arc_label) {
+  tdnnf_adapter::AlignGraphsAssign(graphs, num_graphs, graph_state_begin.data(), graph_arc_begin.data(), arc_src.data(), arc_dst.data(), arc_pdf.data(),
+                                   arc_logprob.data(), initial_logprob.data(), final_logprob.data(), arc_label.empty() ? nullptr : arc_label.data(), Hooks().stream);
+}
+
 // ------------------------------------------------------------------------------------------------ best-path alignment
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames

@@ -155,6 +155,7 @@ int fb_compact_layout(const tdnnf_align_graphs *g, bool labels, const char *who,
   int rc;
   if (labels && (rc = align_need_labels(g, who))) return rc;
   TDNNF_REQUIRE(g && num_utts > 0 && utt_frames, "%snull graphs, no utterances or null utt_frames", who);
+  if ((rc = align_need_batch(g, who))) return rc;
   TDNNF_REQUIRE(utt_graph || g->G == 1 || g->G == num_utts, "%sutt_graph may be null only for one graph or one graph per utterance", who);
   begin->assign(1, 0);
   for (int u = 0; u < num_utts; u++) {

@@ -1,6 +1,7 @@
 // align_graphs.h -- the device copy of a set of pdf-labelled graphs (tdnnf_align_graphs) and what its three readers share on the host:
 // align.hip (best path), align_fb.hip (forward-backward), align_sparse.hip (its sparse output) and chain_num_e2e.hip (the end-to-end numerator).  align_graphs.hip creates and
-// destroys the handle from the tables of align_tables.h; the kernels take its AlignDev by value.
+// destroys the handle from the tables of align_tables.h, or reserves it once and has align_build.hip build the tables of each assigned batch on
+// the device; the kernels take its AlignDev by value.
 #pragma once
 #include <string>
 #include <vector>
@@ -39,6 +40,31 @@ struct AlignUtt {  // one utterance of a call (device table at the head of the w
 
 static_assert(sizeof(AlignUtt) == 32, "the workspace formula of include/tdnnf_hip.h counts 32 bytes an utterance");
 
+// ---- the device build of a reserved handle (align_build.hip, align_build_kernels.h): what its three kernels take by value
+struct AlignBuildTable {  // one table as the build writes it, with its scratch
+  int4 *slots, *heavy, *arcs;
+  int cap_slots, cap_heavy, cap_arcs;  // the allocation's bounds (align_table_bound): no store goes beyond them
+  int *len;     // [row capacity] arcs of a row; graph k's rows start at its row base (by_dst / by_src: its first state; by_pdf / by_label:
+                // its first column), row r of by_pdf / by_label is the r-th entry of its column list
+  int *order;   // [row capacity] per graph: its light rows by descending length (stable), behind them its heavy rows in row order
+  int *rowpos;  // [row capacity] where a row stands in `order`
+  int *off;     // [row capacity] per graph, local to its share of `arcs`: the first entry of each slice, behind them of each heavy row
+  int *arcpos;  // [arc capacity] an arc's place in its row: the number of earlier arcs of its graph in the same row
+  int4 *ginfo;  // [graph capacity] (slots, heavy rows, arc entries, light rows) of a graph
+  int4 *gbase;  // [graph capacity] (first slot, first heavy row, first arc entry, 0) of a graph
+  int *totals;  // [4] slots, heavy rows, arc entries of the batch
+};
+struct AlignBuildDev {
+  // the batch's raw arrays (device staging)
+  const int *state_begin, *arc_begin, *col_begin, *lcol_begin;  // [G + 1]
+  const int *src, *dst, *pdf, *lp_bits, *label;                 // [arcs]; label null for an unlabelled handle
+  const int *col_pdfs, *col_labels;                             // the column lists (the handle's own arrays)
+  AlignBuildTable t[4];
+  AlignGraphDev *graphs;    // [graph capacity]
+  AlignRange *label_range;  // [graph capacity], labelled handles
+  int G, num_tables;        // 3, or 4 with labels
+};
+
 }  // namespace tdnnf
 
 struct tdnnf_align_graphs {
@@ -57,13 +83,39 @@ struct tdnnf_align_graphs {
   const int *num_lcols_dev;                  // device, owned: [G] the lengths of the label column lists
   const int *col_labels_dev;                 // device, owned: col_labels
   const int *arc_label_dev;                  // device, owned: [arcs] the caller's labels in the caller's arc order (the labelled best path)
+  // what tdnnf_align_graphs_dump copies out: [table 0 by_dst, 1 by_src, 2 by_pdf, 3 by_label][slots, heavy, arcs] entries.  A created handle's
+  // are set at creation; a reserved handle's follow each assign on the device (AlignBuildDev::totals)
+  long long table_counts[4][3];
+  // ---- a RESERVED handle (tdnnf_align_graphs_reserve): every device array above is a piece of ONE allocation made for the capacities, the
+  // pointers never change, and tdnnf_align_graphs_assign refills them in stream order (align_build.hip).  All zero for a created handle.
+  bool reserved;
+  int assigns;                           // assigns that succeeded; 0: the handle holds no graphs yet (G = 0)
+  int cap_graphs, cap_states, cap_arcs;  // the capacities: graphs, total states, total arcs of a batch
+  void *arena;                           // device, owned: the one allocation
+  size_t arena_bytes;
+  int device_allocs;                     // hipMallocs made for the handle (the witness that assign makes none)
+  char *stage_host[2];                   // pinned host staging, two buffers used in turn
+  hipEvent_t stage_event[2];             // recorded behind the copies out of stage_host[i]; waited for before it is overwritten
+  bool stage_used[2];
+  size_t stage_bytes;
+  char *stage_dev;                       // device: the raw arrays of the batch being built, packed as in the staging buffer
+  hipStream_t last_stream;               // the stream of the last assign (tdnnf_align_graphs_dump waits for it)
+  tdnnf::AlignBuildDev build;            // the tables as the build kernels write them, and the build's scratch
 };
 
 namespace tdnnf {
 
 // The refusal every label entry gives a handle that tdnnf_align_graphs_create made.  who: the prefix of the message, the call's name.
+// The refusal every entry gives a reserved handle that was never assigned a batch.  who: the prefix of the message, the call's name.
+inline int align_need_batch(const tdnnf_align_graphs *g, const char *who) {
+  TDNNF_REQUIRE(!g || !g->reserved || g->assigns > 0,
+                "%sthe reserved graph set holds no graphs yet (tdnnf_align_graphs_assign gives it a batch)", who);
+  return TDNNF_OK;
+}
+
 inline int align_need_labels(const tdnnf_align_graphs *g, const char *who) {
   TDNNF_REQUIRE(g, "%snull graphs", who);
+  if (int rc = align_need_batch(g, who)) return rc;
   TDNNF_REQUIRE(g->L > 0, "%sthe graphs carry no labels (tdnnf_align_graphs_create_labelled makes the handle this call takes)", who);
   return TDNNF_OK;
 }
@@ -85,6 +137,7 @@ inline int align_call(const tdnnf_align_graphs *g, bool best_path, const char *p
                       const int *utt_frames, const int *utt_row_begin, int row_stride, const tdnnf_mat *nnet_output, const tdnnf_mat *post_out,
                       AlignCall *c) {
   TDNNF_REQUIRE(g && num_utts > 0 && utt_frames, "%snull graphs, no utterances or null utt_frames", plan);
+  if (int rc = align_need_batch(g, plan)) return rc;
   TDNNF_REQUIRE(utt_graph || g->G == 1 || g->G == num_utts, "%sutt_graph may be null only for one graph or one graph per utterance", plan);
   c->utts.resize(num_utts);
   c->max_states = 0;

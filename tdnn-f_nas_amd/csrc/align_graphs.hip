@@ -1,6 +1,12 @@
 // align_graphs.hip -- creates, describes and destroys a tdnnf_align_graphs (include/tdnnf_hip.h, "best-path alignment"): validates the caller's
-// arrays, builds the three arc tables (four for labelled graphs) on the host (align_tables.h) and uploads them.  Its readers: align.hip, align_fb.hip, align_sparse.hip, chain_num_e2e.hip.
+// arrays, builds the three arc tables (four for labelled graphs) on the host (align_tables.h) and uploads them.  And the reusable kind:
+// tdnnf_align_graphs_reserve allocates a handle once for a capacity, tdnnf_align_graphs_assign validates a batch, stages it and enqueues the
+// copies and the device build (align_build.hip) on the caller's stream; tdnnf_align_graphs_dump copies the device arrays of either kind out
+// for tests.  Its readers: align.hip, align_fb.hip, align_sparse.hip, chain_num_e2e.hip.
 #include <math.h>
+#include <string.h>
+
+#include <utility>
 
 #include "align_graphs.h"
 
@@ -24,15 +30,14 @@ int align_table_to_device(const AlignHostTable &h, AlignTable *t) {
   return align_to_device(h.arcs, &t->arcs);
 }
 
-// tdnnf_align_graphs_create (arc_label null) and tdnnf_align_graphs_create_labelled.  who: the prefix of the messages, the call's name.
-int align_graphs_create(const char *who, int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
-                        const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob, const float *final_logprob,
-                        const int *arc_label, int num_labels, tdnnf_align_graphs **out) {
-  TDNNF_REQUIRE(out && num_graphs > 0 && num_pdfs > 0 && graph_state_begin && graph_arc_begin && arc_src && arc_dst && arc_pdf && arc_logprob &&
+// What tdnnf_align_graphs_create and tdnnf_align_graphs_assign validate of the caller's arrays.  who: the prefix of the messages, the call's name.
+int align_validate(const char *who, bool have_out, int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                   const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob, const float *final_logprob,
+                   const int *arc_label, int num_labels) {
+  TDNNF_REQUIRE(have_out && num_graphs > 0 && num_pdfs > 0 && graph_state_begin && graph_arc_begin && arc_src && arc_dst && arc_pdf && arc_logprob &&
                     initial_logprob && final_logprob,
                 "%sbad arguments", who);
   TDNNF_REQUIRE(graph_state_begin[0] == 0 && graph_arc_begin[0] == 0, "%sgraph_state_begin and graph_arc_begin must start at 0", who);
-  const int NS = graph_state_begin[num_graphs];
   for (int g = 0; g < num_graphs; g++) {
     const int s0 = graph_state_begin[g], s1 = graph_state_begin[g + 1], a0 = graph_arc_begin[g], a1 = graph_arc_begin[g + 1];
     TDNNF_REQUIRE(s1 > s0 && a1 >= a0, "%sgraph %d must have at least one state and a non-negative arc count", who, g);
@@ -52,6 +57,17 @@ int align_graphs_create(const char *who, int num_graphs, int num_pdfs, const int
                     arc_label ? arc_label[a] : 0, num_labels);
     }
   }
+  return TDNNF_OK;
+}
+
+// tdnnf_align_graphs_create (arc_label null) and tdnnf_align_graphs_create_labelled.  who: the prefix of the messages, the call's name.
+int align_graphs_create(const char *who, int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                        const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob, const float *final_logprob,
+                        const int *arc_label, int num_labels, tdnnf_align_graphs **out) {
+  if (int rc = align_validate(who, out != nullptr, num_graphs, num_pdfs, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob,
+                              initial_logprob, final_logprob, arc_label, num_labels))
+    return rc;
+  const int NS = graph_state_begin[num_graphs];
   AlignHostTables t;
   align_build_tables(num_graphs, num_pdfs, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, &t, true, arc_label);
   TDNNF_REQUIRE(t.by_dst.arcs.size() < (size_t)1 << 31, "%sthe sliced arc table has more than 2^31 entries", who);
@@ -61,6 +77,12 @@ int align_graphs_create(const char *who, int num_graphs, int num_pdfs, const int
   tdnnf_align_graphs *g = new tdnnf_align_graphs();
   g->G = num_graphs;
   g->P = num_pdfs;
+  const AlignHostTable *tables[4] = {&t.by_dst, &t.by_src, &t.by_pdf, &t.by_label};
+  for (int i = 0; i < 4; i++) {
+    g->table_counts[i][0] = (long long)tables[i]->slots.size();
+    g->table_counts[i][1] = (long long)tables[i]->heavy.size();
+    g->table_counts[i][2] = (long long)tables[i]->arcs.size();
+  }
   g->dev = AlignDev{};
   g->state_begin.assign(graph_state_begin, graph_state_begin + num_graphs + 1);
   for (int k = 0; k < num_graphs; k++) g->num_arcs.push_back(graph_arc_begin[k + 1] - graph_arc_begin[k]);
@@ -101,12 +123,279 @@ int align_graphs_create(const char *who, int num_graphs, int num_pdfs, const int
   return TDNNF_OK;
 }
 
+// ---- reserved handles: one device allocation for the capacities, refilled in stream order by tdnnf_align_graphs_assign
+
+// Hands out pieces of the handle's one allocation, 256 bytes apart at least; with a null base it only counts.
+struct AlignCarve {
+  char *base;
+  size_t at;
+  template <class T>
+  T *take(size_t n) {
+    at = align_round_up(at, 256);
+    T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+    at += sizeof(T) * std::max<size_t>(n, 1);
+    return p;
+  }
+};
+
+// the rows a table can have in a batch at the capacities: a state table's are the states; by_pdf's and by_label's the distinct pdfs / labels
+// of each graph, at most its arcs and at most num_pdfs / num_labels a graph
+long long align_row_capacity(const tdnnf_align_graphs *g, int table) {
+  if (table < 2) return g->cap_states;
+  return std::min<long long>(g->cap_arcs, (long long)g->cap_graphs * (table == 2 ? g->P : g->L));
+}
+
+// Every device array of a reserved handle, the build's scratch and the device staging, out of c.  Run once with a null base for the size.
+void align_reserve_layout(tdnnf_align_graphs *g, AlignCarve *c) {
+  const size_t Gc = g->cap_graphs, Sc = g->cap_states, Ac = g->cap_arcs;
+  AlignBuildDev &b = g->build;
+  b.graphs = c->take<AlignGraphDev>(Gc);
+  g->dev.graphs = b.graphs;
+  g->dev.init = c->take<float>(Sc);
+  g->dev.final = c->take<float>(Sc);
+  g->num_cols_dev = c->take<int>(Gc);
+  g->col_pdfs_dev = b.col_pdfs = c->take<int>(align_row_capacity(g, 2));
+  b.num_tables = g->L > 0 ? 4 : 3;
+  if (g->L > 0) {
+    g->label_range_dev = b.label_range = c->take<AlignRange>(Gc);
+    g->num_lcols_dev = c->take<int>(Gc);
+    g->col_labels_dev = b.col_labels = c->take<int>(align_row_capacity(g, 3));
+    g->arc_label_dev = b.label = c->take<int>(Ac);
+  }
+  AlignTable *tables[4] = {&g->dev.by_dst, &g->dev.by_src, &g->dev.by_pdf, &g->by_label};
+  for (int i = 0; i < b.num_tables; i++) {
+    const long long rows = align_row_capacity(g, i);
+    const AlignTableBound bound = align_table_bound(g->cap_graphs, rows, g->cap_arcs);
+    AlignBuildTable &t = b.t[i];
+    t.cap_slots = (int)bound.slots;
+    t.cap_heavy = (int)bound.heavy;
+    t.cap_arcs = (int)bound.arcs;
+    tables[i]->slots = t.slots = c->take<int4>(bound.slots);
+    tables[i]->heavy = t.heavy = c->take<int4>(bound.heavy);
+    tables[i]->arcs = t.arcs = c->take<int4>(bound.arcs);
+    t.len = c->take<int>(rows);
+    t.order = c->take<int>(rows);
+    t.rowpos = c->take<int>(rows);
+    t.off = c->take<int>(rows);
+    t.arcpos = c->take<int>(Ac);
+    t.ginfo = c->take<int4>(Gc);
+    t.gbase = c->take<int4>(Gc);
+    t.totals = c->take<int>(4);
+  }
+  g->stage_dev = c->take<char>(g->stage_bytes);
+}
+
+// One array of a batch in the staging buffer: copies it in and moves *at on; the offset is the same in the device staging.
+template <class T>
+size_t align_stage(char *host, size_t *at, const T *v, size_t n) {
+  const size_t begin = *at;
+  if (n) memcpy(host + begin, v, sizeof(T) * n);
+  *at += sizeof(T) * n;
+  return begin;
+}
+
 }  // namespace
+
+int align_build_launch(const AlignBuildDev &b, int max_graph_arcs, int max_graph_rows, hipStream_t s);  // align_build.hip
+
 }  // namespace tdnnf
 
 using namespace tdnnf;
 
 extern "C" {
+
+int tdnnf_align_graphs_reserve(int max_graphs, int num_pdfs, int num_labels, int max_states, int max_arcs, tdnnf_align_graphs **out) {
+  const char *who = "align_graphs_reserve: ";
+  TDNNF_REQUIRE(out && max_graphs > 0 && num_pdfs > 0 && num_labels >= 0 && max_states > 0 && max_arcs >= 0,
+                "%sbad arguments (max_graphs %d, num_pdfs %d, num_labels %d, max_states %d, max_arcs %d)", who, max_graphs, num_pdfs, num_labels, max_states,
+                max_arcs);
+  TDNNF_REQUIRE(max_states >= max_graphs, "%smax_states %d is below max_graphs %d: every graph has a state", who, max_states, max_graphs);
+  const AlignTableBound most = align_table_bound(max_graphs, std::max(max_states, max_arcs), max_arcs);
+  TDNNF_REQUIRE(most.arcs < 1ll << 31 && most.slots < 1ll << 31, "%sa sliced arc table at these capacities has more than 2^31 entries", who);
+  tdnnf_align_graphs *g = new tdnnf_align_graphs();
+  g->P = num_pdfs;
+  g->L = num_labels;
+  g->reserved = true;
+  g->cap_graphs = max_graphs;
+  g->cap_states = max_states;
+  g->cap_arcs = max_arcs;
+  // staging: four begin arrays, four arrays per arc and the labels, two per state, the two column lists and their lengths
+  g->stage_bytes = sizeof(int) * (4 * ((size_t)max_graphs + 1) + 7 * (size_t)max_arcs + 2 * (size_t)max_states + 2 * (size_t)max_graphs);
+  AlignCarve size{nullptr, 0};
+  align_reserve_layout(g, &size);
+  g->arena_bytes = size.at;
+  hipError_t e = hipMalloc(&g->arena, g->arena_bytes);
+  if (e == hipSuccess) g->device_allocs = 1;
+  for (int i = 0; i < 2 && e == hipSuccess; i++)
+    if ((e = hipHostMalloc((void **)&g->stage_host[i], std::max<size_t>(g->stage_bytes, 1), hipHostMallocDefault)) == hipSuccess)
+      e = hipEventCreateWithFlags(&g->stage_event[i], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    tdnnf_align_graphs_destroy(g);
+    return hip_status(e, "align_graphs_reserve: allocation");
+  }
+  AlignCarve carve{static_cast<char *>(g->arena), 0};
+  align_reserve_layout(g, &carve);
+  *out = g;
+  return TDNNF_OK;
+}
+
+int tdnnf_align_graphs_assign(tdnnf_align_graphs *g, int num_graphs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
+                              const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
+                              const float *final_logprob, const int *arc_label, tdnnf_stream stream) {
+  const char *who = "align_graphs_assign: ";
+  TDNNF_REQUIRE(g, "%snull graphs", who);
+  TDNNF_REQUIRE(g->reserved, "%sthe handle was made by tdnnf_align_graphs_create: only a handle of tdnnf_align_graphs_reserve can be assigned", who);
+  TDNNF_REQUIRE(g->L == 0 || arc_label, "%sthe handle was reserved for labels (num_labels %d), and arc_label is null", who, g->L);
+  TDNNF_REQUIRE(g->L > 0 || !arc_label, "%sarc_label given to a handle that was reserved without labels (num_labels 0)", who);
+  int rc = align_validate(who, true, num_graphs, g->P, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob,
+                          final_logprob, arc_label, g->L);
+  if (rc) return rc;
+  const int G = num_graphs, NS = graph_state_begin[G], NA = graph_arc_begin[G];
+  TDNNF_REQUIRE(G <= g->cap_graphs, "%s%d graphs exceed the capacity max_graphs = %d by %d", who, G, g->cap_graphs, G - g->cap_graphs);
+  TDNNF_REQUIRE(NS <= g->cap_states, "%s%d states exceed the capacity max_states = %d by %d", who, NS, g->cap_states, NS - g->cap_states);
+  TDNNF_REQUIRE(NA <= g->cap_arcs, "%s%d arcs exceed the capacity max_arcs = %d by %d", who, NA, g->cap_arcs, NA - g->cap_arcs);
+
+  // the metadata the host answers layout questions from: lengths, largest in-degree, the column lists (sort and unique over a graph's arcs)
+  std::vector<int> num_arcs(G), max_in_degree(G), col_begin(1, 0), col_pdfs, lcol_begin(1, 0), col_labels, num_cols(G), num_lcols(G), in_degree(NS, 0), list;
+  int max_graph_arcs = 0, max_graph_rows = 0;
+  const auto columns = [&](const int *of_arc, int a0, int a1, std::vector<int> *begin, std::vector<int> *cols) {
+    list.assign(of_arc + a0, of_arc + a1);
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    cols->insert(cols->end(), list.begin(), list.end());
+    begin->push_back((int)cols->size());
+    return (int)list.size();
+  };
+  for (int k = 0; k < G; k++) {
+    const int a0 = graph_arc_begin[k], a1 = graph_arc_begin[k + 1];
+    num_arcs[k] = a1 - a0;
+    for (int a = a0; a < a1; a++) in_degree[arc_dst[a]]++;
+    max_in_degree[k] = *std::max_element(in_degree.begin() + graph_state_begin[k], in_degree.begin() + graph_state_begin[k + 1]);
+    num_cols[k] = columns(arc_pdf, a0, a1, &col_begin, &col_pdfs);
+    if (arc_label) num_lcols[k] = columns(arc_label, a0, a1, &lcol_begin, &col_labels);
+    max_graph_arcs = std::max(max_graph_arcs, a1 - a0);
+    max_graph_rows = std::max(max_graph_rows, std::max(graph_state_begin[k + 1] - graph_state_begin[k], std::max(num_cols[k], num_lcols[k])));
+  }
+
+  // staging: the one wait of this path, for the copies of the assign before last out of the buffer that is now overwritten
+  const int slot = g->assigns & 1;
+  if (g->stage_used[slot]) TDNNF_HIP(hipEventSynchronize(g->stage_event[slot]));
+  char *host = g->stage_host[slot];
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  AlignBuildDev &b = g->build;
+  size_t at = 0;
+  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(g->stage_dev + align_stage(host, &at, static_cast<const int *>(v), n)); };
+  b.G = G;
+  b.state_begin = raw(graph_state_begin, (size_t)G + 1);
+  b.arc_begin = raw(graph_arc_begin, (size_t)G + 1);
+  b.col_begin = raw(col_begin.data(), (size_t)G + 1);
+  b.lcol_begin = raw(lcol_begin.data(), arc_label ? (size_t)G + 1 : 0);
+  b.src = raw(arc_src, NA);
+  b.dst = raw(arc_dst, NA);
+  b.pdf = raw(arc_pdf, NA);
+  b.lp_bits = raw(arc_logprob, NA);
+  const size_t raw_bytes = at;
+  // the arrays that go to the handle's own device arrays as they are
+  struct Copy {
+    const void *to;
+    size_t from, bytes;
+  } copies[7];
+  int num_copies = 0;
+  const auto direct = [&](const void *to, const void *v, size_t n) {
+    const size_t from = align_stage(host, &at, static_cast<const int *>(v), n);
+    if (n) copies[num_copies++] = Copy{to, from, sizeof(int) * n};
+  };
+  direct(g->dev.init, initial_logprob, NS);
+  direct(g->dev.final, final_logprob, NS);
+  direct(g->num_cols_dev, num_cols.data(), G);
+  direct(g->col_pdfs_dev, col_pdfs.data(), col_pdfs.size());
+  if (arc_label) {
+    direct(g->arc_label_dev, arc_label, NA);
+    direct(g->num_lcols_dev, num_lcols.data(), G);
+    direct(g->col_labels_dev, col_labels.data(), col_labels.size());
+  }
+  TDNNF_REQUIRE(at <= g->stage_bytes, "%sinternal: the batch needs %zu bytes of staging, the handle has %zu", who, at, g->stage_bytes);
+  TDNNF_HIP(hipMemcpyAsync(g->stage_dev, host, raw_bytes, hipMemcpyHostToDevice, s));
+  for (int i = 0; i < num_copies; i++)
+    TDNNF_HIP(hipMemcpyAsync(const_cast<void *>(copies[i].to), host + copies[i].from, copies[i].bytes, hipMemcpyHostToDevice, s));
+  TDNNF_HIP(hipEventRecord(g->stage_event[slot], s));
+  g->stage_used[slot] = true;
+  if ((rc = align_build_launch(b, max_graph_arcs, max_graph_rows, s))) return rc;
+
+  g->G = G;
+  g->state_begin.assign(graph_state_begin, graph_state_begin + G + 1);
+  g->num_arcs.swap(num_arcs);
+  g->max_in_degree.swap(max_in_degree);
+  g->col_begin.swap(col_begin);
+  g->col_pdfs.swap(col_pdfs);
+  g->lcol_begin.swap(lcol_begin);
+  g->col_labels.swap(col_labels);
+  g->last_stream = s;
+  g->assigns++;
+  return TDNNF_OK;
+}
+
+int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *g, int *max_graphs, int *max_states, int *max_arcs, long long *device_bytes, int *device_allocs,
+                                int *assigns) {
+  TDNNF_REQUIRE(g && g->reserved, "align_graphs_capacity: null graphs, or a handle that tdnnf_align_graphs_create made (it has no capacity)");
+  if (max_graphs) *max_graphs = g->cap_graphs;
+  if (max_states) *max_states = g->cap_states;
+  if (max_arcs) *max_arcs = g->cap_arcs;
+  if (device_bytes) *device_bytes = (long long)g->arena_bytes;
+  if (device_allocs) *device_allocs = g->device_allocs;
+  if (assigns) *assigns = g->assigns;
+  return TDNNF_OK;
+}
+
+int tdnnf_align_graphs_dump(const tdnnf_align_graphs *g, int table, int which, int *out, long long capacity, long long *count) {
+  const char *who = "align_graphs_dump: ";
+  TDNNF_REQUIRE(g && count, "%snull graphs or null count", who);
+  if (int rc = align_need_batch(g, who)) return rc;
+  TDNNF_REQUIRE(table >= 0 && table <= 4 && which >= 0 && which <= (table < 4 ? 2 : 6), "%stable %d, which %d", who, table, which);
+  TDNNF_REQUIRE(table != 3 || g->L > 0, "%sthe graphs carry no labels: there is no table 3", who);
+  if (g->reserved) TDNNF_HIP(hipStreamSynchronize(g->last_stream));
+  const int NS = g->state_begin[g->G];
+  long long NA = 0;
+  for (int n : g->num_arcs) NA += n;
+  // the pieces of the answer: (device array, ints)
+  std::vector<std::pair<const void *, long long>> parts;
+  if (table < 4) {
+    const AlignTable &t = table == 0 ? g->dev.by_dst : table == 1 ? g->dev.by_src : table == 2 ? g->dev.by_pdf : g->by_label;
+    long long entries = g->table_counts[table][which];
+    if (g->reserved) {
+      int totals[4];
+      TDNNF_HIP(hipMemcpy(totals, g->build.t[table].totals, sizeof(totals), hipMemcpyDeviceToHost));
+      entries = totals[which];
+    }
+    parts.push_back({which == 0 ? t.slots : which == 1 ? t.heavy : t.arcs, 4 * entries});
+  } else if (which == 0) {
+    parts.push_back({g->dev.graphs, (long long)(sizeof(AlignGraphDev) / sizeof(int)) * g->G});
+  } else if (which == 1) {
+    if (g->L > 0) parts.push_back({g->label_range_dev, (long long)(sizeof(AlignRange) / sizeof(int)) * g->G});
+  } else if (which == 2) {
+    parts.push_back({g->num_cols_dev, g->G});
+    parts.push_back({g->col_pdfs_dev, (long long)g->col_pdfs.size()});
+  } else if (which == 3) {
+    if (g->L > 0) parts.push_back({g->num_lcols_dev, g->G});
+    if (g->L > 0) parts.push_back({g->col_labels_dev, (long long)g->col_labels.size()});
+  } else if (which == 4) {
+    parts.push_back({g->dev.init, NS});
+  } else if (which == 5) {
+    parts.push_back({g->dev.final, NS});
+  } else if (g->L > 0) {
+    parts.push_back({g->arc_label_dev, NA});
+  }
+  long long total = 0;
+  for (const auto &p : parts) total += p.second;
+  *count = total;
+  if (!out) return TDNNF_OK;
+  TDNNF_REQUIRE(capacity >= total, "%sout holds %lld ints, the answer has %lld", who, capacity, total);
+  for (const auto &p : parts) {
+    if (p.second) TDNNF_HIP(hipMemcpy(out, p.first, sizeof(int) * (size_t)p.second, hipMemcpyDeviceToHost));
+    out += p.second;
+  }
+  return TDNNF_OK;
+}
 
 int tdnnf_align_graphs_create(int num_graphs, int num_pdfs, const int *graph_state_begin, const int *graph_arc_begin, const int *arc_src,
                               const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob,
@@ -126,6 +415,15 @@ int tdnnf_align_graphs_create_labelled(int num_graphs, int num_pdfs, const int *
 
 void tdnnf_align_graphs_destroy(tdnnf_align_graphs *g) {
   if (!g) return;
+  if (g->reserved) {  // every device array is a piece of the one allocation
+    (void)hipFree(g->arena);
+    for (int i = 0; i < 2; i++) {
+      if (g->stage_host[i]) (void)hipHostFree(g->stage_host[i]);
+      if (g->stage_event[i]) (void)hipEventDestroy(g->stage_event[i]);
+    }
+    delete g;
+    return;
+  }
   const AlignDev &d = g->dev;
   const void *ptrs[] = {d.graphs,      d.by_dst.slots, d.by_dst.heavy, d.by_dst.arcs, d.by_src.slots, d.by_src.heavy,
                         d.by_src.arcs, d.by_pdf.slots, d.by_pdf.heavy, d.by_pdf.arcs, d.init,         d.final,
@@ -136,6 +434,7 @@ void tdnnf_align_graphs_destroy(tdnnf_align_graphs *g) {
 }
 
 int tdnnf_align_graphs_info(const tdnnf_align_graphs *g, int graph, int *num_states, int *num_arcs, int *max_in_degree) {
+  if (int rc = align_need_batch(g, "align_graphs_info: ")) return rc;
   TDNNF_REQUIRE(g && graph >= 0 && graph < g->G, "align_graphs_info: null graphs or graph %d out of range", graph);
   if (num_states) *num_states = g->state_begin[graph + 1] - g->state_begin[graph];
   if (num_arcs) *num_arcs = g->num_arcs[graph];
@@ -144,6 +443,7 @@ int tdnnf_align_graphs_info(const tdnnf_align_graphs *g, int graph, int *num_sta
 }
 
 int tdnnf_align_graphs_pdfs(const tdnnf_align_graphs *g, int graph, int *num, int *pdfs_out) {
+  if (int rc = align_need_batch(g, "align_graphs_pdfs: ")) return rc;
   TDNNF_REQUIRE(g && graph >= 0 && graph < g->G, "align_graphs_pdfs: null graphs or graph %d out of range", graph);
   const int c0 = g->col_begin[graph], c1 = g->col_begin[graph + 1];
   if (num) *num = c1 - c0;

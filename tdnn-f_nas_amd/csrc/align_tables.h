@@ -89,6 +89,27 @@ AlignRange align_add_graph(AlignHostTable &t, const std::vector<std::vector<int>
   return g;
 }
 
+// Upper bounds on the three counts of ONE table that holds at most max_graphs graphs with total_rows rows and total_arcs arcs between them
+// (a state table's rows are the states; by_pdf's and by_label's are the distinct pdfs / labels of each graph, never more than its arcs).
+// A reserved tdnnf_align_graphs (align_graphs.hip) allocates its tables at these.  Per graph:
+//   slots   a multiple of 64 that covers its light rows: at most roundup64(rows) <= rows + 63.
+//   heavy   a heavy row has at least kAlignHeavy + 1 arcs and is a row: at most min(rows, arcs / 65).
+//   arcs    its arcs and the padding of its slices.  The light rows are sorted by descending length, so in slice i, of width w_i (its first
+//           row's length), lane 0 pads nothing and each of the 63 other lanes holds a row at least as long as the next slice's first, w_i+1:
+//           the slice pads at most 63 (w_i - w_i+1).  The last slice, whose other lanes may be empty, pads at most 63 w_last.  The sum
+//           telescopes to 63 w_0 <= 63 * kAlignHeavy = 4032 entries; a row of 64 arcs beside 63 empty rows (or alone) attains it.
+struct AlignTableBound {
+  long long slots, heavy, arcs;
+};
+constexpr int kAlignPadPerGraph = 63 * kAlignHeavy;
+inline AlignTableBound align_table_bound(long long max_graphs, long long total_rows, long long total_arcs) {
+  AlignTableBound b;
+  b.slots = total_rows + 63 * max_graphs;
+  b.heavy = std::min(total_rows, total_arcs / (kAlignHeavy + 1));
+  b.arcs = total_arcs + (long long)kAlignPadPerGraph * max_graphs;
+  return b;
+}
+
 struct AlignHostTables {
   std::vector<AlignGraphDev> graphs;
   AlignHostTable by_dst, by_src, by_pdf;

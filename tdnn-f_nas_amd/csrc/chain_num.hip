@@ -327,6 +327,7 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision
                                double *results, tdnnf_mat *deriv, tdnnf_mat *xent_deriv, void *ws, size_t ws_bytes,
                                tdnnf_stream stream) {
   TDNNF_REQUIRE(g && sp && mat_ok(y) && mat_ok(deriv) && results, "chain_objf_and_deriv: bad arguments");
+  TDNNF_REQUIRE(!sp->e2e_reserved || sp->e2e_assigns > 0, "chain_objf_and_deriv: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign_e2e gives it one)");
   const int B = sp->B, T = sp->T;
   TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P && same_dim(y, deriv), "chain_objf_and_deriv: nnet_output must be (B*T) x num_pdfs, t-major");
   TDNNF_REQUIRE(!xent_deriv || (mat_ok(xent_deriv) && same_dim(y, xent_deriv)), "chain_objf_and_deriv: bad xent_deriv");
@@ -343,6 +344,7 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision
 int tdnnf_chain_objf(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, float leaky, float l2_regularize,
                      double *results, void *ws, size_t ws_bytes, tdnnf_stream stream) {
   TDNNF_REQUIRE(g && sp && mat_ok(y) && results, "chain_objf: bad arguments");
+  TDNNF_REQUIRE(!sp->e2e_reserved || sp->e2e_assigns > 0, "chain_objf: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign_e2e gives it one)");
   const int B = sp->B, T = sp->T;
   TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P, "chain_objf: nnet_output must be (B*T) x num_pdfs, t-major");
   TDNNF_REQUIRE(!xent_output || (mat_ok(xent_output) && same_dim(y, xent_output)), "chain_objf: bad xent_output");
@@ -359,6 +361,7 @@ int tdnnf_chain_objf(const tdnnf_den_graph *g, const tdnnf_supervision *sp, cons
 int tdnnf_chain_numerator_part(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, int part, double *results, tdnnf_mat *deriv,
                                tdnnf_mat *xent_deriv, void *ws, size_t ws_bytes, tdnnf_stream stream) {
   TDNNF_REQUIRE(g && sp && mat_ok(y) && y->rows == sp->B * sp->T && y->cols == g->P, "chain_numerator_part: bad arguments");
+  TDNNF_REQUIRE(!sp->e2e_reserved || sp->e2e_assigns > 0, "chain_numerator_part: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign_e2e gives it one)");
   TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_workspace_bytes(g, sp->B, sp->T), "chain_numerator_part: workspace too small");
   TDNNF_REQUIRE(sp->kind == 0 || sp->num_pdfs <= g->P, "chain_numerator_part: the supervision's num_pdfs %d exceeds the denominator graph's %d", sp->num_pdfs, g->P);
   hipStream_t s = (hipStream_t)stream;

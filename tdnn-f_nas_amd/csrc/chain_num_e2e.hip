@@ -1,6 +1,7 @@
 // chain_num_e2e.hip -- the chain numerator on cyclic per-sequence graphs (flat-start / end-to-end LF-MMI): creates the second kind of
 // tdnnf_supervision (its graphs are a tdnnf_align_graphs, its scratch its own) and launches num_e2e_kernels.h for the host functions of
-// chain_num.hip, which dispatch on the supervision's kind.
+// chain_num.hip, which dispatch on the supervision's kind.  tdnnf_supervision_reserve_e2e / _assign_e2e: the same kind allocated once for a
+// capacity and given each minibatch in stream order, on a reserved graph set (align_graphs.hip).
 #include <math.h>
 #include <string.h>
 
@@ -121,6 +122,65 @@ int tdnnf_supervision_create_e2e(int B, int T, int num_pdfs, const int *seq_stat
     return hip_status(e, "supervision_create_e2e: hipMalloc");
   }
   *out = sp;
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_reserve_e2e(int max_sequences, int max_frames, int num_pdfs, int max_states, int max_arcs, tdnnf_supervision **out) {
+  const char *who = "supervision_reserve_e2e: ";
+  TDNNF_REQUIRE(out && max_sequences > 0 && max_frames > 0 && num_pdfs > 0 && max_states > 0 && max_arcs >= 0, "%sbad arguments", who);
+  tdnnf_align_graphs *graphs = nullptr;
+  int rc = tdnnf_align_graphs_reserve(max_sequences, num_pdfs, 0, max_states, max_arcs, &graphs);
+  if (rc) return rc;
+  tdnnf_supervision *sp = new tdnnf_supervision();
+  memset(sp, 0, sizeof(*sp));
+  sp->kind = 1;
+  sp->num_pdfs = num_pdfs;
+  sp->e2e_graphs = graphs;
+  sp->e2e_reserved = true;
+  sp->e2e_max_sequences = max_sequences;
+  sp->e2e_max_frames = max_frames;
+  // the scratch at the capacities; the two state vectors always, because the launch form follows the assigned minibatch
+  const size_t frames = sizeof(double) * ((size_t)max_frames + 1) * (size_t)max_states;
+  const size_t parts = (size_t)max_sequences * ((max_frames + kNumE2eFrames - 1) / kNumE2eFrames);
+  hipError_t e = hipSuccess;
+  if ((e = hipMalloc((void **)&sp->e2e_alpha, frames)) != hipSuccess || (e = hipMalloc((void **)&sp->e2e_beta, frames)) != hipSuccess ||
+      (e = hipMalloc((void **)&sp->xent_part, sizeof(double) * parts)) != hipSuccess ||
+      (e = hipMalloc((void **)&sp->l2_part, sizeof(double) * kFinishL2Parts)) != hipSuccess ||
+      (e = hipMalloc((void **)&sp->e2e_vecs, 2 * sizeof(double) * (size_t)max_states)) != hipSuccess) {
+    tdnnf_supervision_destroy(sp);
+    return hip_status(e, "supervision_reserve_e2e: hipMalloc");
+  }
+  *out = sp;
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_assign_e2e(tdnnf_supervision *sp, int B, int T, const int *seq_state_begin, const int *seq_arc_begin, const int *arc_src,
+                                 const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob, const float *final_logprob,
+                                 float weight, tdnnf_stream stream) {
+  const char *who = "supervision_assign_e2e: ";
+  TDNNF_REQUIRE(sp && sp->kind == 1 && sp->e2e_reserved, "%snot a supervision of tdnnf_supervision_reserve_e2e", who);
+  TDNNF_REQUIRE(B > 0 && T > 0 && seq_state_begin && seq_arc_begin, "%sbad arguments", who);
+  TDNNF_REQUIRE(B <= sp->e2e_max_sequences, "%s%d sequences exceed the capacity max_sequences = %d by %d", who, B, sp->e2e_max_sequences,
+                B - sp->e2e_max_sequences);
+  TDNNF_REQUIRE(T <= sp->e2e_max_frames, "%s%d frames exceed the capacity max_frames = %d by %d", who, T, sp->e2e_max_frames, T - sp->e2e_max_frames);
+  // the recursion's launch form, from this minibatch's largest graph (the graph set's assign refuses an array that is not what it seems)
+  int max_states = 0;
+  for (int s = 0; s < B; s++) max_states = std::max(max_states, seq_state_begin[s + 1] - seq_state_begin[s]);
+  AlignFormPlan form;
+  std::string err;
+  TDNNF_REQUIRE(align_form_plan(max_states, sp->num_pdfs, options().align_form, false, kLdsBudget, who, &form, &err), "%s", err.c_str());
+  // (validates what tdnnf_align_graphs_create validates and the capacities max_states and max_arcs; a refusal leaves everything as it was)
+  int rc = tdnnf_align_graphs_assign(sp->e2e_graphs, B, seq_state_begin, seq_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob, final_logprob,
+                                     nullptr, stream);
+  if (rc) return rc;
+  sp->B = B;
+  sp->T = T;
+  sp->weight = weight;
+  sp->num_states = seq_state_begin[B];
+  sp->num_arcs = seq_arc_begin[B];
+  sp->max_states_per_seq = sp->max_states_per_frame = max_states;
+  sp->e2e_form = form;
+  sp->e2e_assigns++;
   return TDNNF_OK;
 }
 

@@ -74,7 +74,13 @@ struct tdnnf_supervision {
   struct tdnnf_align_graphs *e2e_graphs;  // the arcs by destination, by source and by pdf (align_tables.h); graph s is sequence s's
   double *e2e_alpha, *e2e_beta;           // (T + 1) * num_states doubles each: alpha_t / beta_t of every frame, sequence after sequence
   double *e2e_vecs;                       // 2 * num_states doubles where the two state vectors do not live in LDS, else null
-  tdnnf::AlignFormPlan e2e_form;          // the recursion's launch form (align_tables.h), fixed at creation: e2e_vecs depends on it
+  tdnnf::AlignFormPlan e2e_form;          // the recursion's launch form (align_tables.h), fixed at creation (e2e_vecs depends on it) or planned at every assign
+  // ---- kind 1, RESERVED (tdnnf_supervision_reserve_e2e): e2e_graphs is a reserved graph set, the scratch above is sized for the capacities
+  // (e2e_vecs always: the launch form follows the assigned batch), and tdnnf_supervision_assign_e2e sets B, T, weight, the totals and
+  // e2e_form per minibatch.  All zero for a created supervision.
+  bool e2e_reserved;
+  int e2e_assigns;                        // 0: no minibatch yet, every entry refuses the supervision
+  int e2e_max_sequences, e2e_max_frames;  // the capacities beside the graph set's own
 };
 
 namespace tdnnf {

@@ -252,16 +252,40 @@ class Supervision:
         self._create_e2e(graphs, int(frames_per_sequence), float(weight), num_pdfs)
         return self
 
-    def _create_e2e(self, graphs, T, weight, num_pdfs):
+    @staticmethod
+    def _stack_e2e(graphs):
+        """(graphs as a list, the eight arrays of tdnnf_supervision_create_e2e stacked as AlignGraphs stacks them)"""
         import numpy as np
         graphs = [graphs] if isinstance(graphs, dict) else list(graphs)
-        P = int(num_pdfs if num_pdfs is not None else max(int(g["P"]) for g in graphs))
         sb = np.concatenate([[0], np.cumsum([int(g["S"]) for g in graphs])])
         ab = np.concatenate([[0], np.cumsum([len(g["src"]) for g in graphs])])
         cat = lambda key, off=None: np.concatenate([np.asarray(g[key]) + (0 if off is None else off[i]) for i, g in enumerate(graphs)])
-        k = [iarr(sb), iarr(ab), iarr(cat("src", sb)), iarr(cat("dst", sb)), iarr(cat("pdf")), farr(cat("logprob")), farr(cat("init")), farr(cat("final"))]
+        return graphs, [iarr(sb), iarr(ab), iarr(cat("src", sb)), iarr(cat("dst", sb)), iarr(cat("pdf")), farr(cat("logprob")), farr(cat("init")),
+                        farr(cat("final"))]
+
+    def _create_e2e(self, graphs, T, weight, num_pdfs):
+        graphs, k = self._stack_e2e(graphs)
+        P = int(num_pdfs if num_pdfs is not None else max(int(g["P"]) for g in graphs))
         check(load().tdnnf_supervision_create_e2e(len(graphs), T, P, *[x[1] for x in k], weight, C.byref(self.h)))
         self.B, self.T, self.P = len(graphs), T, P
+
+    @classmethod
+    def reserve_e2e(cls, max_sequences, max_frames, num_pdfs, max_states, max_arcs):
+        """A reusable end-to-end supervision (tdnnf_supervision_reserve_e2e): every allocation is made here, for minibatches of at most
+        max_sequences graphs with max_states states and max_arcs arcs between them and max_frames frames per sequence.  It holds no
+        minibatch until assign (B = T = 0) and is refused until then."""
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        self.B, self.T, self.P = 0, 0, int(num_pdfs)
+        check(load().tdnnf_supervision_reserve_e2e(int(max_sequences), int(max_frames), self.P, int(max_states), int(max_arcs), C.byref(self.h)))
+        return self
+
+    def assign(self, graphs, frames_per_sequence, weight=1.0):
+        """tdnnf_supervision_assign_e2e on the current stream: the reserved supervision's next minibatch -- graphs, frames and weight may all
+        change.  Nothing is allocated or synchronised; B and T follow.  A refused minibatch (HipAbiError) leaves the previous one."""
+        graphs, k = self._stack_e2e(graphs)
+        check(load().tdnnf_supervision_assign_e2e(self.h, len(graphs), int(frames_per_sequence), *[x[1] for x in k], float(weight), stream()))
+        self.B, self.T = len(graphs), int(frames_per_sequence)
 
     @property
     def kind(self):
@@ -295,25 +319,14 @@ class AlignGraphs:
     serves the label methods (labels, best_path_labels, label_posteriors_*) as well.  num_labels: default the largest label + 1."""
 
     def __init__(self, graphs, num_pdfs=None, num_labels=None):
-        import numpy as np
         lib = load()
         graphs = [graphs] if isinstance(graphs, dict) else list(graphs)
         self.h = C.c_void_p()
-        self.G = len(graphs)
+        self.reserved = False
         self.P = int(num_pdfs if num_pdfs is not None else max(int(g["P"]) for g in graphs))
-        sb = np.concatenate([[0], np.cumsum([int(g["S"]) for g in graphs])])
-        ab = np.concatenate([[0], np.cumsum([len(g["src"]) for g in graphs])])
-        cat = lambda key, off=None: np.concatenate([np.asarray(g[key]) + (0 if off is None else off[i]) for i, g in enumerate(graphs)])
-        self._keep = [iarr(sb), iarr(ab), iarr(cat("src", sb)), iarr(cat("dst", sb)), iarr(cat("pdf")), farr(cat("logprob")),
-                      farr(cat("init")), farr(cat("final"))]
-        with_label = ["label" in g for g in graphs]
-        if any(with_label) != all(with_label):
-            raise HipAbiError("AlignGraphs: every graph carries a \"label\" array, or none does")
-        self.labelled = all(with_label)
-        self.arc_begin = ab.astype(np.int64)
+        self.labelled = self._stack(graphs)
         if self.labelled:
-            lab = iarr(cat("label"))
-            self._keep.append(lab)
+            lab = self._keep[8]
             self.L = int(num_labels if num_labels is not None else (int(lab[0].max()) + 1 if len(lab[0]) else 1))
             check(lib.tdnnf_align_graphs_create_labelled(self.G, self.P, *[k[1] for k in self._keep], self.L, C.byref(self.h)))
         else:
@@ -322,6 +335,82 @@ class AlignGraphs:
             self.L = 0
             check(lib.tdnnf_align_graphs_create(self.G, self.P, *[k[1] for k in self._keep], C.byref(self.h)))
         self.num_states = [int(g["S"]) for g in graphs]
+
+    def _stack(self, graphs):
+        """The graphs' arrays stacked with the state numbering of tdnnf_align_graphs_create into self._keep (the eight arrays, and the labels
+        where every graph carries them); sets G and arc_begin.  Returns whether the graphs carry labels."""
+        import numpy as np
+        self.G = len(graphs)
+        sb = np.concatenate([[0], np.cumsum([int(g["S"]) for g in graphs])])
+        ab = np.concatenate([[0], np.cumsum([len(g["src"]) for g in graphs])])
+        cat = lambda key, off=None: np.concatenate([np.asarray(g[key]) + (0 if off is None else off[i]) for i, g in enumerate(graphs)])
+        self._keep = [iarr(sb), iarr(ab), iarr(cat("src", sb)), iarr(cat("dst", sb)), iarr(cat("pdf")), farr(cat("logprob")),
+                      farr(cat("init")), farr(cat("final"))]
+        with_label = ["label" in g for g in graphs]
+        if any(with_label) != all(with_label):
+            raise HipAbiError("AlignGraphs: every graph carries a \"label\" array, or none does")
+        self.arc_begin = ab.astype(np.int64)
+        if all(with_label):
+            self._keep.append(iarr(cat("label")))
+        return all(with_label)
+
+    @classmethod
+    def reserve(cls, max_graphs, num_pdfs, max_states, max_arcs, num_labels=None):
+        """A reusable graph set (tdnnf_align_graphs_reserve): every allocation is made here for max_graphs graphs with max_states states and
+        max_arcs arcs between them; num_labels: None or 0 an unlabelled handle, else one whose every batch carries "label" arrays.  It holds
+        no graphs until assign, and every method refuses it until then."""
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        self.reserved = True
+        self.P, self.L = int(num_pdfs), int(num_labels or 0)
+        self.labelled = self.L > 0
+        self.G, self.num_states, self.arc_begin, self._keep = 0, [], None, []
+        check(load().tdnnf_align_graphs_reserve(int(max_graphs), self.P, self.L, int(max_states), int(max_arcs), C.byref(self.h)))
+        return self
+
+    def assign(self, graphs, stream=None):
+        """tdnnf_align_graphs_assign: the handle's next batch, built on the device in stream order (stream: a raw stream, default the current
+        one).  Nothing is allocated or synchronised; G, num_states, arc_begin follow the new batch, and every method works on it.  A refused
+        batch (HipAbiError) leaves the handle and this object on the previous one."""
+        import torch
+        graphs = [graphs] if isinstance(graphs, dict) else list(graphs)
+        before = (self.G, self.arc_begin, self._keep)
+        on = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+        try:
+            labelled = self._stack(graphs)
+            check(load().tdnnf_align_graphs_assign(self.h, self.G, *[k[1] for k in self._keep[:8]], self._keep[8][1] if labelled else None, on))
+        except HipAbiError:
+            self.G, self.arc_begin, self._keep = before
+            raise
+        self.num_states = [int(g["S"]) for g in graphs]
+
+    def capacity(self):
+        """{max_graphs, max_states, max_arcs, device_bytes, device_allocs, assigns} of a reserved handle (tdnnf_align_graphs_capacity)."""
+        v = [C.c_int(), C.c_int(), C.c_int(), C.c_longlong(), C.c_int(), C.c_int()]
+        check(load().tdnnf_align_graphs_capacity(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("max_graphs", "max_states", "max_arcs", "device_bytes", "device_allocs", "assigns"), (int(x.value) for x in v)))
+
+    def tables(self):
+        """The device arrays of the handle as numpy int32 arrays (tdnnf_align_graphs_dump; waits for the last assign): {"by_dst" / "by_src" /
+        "by_pdf" [/ "by_label"]: {"slots", "heavy", "arcs"} of shape [n, 4], "graphs" [G, 14], "label_ranges", "pdf_columns",
+        "label_columns", "init", "final", "labels"}."""
+        import numpy as np
+        lib = load()
+
+        def dump(table, which):
+            n = C.c_longlong()
+            check(lib.tdnnf_align_graphs_dump(self.h, table, which, None, 0, C.byref(n)))
+            out = np.zeros(n.value, np.int32)
+            check(lib.tdnnf_align_graphs_dump(self.h, table, which, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+            return out
+
+        t = {}
+        for i, name in enumerate(("by_dst", "by_src", "by_pdf", "by_label")[:4 if self.L > 0 else 3]):
+            t[name] = {w: dump(i, j).reshape(-1, 4) for j, w in enumerate(("slots", "heavy", "arcs"))}
+        for j, name in enumerate(("graphs", "label_ranges", "pdf_columns", "label_columns", "init", "final", "labels")):
+            t[name] = dump(4, j)
+        t["graphs"] = t["graphs"].reshape(-1, 14)
+        return t
 
     @classmethod
     def from_den_graph(cls, g):

@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""What a NEW batch of graphs costs per call: (a) tdnnf_align_graphs_create + the call + tdnnf_align_graphs_destroy against (b)
+tdnnf_align_graphs_assign on one reserved handle + the call -- and the same for the end-to-end supervision (tdnnf_supervision_create_e2e /
+_destroy against tdnnf_supervision_assign_e2e) through tdnnf_chain_objf_and_deriv.  Every iteration has different graphs, from a cycle of
+--cycle (at least 8) batches generated and stacked beforehand, so the time is the C path's: host validation and table build or staging,
+allocations and copies or the device build, the call, the frees.
+  forced     64 transcript graphs of some 300 states x 500 frames: tdnnf_align_best_path, and tdnnf_align_posteriors_compact
+  free       the 4 000-state denominator-like graph (one graph a batch, its arcs reordered per batch), 16 utterances x 100 frames: best path
+  numerator  128 graphs of 70 states x 150 frames through tdnnf_chain_objf_and_deriv
+The clock is the host's around a loop over the cycle that ends in ONE synchronise; (a) and (b) alternate in one process, medians of
+--repeats.  After the timing every batch of the cycle runs once either way and the outputs are compared for equality.  One JSON line.
+usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import __graft_entry__ as ge  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--cycle", type=int, default=8)
+    ap.add_argument("--pdfs", type=int, default=6034)
+    ap.add_argument("--only", choices=["forced", "free", "numerator"])
+    args = ap.parse_args()
+    assert args.cycle >= 8, "different graphs every iteration: a cycle of at least 8 batches"
+    pkg = ge.load_package()
+    abi, synth = pkg.hipabi, pkg.synth
+    lib = abi.load()
+    P = args.pdfs
+    res = dict(metric="graphs_per_batch", pdfs=P, cycle=args.cycle, repeats=args.repeats)
+
+    def stacked(graphs):
+        """the eight host arrays of one batch as ctypes pointers (kept alive beside them)"""
+        keep = abi.Supervision._stack_e2e(graphs)[1]
+        return dict(G=len(graphs), S=int(keep[0][0][-1]), A=int(keep[1][0][-1]), keep=keep, ptrs=[k[1] for k in keep])
+
+    def median_ms(fn_a, fn_b, batches):
+        """fn(batch) enqueues one batch's work; ms per batch of each, alternating, medians of --repeats"""
+        def loop(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for b in batches:
+                fn(b)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / len(batches)
+        loop(fn_a), loop(fn_b)  # warm-up: kernels loaded, the allocator's pools filled
+        ms = ([], [])
+        for _ in range(args.repeats):
+            ms[0].append(loop(fn_a))
+            ms[1].append(loop(fn_b))
+        return [dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v]) for v in ms]
+
+    def align_case(name, batches, B, T, utt_graph, entries):
+        """batches: stacked batches of graphs; B utterances x T frames, utterance u on graph utt_graph[u]"""
+        cap = [max(b[k] for b in batches) for k in ("G", "S", "A")]
+        reserved = C.c_void_p()
+        abi.check(lib.tdnnf_align_graphs_reserve(cap[0], P, 0, cap[1], cap[2], C.byref(reserved)))
+        y = torch.randn(B * T, P, device="cuda")
+        frames, rows, ug = abi.iarr([T] * B), abi.iarr(np.arange(B) * T), abi.iarr(utt_graph)
+        s = abi.stream()
+        # per batch the workspace and the compact layout (host questions, asked once on a created handle), one buffer at the largest
+        for b in batches:
+            h = C.c_void_p()
+            abi.check(lib.tdnnf_align_graphs_create(b["G"], P, *b["ptrs"], C.byref(h)))
+            b["nb_path"] = int(lib.tdnnf_align_workspace_bytes(h, B, ug[1], frames[1]))
+            b["nb_post"] = int(lib.tdnnf_align_posteriors_workspace_bytes(h, B, ug[1], frames[1], 1))
+            elems = C.c_longlong()
+            abi.check(lib.tdnnf_align_posteriors_compact_layout(h, B, ug[1], frames[1], C.byref(elems), None))
+            b["elems"] = int(elems.value)
+            lib.tdnnf_align_graphs_destroy(h)
+        nb = max(max(b["nb_path"], b["nb_post"]) for b in batches)
+        ws = abi.workspace(nb)
+        out = {k: (torch.zeros(B * T, dtype=torch.int32, device="cuda"), torch.zeros(max(b["elems"] for b in batches), device="cuda"),
+                   torch.zeros(B, 2, dtype=torch.float64, device="cuda")) for k in "ab"}
+
+        def call(entry, h, b, o):
+            pdfs, values, results = o
+            if entry == "best_path":
+                abi.check(lib.tdnnf_align_best_path(h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, abi.ptr(pdfs), None, abi.ptr(results), abi.ptr(ws), nb, s))
+            else:
+                abi.check(lib.tdnnf_align_posteriors_compact(h, B, ug[1], frames[1], rows[1], 1, abi.pmat(y), 1.0, 1.0, abi.ptr(values), b["elems"], abi.ptr(results),
+                                                             abi.ptr(ws), nb, s))
+
+        d = dict(graphs=cap[0], states=cap[1], arcs=cap[2], utterances=B, frames=T)
+        for entry in entries:
+            def created(b, o=out["a"]):
+                h = C.c_void_p()
+                abi.check(lib.tdnnf_align_graphs_create(b["G"], P, *b["ptrs"], C.byref(h)))
+                call(entry, h, b, o)
+                lib.tdnnf_align_graphs_destroy(h)
+
+            def assigned(b, o=out["b"]):
+                abi.check(lib.tdnnf_align_graphs_assign(reserved, b["G"], *b["ptrs"], None, s))
+                call(entry, reserved, b, o)
+
+            a, bb = median_ms(created, assigned, batches)
+            equal = True
+            for b in batches:
+                for o in out.values():
+                    for t in o:
+                        t.zero_()
+                created(b), assigned(b)
+                torch.cuda.synchronize()
+                equal = equal and all(torch.equal(x.view(torch.int64) if x.dtype == torch.float64 else x.view(torch.int32),
+                                                  z.view(torch.int64) if z.dtype == torch.float64 else z.view(torch.int32)) for x, z in zip(out["a"], out["b"]))
+            d[entry] = dict(create_call_destroy=a, assign_call=bb, assign_over_create=round(bb["ms"] / a["ms"], 3), outputs_equal=bool(equal))
+        lib.tdnnf_align_graphs_destroy(reserved)
+        res[name] = d
+
+    rng = np.random.default_rng(0)
+    if args.only in (None, "forced"):
+        batches = []
+        for c in range(args.cycle):
+            batches.append(stacked([synth.make_alignment_graph(rng.integers(0, P, size=120).tolist(), optional=list(range(5, 120, 10)),
+                                                               alternatives={k: rng.integers(0, P, size=12).tolist() for k in range(3, 120, 8)}, num_pdfs=P,
+                                                               seed=64 * c + u) for u in range(64)]))
+        align_case("forced", batches, 64, 500, np.arange(64), ("best_path", "posteriors_compact"))
+    if args.only in (None, "free"):
+        g = synth.alignment_graph_from_den(synth.make_den_graph(4000, P, mean_out_degree=12.0, seed=1))
+        batches = []
+        for c in range(args.cycle):  # the same graph with its arcs in another order: other arrays, other tables
+            order = np.random.default_rng(c).permutation(len(g["src"]))
+            batches.append(stacked([dict(g, **{k: g[k][order] for k in ("src", "dst", "pdf", "logprob")})]))
+        align_case("free", batches, 16, 100, np.zeros(16, np.int64), ("best_path",))
+    if args.only in (None, "numerator"):
+        B, T = 128, 150
+        batches = [stacked(synth.make_e2e_supervision(B, T, P, units=(69, 69), seed=10 + c)["graphs"]) for c in range(args.cycle)]
+        dg = abi.DenGraph(synth.make_den_graph(64, P, mean_out_degree=4.0, seed=1))  # (the numerator takes the workspace layout from it, nothing else)
+        reserved = C.c_void_p()
+        abi.check(lib.tdnnf_supervision_reserve_e2e(B, T, P, max(b["S"] for b in batches), max(b["A"] for b in batches), C.byref(reserved)))
+        y = torch.randn(B * T, P, device="cuda")
+        xo = torch.log_softmax(torch.randn(B * T, P, device="cuda"), dim=1)
+        nb = int(lib.tdnnf_chain_workspace_bytes(dg.h, B, T))
+        ws = abi.workspace(nb)
+        ws.zero_()
+        s = abi.stream()
+        out = {k: (torch.zeros(8, dtype=torch.float64, device="cuda"), torch.zeros_like(y), torch.zeros_like(y)) for k in "ab"}
+
+        def call(h, o):
+            abi.check(lib.tdnnf_chain_objf_and_deriv(dg.h, h, abi.pmat(y), abi.pmat(xo), 0.1, 5e-5, 0.1, abi.ptr(o[0]), abi.pmat(o[1]), abi.pmat(o[2]), abi.ptr(ws), nb, s))
+
+        def created(b, o=out["a"]):
+            h = C.c_void_p()
+            abi.check(lib.tdnnf_supervision_create_e2e(B, T, P, *b["ptrs"], 1.0, C.byref(h)))
+            call(h, o)
+            lib.tdnnf_supervision_destroy(h)
+
+        def assigned(b, o=out["b"]):
+            abi.check(lib.tdnnf_supervision_assign_e2e(reserved, B, T, *b["ptrs"], 1.0, s))
+            call(reserved, o)
+
+        a, bb = median_ms(created, assigned, batches)
+        equal = True
+        for b in batches:
+            created(b), assigned(b)
+            torch.cuda.synchronize()
+            equal = equal and torch.equal(out["a"][0].view(torch.int64), out["b"][0].view(torch.int64)) and all(
+                torch.equal(x.view(torch.int32), z.view(torch.int32)) for x, z in zip(out["a"][1:], out["b"][1:]))
+        res["numerator"] = dict(sequences=B, frames=T, states=max(b["S"] for b in batches), arcs=max(b["A"] for b in batches), create_call_destroy=a,
+                                assign_call=bb, assign_over_create=round(bb["ms"] / a["ms"], 3), outputs_equal=bool(equal))
+        lib.tdnnf_supervision_destroy(reserved)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
