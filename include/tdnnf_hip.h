@@ -355,8 +355,8 @@ int tdnnf_supervision_info(const tdnnf_supervision *, int *num_states, int *num_
    not live in LDS: option "align_form" 2, or a graph of more than about 9 600 states; the option is read HERE] -- 150 output frames x
    128 transcripts of 200 states: 62 MB.  The chain workspace formulas do not change.
    tdnnf_supervision_info: the total states and arcs, max_states_per_frame = the largest graph's states, wide = 0.
-   Not built: reading end-to-end egs (the egs readers below still refuse <End2End> supervisions), compiling graphs from transcripts,
-   transition-id level output.  All sequences of a call share frames_per_sequence. */
+   Not built: reading end-to-end egs (the egs readers below still refuse <End2End> supervisions), transition-id level output.  Graphs
+   from transcripts: tdnnf_supervision_assign_e2e_transcripts below, for a reserved supervision.  All sequences of a call share frames_per_sequence. */
 int tdnnf_supervision_create_e2e(int num_sequences, int frames_per_sequence, int num_pdfs, const int *seq_state_begin, const int *seq_arc_begin,
                                  const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
                                  const float *initial_logprob, const float *final_logprob, float weight, tdnnf_supervision **out);
@@ -375,6 +375,15 @@ int tdnnf_supervision_reserve_e2e(int max_sequences, int max_frames, int num_pdf
 int tdnnf_supervision_assign_e2e(tdnnf_supervision *, int num_sequences, int frames_per_sequence, const int *seq_state_begin,
                                  const int *seq_arc_begin, const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
                                  const float *initial_logprob, const float *final_logprob, float weight, tdnnf_stream stream);
+/* tdnnf_supervision_assign_e2e from transcripts: the next minibatch of a supervision of tdnnf_supervision_reserve_e2e compiled on the
+   device from unit sequences ("transcript graphs" below: the unit set, the slots, the graph of a transcript and what is refused;
+   tdnnf_align_graphs_assign_transcripts does the work on the supervision's graph set).  num_sequences transcripts, one per sequence.
+   The capacities, the launch form planned from the largest graph, stream order and what a refusal leaves in place are
+   tdnnf_supervision_assign_e2e's.  A transcript with more mandatory slots than frames_per_sequence is not refused: the objective's
+   failure path, as for any graph without an accepting path of that length. */
+int tdnnf_supervision_assign_e2e_transcripts(tdnnf_supervision *, const struct tdnnf_unit_set *units, int num_sequences, int frames_per_sequence,
+                                             const int *slot_begin, const int *slot_unit, const int *slot_optional, float weight,
+                                             tdnnf_stream stream);
 /* 0 time-synchronous (tdnnf_supervision_create), 1 end-to-end (tdnnf_supervision_create_e2e); -1 for NULL */
 int tdnnf_supervision_kind(const tdnnf_supervision *);
 /* diagnostics, end-to-end kind only: the launch form of its recursion -- threads per workgroup (64 up to 64 states in the largest graph,
@@ -438,7 +447,8 @@ int tdnnf_chain_numerator_part(const tdnnf_den_graph *, const tdnnf_supervision 
 /* ------------------------------------------------------------------ A7, best-path alignment
  * The best path (Viterbi) of a cyclic, epsilon-free acceptor with pdf-ids on its arcs, scored on rows of the model's output: forced
  * alignment on transcript graphs (what nnet3-align-compiled | ali-to-pdf prints) and the free best path through the denominator graph.
- * Not a decoder: no beam, no lattice; compiling graphs from transcripts stays the caller's job.  Transition-ids, phones and word positions
+ * Not a decoder: no beam, no lattice.  Graphs are the caller's arrays, or compiled on the device from unit sequences for the chain
+ * topology (tdnnf_align_graphs_assign_transcripts below); lexicon and tree handling stay the caller's job.  Transition-ids, phones and word positions
  * are the caller's: a second integer per arc, the arc's LABEL (tdnnf_align_graphs_create_labelled), which the labelled entries below report
  * per frame (tdnnf_align_best_path_labels) and form posteriors over (tdnnf_align_label_posteriors_compact / _sparse).
  *
@@ -520,6 +530,53 @@ int tdnnf_align_graphs_assign(tdnnf_align_graphs *, int num_graphs, const int *g
    since it exists (the witness that assign makes none) and the assigns that succeeded.  Any out-pointer may be NULL. */
 int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *, int *max_graphs, int *max_states, int *max_arcs, long long *device_bytes,
                                 int *device_allocs, int *assigns);
+/* TRANSCRIPT GRAPHS: a reserved handle's batch compiled on the device from unit (phone) sequences, so that the caller hands over
+   transcripts and never builds an arc array.
+   A UNIT SET is made once and is device-resident: num_units units over num_pdfs pdfs with the chain topology -- one state per unit, an
+   entry pdf on its first frame, a loop pdf on every later frame.  context 0 (context-independent): entry_pdf and loop_pdf have num_units
+   ints each.  context 1 (left-biphone): (num_units + 1) * num_units ints each, at index (left + 1) * num_units + u, left = -1 meaning
+   "nothing before it".  loop_logprob[u] and leave_logprob[u] (num_units floats each) weigh the self-loop and EVERY arc that leaves the
+   unit (for a transcript's last unit: its final weight); take_logprob and skip_logprob apply to a slot marked optional when it is taken or
+   skipped (optional silence).  TDNNF_EINVAL: a pdf outside [0, num_pdfs), num_units above 32767.
+   A TRANSCRIPT is n >= 1 slots, slot k a unit u_k and a flag opt_k; transcript g owns the slots [slot_begin[g], slot_begin[g + 1]) of
+   slot_unit and slot_optional (slot_begin[0] = 0).  Refused with TDNNF_EINVAL naming the transcript and the slot: a unit outside
+   [0, num_units), two adjacent optional slots, a transcript without a mandatory slot.  Its graph:
+     states   0 the start; then for every slot k in order A_k, whose left neighbour is slot k-1 (nothing for k = 0), and directly behind it
+              B_k -- only in context 1, for k >= 1 and opt_k-1 -- whose left neighbour is slot k-2 (nothing for k = 1): slot k-1 was skipped.
+              A state's pdfs are entry_pdf and loop_pdf at (unit of its left neighbour or -1, u_k).  S = 1 + n + #B.
+     arcs     on every unit state a self-loop with its loop pdf and loop_logprob[u_k];
+              into A_k from every state of slot k-1 with leave_logprob[u_k-1], from the start with 0 for k = 0, plus take_logprob if opt_k;
+              where opt_k-1, k >= 1: from every state of slot k-2 with leave_logprob[u_k-2] + skip_logprob (from the start with
+              skip_logprob for k = 1) into B_k in context 1, into A_k in context 0;
+              an arc that enters a state carries the state's entry pdf.  Every weight is a float formed by at most one float addition.
+              Ordered by (source, destination), no pair twice; every state of slot k has 1 + [k+1 < n] + [k+2 < n and opt_k+1] arcs, the
+              start 1 + [n >= 2 and opt_0]; at most 3 arcs enter a state.
+     initial  0 at state 0;  final  leave_logprob[u_n-1] on the states of slot n-1 and, if opt_n-1, leave_logprob[u_n-2] + skip_logprob on
+              those of slot n-2;  -inf elsewhere.
+     labels   (labelled handles) an arc's label is the slot of its destination: tdnnf_align_best_path_labels gives every frame's position
+              in the transcript, and its run lengths are the segmentation.  num_labels must cover the longest transcript's slots.
+   With context 0 and entry_pdf = loop_pdf this is the graph of one unit per entry with skips over the optional ones.
+   tdnnf_transcript_graph_sizes is host-only: the states and arcs of every transcript (either out-pointer may be NULL), for sizing a
+   reserve; it refuses what the assign refuses with the same messages under its own name.
+   tdnnf_align_graphs_assign_transcripts is tdnnf_align_graphs_assign from transcripts: reserved handles only, of the unit set's num_pdfs
+   (else TDNNF_EINVAL); it validates the slots and the three capacities (named with their excess as assign names them) and, for a labelled
+   handle, num_labels before anything is written, so a refused call leaves the previous batch in place.  The host works in O(slots): from
+   the closed forms it derives the begins, per graph the arcs and the largest in-degree, and the column lists, stages 4 bytes a slot where
+   assign stages 28 bytes an arc, and enqueues on `stream` the copies, ONE kernel that writes the arcs, initial and final weights and labels
+   (csrc/align_compile_kernels.h) and the three build kernels of tdnnf_align_graphs_assign, unchanged: the tables are the bytes an assign
+   of the same graphs builds.  No allocation, no free, no device-wide or stream-wide wait; the one host wait there can be is for the
+   staging copy of the assign before last.  Stream order, the host-side answers and tdnnf_align_graphs_capacity's `assigns` are
+   tdnnf_align_graphs_assign's; both kinds of assign may alternate on one handle.
+   Not built: pronunciation alternatives and adjacent optional slots, lexicon and tree handling (the caller maps words to units and
+   (left, unit) to pdfs), right context, units of several states, capture into a HIP graph. */
+typedef struct tdnnf_unit_set tdnnf_unit_set;
+int tdnnf_unit_set_create(int num_units, int num_pdfs, int context, const int *entry_pdf, const int *loop_pdf, const float *loop_logprob,
+                          const float *leave_logprob, float take_logprob, float skip_logprob, tdnnf_unit_set **out);
+void tdnnf_unit_set_destroy(tdnnf_unit_set *);
+int tdnnf_transcript_graph_sizes(const tdnnf_unit_set *, int num_transcripts, const int *slot_begin, const int *slot_unit,
+                                 const int *slot_optional, int *states_out, int *arcs_out);
+int tdnnf_align_graphs_assign_transcripts(tdnnf_align_graphs *, const tdnnf_unit_set *, int num_transcripts, const int *slot_begin,
+                                          const int *slot_unit, const int *slot_optional, tdnnf_stream stream);
 /* diagnostics (tests): a copy-out of the device arrays of a created or an assigned handle, as ints, after waiting for the stream of the last
    assign.  table 0 by destination, 1 by source, 2 by pdf, 3 by label (labelled handles): which 0 the slots, 1 the heavy-row descriptors,
    2 the arc entries, 4 ints each.  table 4: which 0 the graph descriptors (14 ints a graph), 1 the by-label ranges (4 ints a graph), 2 the

@@ -415,6 +415,27 @@ inline void AlignGraphsAssign(tdnnf_align_graphs *graphs, int num_graphs, const 
                                   final_logprob, arc_label, stream));
 }
 
+// Transcript graphs (tdnnf_hip.h, "TRANSCRIPT GRAPHS"): the same two assigns from unit (phone) sequences, the graphs compiled on the
+// device.  A unit set is made once from the tree's answers -- per unit, or per (left unit, unit) with context 1, the pdf of the first frame
+// and of the later frames, and the transition model's loop and leave log-probabilities; release with tdnnf_unit_set_destroy.  Transcript g
+// is the slots [slot_begin[g], slot_begin[g + 1]) of slot_unit / slot_optional (optional: silence that may be skipped).  Throws on a bad
+// slot, naming the transcript and the slot, and on a batch beyond a capacity; the handle then still holds its previous batch.
+inline tdnnf_unit_set *UnitSetCreate(int num_units, int num_pdfs, int context, const int *entry_pdf, const int *loop_pdf, const float *loop_logprob,
+                                     const float *leave_logprob, float take_logprob, float skip_logprob) {
+  tdnnf_unit_set *units = nullptr;
+  Check(tdnnf_unit_set_create(num_units, num_pdfs, context, entry_pdf, loop_pdf, loop_logprob, leave_logprob, take_logprob, skip_logprob, &units));
+  return units;
+}
+inline void AlignGraphsAssignTranscripts(tdnnf_align_graphs *graphs, const tdnnf_unit_set *units, int num_transcripts, const int *slot_begin,
+                                         const int *slot_unit, const int *slot_optional, tdnnf_stream stream) {
+  Check(tdnnf_align_graphs_assign_transcripts(graphs, units, num_transcripts, slot_begin, slot_unit, slot_optional, stream));
+}
+inline void SupervisionAssignE2eTranscripts(tdnnf_supervision *sup, const tdnnf_unit_set *units, int num_sequences, int frames_per_sequence,
+                                            const int *slot_begin, const int *slot_unit, const int *slot_optional, float weight,
+                                            tdnnf_stream stream) {
+  Check(tdnnf_supervision_assign_e2e_transcripts(sup, units, num_sequences, frames_per_sequence, slot_begin, slot_unit, slot_optional, weight, stream));
+}
+
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance

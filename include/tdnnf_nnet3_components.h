@@ -2057,6 +2057,30 @@ inline void AssignAlignGraphs(tdnnf_align_graphs *graphs, int32 num_graphs, cons
                                    arc_logprob.data(), initial_logprob.data(), final_logprob.data(), arc_label.empty() ? nullptr : arc_label.data(), Hooks().stream);
 }
 
+// The two assigns from TRANSCRIPTS: the graphs are compiled on the device from unit (phone) sequences (tdnnf_hip.h, "TRANSCRIPT GRAPHS"), so
+// the caller maps words to phones and (left phone, phone) to pdfs and builds no arc array.  A unit set is made once -- context 0: entry_pdf
+// and loop_pdf have num_units entries; context 1 (left-biphone): (num_units + 1) * num_units, at (left + 1) * num_units + unit -- and
+// released with tdnnf_unit_set_destroy.  Transcript g is the slots [slot_begin[g], slot_begin[g + 1]); slot_optional marks optional silence.
+inline tdnnf_unit_set *CreateUnitSet(int32 num_pdfs, int32 context, const std::vector<int32> &entry_pdf, const std::vector<int32> &loop_pdf,
+                                     const std::vector<float> &loop_logprob, const std::vector<float> &leave_logprob, float take_logprob, float skip_logprob) {
+  if (loop_logprob.size() != leave_logprob.size() || entry_pdf.size() != loop_pdf.size() ||
+      entry_pdf.size() != (context ? loop_logprob.size() + 1 : 1) * loop_logprob.size())
+    throw std::runtime_error("tdnnf_nnet3: CreateUnitSet: the tables' sizes do not fit the context");
+  return tdnnf_adapter::UnitSetCreate(static_cast<int32>(loop_logprob.size()), num_pdfs, context, entry_pdf.data(), loop_pdf.data(), loop_logprob.data(),
+                                      leave_logprob.data(), take_logprob, skip_logprob);
+}
+inline void AssignAlignGraphsFromTranscripts(tdnnf_align_graphs *graphs, const tdnnf_unit_set *units, const std::vector<int32> &slot_begin,
+                                             const std::vector<int32> &slot_unit, const std::vector<int32> &slot_optional) {
+  tdnnf_adapter::AlignGraphsAssignTranscripts(graphs, units, static_cast<int32>(slot_begin.size()) - 1, slot_begin.data(), slot_unit.data(), slot_optional.data(),
+                                              Hooks().stream);
+}
+inline void AssignEnd2EndSupervisionFromTranscripts(tdnnf_supervision *supervision, const tdnnf_unit_set *units, int32 frames_per_sequence,
+                                                    const std::vector<int32> &slot_begin, const std::vector<int32> &slot_unit,
+                                                    const std::vector<int32> &slot_optional, float weight) {
+  tdnnf_adapter::SupervisionAssignE2eTranscripts(supervision, units, static_cast<int32>(slot_begin.size()) - 1, frames_per_sequence, slot_begin.data(),
+                                                 slot_unit.data(), slot_optional.data(), weight, Hooks().stream);
+}
+
 // ------------------------------------------------------------------------------------------------ best-path alignment
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames

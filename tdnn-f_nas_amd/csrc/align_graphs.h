@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "align_tables.h"
+#include "align_transcripts.h"
 #include "common.h"
 
 namespace tdnnf {
@@ -65,7 +66,30 @@ struct AlignBuildDev {
   int G, num_tables;        // 3, or 4 with labels
 };
 
+// ---- the transcript compile of a reserved handle (align_compile.hip, align_compile_kernels.h): what its kernel takes by value
+struct AlignUnitDev {  // a unit set's tables on the device (align_transcripts.h TranscriptUnits)
+  const int *entry_pdf, *loop_pdf;
+  const float *loop_logprob, *leave_logprob;
+  float take_logprob, skip_logprob;
+  int U, context;
+};
+struct AlignCompileDev {
+  const int *slot_begin;               // [G + 1] (device staging)
+  const int *slots;                    // per slot 2 * unit + optional (device staging)
+  const int *state_begin, *arc_begin;  // [G + 1] (device staging)
+  int *src, *dst, *pdf, *lp_bits;      // [arcs] device staging: what AlignBuildDev reads
+  int *label;                          // [arcs] the handle's arc labels; null for an unlabelled handle
+  float *init, *final;                 // [states] the handle's
+  AlignUnitDev units;
+};
+
 }  // namespace tdnnf
+
+struct tdnnf_unit_set {
+  tdnnf::TranscriptUnits host;  // the tables as the caller gave them: validation, sizes and the column lists are host work
+  tdnnf::AlignUnitDev dev;      // the same on the device, pieces of `arena`
+  void *arena;                  // device, owned: the one allocation
+};
 
 struct tdnnf_align_graphs {
   int G, P;

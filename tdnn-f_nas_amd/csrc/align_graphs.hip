@@ -1,8 +1,9 @@
 // align_graphs.hip -- creates, describes and destroys a tdnnf_align_graphs (include/tdnnf_hip.h, "best-path alignment"): validates the caller's
 // arrays, builds the three arc tables (four for labelled graphs) on the host (align_tables.h) and uploads them.  And the reusable kind:
 // tdnnf_align_graphs_reserve allocates a handle once for a capacity, tdnnf_align_graphs_assign validates a batch, stages it and enqueues the
-// copies and the device build (align_build.hip) on the caller's stream; tdnnf_align_graphs_dump copies the device arrays of either kind out
-// for tests.  Its readers: align.hip, align_fb.hip, align_sparse.hip, chain_num_e2e.hip.
+// copies and the device build (align_build.hip) on the caller's stream; tdnnf_align_graphs_assign_transcripts does the same from unit
+// sequences (a tdnnf_unit_set; the host side in align_transcripts.h), with the compile kernel (align_compile.hip) writing the arc arrays in
+// front of the build; tdnnf_align_graphs_dump copies the device arrays of either kind out for tests.  Its readers: align.hip, align_fb.hip, align_sparse.hip, chain_num_e2e.hip.
 #include <math.h>
 #include <string.h>
 
@@ -197,6 +198,7 @@ size_t align_stage(char *host, size_t *at, const T *v, size_t n) {
 }  // namespace
 
 int align_build_launch(const AlignBuildDev &b, int max_graph_arcs, int max_graph_rows, hipStream_t s);  // align_build.hip
+int align_compile_launch(const AlignCompileDev &c, int G, hipStream_t s);                                // align_compile.hip
 
 }  // namespace tdnnf
 
@@ -330,6 +332,159 @@ int tdnnf_align_graphs_assign(tdnnf_align_graphs *g, int num_graphs, const int *
   g->col_pdfs.swap(col_pdfs);
   g->lcol_begin.swap(lcol_begin);
   g->col_labels.swap(col_labels);
+  g->last_stream = s;
+  g->assigns++;
+  return TDNNF_OK;
+}
+
+// ---- transcript graphs: a unit set made once, and the assign that compiles a batch of transcripts on the device (align_transcripts.h,
+// align_compile.hip)
+
+int tdnnf_unit_set_create(int num_units, int num_pdfs, int context, const int *entry_pdf, const int *loop_pdf, const float *loop_logprob,
+                          const float *leave_logprob, float take_logprob, float skip_logprob, tdnnf_unit_set **out) {
+  const char *who = "unit_set_create: ";
+  TDNNF_REQUIRE(out && num_units > 0 && num_units < 1 << 15 && num_pdfs > 0 && (context == 0 || context == 1) && entry_pdf && loop_pdf && loop_logprob &&
+                    leave_logprob,
+                "%sbad arguments (num_units %d of at most 32767, num_pdfs %d, context %d, or a null array)", who, num_units, num_pdfs, context);
+  const size_t U = num_units, n = context ? (U + 1) * U : U;
+  for (size_t i = 0; i < n; i++) {
+    TDNNF_REQUIRE(entry_pdf[i] >= 0 && entry_pdf[i] < num_pdfs, "%sentry_pdf[%zu] is %d, outside [0, %d)", who, i, entry_pdf[i], num_pdfs);
+    TDNNF_REQUIRE(loop_pdf[i] >= 0 && loop_pdf[i] < num_pdfs, "%sloop_pdf[%zu] is %d, outside [0, %d)", who, i, loop_pdf[i], num_pdfs);
+  }
+  tdnnf_unit_set *u = new tdnnf_unit_set();
+  u->host.U = num_units;
+  u->host.P = num_pdfs;
+  u->host.context = context;
+  u->host.entry_pdf.assign(entry_pdf, entry_pdf + n);
+  u->host.loop_pdf.assign(loop_pdf, loop_pdf + n);
+  u->host.loop_logprob.assign(loop_logprob, loop_logprob + U);
+  u->host.leave_logprob.assign(leave_logprob, leave_logprob + U);
+  u->host.take_logprob = take_logprob;
+  u->host.skip_logprob = skip_logprob;
+  u->arena = nullptr;
+  const auto layout = [&](AlignCarve c) {  // the four tables out of one allocation; with a null base only their size
+    u->dev.entry_pdf = c.take<int>(n);
+    u->dev.loop_pdf = c.take<int>(n);
+    u->dev.loop_logprob = c.take<float>(U);
+    u->dev.leave_logprob = c.take<float>(U);
+    return c.at;
+  };
+  if (hipError_t e = hipMalloc(&u->arena, layout(AlignCarve{nullptr, 0}))) {
+    delete u;
+    return hip_status(e, "unit_set_create: hipMalloc");
+  }
+  layout(AlignCarve{static_cast<char *>(u->arena), 0});
+  u->dev.take_logprob = take_logprob;
+  u->dev.skip_logprob = skip_logprob;
+  u->dev.U = num_units;
+  u->dev.context = context;
+  hipError_t e = hipMemcpy(const_cast<int *>(u->dev.entry_pdf), entry_pdf, sizeof(int) * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(const_cast<int *>(u->dev.loop_pdf), loop_pdf, sizeof(int) * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(const_cast<float *>(u->dev.loop_logprob), loop_logprob, sizeof(float) * U, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(const_cast<float *>(u->dev.leave_logprob), leave_logprob, sizeof(float) * U, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    tdnnf_unit_set_destroy(u);
+    return hip_status(e, "unit_set_create: hipMemcpy");
+  }
+  *out = u;
+  return TDNNF_OK;
+}
+
+void tdnnf_unit_set_destroy(tdnnf_unit_set *u) {
+  if (!u) return;
+  (void)hipFree(u->arena);
+  delete u;
+}
+
+int tdnnf_transcript_graph_sizes(const tdnnf_unit_set *units, int num_transcripts, const int *slot_begin, const int *slot_unit, const int *slot_optional,
+                                 int *states_out, int *arcs_out) {
+  const char *who = "transcript_graph_sizes: ";
+  TDNNF_REQUIRE(units, "%snull unit set", who);
+  std::string err;
+  TDNNF_REQUIRE(transcripts_validate(who, units->host, num_transcripts, slot_begin, slot_unit, slot_optional, &err), "%s", err.c_str());
+  for (int k = 0; k < num_transcripts; k++) {
+    int S, A;
+    transcript_graph_size(units->host.context, slot_begin[k + 1] - slot_begin[k], slot_optional + slot_begin[k], &S, &A);
+    if (states_out) states_out[k] = S;
+    if (arcs_out) arcs_out[k] = A;
+  }
+  return TDNNF_OK;
+}
+
+int tdnnf_align_graphs_assign_transcripts(tdnnf_align_graphs *g, const tdnnf_unit_set *units, int num_transcripts, const int *slot_begin,
+                                          const int *slot_unit, const int *slot_optional, tdnnf_stream stream) {
+  const char *who = "align_graphs_assign_transcripts: ";
+  TDNNF_REQUIRE(g && units, "%snull graphs or null unit set", who);
+  TDNNF_REQUIRE(g->reserved, "%sthe handle was made by tdnnf_align_graphs_create: only a handle of tdnnf_align_graphs_reserve can be assigned", who);
+  TDNNF_REQUIRE(units->host.P == g->P, "%sthe unit set names %d pdfs, the handle was reserved for num_pdfs %d", who, units->host.P, g->P);
+  std::string err;
+  TDNNF_REQUIRE(transcripts_validate(who, units->host, num_transcripts, slot_begin, slot_unit, slot_optional, &err), "%s", err.c_str());
+  const bool labelled = g->L > 0;
+  TranscriptPlan p;
+  TDNNF_REQUIRE(transcripts_plan(who, units->host, num_transcripts, slot_begin, slot_unit, slot_optional, labelled, &p, &err), "%s", err.c_str());
+  const int G = num_transcripts, NS = p.state_begin[G], NA = p.arc_begin[G], N = slot_begin[G];
+  TDNNF_REQUIRE(!labelled || p.max_slots <= g->L, "%sthe longest transcript has %d slots, and a slot is a label: the handle's num_labels = %d is short by %d", who,
+                p.max_slots, g->L, p.max_slots - g->L);
+  TDNNF_REQUIRE(G <= g->cap_graphs, "%s%d graphs exceed the capacity max_graphs = %d by %d", who, G, g->cap_graphs, G - g->cap_graphs);
+  TDNNF_REQUIRE(NS <= g->cap_states, "%s%d states exceed the capacity max_states = %d by %d", who, NS, g->cap_states, NS - g->cap_states);
+  TDNNF_REQUIRE(NA <= g->cap_arcs, "%s%d arcs exceed the capacity max_arcs = %d by %d", who, NA, g->cap_arcs, NA - g->cap_arcs);
+  // the staging's two shapes: on the host the begins, the slots and the column lists; on the device the begins and the slots, behind them
+  // the four arc arrays the kernel writes.  Both fit what tdnnf_align_graphs_reserve sized for 28 bytes an arc (slots < states, 2 <= arcs a graph)
+  const size_t begins = sizeof(int) * ((size_t)G + 1) * (labelled ? 5 : 4), lists = sizeof(int) * (2 * (size_t)G + p.col_pdfs.size() + p.col_labels.size());
+  const size_t raw_bytes = begins + sizeof(int) * (size_t)N;
+  TDNNF_REQUIRE(raw_bytes + lists <= g->stage_bytes && raw_bytes + 4 * sizeof(int) * (size_t)NA <= g->stage_bytes,
+                "%sinternal: the batch needs %zu bytes of staging on the host and %zu on the device, the handle has %zu", who, raw_bytes + lists,
+                raw_bytes + 4 * sizeof(int) * (size_t)NA, g->stage_bytes);
+
+  // staging: the one wait of this path, for the copies of the assign before last out of the buffer that is now overwritten
+  const int slot = g->assigns & 1;
+  if (g->stage_used[slot]) TDNNF_HIP(hipEventSynchronize(g->stage_event[slot]));
+  char *host = g->stage_host[slot];
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  AlignBuildDev &b = g->build;
+  AlignCompileDev c;
+  size_t at = 0;
+  const auto raw = [&](const std::vector<int> &v, size_t n) { return reinterpret_cast<const int *>(g->stage_dev + align_stage(host, &at, v.data(), n)); };
+  b.G = G;
+  b.state_begin = c.state_begin = raw(p.state_begin, (size_t)G + 1);
+  b.arc_begin = c.arc_begin = raw(p.arc_begin, (size_t)G + 1);
+  b.col_begin = raw(p.col_begin, (size_t)G + 1);
+  b.lcol_begin = raw(p.lcol_begin, labelled ? (size_t)G + 1 : 0);
+  c.slot_begin = reinterpret_cast<const int *>(g->stage_dev + align_stage(host, &at, slot_begin, (size_t)G + 1));
+  c.slots = raw(p.packed, N);
+  int *arcs = reinterpret_cast<int *>(g->stage_dev + at);  // (device only: the kernel writes them)
+  b.src = c.src = arcs;
+  b.dst = c.dst = arcs + NA;
+  b.pdf = c.pdf = arcs + 2 * (size_t)NA;
+  b.lp_bits = c.lp_bits = arcs + 3 * (size_t)NA;
+  c.label = labelled ? const_cast<int *>(g->arc_label_dev) : nullptr;
+  c.init = const_cast<float *>(g->dev.init);
+  c.final = const_cast<float *>(g->dev.final);
+  c.units = units->dev;
+  TDNNF_HIP(hipMemcpyAsync(g->stage_dev, host, at, hipMemcpyHostToDevice, s));
+  const auto direct = [&](const void *to, const std::vector<int> &v) {
+    const size_t from = align_stage(host, &at, v.data(), v.size());
+    return v.empty() ? hipSuccess : hipMemcpyAsync(const_cast<void *>(to), host + from, sizeof(int) * v.size(), hipMemcpyHostToDevice, s);
+  };
+  TDNNF_HIP(direct(g->num_cols_dev, p.num_cols));
+  TDNNF_HIP(direct(g->col_pdfs_dev, p.col_pdfs));
+  if (labelled) {
+    TDNNF_HIP(direct(g->num_lcols_dev, p.num_lcols));
+    TDNNF_HIP(direct(g->col_labels_dev, p.col_labels));
+  }
+  TDNNF_HIP(hipEventRecord(g->stage_event[slot], s));
+  g->stage_used[slot] = true;
+  int rc;
+  if ((rc = align_compile_launch(c, G, s)) || (rc = align_build_launch(b, p.max_graph_arcs, p.max_graph_rows, s))) return rc;
+
+  g->G = G;
+  g->state_begin.swap(p.state_begin);
+  g->num_arcs.swap(p.num_arcs);
+  g->max_in_degree.swap(p.max_in_degree);
+  g->col_begin.swap(p.col_begin);
+  g->col_pdfs.swap(p.col_pdfs);
+  g->lcol_begin.swap(p.lcol_begin);
+  g->col_labels.swap(p.col_labels);
   g->last_stream = s;
   g->assigns++;
   return TDNNF_OK;

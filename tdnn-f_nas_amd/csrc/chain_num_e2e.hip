@@ -184,6 +184,42 @@ int tdnnf_supervision_assign_e2e(tdnnf_supervision *sp, int B, int T, const int 
   return TDNNF_OK;
 }
 
+int tdnnf_supervision_assign_e2e_transcripts(tdnnf_supervision *sp, const tdnnf_unit_set *units, int B, int T, const int *slot_begin, const int *slot_unit,
+                                             const int *slot_optional, float weight, tdnnf_stream stream) {
+  const char *who = "supervision_assign_e2e_transcripts: ";
+  TDNNF_REQUIRE(sp && sp->kind == 1 && sp->e2e_reserved, "%snot a supervision of tdnnf_supervision_reserve_e2e", who);
+  TDNNF_REQUIRE(units && B > 0 && T > 0, "%sbad arguments", who);
+  TDNNF_REQUIRE(B <= sp->e2e_max_sequences, "%s%d sequences exceed the capacity max_sequences = %d by %d", who, B, sp->e2e_max_sequences,
+                B - sp->e2e_max_sequences);
+  TDNNF_REQUIRE(T <= sp->e2e_max_frames, "%s%d frames exceed the capacity max_frames = %d by %d", who, T, sp->e2e_max_frames, T - sp->e2e_max_frames);
+  // the recursion's launch form, from this minibatch's largest graph: the closed forms of align_transcripts.h, O(slots)
+  std::string err;
+  TDNNF_REQUIRE(transcripts_validate(who, units->host, B, slot_begin, slot_unit, slot_optional, &err), "%s", err.c_str());
+  int max_states = 0;
+  long long num_states = 0, num_arcs = 0;
+  for (int s = 0; s < B; s++) {
+    int S, A;
+    transcript_graph_size(units->host.context, slot_begin[s + 1] - slot_begin[s], slot_optional + slot_begin[s], &S, &A);
+    max_states = std::max(max_states, S);
+    num_states += S;
+    num_arcs += A;
+  }
+  AlignFormPlan form;
+  TDNNF_REQUIRE(align_form_plan(max_states, sp->num_pdfs, options().align_form, false, kLdsBudget, who, &form, &err), "%s", err.c_str());
+  // (the capacities max_states and max_arcs and the unit set's num_pdfs; a refusal leaves everything as it was)
+  int rc = tdnnf_align_graphs_assign_transcripts(sp->e2e_graphs, units, B, slot_begin, slot_unit, slot_optional, stream);
+  if (rc) return rc;
+  sp->B = B;
+  sp->T = T;
+  sp->weight = weight;
+  sp->num_states = (int)num_states;
+  sp->num_arcs = (int)num_arcs;
+  sp->max_states_per_seq = sp->max_states_per_frame = max_states;
+  sp->e2e_form = form;
+  sp->e2e_assigns++;
+  return TDNNF_OK;
+}
+
 int tdnnf_supervision_kind(const tdnnf_supervision *sp) {
   if (!sp) {
     set_error("supervision_kind: null supervision");

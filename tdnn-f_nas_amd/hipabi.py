@@ -226,6 +226,55 @@ class DenGraph:
             self.h = None
 
 
+def _slots(transcripts):
+    """A batch of transcripts -- each a (units, optional) pair of int sequences of one length -- as the three arrays of the C entries:
+    (slot_begin, slot_unit, slot_optional), each an (array, pointer) pair of iarr."""
+    import numpy as np
+    transcripts = [(np.asarray(u, dtype=np.int64).reshape(-1), np.asarray(o, dtype=np.int64).reshape(-1)) for u, o in transcripts]
+    for g, (u, o) in enumerate(transcripts):
+        if len(u) != len(o):
+            raise HipAbiError(f"transcript {g}: {len(u)} units and {len(o)} optional flags")
+    begin = np.concatenate([[0], np.cumsum([len(u) for u, _ in transcripts])])
+    cat = lambda i: np.concatenate([t[i] for t in transcripts]) if transcripts else np.zeros(0, np.int64)
+    return iarr(begin), iarr(cat(0)), iarr(cat(1) != 0)
+
+
+class UnitSet:
+    """Device-resident unit set for transcript graphs (tdnnf_unit_set): U units over num_pdfs pdfs, one state per unit with an entry pdf on
+    its first frame and a loop pdf on every later one.  entry_pdf / loop_pdf: shape (U,) -- context 0, context-independent -- or (U + 1, U)
+    -- context 1, left-biphone: row left + 1, row 0 for "nothing before it".  loop_logprob / leave_logprob: U floats, the weight of the
+    self-loop and of every arc that leaves the unit.  take_logprob / skip_logprob: an optional slot taken or skipped.  A transcript is a
+    (units, optional) pair of int sequences; AlignGraphs.assign_transcripts and Supervision.assign_transcripts take a list of them."""
+
+    def __init__(self, entry_pdf, loop_pdf, loop_logprob, leave_logprob, num_pdfs, take_logprob=0.0, skip_logprob=0.0):
+        import numpy as np
+        entry, loop = np.asarray(entry_pdf), np.asarray(loop_pdf)
+        self.h = C.c_void_p()
+        if entry.ndim not in (1, 2) or entry.shape != loop.shape or (entry.ndim == 2 and entry.shape[0] != entry.shape[1] + 1):
+            raise HipAbiError(f"UnitSet: entry_pdf {entry.shape} and loop_pdf {loop.shape} must both be (U,) or (U + 1, U)")
+        self.context, self.U, self.P = entry.ndim - 1, int(entry.shape[-1]), int(num_pdfs)
+        if len(loop_logprob) != self.U or len(leave_logprob) != self.U:
+            raise HipAbiError(f"UnitSet: loop_logprob and leave_logprob must have U = {self.U} entries")
+        k = [iarr(entry.reshape(-1)), iarr(loop.reshape(-1)), farr(loop_logprob), farr(leave_logprob)]
+        check(load().tdnnf_unit_set_create(self.U, self.P, self.context, k[0][1], k[1][1], k[2][1], k[3][1], float(take_logprob), float(skip_logprob),
+                                           C.byref(self.h)))
+
+    def sizes(self, transcripts):
+        """tdnnf_transcript_graph_sizes (host only): (states, arcs), numpy int32 arrays with one entry per transcript -- what a reserve
+        must cover.  Refuses (HipAbiError) what assign_transcripts refuses."""
+        import numpy as np
+        begin, unit, opt = _slots(transcripts)
+        states, arcs = np.zeros(len(begin[0]) - 1, np.int32), np.zeros(len(begin[0]) - 1, np.int32)
+        check(load().tdnnf_transcript_graph_sizes(self.h, len(states), begin[1], unit[1], opt[1], states.ctypes.data_as(C.c_void_p),
+                                                  arcs.ctypes.data_as(C.c_void_p)))
+        return states, arcs
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.tdnnf_unit_set_destroy(self.h)
+            self.h = None
+
+
 class Supervision:
     """Device-resident numerator graphs of one minibatch (tdnnf_supervision).  `s`: a time-synchronous supervision dict
     (synth.make_supervision ...), or -- with a "graphs" key -- an end-to-end one (synth.make_e2e_supervision: {B, T, P, weight, graphs}),
@@ -286,6 +335,14 @@ class Supervision:
         graphs, k = self._stack_e2e(graphs)
         check(load().tdnnf_supervision_assign_e2e(self.h, len(graphs), int(frames_per_sequence), *[x[1] for x in k], float(weight), stream()))
         self.B, self.T = len(graphs), int(frames_per_sequence)
+
+    def assign_transcripts(self, unit_set, transcripts, frames_per_sequence, weight=1.0):
+        """tdnnf_supervision_assign_e2e_transcripts on the current stream: assign with the graphs compiled on the device from one
+        (units, optional) transcript per sequence (UnitSet).  A refused minibatch (HipAbiError) leaves the previous one."""
+        begin, unit, opt = _slots(transcripts)
+        check(load().tdnnf_supervision_assign_e2e_transcripts(self.h, unit_set.h, len(begin[0]) - 1, int(frames_per_sequence), begin[1], unit[1], opt[1],
+                                                              float(weight), stream()))
+        self.B, self.T = len(begin[0]) - 1, int(frames_per_sequence)
 
     @property
     def kind(self):
@@ -383,6 +440,20 @@ class AlignGraphs:
             self.G, self.arc_begin, self._keep = before
             raise
         self.num_states = [int(g["S"]) for g in graphs]
+
+    def assign_transcripts(self, unit_set, transcripts, stream=None):
+        """tdnnf_align_graphs_assign_transcripts: the handle's next batch compiled on the device from (units, optional) transcripts (UnitSet),
+        in stream order as assign; on a labelled handle an arc's label is the slot it enters.  G, num_states and arc_begin follow the new
+        batch.  A refused batch (HipAbiError) leaves the handle and this object on the previous one."""
+        import numpy as np
+        import torch
+        begin, unit, opt = _slots(transcripts)
+        on = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+        check(load().tdnnf_align_graphs_assign_transcripts(self.h, unit_set.h, len(begin[0]) - 1, begin[1], unit[1], opt[1], on))
+        states, arcs = unit_set.sizes(transcripts)
+        self.G, self._keep = len(states), []
+        self.num_states = [int(s) for s in states]
+        self.arc_begin = np.concatenate([[0], np.cumsum(arcs)]).astype(np.int64)
 
     def capacity(self):
         """{max_graphs, max_states, max_arcs, device_bytes, device_allocs, assigns} of a reserved handle (tdnnf_align_graphs_capacity)."""

@@ -356,3 +356,43 @@ def e2e_supervision_from_supervision(sup, P):
     weight.  Both forms have the same paths, so the chain objective and its derivatives agree."""
     return {"B": int(sup["B"]), "T": int(sup["T"]), "P": int(P), "weight": float(sup.get("weight", 1.0)),
             "graphs": alignment_graphs_from_supervision(sup)}
+
+
+def make_unit_set(U, context=0, seed=0, distinct=True, P=None):
+    """A unit set for transcript graphs (hipabi.UnitSet): {U, P, context, entry_pdf, loop_pdf, loop_logprob, leave_logprob, take_logprob,
+    skip_logprob}.  context 0: entry_pdf / loop_pdf of shape (U,); context 1 (left-biphone): (U + 1, U), row left + 1.  distinct: every
+    entry and loop pdf is a pdf of its own (P = twice their number), so that a pdf sequence names its states; otherwise they are drawn
+    from P (default U + 2) pdfs and collide.  The weights are multiples of 1/8 in [-2, 0]: sums of a few of them are exact in float32."""
+    rng = np.random.default_rng(seed)
+    shape = (U + 1, U) if context else (U,)
+    n = int(np.prod(shape))
+    if distinct:
+        P = 2 * n if P is None else int(P)
+        assert P >= 2 * n
+        perm = rng.permutation(P)[:2 * n]
+        entry, loop = perm[:n].reshape(shape), perm[n:].reshape(shape)
+    else:
+        P = U + 2 if P is None else int(P)
+        entry, loop = rng.integers(0, P, size=shape), rng.integers(0, P, size=shape)
+    eighths = lambda size=None: (-rng.integers(0, 17, size=size) / 8.0)
+    return {"U": int(U), "P": int(P), "context": int(context), "entry_pdf": entry.astype(np.int32), "loop_pdf": loop.astype(np.int32),
+            "loop_logprob": eighths(U).astype(np.float32), "leave_logprob": eighths(U).astype(np.float32),
+            "take_logprob": float(eighths()), "skip_logprob": float(eighths())}
+
+
+def make_transcripts(B, U, slots=(1, 8), optional_rate=0.3, seed=0):
+    """B transcripts for hipabi.UnitSet: each a (units, optional) pair of int32 arrays of lo .. hi slots, units at random from U, a slot
+    optional with probability optional_rate where the slot before it is not -- never two adjacent -- and at least one slot mandatory."""
+    rng = np.random.default_rng(seed)
+    lo, hi = slots
+    out = []
+    for _ in range(B):
+        n = int(rng.integers(lo, hi + 1))
+        units = rng.integers(0, U, size=n).astype(np.int32)
+        opt = np.zeros(n, np.int32)
+        for k in range(n):
+            opt[k] = int(rng.random() < optional_rate and not (k and opt[k - 1]))
+        if opt.all():  # (n = 1)
+            opt[0] = 0
+        out.append((units, opt))
+    return out

@@ -9,7 +9,9 @@ allocations and copies or the device build, the call, the frees.
   numerator  128 graphs of 70 states x 150 frames through tdnnf_chain_objf_and_deriv
 The clock is the host's around a loop over the cycle that ends in ONE synchronise; (a) and (b) alternate in one process, medians of
 --repeats.  After the timing every batch of the cycle runs once either way and the outputs are compared for equality.  One JSON line.
-usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator]"""
+--transcripts: instead, the cost of a new batch for a caller who starts from transcripts (see transcripts() below): arc arrays built on the
+host + assign, assign alone, and tdnnf_align_graphs_assign_transcripts / tdnnf_supervision_assign_e2e_transcripts, alternating.
+usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts]"""
 import argparse
 import ctypes as C
 import json
@@ -24,15 +26,114 @@ import torch  # noqa: E402
 import __graft_entry__ as ge  # noqa: E402
 
 
+def transcripts(args, pkg):
+    """--transcripts: what a new batch costs when the caller starts from TRANSCRIPTS, three ways, alternating in one process, a different
+    batch every iteration, medians of --repeats:
+      host_graphs_assign  (a) the arc arrays made on the host (tests/transcript_graphs_ref.py transcript_graph_vectorised, then stacked), assign,
+                          the call -- what a caller had to do before tdnnf_align_graphs_assign_transcripts;
+      assign              (b) assign from arrays made outside the timed region, the call: the assign's own cost, the control;
+      assign_transcripts  (c) assign_transcripts, the call.
+    forced: 64 transcripts of some 300 states x 500 frames, tdnnf_align_best_path.  numerator: 128 of some 70 states x 150 frames through
+    tdnnf_chain_objf_and_deriv on a reserved supervision.  The outputs of the three are compared for equality in the same run."""
+    from tests import transcript_graphs_ref as ref
+    abi, synth = pkg.hipabi, pkg.synth
+    lib = abi.load()
+    P = args.pdfs
+    us = synth.make_unit_set(42, context=1, seed=1, distinct=False, P=P)
+    units = abi.UnitSet(us["entry_pdf"], us["loop_pdf"], us["loop_logprob"], us["leave_logprob"], P, us["take_logprob"], us["skip_logprob"])
+    res = dict(metric="transcripts_per_batch", pdfs=P, cycle=args.cycle, repeats=args.repeats, units=42, context=1)
+    s = abi.stream()
+
+    def host_graphs(batch):
+        return abi.Supervision._stack_e2e([ref.transcript_graph_vectorised(us, u, o) for u, o in batch])[1]
+
+    def case(name, B, T, slots, assign, assign_transcripts, call, outputs):
+        batches = [synth.make_transcripts(B, 42, slots=slots, optional_rate=0.15, seed=100 + c) for c in range(args.cycle)]
+        slot_arrays = [abi._slots(b) for b in batches]
+        stacked = [host_graphs(b) for b in batches]
+        fns = dict(host_graphs_assign=lambda i: (assign(host_graphs(batches[i])), call()),
+                   assign=lambda i: (assign(stacked[i]), call()),
+                   assign_transcripts=lambda i: (assign_transcripts(slot_arrays[i]), call()))
+
+        def loop(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(args.cycle):
+                fn(i)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / args.cycle
+
+        ms = {k: [] for k in fns}
+        for r in range(args.repeats + 1):  # the first round warms up: kernels loaded, the allocator's pools filled
+            for k, fn in fns.items():
+                t = loop(fn)
+                if r:
+                    ms[k].append(t)
+        equal = True
+        for i in range(args.cycle):
+            got = []
+            for fn in fns.values():
+                for t in outputs:
+                    t.zero_()
+                fn(i)
+                torch.cuda.synchronize()
+                got.append([t.clone() for t in outputs])
+            equal = equal and all(torch.equal(x.view(torch.uint8), z.view(torch.uint8)) for other in got[1:] for x, z in zip(got[0], other))
+        d = dict(sequences=B, frames=T, states=int(max(k[0][0][-1] for k in stacked)), arcs=int(max(k[1][0][-1] for k in stacked)), outputs_equal=bool(equal))
+        for k, v in ms.items():
+            d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v])
+        d["transcripts_over_host_graphs"] = round(d["assign_transcripts"]["ms"] / d["host_graphs_assign"]["ms"], 3)
+        d["transcripts_over_assign"] = round(d["assign_transcripts"]["ms"] / d["assign"]["ms"], 3)
+        res[name] = d
+
+    # forced alignment
+    B, T = 64, 500
+    graphs = C.c_void_p()
+    abi.check(lib.tdnnf_align_graphs_reserve(B, P, 0, B * 340, B * 1000, C.byref(graphs)))
+    y = torch.randn(B * T, P, device="cuda")
+    frames, rows = abi.iarr([T] * B), abi.iarr(np.arange(B) * T)
+    nb = 16 + 32 * B + 256 + 4 * T * B * 340 + 16 * B * 340  # the header's formula at the capacity
+    ws = abi.workspace(nb)
+    pdfs, results = torch.zeros(B * T, dtype=torch.int32, device="cuda"), torch.zeros(B, 2, dtype=torch.float64, device="cuda")
+    case("forced", B, T, (255, 265),
+         lambda k: abi.check(lib.tdnnf_align_graphs_assign(graphs, B, *[x[1] for x in k], None, s)),
+         lambda a: abi.check(lib.tdnnf_align_graphs_assign_transcripts(graphs, units.h, B, a[0][1], a[1][1], a[2][1], s)),
+         lambda: abi.check(lib.tdnnf_align_best_path(graphs, B, None, frames[1], rows[1], 1, abi.pmat(y), 1.0, abi.ptr(pdfs), None, abi.ptr(results), abi.ptr(ws), nb, s)),
+         [pdfs, results])
+    lib.tdnnf_align_graphs_destroy(graphs)
+    # the flat-start numerator
+    B, T = 128, 150
+    sup = C.c_void_p()
+    abi.check(lib.tdnnf_supervision_reserve_e2e(B, T, P, B * 90, B * 270, C.byref(sup)))
+    dg = abi.DenGraph(synth.make_den_graph(64, P, mean_out_degree=4.0, seed=1))  # (the numerator takes the workspace layout from it, nothing else)
+    y = torch.randn(B * T, P, device="cuda")
+    xo = torch.log_softmax(torch.randn(B * T, P, device="cuda"), dim=1)
+    nb = int(lib.tdnnf_chain_workspace_bytes(dg.h, B, T))
+    ws = abi.workspace(nb)
+    ws.zero_()
+    out = (torch.zeros(8, dtype=torch.float64, device="cuda"), torch.zeros_like(y), torch.zeros_like(y))
+    case("numerator", B, T, (60, 62),
+         lambda k: abi.check(lib.tdnnf_supervision_assign_e2e(sup, B, T, *[x[1] for x in k], 1.0, s)),
+         lambda a: abi.check(lib.tdnnf_supervision_assign_e2e_transcripts(sup, units.h, B, T, a[0][1], a[1][1], a[2][1], 1.0, s)),
+         lambda: abi.check(lib.tdnnf_chain_objf_and_deriv(dg.h, sup, abi.pmat(y), abi.pmat(xo), 0.1, 5e-5, 0.1, abi.ptr(out[0]), abi.pmat(out[1]), abi.pmat(out[2]),
+                                                         abi.ptr(ws), nb, s)),
+         list(out))
+    lib.tdnnf_supervision_destroy(sup)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--cycle", type=int, default=8)
     ap.add_argument("--pdfs", type=int, default=6034)
     ap.add_argument("--only", choices=["forced", "free", "numerator"])
+    ap.add_argument("--transcripts", action="store_true", help="graphs from transcripts: host-built arrays + assign against assign_transcripts")
     args = ap.parse_args()
     assert args.cycle >= 8, "different graphs every iteration: a cycle of at least 8 batches"
     pkg = ge.load_package()
+    if args.transcripts:
+        return transcripts(args, pkg)
     abi, synth = pkg.hipabi, pkg.synth
     lib = abi.load()
     P = args.pdfs
