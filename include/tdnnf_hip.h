@@ -329,8 +329,47 @@ void tdnnf_supervision_destroy(tdnnf_supervision *);
    bound on the number of states or arcs per frame (alignments, lattices with a frame tolerance, several alternative transcripts).  A
    supervision of more than 4 * (frames_per_sequence + 1) states per sequence on average holds its own numerator scratch on the device
    (16 bytes per state) and a second copy of its arcs (20 bytes per arc); the chain workspace does not depend on the supervision.
-   Any of the out-pointers may be NULL; *wide: 1 if the supervision is over that mark. */
+   Any of the out-pointers may be NULL; *wide: 1 if the supervision is over that mark.
+   A supervision of this kind is either CREATED (above: one minibatch for its lifetime) or RESERVED and assigned a minibatch at a time
+   (below); the functions that take a supervision do not tell the two apart. */
 int tdnnf_supervision_info(const tdnnf_supervision *, int *num_states, int *num_arcs, int *max_states_per_frame, int *wide);
+/* The time-synchronous kind, REUSABLE: the egs readers give a new supervision every minibatch, and tdnnf_supervision_create builds its
+   tables on the host, allocates and copies synchronously array by array and (at destroy) waits for the whole device array by array.
+   tdnnf_supervision_reserve makes every allocation once, for minibatches of at most max_sequences sequences of at most max_frames frames
+   with max_states states and max_arcs arcs between them: every array a supervision of this kind can carry -- the second copy of the arcs
+   ordered by pdf within a frame and the numerator's own scratch included, whatever the minibatch's width -- the build's scratch and a
+   device staging area in ONE device allocation (48 bytes per state, 72 per arc, 8 per (sequence, frame + 2), 8 per (sequence, 8 frames)
+   and 2 KB), and two pinned staging buffers (8 bytes per state, 16 per arc, 4 per (sequence, frame + 2) each) with an event each.
+   Until the first assign it holds no minibatch, and every function that takes a supervision refuses it (TDNNF_EINVAL naming
+   tdnnf_supervision_assign).
+   tdnnf_supervision_assign gives it the next minibatch in stream order, with the arrays of tdnnf_supervision_create.  On the host,
+   O(states + arcs + sequences * frames): what tdnnf_supervision_create refuses is refused in the same words under this entry's name
+   (and, because the device build indexes by them, begin arrays that do not start at 0 or a seq_arc_begin that decreases); a minibatch over
+   a capacity is refused naming the capacity, its value and the excess; the widths and `wide` are found as tdnnf_supervision_create finds
+   them.  A refused assign leaves the supervision on its previous minibatch (an error of the runtime behind this point, TDNNF_EHIP from a
+   copy or a launch, leaves it without one: refused like a fresh handle until an assign succeeds).  Then the raw arrays are staged in pinned memory, and their
+   copies and two build kernels are enqueued on `stream`: the by-destination and by-source lists in original arc order and the per-frame
+   lists ordered stably by pdf, byte for byte what tdnnf_supervision_create uploads.  Nothing is allocated, freed or waited for
+   device-wide; the only wait is for the copies of the assign before last out of the staging buffer that is written again.  Work enqueued
+   on `stream` before the assign still sees the previous minibatch; work that uses the supervision on ANOTHER stream must be ordered
+   against `stream` by the caller.  num_sequences, frames_per_sequence, weight, the counts and `wide` follow the minibatch; the numerator
+   takes the form and the scratch it takes for a created supervision of the same arrays (option "num_form" 2 works for any assigned
+   minibatch), and gives the same bits.
+   tdnnf_supervision_capacity: the four capacities, the assigns so far, the device and pinned allocations made for the handle since
+   tdnnf_supervision_reserve returned (0, always) and the bytes of the device allocation; any out-pointer may be NULL.  TDNNF_EINVAL for a
+   supervision that tdnnf_supervision_reserve did not make. */
+int tdnnf_supervision_reserve(int max_sequences, int max_frames, int max_states, int max_arcs, tdnnf_supervision **out);
+int tdnnf_supervision_assign(tdnnf_supervision *, int num_sequences, int frames_per_sequence, const int *seq_state_begin,
+                             const int *seq_arc_begin, const int *state_time, const float *final_logprob, const int *arc_src,
+                             const int *arc_dst, const int *arc_pdf, const float *arc_logprob, float weight, tdnnf_stream stream);
+int tdnnf_supervision_capacity(const tdnnf_supervision *, int *max_sequences, int *max_frames, int *max_states, int *max_arcs, int *assigns,
+                               int *allocations_since_reserve, long long *device_bytes);
+/* diagnostics (tests), time-synchronous kind, created or assigned: one device table by name, copied to host memory as 4-byte elements --
+   "seq_state_begin", "state_time", "final_logprob", "frame_state_begin", "in_begin", "in_src", "in_pdf", "in_lp", "out_begin", "out_dst",
+   "out_pdf", "out_lp", "pf_src", "pf_dst", "pf_pdf", "pf_t", "pf_lp" (ints; the three *_lp and final_logprob are floats).  *count: the
+   table's elements, 0 for a table the supervision does not carry (pf_* of a narrow created one); out NULL: the size query alone.
+   Synchronises `stream` (and the stream of the last assign) itself. */
+int tdnnf_supervision_dump(const tdnnf_supervision *, const char *table, void *out, long long capacity, long long *count, tdnnf_stream stream);
 /* The second kind of supervision: flat-start ("end-to-end") LF-MMI, Kaldi's GenericNumeratorComputation branch of
    chain::ComputeChainObjfAndDeriv.  Per sequence ONE cyclic, epsilon-free acceptor with pdf-ids on its arcs (a transcript graph with
    self-loops), every path of exactly frames_per_sequence arcs from an initial to a final state counts.  Host arrays in, device copy out;

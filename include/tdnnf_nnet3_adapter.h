@@ -400,6 +400,24 @@ inline void SupervisionAssignE2e(tdnnf_supervision *sup, int num_sequences, int 
                                      initial_logprob, final_logprob, weight, stream));
 }
 
+// The time-synchronous supervision of regular LF-MMI, reusable (tdnnf_hip.h, tdnnf_supervision_reserve): reserved once for the largest
+// minibatch of the run -- max_states and max_arcs are totals over a minibatch -- then assigned every minibatch's arrays (those of
+// tdnnf_supervision_create, as the egs readers merge them) on the trainer's stream, where the arc tables are built on the device: no
+// allocation, no device-wide wait per step.  Calls enqueued on `stream` before the assign still see the previous minibatch.  Throws on what
+// tdnnf_supervision_create refuses and on a minibatch beyond a capacity (the supervision then still holds the previous minibatch); release
+// with tdnnf_supervision_destroy.
+inline tdnnf_supervision *SupervisionReserve(int max_sequences, int max_frames, int max_states, int max_arcs) {
+  tdnnf_supervision *sup = nullptr;
+  Check(tdnnf_supervision_reserve(max_sequences, max_frames, max_states, max_arcs, &sup));
+  return sup;
+}
+inline void SupervisionAssign(tdnnf_supervision *sup, int num_sequences, int frames_per_sequence, const int *seq_state_begin, const int *seq_arc_begin,
+                              const int *state_time, const float *final_logprob, const int *arc_src, const int *arc_dst, const int *arc_pdf,
+                              const float *arc_logprob, float weight, tdnnf_stream stream) {
+  Check(tdnnf_supervision_assign(sup, num_sequences, frames_per_sequence, seq_state_begin, seq_arc_begin, state_time, final_logprob, arc_src, arc_dst,
+                                 arc_pdf, arc_logprob, weight, stream));
+}
+
 // A reusable graph set for the Align* calls below (tdnnf_hip.h, tdnnf_align_graphs_reserve): reserved once for the largest batch -- max_states
 // and max_arcs are totals over a batch; num_labels 0: no labels -- then assigned each batch of transcript graphs on `stream`, where the
 // tables are built on the device.  arc_label: null exactly for a handle reserved without labels.  Release with tdnnf_align_graphs_destroy.

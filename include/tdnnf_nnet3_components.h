@@ -2043,6 +2043,21 @@ inline void AssignEnd2EndSupervision(tdnnf_supervision *supervision, int32 num_s
                                       arc_dst.data(), arc_pdf.data(), arc_logprob.data(), initial_logprob.data(), final_logprob.data(), weight, Hooks().stream);
 }
 
+// The supervision of regular LF-MMI for a training run: reserved once for the largest minibatch (max_states and max_arcs are totals over a
+// minibatch), then assigned each minibatch's merged arrays -- those of tdnnf_supervision_create -- on the hooks' stream; the arc tables are
+// built on the device, nothing is allocated and the device is not waited for; the chain calls enqueued before an assign still see the
+// minibatch before.  Release with tdnnf_supervision_destroy.
+inline tdnnf_supervision *ReserveSupervision(int32 max_sequences, int32 max_frames, int32 max_states, int32 max_arcs) {
+  return tdnnf_adapter::SupervisionReserve(max_sequences, max_frames, max_states, max_arcs);
+}
+inline void AssignSupervision(tdnnf_supervision *supervision, int32 num_sequences, int32 frames_per_sequence, const std::vector<int32> &seq_state_begin,
+                              const std::vector<int32> &seq_arc_begin, const std::vector<int32> &state_time, const std::vector<float> &final_logprob,
+                              const std::vector<int32> &arc_src, const std::vector<int32> &arc_dst, const std::vector<int32> &arc_pdf,
+                              const std::vector<float> &arc_logprob, float weight) {
+  tdnnf_adapter::SupervisionAssign(supervision, num_sequences, frames_per_sequence, seq_state_begin.data(), seq_arc_begin.data(), state_time.data(),
+                                   final_logprob.data(), arc_src.data(), arc_dst.data(), arc_pdf.data(), arc_logprob.data(), weight, Hooks().stream);
+}
+
 // A graph set for the Align* calls below that is reserved once and assigned each batch of utterances' transcript graphs on the hooks' stream
 // (tdnnf_align_graphs_reserve / _assign: the tables are built on the device, nothing is allocated per batch).  arc_label: empty for a set
 // reserved with num_labels 0, else one label per arc.  Release with tdnnf_align_graphs_destroy.

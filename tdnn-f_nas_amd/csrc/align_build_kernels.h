@@ -10,14 +10,15 @@
 // chunk's keys, a scan and 66 counters.  No atomics at all: an arc's place in its row, and a row's place among the rows of its length, is
 // the count of earlier entries with the same key -- per chunk of kBuildThreads entries the count of lower threads with the key (a loop over
 // the chunk's keys in LDS) on top of a running counter per key, which the chunk's last thread with that key moves on.  Each such counter
-// has one writer per chunk, and workgroup barriers order the chunks; no workgroup waits on another; every loop's count is known at its start.
+// has one writer per chunk, and workgroup barriers order the chunks (build_stable_place and build_scan: build_place.h, shared with the
+// supervision's build); no workgroup waits on another; every loop's count is known at its start.
 #pragma once
 #include "align_graphs.h"
+#include "build_place.h"
 
 namespace tdnnf {
 namespace {
 
-constexpr int kBuildThreads = 256;
 constexpr int kBuildBuckets = kAlignHeavy + 2;  // a light row of length l: bucket kAlignHeavy - l (descending length); heavy rows: the last
 
 // the first index in list[0 .. n) that is not below v (v is in the list: the rank of a pdf or label in its graph's column list)
@@ -65,44 +66,6 @@ __device__ inline int build_row(const AlignBuildDev &b, int t, const BuildGraph 
 }
 
 __device__ inline int build_bucket(int len) { return len > kAlignHeavy ? kAlignHeavy + 1 : kAlignHeavy - len; }
-
-// One chunk of a stable counting pass: this thread's entry has `key` (valid: the thread has an entry).  Returns the number of earlier
-// entries with the key -- counter[key] plus the lower threads of the chunk that have it -- and moves counter[key] past the chunk.  keys:
-// kBuildThreads ints of LDS.  counter: LDS or this workgroup's global scratch.  Every thread of the workgroup calls it.
-__device__ inline int build_stable_place(int key, bool valid, int *keys, int *counter) {
-  const int tid = threadIdx.x;
-  keys[tid] = valid ? key : -1;
-  __syncthreads();
-  int lower = 0, all = 0;
-  for (int i = 0; i < kBuildThreads; i++) {
-    const int same = keys[i] == key ? 1 : 0;
-    all += same;
-    lower += i < tid ? same : 0;
-  }
-  const int place = valid ? counter[key] + lower : 0;
-  __syncthreads();  // (every read of the counters is done)
-  if (valid && lower == all - 1) counter[key] = place + 1;
-  __syncthreads();
-  return place;
-}
-
-// The exclusive sum over the workgroup of v, on top of *carry (LDS), which moves on by the chunk's sum.  scan: kBuildThreads ints of LDS.
-__device__ inline int build_scan(int v, int *scan, int *carry) {
-  const int tid = threadIdx.x;
-  scan[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < kBuildThreads; d <<= 1) {
-    const int add = tid >= d ? scan[tid - d] : 0;
-    __syncthreads();
-    scan[tid] += add;
-    __syncthreads();
-  }
-  const int before = *carry + scan[tid] - v;
-  __syncthreads();
-  if (tid == kBuildThreads - 1) *carry += scan[tid];
-  __syncthreads();
-  return before;
-}
 
 __global__ __launch_bounds__(kBuildThreads) void align_build_rows_kernel(AlignBuildDev b) {
   __shared__ int keys[kBuildThreads];

@@ -297,6 +297,11 @@ int tdnnf_supervision_info(const tdnnf_supervision *sp, int *num_states, int *nu
 
 void tdnnf_supervision_destroy(tdnnf_supervision *sp) {
   if (!sp) return;
+  if (sp->ts) {  // reserved, time-synchronous: every device array is a piece of the one allocation (chain_sup_build.hip)
+    sup_reserved_free(sp);
+    delete sp;
+    return;
+  }
   void *ptrs[] = {sp->seq_state_begin, sp->state_time, sp->final_logprob, sp->in_begin, sp->in_src, sp->in_pdf,
                   sp->in_lp, sp->out_begin, sp->out_dst, sp->out_pdf, sp->out_lp, sp->frame_state_begin,
                   sp->la_own, sp->lb_own, sp->pf_src, sp->pf_dst, sp->pf_pdf, sp->pf_t, sp->pf_lp, sp->xent_part,

@@ -1,0 +1,301 @@
+// chain_sup_build.hip -- the reusable time-synchronous supervision (include/tdnnf_hip.h): tdnnf_supervision_reserve makes every allocation
+// once for four capacities, tdnnf_supervision_assign validates a minibatch on the host (chain_sup_tables.h), stages its raw arrays in pinned
+// memory and enqueues the copies and the device build (chain_sup_build_kernels.h) on the caller's stream -- nothing allocated, nothing freed,
+// no device-wide wait.  tdnnf_supervision_capacity and tdnnf_supervision_dump (created supervisions too) are the diagnostics the tests read.
+// The numerator's host functions (chain_num.hip) see an assigned supervision as they see a created one.
+#include <string.h>
+
+#include <string>
+
+#include "chain_sup_build_kernels.h"
+#include "chain_sup_tables.h"
+#include "chain_types.h"
+
+namespace tdnnf {
+
+struct SupReserved {
+  int max_sequences, max_frames, max_states, max_arcs;
+  void *arena;  // every device array of the supervision, the build's scratch and the device staging
+  size_t arena_bytes;
+  SupBuildDev build;
+  char *stage_dev;
+  size_t stage_bytes;
+  char *stage_host[2];  // pinned; staging k uses buffer k & 1 and waits for staging k - 2's copies out of it
+  hipEvent_t stage_event[2];
+  bool stage_used[2];
+  int stagings;  // assigns that reached the staging, the failed ones included: the buffer to use next
+  hipStream_t last_stream;
+  int allocs, allocs_at_reserve;  // device and pinned allocations made for the handle; since the end of reserve
+};
+
+namespace {
+
+// Hands out pieces of the handle's one allocation, 256 bytes apart at least; with a null base it only counts.
+struct SupCarve {
+  char *base;
+  size_t at;
+  template <class T>
+  T *take(size_t n) {
+    at = (at + 255) & ~(size_t)255;
+    T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+    at += sizeof(T) * std::max<size_t>(n, 1);
+    return p;
+  }
+};
+
+// Every device array of a reserved supervision at the capacities, out of c.  Run once with a null base for the size.
+void sup_reserve_layout(tdnnf_supervision *sp, SupCarve *c) {
+  SupReserved *r = sp->ts;
+  const size_t Bc = r->max_sequences, Tc = r->max_frames, Sc = r->max_states, Ac = r->max_arcs;
+  SupBuildDev &b = r->build;
+  sp->seq_state_begin = c->take<int>(Bc + 1);
+  sp->state_time = c->take<int>(Sc);
+  sp->final_logprob = c->take<float>(Sc);
+  sp->frame_state_begin = c->take<int>(Bc * (Tc + 2));
+  sp->in_begin = c->take<int>(Sc + 1);
+  sp->in_src = c->take<int>(Ac);
+  sp->in_pdf = c->take<int>(Ac);
+  sp->in_lp = c->take<float>(Ac);
+  sp->out_begin = c->take<int>(Sc + 1);
+  sp->out_dst = c->take<int>(Ac);
+  sp->out_pdf = c->take<int>(Ac);
+  sp->out_lp = c->take<float>(Ac);
+  sp->pf_src = c->take<int>(Ac);
+  sp->pf_dst = c->take<int>(Ac);
+  sp->pf_pdf = c->take<int>(Ac);
+  sp->pf_t = c->take<int>(Ac);
+  sp->pf_lp = c->take<float>(Ac);
+  sp->la_own = c->take<double>(Sc);
+  sp->lb_own = c->take<double>(Sc);
+  sp->xent_part = c->take<double>(Bc * ((Tc + kNumWideFrames - 1) / kNumWideFrames));
+  sp->l2_part = c->take<double>(kFinishL2Parts);
+  for (int t = 0; t < 2; t++) {
+    b.len[t] = c->take<int>(Sc);
+    b.arcpos[t] = c->take<int>(Ac);
+  }
+  b.out_src = c->take<int>(Ac);
+  r->stage_dev = c->take<char>(r->stage_bytes);
+  b.cap_states = r->max_states;
+  b.cap_arcs = r->max_arcs;
+  b.seq_state_begin = sp->seq_state_begin;
+  b.frame_state_begin = sp->frame_state_begin;
+  b.begin[0] = sp->in_begin;
+  b.begin[1] = sp->out_begin;
+  b.other[0] = sp->in_src;
+  b.other[1] = sp->out_dst;
+  b.list_pdf[0] = sp->in_pdf;
+  b.list_pdf[1] = sp->out_pdf;
+  b.list_lp[0] = reinterpret_cast<int *>(sp->in_lp);
+  b.list_lp[1] = reinterpret_cast<int *>(sp->out_lp);
+  b.pf_src = sp->pf_src;
+  b.pf_dst = sp->pf_dst;
+  b.pf_pdf = sp->pf_pdf;
+  b.pf_t = sp->pf_t;
+  b.pf_lp = reinterpret_cast<int *>(sp->pf_lp);
+}
+
+// The two launches of chain_sup_build_kernels.h on s.  b: the handle's tables and scratch with this minibatch's staged arrays, B and T filled in.
+int sup_build_launch(const SupBuildDev &b, hipStream_t s) {
+  hipLaunchKernelGGL(sup_build_lists_kernel, dim3(b.B, 2), dim3(kBuildThreads), 0, s, b);
+  TDNNF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sup_build_frames_kernel, dim3(b.B * b.T), dim3(kSupFrameThreads), 0, s, b);
+  TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+
+}  // namespace
+
+void sup_reserved_free(tdnnf_supervision *sp) {
+  SupReserved *r = sp->ts;
+  if (!r) return;
+  (void)hipFree(r->arena);
+  for (int i = 0; i < 2; i++) {
+    if (r->stage_host[i]) (void)hipHostFree(r->stage_host[i]);
+    if (r->stage_event[i]) (void)hipEventDestroy(r->stage_event[i]);
+  }
+  delete r;
+  sp->ts = nullptr;
+}
+
+}  // namespace tdnnf
+
+using namespace tdnnf;
+
+extern "C" {
+
+int tdnnf_supervision_reserve(int max_sequences, int max_frames, int max_states, int max_arcs, tdnnf_supervision **out) {
+  const char *who = "supervision_reserve: ";
+  TDNNF_REQUIRE(out && max_sequences > 0 && max_frames > 0 && max_states > 0 && max_arcs >= 0,
+                "%sbad arguments (max_sequences %d, max_frames %d, max_states %d, max_arcs %d)", who, max_sequences, max_frames, max_states, max_arcs);
+  TDNNF_REQUIRE(max_states >= max_sequences, "%smax_states %d is below max_sequences %d: every sequence has a state", who, max_states, max_sequences);
+  // (the build's second launch has a wave per (sequence, frame): 64 * sequences * frames threads, below 2^32)
+  TDNNF_REQUIRE((long long)max_sequences * ((long long)max_frames + 2) <= 1ll << 25, "%smax_sequences * (max_frames + 2) must not exceed 2^25", who);
+  tdnnf_supervision *sp = new tdnnf_supervision();
+  memset(sp, 0, sizeof(*sp));
+  SupReserved *r = new SupReserved();
+  memset(r, 0, sizeof(*r));
+  sp->ts = r;
+  sp->ts_reserved = true;
+  r->max_sequences = max_sequences;
+  r->max_frames = max_frames;
+  r->max_states = max_states;
+  r->max_arcs = max_arcs;
+  r->stage_bytes = sup_stage_bytes(max_sequences, max_frames, max_states, max_arcs);
+  SupCarve size{nullptr, 0};
+  sup_reserve_layout(sp, &size);
+  r->arena_bytes = size.at;
+  hipError_t e = hipMalloc(&r->arena, r->arena_bytes);
+  if (e == hipSuccess) r->allocs++;
+  for (int i = 0; i < 2 && e == hipSuccess; i++)
+    if ((e = hipHostMalloc((void **)&r->stage_host[i], r->stage_bytes, hipHostMallocDefault)) == hipSuccess) {
+      r->allocs++;
+      e = hipEventCreateWithFlags(&r->stage_event[i], hipEventDisableTiming);
+    }
+  if (e != hipSuccess) {
+    tdnnf_supervision_destroy(sp);
+    return hip_status(e, "supervision_reserve: allocation");
+  }
+  SupCarve carve{static_cast<char *>(r->arena), 0};
+  sup_reserve_layout(sp, &carve);
+  // (a created supervision's l2_part starts at zero; every reader writes it first)
+  if ((e = hipMemset(sp->l2_part, 0, sizeof(double) * kFinishL2Parts)) != hipSuccess) {
+    tdnnf_supervision_destroy(sp);
+    return hip_status(e, "supervision_reserve: hipMemset");
+  }
+  r->allocs_at_reserve = r->allocs;
+  *out = sp;
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_assign(tdnnf_supervision *sp, int B, int T, const int *seq_state_begin, const int *seq_arc_begin, const int *state_time,
+                             const float *final_logprob, const int *arc_src, const int *arc_dst, const int *arc_pdf, const float *arc_logprob,
+                             float weight, tdnnf_stream stream) {
+  const char *who = "supervision_assign: ";
+  TDNNF_REQUIRE(sp, "%snull supervision", who);
+  TDNNF_REQUIRE(sp->kind == 0, "%san end-to-end supervision: tdnnf_supervision_assign_e2e assigns those", who);
+  TDNNF_REQUIRE(sp->ts_reserved && sp->ts,
+                "%sthe supervision was made by tdnnf_supervision_create: only a supervision of tdnnf_supervision_reserve can be assigned", who);
+  SupReserved *r = sp->ts;
+  SupPlan p;
+  std::string err;
+  TDNNF_REQUIRE(sup_validate(who, true, B, T, seq_state_begin, seq_arc_begin, state_time, final_logprob, arc_src, arc_dst, arc_pdf, arc_logprob, &p, &err),
+                "%s", err.c_str());
+  TDNNF_REQUIRE(sup_check_capacity(who, B, T, p, r->max_sequences, r->max_frames, r->max_states, r->max_arcs, &err), "%s", err.c_str());
+  sup_widths(B, T, arc_src, &p);
+  const size_t NS = p.num_states, NA = p.num_arcs, nfsb = p.frame_state_begin.size();
+  const size_t need = sizeof(int) * (2 * ((size_t)B + 1) + nfsb + 2 * NS + 4 * NA);
+  TDNNF_REQUIRE(need <= r->stage_bytes, "%sinternal: the minibatch needs %zu bytes of staging, the supervision has %zu", who, need, r->stage_bytes);
+
+  // staging: the one wait of this path, for the copies of the assign before last out of the buffer that is now overwritten
+  const int slot = r->stagings & 1;
+  if (r->stage_used[slot]) TDNNF_HIP(hipEventSynchronize(r->stage_event[slot]));
+  char *host = r->stage_host[slot];
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  size_t at = 0;
+  const auto stage = [&](const void *v, size_t n) {  // n 4-byte elements; the offset is the same in the device staging
+    const size_t begin = at;
+    if (n) memcpy(host + begin, v, sizeof(int) * n);
+    at += sizeof(int) * n;
+    return begin;
+  };
+  SupBuildDev &b = r->build;
+  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(r->stage_dev + stage(v, n)); };
+  b.B = B;
+  b.T = T;
+  b.seq_arc_begin = raw(seq_arc_begin, (size_t)B + 1);
+  b.src = raw(arc_src, NA);
+  b.dst = raw(arc_dst, NA);
+  b.pdf = raw(arc_pdf, NA);
+  b.lp_bits = raw(arc_logprob, NA);
+  const size_t raw_bytes = at;
+  // the arrays that go to the supervision's own device arrays as they are
+  const struct {
+    void *to;
+    size_t from, bytes;
+  } copies[4] = {{sp->seq_state_begin, stage(seq_state_begin, (size_t)B + 1), sizeof(int) * ((size_t)B + 1)},
+                 {sp->state_time, stage(state_time, NS), sizeof(int) * NS},
+                 {sp->final_logprob, stage(final_logprob, NS), sizeof(float) * NS},
+                 {sp->frame_state_begin, stage(p.frame_state_begin.data(), nfsb), sizeof(int) * nfsb}};
+  // From here on the device tables are being overwritten.  A refusal above left the previous minibatch; an error of the runtime below
+  // (a copy or a launch that fails) leaves NO minibatch: the handle is refused like a fresh one until an assign succeeds.
+  const int assigns_before = sp->ts_assigns;
+  sp->ts_assigns = 0;
+  r->stagings++;
+  TDNNF_HIP(hipMemcpyAsync(r->stage_dev, host, raw_bytes, hipMemcpyHostToDevice, s));
+  for (const auto &c : copies)
+    if (c.bytes) TDNNF_HIP(hipMemcpyAsync(c.to, host + c.from, c.bytes, hipMemcpyHostToDevice, s));
+  TDNNF_HIP(hipEventRecord(r->stage_event[slot], s));
+  r->stage_used[slot] = true;
+  if (int rc = sup_build_launch(b, s)) return rc;
+
+  sp->B = B;
+  sp->T = T;
+  sp->weight = weight;
+  sp->num_states = p.num_states;
+  sp->num_arcs = p.num_arcs;
+  sp->max_states_per_seq = p.max_states_per_seq;
+  sp->max_states_per_frame = p.max_states_per_frame;
+  sp->max_arcs_per_frame = p.max_arcs_per_frame;
+  sp->wide = p.wide;
+  r->last_stream = s;
+  sp->ts_assigns = assigns_before + 1;
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_capacity(const tdnnf_supervision *sp, int *max_sequences, int *max_frames, int *max_states, int *max_arcs, int *assigns,
+                               int *allocations_since_reserve, long long *device_bytes) {
+  TDNNF_REQUIRE(sp && sp->kind == 0 && sp->ts_reserved && sp->ts,
+                "supervision_capacity: null supervision, or one that tdnnf_supervision_reserve did not make (it has no capacity)");
+  const SupReserved *r = sp->ts;
+  if (max_sequences) *max_sequences = r->max_sequences;
+  if (max_frames) *max_frames = r->max_frames;
+  if (max_states) *max_states = r->max_states;
+  if (max_arcs) *max_arcs = r->max_arcs;
+  if (assigns) *assigns = sp->ts_assigns;
+  if (allocations_since_reserve) *allocations_since_reserve = r->allocs - r->allocs_at_reserve;
+  if (device_bytes) *device_bytes = (long long)r->arena_bytes;
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_dump(const tdnnf_supervision *sp, const char *table, void *out, long long capacity, long long *count, tdnnf_stream stream) {
+  const char *who = "supervision_dump: ";
+  TDNNF_REQUIRE(sp && table && count, "%snull supervision, table name or count", who);
+  TDNNF_REQUIRE(sp->kind == 0, "%san end-to-end supervision has none of these tables (tdnnf_align_graphs_dump shows a graph set's)", who);
+  TDNNF_REQUIRE(!sp->ts_reserved || sp->ts_assigns > 0, "%sthe reserved supervision holds no minibatch yet (tdnnf_supervision_assign gives it one)", who);
+  const long long NS = sp->num_states, NA = sp->num_arcs, pf = sp->pf_src ? NA : 0;
+  const struct {
+    const char *name;
+    const void *data;
+    long long n;
+  } tables[] = {{"seq_state_begin", sp->seq_state_begin, sp->B + 1ll},
+                {"state_time", sp->state_time, NS},
+                {"final_logprob", sp->final_logprob, NS},
+                {"frame_state_begin", sp->frame_state_begin, (long long)sp->B * (sp->T + 2)},
+                {"in_begin", sp->in_begin, NS + 1},
+                {"in_src", sp->in_src, NA},
+                {"in_pdf", sp->in_pdf, NA},
+                {"in_lp", sp->in_lp, NA},
+                {"out_begin", sp->out_begin, NS + 1},
+                {"out_dst", sp->out_dst, NA},
+                {"out_pdf", sp->out_pdf, NA},
+                {"out_lp", sp->out_lp, NA},
+                {"pf_src", sp->pf_src, pf},
+                {"pf_dst", sp->pf_dst, pf},
+                {"pf_pdf", sp->pf_pdf, pf},
+                {"pf_t", sp->pf_t, pf},
+                {"pf_lp", sp->pf_lp, pf}};
+  for (const auto &t : tables) {
+    if (strcmp(t.name, table)) continue;
+    *count = t.n;
+    if (!out) return TDNNF_OK;
+    TDNNF_REQUIRE(capacity >= t.n, "%sout holds %lld elements, table %s has %lld", who, capacity, table, t.n);
+    TDNNF_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    if (sp->ts && sp->ts->last_stream != static_cast<hipStream_t>(stream)) TDNNF_HIP(hipStreamSynchronize(sp->ts->last_stream));
+    if (t.n) TDNNF_HIP(hipMemcpy(out, t.data, 4 * (size_t)t.n, hipMemcpyDeviceToHost));
+    return TDNNF_OK;
+  }
+  TDNNF_REQUIRE(false, "%sno table \"%s\" (seq_state_begin, state_time, final_logprob, frame_state_begin, in_begin/src/pdf/lp, out_begin/dst/pdf/lp, pf_src/dst/pdf/t/lp)",
+                who, table);
+}
+
+}  // extern "C"

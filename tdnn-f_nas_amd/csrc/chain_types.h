@@ -22,6 +22,15 @@
 #include "align_tables.h"
 #include "common.h"
 
+namespace tdnnf {
+struct SupReserved;  // chain_sup_build.hip
+}
+struct tdnnf_supervision;
+namespace tdnnf {
+// frees what a reserved time-synchronous supervision holds (tdnnf_supervision_destroy, chain_graph.hip)
+__attribute__((visibility("hidden"))) void sup_reserved_free(tdnnf_supervision *sp);
+}
+
 struct tdnnf_den_graph {
   int H, A, P;
   // SELL-64 over rows sorted by descending degree (so a slice's rows have near-equal degree and padding is
@@ -81,6 +90,12 @@ struct tdnnf_supervision {
   bool e2e_reserved;
   int e2e_assigns;                        // 0: no minibatch yet, every entry refuses the supervision
   int e2e_max_sequences, e2e_max_frames;  // the capacities beside the graph set's own
+  // ---- kind 0, RESERVED (tdnnf_supervision_reserve, chain_sup_build.hip): every array a time-synchronous supervision can carry -- the
+  // pf_* tables, xent_part, la_own / lb_own included -- is a piece of ONE allocation sized for the capacities, and tdnnf_supervision_assign
+  // sets B, T, weight, the counts, the widths and `wide` per minibatch and has the tables built on the device.  All zero / null for a created one.
+  bool ts_reserved;
+  int ts_assigns;              // 0: no minibatch yet, every entry refuses the supervision
+  tdnnf::SupReserved *ts;      // the capacities, the allocation, the build's scratch, the staging
 };
 
 namespace tdnnf {

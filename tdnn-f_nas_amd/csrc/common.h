@@ -135,6 +135,8 @@ inline unsigned long long tdnnf_decision(unsigned long long step, unsigned long 
 bool log_softmax_propagate_with_aux(const tdnnf_mat *in, tdnnf_mat *out, tdnnf_mat *aux, float aux_scale, hipStream_t s);
 // the three separately launchable parts of the chain objective (chain_den.hip, chain_num.hip)
 float chain_supervision_weight(const tdnnf_supervision *sp);
+// a supervision of tdnnf_supervision_reserve that holds no minibatch yet (chain_sup_build.hip)
+bool chain_supervision_needs_assign(const tdnnf_supervision *sp);
 // beside_other_work: the caller runs other kernels next to the denominator (the trainer: the xent head), so the persistent form keeps
 // its one-kernel backward pass instead of running the two recursions side by side on a further stream
 size_t chain_split_region_bytes(const tdnnf_den_graph *g, int B, int T);

@@ -511,6 +511,7 @@ int enter(const char *who, tdnnf_net *n, bool needs_grads, int flags, const tdnn
   TDNNF_REQUIRE(n && n->params && (n->grads || !needs_grads), "%s: call net_set_buffers first", who);
   TDNNF_REQUIRE(mat_ok(feats) && mat_ok(ivectors) && den && sup && results, "%s: bad arguments", who);
   TDNNF_REQUIRE((flags & ~TDNNF_OBJECTIVE_STORE_BATCHNORM_STATS) == 0, "%s: unknown flags %d", who, flags);
+  TDNNF_REQUIRE(!chain_supervision_needs_assign(sup), "%s: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign gives it one)", who);
   const tdnnf_net_config &c = n->cfg;
   TDNNF_REQUIRE(feats->rows == n->g_feat.n * n->B && feats->cols == c.feat_dim, "%s: feats must be %d x %d (t-major)", who, n->g_feat.n * n->B, c.feat_dim);
   TDNNF_REQUIRE(ivectors->rows == n->B && ivectors->cols == c.ivector_dim, "%s: ivectors must be %d x %d", who, n->B, c.ivector_dim);

@@ -136,11 +136,39 @@ class Writer:
         self.close()
 
 
-def minibatches(path, net, frame_shift=0, discard_partial=True, prefetch=0):
+class ReusedSupervision:
+    """One reserved hipabi.Supervision (tdnnf_supervision_reserve) that takes minibatch after minibatch by assign: no allocation, no
+    device-wide wait per minibatch.  It is sized from the first minibatch -- its sequences and frames, its states and arcs with HEADROOM --
+    and reserved again, larger, when a minibatch exceeds a capacity (the old handle is destroyed, which waits for the device once).
+    .reserves counts the reserves; the handle carries the same number as its .reserves attribute."""
+    HEADROOM = 1.25
+
+    def __init__(self):
+        self.sup, self.caps, self.reserves = None, (0, 0, 0, 0), 0
+
+    def assign(self, s):
+        """The handle holding supervision dict `s`; valid until the next assign."""
+        need = (int(s["B"]), int(s["T"]), len(s["state_time"]), len(s["arc_src"]))
+        if self.sup is None or any(n > c for n, c in zip(need, self.caps)):
+            room = (need[0], need[1], int(need[2] * self.HEADROOM) + 1, int(need[3] * self.HEADROOM) + 1)
+            self.caps = tuple(max(c, r) for c, r in zip(self.caps, room))
+            self.sup = None  # (the old handle goes first: its memory is free for the new one)
+            self.sup = hipabi.Supervision.reserve(*self.caps)
+            self.reserves += 1
+        self.sup.assign(s)
+        self.sup.reserves = self.reserves
+        return self.sup
+
+
+def minibatches(path, net, frame_shift=0, discard_partial=True, prefetch=0, reuse=False):
     """Reads an archive and yields (feats, ivectors, hipabi.Supervision) device objects for ChainNet.forward_backward, merging
     net.cfg.num_sequences examples at a time in archive order (nnet3-chain-merge-egs --minibatch-size; the archive is expected to
     be shuffled already, as nnet3-chain-shuffle-egs leaves it).  prefetch > 0: reading, decompression and the merge run on a
-    worker thread that many minibatches ahead (the C calls release the GIL), the copy to the device stays on the caller."""
+    worker thread that many minibatches ahead (the C calls release the GIL), the copy to the device stays on the caller.
+    reuse: every item carries the SAME supervision handle, a reserved one that is assigned the minibatch on the current stream
+    (ReusedSupervision: its tables are built on the device, nothing is allocated or freed per minibatch; .reserves on the handle says how
+    often it had to be reserved).  A yielded supervision is then valid until the next item is requested: work enqueued on the current
+    stream before that still sees it, a reference kept beyond it sees the next minibatch.  Default: a new hipabi.Supervision per item."""
     import torch
     B = net.cfg.num_sequences
     first_t, num_t, with_iv = net.first_t, net.num_t_in, net.cfg.ivector_dim > 0
@@ -168,8 +196,11 @@ def minibatches(path, net, frame_shift=0, discard_partial=True, prefetch=0):
             if hasattr(reader, "close"):
                 reader.close()
 
+    reused = ReusedSupervision() if reuse else None
+
     def to_device(f, iv, sup):
-        return torch.from_numpy(f).cuda(), torch.from_numpy(iv).cuda() if iv is not None else None, hipabi.Supervision(sup)
+        return (torch.from_numpy(f).cuda(), torch.from_numpy(iv).cuda() if iv is not None else None,
+                reused.assign(sup) if reuse else hipabi.Supervision(sup))
 
     if prefetch <= 0:
         for item in host_batches():
@@ -217,12 +248,15 @@ def minibatches(path, net, frame_shift=0, discard_partial=True, prefetch=0):
         th.join(timeout=5)
 
 
-def minibatches_by_width(path, nets, frame_shift=0):
+def minibatches_by_width(path, nets, frame_shift=0, reuse=False):
     """An archive with examples of several chunk widths (--egs.chunk-width 150,110,100) and one ChainNet per width
     (ChainNet(cfg, share=primary)): examples are binned by their number of output frames and a minibatch is emitted for a
     width as soon as its bin holds that net's num_sequences examples (nnet3-chain-merge-egs).  Yields (net, feats, ivectors,
-    hipabi.Supervision); what is left in the bins at the end of the archive is dropped."""
+    hipabi.Supervision); what is left in the bins at the end of the archive is dropped.
+    reuse: one reserved supervision per net (ReusedSupervision), assigned per minibatch as minibatches(reuse=True) does; a yielded
+    supervision is valid until the next item is requested."""
     import torch
+    reused = {id(n): ReusedSupervision() for n in nets} if reuse else None
     by_frames = {n.cfg.frames_per_chunk // n.cfg.frame_subsampling: n for n in nets}
     bins = {k: [] for k in by_frames}
     for eg in Reader(path):
@@ -236,4 +270,5 @@ def minibatches_by_width(path, nets, frame_shift=0):
             for e in group:
                 e.close()
             bins[T] = []
-            yield net, torch.from_numpy(f).cuda(), torch.from_numpy(iv).cuda() if iv is not None else None, hipabi.Supervision(sup)
+            yield (net, torch.from_numpy(f).cuda(), torch.from_numpy(iv).cuda() if iv is not None else None,
+                   reused[id(net)].assign(sup) if reuse else hipabi.Supervision(sup))

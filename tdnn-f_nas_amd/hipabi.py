@@ -329,9 +329,43 @@ class Supervision:
         check(load().tdnnf_supervision_reserve_e2e(int(max_sequences), int(max_frames), self.P, int(max_states), int(max_arcs), C.byref(self.h)))
         return self
 
-    def assign(self, graphs, frames_per_sequence, weight=1.0):
-        """tdnnf_supervision_assign_e2e on the current stream: the reserved supervision's next minibatch -- graphs, frames and weight may all
-        change.  Nothing is allocated or synchronised; B and T follow.  A refused minibatch (HipAbiError) leaves the previous one."""
+    @classmethod
+    def reserve(cls, max_sequences, max_frames, max_states, max_arcs):
+        """A reusable time-synchronous supervision (tdnnf_supervision_reserve): every allocation is made here, for minibatches of at most
+        max_sequences sequences of max_frames frames with max_states states and max_arcs arcs between them.  It holds no minibatch until
+        assign (B = T = 0) and is refused until then."""
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        self.B, self.T = 0, 0
+        check(load().tdnnf_supervision_reserve(int(max_sequences), int(max_frames), int(max_states), int(max_arcs), C.byref(self.h)))
+        return self
+
+    def assign(self, graphs, frames_per_sequence=None, weight=None):
+        """The reserved supervision's next minibatch, on the current stream.  Nothing is allocated or synchronised; B and T follow.  A
+        refused minibatch (HipAbiError) leaves the previous one.
+        A supervision of reserve: assign(s), s the dict of synth.make_supervision that Supervision(s) takes (tdnnf_supervision_assign:
+        the tables are built on the device); weight overrides the dict's.
+        A supervision of reserve_e2e: assign(graphs, frames_per_sequence, weight=1.0) (tdnnf_supervision_assign_e2e: graphs, frames and
+        weight may all change)."""
+        if isinstance(graphs, dict) and "seq_state_begin" in graphs:
+            s = graphs
+            if self.kind != 0:
+                raise HipAbiError("Supervision.assign: a time-synchronous supervision dict given to an end-to-end supervision "
+                                  "(reserve_e2e); its assign takes (graphs, frames_per_sequence, weight)")
+            if frames_per_sequence is not None:
+                raise HipAbiError("Supervision.assign: a supervision dict carries its frames (\"T\"); frames_per_sequence belongs to the end-to-end form")
+            k = [iarr(s["seq_state_begin"]), iarr(s["seq_arc_begin"]), iarr(s["state_time"]), farr(s["final_logprob"]),
+                 iarr(s["arc_src"]), iarr(s["arc_dst"]), iarr(s["arc_pdf"]), farr(s["arc_logprob"])]
+            w = float(s.get("weight", 1.0) if weight is None else weight)
+            check(load().tdnnf_supervision_assign(self.h, int(s["B"]), int(s["T"]), *[x[1] for x in k], w, stream()))
+            self.B, self.T = int(s["B"]), int(s["T"])
+            return
+        if self.kind != 1:
+            raise HipAbiError("Supervision.assign: graphs and frames_per_sequence given to a time-synchronous supervision (reserve); its "
+                              "assign takes the dict of synth.make_supervision")
+        if frames_per_sequence is None:
+            raise HipAbiError("Supervision.assign: the end-to-end form needs frames_per_sequence")
+        weight = 1.0 if weight is None else weight
         graphs, k = self._stack_e2e(graphs)
         check(load().tdnnf_supervision_assign_e2e(self.h, len(graphs), int(frames_per_sequence), *[x[1] for x in k], float(weight), stream()))
         self.B, self.T = len(graphs), int(frames_per_sequence)
@@ -353,6 +387,30 @@ class Supervision:
         v = [C.c_int() for _ in range(3)]
         check(load().tdnnf_supervision_e2e_form(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("threads", "vectors_in_lds", "rows_in_lds"), (x.value for x in v)))
+
+    TABLES = ("seq_state_begin", "state_time", "final_logprob", "frame_state_begin", "in_begin", "in_src", "in_pdf", "in_lp", "out_begin",
+              "out_dst", "out_pdf", "out_lp", "pf_src", "pf_dst", "pf_pdf", "pf_t", "pf_lp")
+
+    def capacity(self):
+        """{max_sequences, max_frames, max_states, max_arcs, assigns, allocations, device_bytes} of a supervision of reserve
+        (tdnnf_supervision_capacity); allocations: device and pinned allocations since reserve returned."""
+        v = [C.c_int() for _ in range(6)] + [C.c_longlong()]
+        check(load().tdnnf_supervision_capacity(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("max_sequences", "max_frames", "max_states", "max_arcs", "assigns", "allocations", "device_bytes"), (int(x.value) for x in v)))
+
+    def tables(self):
+        """The device tables of a time-synchronous supervision, created or assigned, as numpy arrays by name (tdnnf_supervision_dump; waits
+        for the current stream): Supervision.TABLES, int32 but for final_logprob and the *_lp (float32).  A table the supervision does not
+        carry (pf_* of a narrow created one) is empty."""
+        import numpy as np
+        lib, t = load(), {}
+        for name in self.TABLES:
+            n = C.c_longlong()
+            check(lib.tdnnf_supervision_dump(self.h, name.encode(), None, 0, C.byref(n), stream()))
+            out = np.zeros(n.value, np.float32 if name.endswith("_lp") or name == "final_logprob" else np.int32)
+            check(lib.tdnnf_supervision_dump(self.h, name.encode(), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), stream()))
+            t[name] = out
+        return t
 
     def info(self):
         """{num_states, num_arcs, max_states_per_frame, wide} (tdnnf_supervision_info); wide: over 4 states per frame on average,

@@ -11,7 +11,10 @@ The clock is the host's around a loop over the cycle that ends in ONE synchronis
 --repeats.  After the timing every batch of the cycle runs once either way and the outputs are compared for equality.  One JSON line.
 --transcripts: instead, the cost of a new batch for a caller who starts from transcripts (see transcripts() below): arc arrays built on the
 host + assign, assign alone, and tdnnf_align_graphs_assign_transcripts / tdnnf_supervision_assign_e2e_transcripts, alternating.
-usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts]"""
+--supervision [--tolerance N --alternatives N]: instead, the time-synchronous supervision of regular LF-MMI (see supervision() below):
+tdnnf_supervision_create + tdnnf_chain_objf_and_deriv + tdnnf_supervision_destroy against tdnnf_supervision_assign + the same call.
+usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts]
+                                              [--supervision [--tolerance N --alternatives N] [--sequences B --frames T]]"""
 import argparse
 import ctypes as C
 import json
@@ -122,6 +125,110 @@ def transcripts(args, pkg):
     print(json.dumps(res))
 
 
+def supervision(args, pkg):
+    """--supervision: what a NEW time-synchronous minibatch costs per step, two ways alternating in one process, a different synthetic
+    minibatch every iteration (a cycle generated beforehand), medians of --repeats:
+      create_call_destroy  tdnnf_supervision_create, tdnnf_chain_objf_and_deriv, tdnnf_supervision_destroy;
+      assign_call          tdnnf_supervision_assign on ONE reserved supervision, the same call.
+    --tolerance 0 (default): synth.make_supervision (alignment-like, narrow); --tolerance N --alternatives M: synth.make_supervision_lattice
+    (tolerance lattices, the wide case).  Also reported: the host time of the assign call alone (a clock around the call, no synchronise)
+    and the device time of what an assign enqueues -- its copies and the two build kernels -- between two events on an otherwise idle
+    stream.  After the timing every minibatch of the cycle runs once either way and results, nnet_output_deriv and xent_deriv are compared
+    for equality.  One JSON line."""
+    abi, synth = pkg.hipabi, pkg.synth
+    lib = abi.load()
+    P, B, T = args.pdfs, args.sequences, args.frames
+    if args.tolerance > 0:
+        sups = [synth.make_supervision_lattice(B, T, P, tolerance=args.tolerance, alternatives=args.alternatives, seed=10 + c) for c in range(args.cycle)]
+    else:
+        sups = [synth.make_supervision(B, T, P, max_alt=2, seed=10 + c) for c in range(args.cycle)]
+    batches = []
+    for sup in sups:
+        keep = [abi.iarr(sup["seq_state_begin"]), abi.iarr(sup["seq_arc_begin"]), abi.iarr(sup["state_time"]), abi.farr(sup["final_logprob"]),
+                abi.iarr(sup["arc_src"]), abi.iarr(sup["arc_dst"]), abi.iarr(sup["arc_pdf"]), abi.farr(sup["arc_logprob"])]
+        batches.append(dict(S=len(keep[2][0]), A=len(keep[4][0]), keep=keep, ptrs=[k[1] for k in keep]))
+    dg = abi.DenGraph(synth.make_den_graph(64, P, mean_out_degree=4.0, seed=1))
+    reserved = C.c_void_p()
+    abi.check(lib.tdnnf_supervision_reserve(B, T, max(b["S"] for b in batches), max(b["A"] for b in batches), C.byref(reserved)))
+    y = torch.randn(B * T, P, device="cuda")
+    xo = torch.log_softmax(torch.randn(B * T, P, device="cuda"), dim=1)
+    nb = int(lib.tdnnf_chain_workspace_bytes(dg.h, B, T))
+    ws = abi.workspace(nb)
+    ws.zero_()
+    s = abi.stream()
+    out = {k: (torch.zeros(8, dtype=torch.float64, device="cuda"), torch.zeros_like(y), torch.zeros_like(y)) for k in "ab"}
+
+    def call(h, o):
+        abi.check(lib.tdnnf_chain_objf_and_deriv(dg.h, h, abi.pmat(y), abi.pmat(xo), 0.1, 5e-5, 0.1, abi.ptr(o[0]), abi.pmat(o[1]), abi.pmat(o[2]), abi.ptr(ws), nb, s))
+
+    def created(b, o=out["a"]):
+        h = C.c_void_p()
+        abi.check(lib.tdnnf_supervision_create(B, T, *b["ptrs"], 1.0, C.byref(h)))
+        call(h, o)
+        lib.tdnnf_supervision_destroy(h)
+
+    def assign(b):
+        abi.check(lib.tdnnf_supervision_assign(reserved, B, T, *b["ptrs"], 1.0, s))
+
+    def assigned(b, o=out["b"]):
+        assign(b)
+        call(reserved, o)
+
+    def loop(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for b in batches:
+            fn(b)
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / len(batches)
+
+    def assign_alone():
+        """(host ms per assign call, device ms per assign between two events), the stream idle before each"""
+        host_ms, dev_ms = [], []
+        for b in batches:
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            t0 = time.perf_counter()
+            assign(b)
+            host_ms.append(1e3 * (time.perf_counter() - t0))
+            e1.record()
+            torch.cuda.synchronize()
+            dev_ms.append(e0.elapsed_time(e1))
+        return float(np.median(host_ms)), float(np.median(dev_ms))
+
+    loop(created), loop(assigned), loop(lambda b: call(reserved, out["b"]))  # warm-up: kernels loaded, the allocator's pools filled
+    ms = dict(create_call_destroy=[], assign_call=[], call_alone=[], assign_host=[], assign_device=[])
+    for _ in range(args.repeats):
+        ms["create_call_destroy"].append(loop(created))
+        ms["assign_call"].append(loop(assigned))
+        ms["call_alone"].append(loop(lambda b: call(reserved, out["b"])))
+        h, d = assign_alone()
+        ms["assign_host"].append(h)
+        ms["assign_device"].append(d)
+    equal = True
+    for b in batches:
+        for o in out.values():
+            for t in o:
+                t.zero_()
+        created(b), assigned(b)
+        torch.cuda.synchronize()
+        equal = equal and torch.equal(out["a"][0].view(torch.int64), out["b"][0].view(torch.int64)) and all(
+            torch.equal(x.view(torch.int32), z.view(torch.int32)) for x, z in zip(out["a"][1:], out["b"][1:]))
+    info = [C.c_int() for _ in range(4)]
+    abi.check(lib.tdnnf_supervision_info(reserved, *[C.byref(x) for x in info]))
+    cap = [C.c_int() for _ in range(6)] + [C.c_longlong()]
+    abi.check(lib.tdnnf_supervision_capacity(reserved, *[C.byref(x) for x in cap]))
+    res = dict(metric="supervision_per_minibatch", pdfs=P, cycle=args.cycle, repeats=args.repeats, sequences=B, frames=T, tolerance=args.tolerance,
+               alternatives=args.alternatives, states=max(b["S"] for b in batches), arcs=max(b["A"] for b in batches), wide=int(info[3].value),
+               max_states_per_frame=int(info[2].value), device_bytes=int(cap[6].value), allocations_since_reserve=int(cap[5].value), outputs_equal=bool(equal))
+    for k, v in ms.items():
+        res[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v])
+    res["assign_over_create"] = round(res["assign_call"]["ms"] / res["create_call_destroy"]["ms"], 3)
+    lib.tdnnf_supervision_destroy(reserved)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -129,9 +236,16 @@ def main():
     ap.add_argument("--pdfs", type=int, default=6034)
     ap.add_argument("--only", choices=["forced", "free", "numerator"])
     ap.add_argument("--transcripts", action="store_true", help="graphs from transcripts: host-built arrays + assign against assign_transcripts")
+    ap.add_argument("--supervision", action="store_true", help="time-synchronous supervisions: create + call + destroy against assign + call")
+    ap.add_argument("--tolerance", type=int, default=0, help="--supervision: > 0 tolerance lattices (synth.make_supervision_lattice)")
+    ap.add_argument("--alternatives", type=int, default=1)
+    ap.add_argument("--sequences", type=int, default=128)
+    ap.add_argument("--frames", type=int, default=150)
     args = ap.parse_args()
     assert args.cycle >= 8, "different graphs every iteration: a cycle of at least 8 batches"
     pkg = ge.load_package()
+    if args.supervision:
+        return supervision(args, pkg)
     if args.transcripts:
         return transcripts(args, pkg)
     abi, synth = pkg.hipabi, pkg.synth
