@@ -347,7 +347,8 @@ int tdnnf_supervision_info(const tdnnf_supervision *, int *num_states, int *num_
    (and, because the device build indexes by them, begin arrays that do not start at 0 or a seq_arc_begin that decreases); a minibatch over
    a capacity is refused naming the capacity, its value and the excess; the widths and `wide` are found as tdnnf_supervision_create finds
    them.  A refused assign leaves the supervision on its previous minibatch (an error of the runtime behind this point, TDNNF_EHIP from a
-   copy or a launch, leaves it without one: refused like a fresh handle until an assign succeeds).  Then the raw arrays are staged in pinned memory, and their
+   copy or a launch, leaves it without one: refused like a fresh handle until an assign succeeds -- the failure rule of
+   tdnnf_align_graphs_assign below).  Then the raw arrays are staged in pinned memory, and their
    copies and two build kernels are enqueued on `stream`: the by-destination and by-source lists in original arc order and the per-frame
    lists ordered stably by pdf, byte for byte what tdnnf_supervision_create uploads.  Nothing is allocated, freed or waited for
    device-wide; the only wait is for the copies of the assign before last out of the staging buffer that is written again.  Work enqueued
@@ -406,7 +407,8 @@ int tdnnf_supervision_create_e2e(int num_sequences, int frames_per_sequence, int
    the launch form now follows the minibatch).  tdnnf_supervision_assign_e2e gives it the next minibatch in stream order, with the arrays of
    tdnnf_supervision_create_e2e: num_sequences, frames_per_sequence, weight and the graphs may all change, within the capacities
    (TDNNF_EINVAL naming the capacity and the excess: max_sequences, max_frames here, max_states and max_arcs from tdnnf_align_graphs_assign,
-   which also validates the arrays; a refused assign leaves the supervision on its previous minibatch).  The launch form of the recursion is
+   which also validates the arrays; a refused assign leaves the supervision on its previous minibatch, and where an error of the runtime
+   leaves the graph set without a batch -- tdnnf_align_graphs_assign's failure rule -- the supervision holds no minibatch either).  The launch form of the recursion is
    planned here from the minibatch's largest graph (option "align_form" is read HERE).  No allocation, no free, no device-wide wait; stream
    order as tdnnf_align_graphs_assign documents.  Every function that takes a supervision runs what it runs for a created one and gives the
    same bits; before the first assign they refuse it. */
@@ -552,7 +554,10 @@ void tdnnf_align_graphs_destroy(tdnnf_align_graphs *);
    tdnnf_align_graphs_assign takes the eight host arrays of tdnnf_align_graphs_create and arc_label (non-NULL exactly when the handle was
    reserved with labels), validates what create validates with the same messages under its own name, and refuses a batch beyond one of the
    three capacities with TDNNF_EINVAL, naming the capacity and the excess.  All checks run before anything is written: a refused assign
-   leaves the handle serving its previous batch.  It then copies the arrays into pinned staging, enqueues asynchronous copies and three
+   leaves the handle serving its previous batch.  ONE FAILURE RULE for every assign of a reserved handle (this one,
+   tdnnf_align_graphs_assign_transcripts, tdnnf_supervision_assign): from the first enqueued copy until the call succeeds the handle holds
+   NO batch, so an error of the runtime behind that point (TDNNF_EHIP from a copy or a launch, when the tables are already being
+   overwritten) leaves a handle that every entry refuses like a fresh one until an assign succeeds.  It then copies the arrays into pinned staging, enqueues asynchronous copies and three
    kernels on `stream` that build the tables on the device -- the bytes tdnnf_align_graphs_create uploads for the same arrays, so every
    entry gives the same bits -- and returns.  No allocation, no free, no device-wide or stream-wide wait; the one host wait there can be is
    for the staging copy of the assign BEFORE LAST (the two staging buffers take turns).  The host arrays may be reused when it returns.
@@ -605,7 +610,8 @@ int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *, int *max_graphs, int
    (csrc/align_compile_kernels.h) and the three build kernels of tdnnf_align_graphs_assign, unchanged: the tables are the bytes an assign
    of the same graphs builds.  No allocation, no free, no device-wide or stream-wide wait; the one host wait there can be is for the
    staging copy of the assign before last.  Stream order, the host-side answers and tdnnf_align_graphs_capacity's `assigns` are
-   tdnnf_align_graphs_assign's; both kinds of assign may alternate on one handle.
+   tdnnf_align_graphs_assign's, and so is the failure rule (a refusal leaves the previous batch, an error of the runtime no batch); both
+   kinds of assign may alternate on one handle, on the one pair of staging buffers.
    Not built: pronunciation alternatives and adjacent optional slots, lexicon and tree handling (the caller maps words to units and
    (left, unit) to pdfs), right context, units of several states, capture into a HIP graph. */
 typedef struct tdnnf_unit_set tdnnf_unit_set;

@@ -8,6 +8,7 @@
 
 #include "align_tables.h"
 #include "align_transcripts.h"
+#include "assign_stage.h"
 #include "common.h"
 
 namespace tdnnf {
@@ -113,23 +114,14 @@ struct tdnnf_align_graphs {
   // ---- a RESERVED handle (tdnnf_align_graphs_reserve): every device array above is a piece of ONE allocation made for the capacities, the
   // pointers never change, and tdnnf_align_graphs_assign refills them in stream order (align_build.hip).  All zero for a created handle.
   bool reserved;
-  int assigns;                           // assigns that succeeded; 0: the handle holds no graphs yet (G = 0)
+  int assigns;                           // assigns that succeeded; 0: no graphs (none yet, or an assign failed behind its first enqueued copy)
   int cap_graphs, cap_states, cap_arcs;  // the capacities: graphs, total states, total arcs of a batch
-  void *arena;                           // device, owned: the one allocation
-  size_t arena_bytes;
-  int device_allocs;                     // hipMallocs made for the handle (the witness that assign makes none)
-  char *stage_host[2];                   // pinned host staging, two buffers used in turn
-  hipEvent_t stage_event[2];             // recorded behind the copies out of stage_host[i]; waited for before it is overwritten
-  bool stage_used[2];
-  size_t stage_bytes;
-  char *stage_dev;                       // device: the raw arrays of the batch being built, packed as in the staging buffer
-  hipStream_t last_stream;               // the stream of the last assign (tdnnf_align_graphs_dump waits for it)
+  tdnnf::AssignStage stage;              // the one allocation, the staging of the assigns, the allocation counts (assign_stage.h)
   tdnnf::AlignBuildDev build;            // the tables as the build kernels write them, and the build's scratch
 };
 
 namespace tdnnf {
 
-// The refusal every label entry gives a handle that tdnnf_align_graphs_create made.  who: the prefix of the message, the call's name.
 // The refusal every entry gives a reserved handle that was never assigned a batch.  who: the prefix of the message, the call's name.
 inline int align_need_batch(const tdnnf_align_graphs *g, const char *who) {
   TDNNF_REQUIRE(!g || !g->reserved || g->assigns > 0,
@@ -137,6 +129,7 @@ inline int align_need_batch(const tdnnf_align_graphs *g, const char *who) {
   return TDNNF_OK;
 }
 
+// The refusal every label entry gives a handle that tdnnf_align_graphs_create made.  who: the prefix of the message, the call's name.
 inline int align_need_labels(const tdnnf_align_graphs *g, const char *who) {
   TDNNF_REQUIRE(g, "%snull graphs", who);
   if (int rc = align_need_batch(g, who)) return rc;

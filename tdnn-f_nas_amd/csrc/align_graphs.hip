@@ -124,20 +124,7 @@ int align_graphs_create(const char *who, int num_graphs, int num_pdfs, const int
   return TDNNF_OK;
 }
 
-// ---- reserved handles: one device allocation for the capacities, refilled in stream order by tdnnf_align_graphs_assign
-
-// Hands out pieces of the handle's one allocation, 256 bytes apart at least; with a null base it only counts.
-struct AlignCarve {
-  char *base;
-  size_t at;
-  template <class T>
-  T *take(size_t n) {
-    at = align_round_up(at, 256);
-    T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += sizeof(T) * std::max<size_t>(n, 1);
-    return p;
-  }
-};
+// ---- reserved handles: one device allocation for the capacities, refilled in stream order by tdnnf_align_graphs_assign (assign_stage.h)
 
 // the rows a table can have in a batch at the capacities: a state table's are the states; by_pdf's and by_label's the distinct pdfs / labels
 // of each graph, at most its arcs and at most num_pdfs / num_labels a graph
@@ -147,7 +134,7 @@ long long align_row_capacity(const tdnnf_align_graphs *g, int table) {
 }
 
 // Every device array of a reserved handle, the build's scratch and the device staging, out of c.  Run once with a null base for the size.
-void align_reserve_layout(tdnnf_align_graphs *g, AlignCarve *c) {
+void align_reserve_layout(tdnnf_align_graphs *g, Carve *c) {
   const size_t Gc = g->cap_graphs, Sc = g->cap_states, Ac = g->cap_arcs;
   AlignBuildDev &b = g->build;
   b.graphs = c->take<AlignGraphDev>(Gc);
@@ -183,22 +170,50 @@ void align_reserve_layout(tdnnf_align_graphs *g, AlignCarve *c) {
     t.gbase = c->take<int4>(Gc);
     t.totals = c->take<int>(4);
   }
-  g->stage_dev = c->take<char>(g->stage_bytes);
+  g->stage.dev = c->take<char>(g->stage.bytes);
 }
 
-// One array of a batch in the staging buffer: copies it in and moves *at on; the offset is the same in the device staging.
-template <class T>
-size_t align_stage(char *host, size_t *at, const T *v, size_t n) {
-  const size_t begin = *at;
-  if (n) memcpy(host + begin, v, sizeof(T) * n);
-  *at += sizeof(T) * n;
-  return begin;
+// What both assigns check under the call's name `who`, on either side of their own validation.  In front of it the handle: a reserved
+// one, and reserved for labels exactly when the batch brings them (`labels`).  Behind it the batch's totals: the three capacities.
+int align_assign_handle(const char *who, const tdnnf_align_graphs *g, bool labels) {
+  TDNNF_REQUIRE(g->reserved, "%sthe handle was made by tdnnf_align_graphs_create: only a handle of tdnnf_align_graphs_reserve can be assigned", who);
+  TDNNF_REQUIRE(g->L == 0 || labels, "%sthe handle was reserved for labels (num_labels %d), and arc_label is null", who, g->L);
+  TDNNF_REQUIRE(g->L > 0 || !labels, "%sarc_label given to a handle that was reserved without labels (num_labels 0)", who);
+  return TDNNF_OK;
+}
+int align_assign_fits(const char *who, const tdnnf_align_graphs *g, int G, int NS, int NA) {
+  std::string err;
+  TDNNF_REQUIRE(within_capacity(who, G, "graphs", g->cap_graphs, &err) && within_capacity(who, NS, "states", g->cap_states, &err) && within_capacity(who, NA, "arcs", g->cap_arcs, &err),
+                "%s", err.c_str());
+  return TDNNF_OK;
 }
 
 }  // namespace
 
 int align_build_launch(const AlignBuildDev &b, int max_graph_arcs, int max_graph_rows, hipStream_t s);  // align_build.hip
 int align_compile_launch(const AlignCompileDev &c, int G, hipStream_t s);                                // align_compile.hip
+
+// The end of both assigns: the copies, the transcript compile (c, or null) and the build on s, then the host metadata of the batch (p's,
+// moved out of it).  From the first enqueued copy the device tables are being overwritten: the handle holds no batch until all of it
+// succeeded (assign_stage.h).
+static int align_commit(tdnnf_align_graphs *g, const StagePacker &pk, size_t raw_bytes, const AlignCompileDev *c, TranscriptPlan &&p, hipStream_t s) {
+  const int assigns_before = g->assigns;
+  g->assigns = 0;
+  int rc;
+  if ((rc = g->stage.submit(pk, raw_bytes, s)) || (c && (rc = align_compile_launch(*c, g->build.G, s))) ||
+      (rc = align_build_launch(g->build, p.max_graph_arcs, p.max_graph_rows, s)))
+    return rc;
+  g->G = g->build.G;
+  g->state_begin = std::move(p.state_begin);
+  g->num_arcs = std::move(p.num_arcs);
+  g->max_in_degree = std::move(p.max_in_degree);
+  g->col_begin = std::move(p.col_begin);
+  g->col_pdfs = std::move(p.col_pdfs);
+  g->lcol_begin = std::move(p.lcol_begin);
+  g->col_labels = std::move(p.col_labels);
+  g->assigns = assigns_before + 1;
+  return TDNNF_OK;
+}
 
 }  // namespace tdnnf
 
@@ -222,21 +237,11 @@ int tdnnf_align_graphs_reserve(int max_graphs, int num_pdfs, int num_labels, int
   g->cap_states = max_states;
   g->cap_arcs = max_arcs;
   // staging: four begin arrays, four arrays per arc and the labels, two per state, the two column lists and their lengths
-  g->stage_bytes = sizeof(int) * (4 * ((size_t)max_graphs + 1) + 7 * (size_t)max_arcs + 2 * (size_t)max_states + 2 * (size_t)max_graphs);
-  AlignCarve size{nullptr, 0};
-  align_reserve_layout(g, &size);
-  g->arena_bytes = size.at;
-  hipError_t e = hipMalloc(&g->arena, g->arena_bytes);
-  if (e == hipSuccess) g->device_allocs = 1;
-  for (int i = 0; i < 2 && e == hipSuccess; i++)
-    if ((e = hipHostMalloc((void **)&g->stage_host[i], std::max<size_t>(g->stage_bytes, 1), hipHostMallocDefault)) == hipSuccess)
-      e = hipEventCreateWithFlags(&g->stage_event[i], hipEventDisableTiming);
-  if (e != hipSuccess) {
+  const size_t stage_bytes = sizeof(int) * (4 * ((size_t)max_graphs + 1) + 7 * (size_t)max_arcs + 2 * (size_t)max_states + 2 * (size_t)max_graphs);
+  if (int rc = g->stage.create("align_graphs_reserve: allocation", stage_bytes, [g](Carve *c) { align_reserve_layout(g, c); })) {
     tdnnf_align_graphs_destroy(g);
-    return hip_status(e, "align_graphs_reserve: allocation");
+    return rc;
   }
-  AlignCarve carve{static_cast<char *>(g->arena), 0};
-  align_reserve_layout(g, &carve);
   *out = g;
   return TDNNF_OK;
 }
@@ -246,95 +251,62 @@ int tdnnf_align_graphs_assign(tdnnf_align_graphs *g, int num_graphs, const int *
                               const float *final_logprob, const int *arc_label, tdnnf_stream stream) {
   const char *who = "align_graphs_assign: ";
   TDNNF_REQUIRE(g, "%snull graphs", who);
-  TDNNF_REQUIRE(g->reserved, "%sthe handle was made by tdnnf_align_graphs_create: only a handle of tdnnf_align_graphs_reserve can be assigned", who);
-  TDNNF_REQUIRE(g->L == 0 || arc_label, "%sthe handle was reserved for labels (num_labels %d), and arc_label is null", who, g->L);
-  TDNNF_REQUIRE(g->L > 0 || !arc_label, "%sarc_label given to a handle that was reserved without labels (num_labels 0)", who);
-  int rc = align_validate(who, true, num_graphs, g->P, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob,
-                          final_logprob, arc_label, g->L);
-  if (rc) return rc;
+  int rc;
+  if ((rc = align_assign_handle(who, g, arc_label != nullptr)) ||
+      (rc = align_validate(who, true, num_graphs, g->P, graph_state_begin, graph_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob,
+                           final_logprob, arc_label, g->L)))
+    return rc;
   const int G = num_graphs, NS = graph_state_begin[G], NA = graph_arc_begin[G];
-  TDNNF_REQUIRE(G <= g->cap_graphs, "%s%d graphs exceed the capacity max_graphs = %d by %d", who, G, g->cap_graphs, G - g->cap_graphs);
-  TDNNF_REQUIRE(NS <= g->cap_states, "%s%d states exceed the capacity max_states = %d by %d", who, NS, g->cap_states, NS - g->cap_states);
-  TDNNF_REQUIRE(NA <= g->cap_arcs, "%s%d arcs exceed the capacity max_arcs = %d by %d", who, NA, g->cap_arcs, NA - g->cap_arcs);
+  if ((rc = align_assign_fits(who, g, G, NS, NA))) return rc;
 
   // the metadata the host answers layout questions from: lengths, largest in-degree, the column lists (sort and unique over a graph's arcs)
-  std::vector<int> num_arcs(G), max_in_degree(G), col_begin(1, 0), col_pdfs, lcol_begin(1, 0), col_labels, num_cols(G), num_lcols(G), in_degree(NS, 0), list;
-  int max_graph_arcs = 0, max_graph_rows = 0;
+  TranscriptPlan p;  // (what a transcript batch's plan holds of its graphs, align_transcripts.h: the same fields)
+  p.state_begin.assign(graph_state_begin, graph_state_begin + G + 1);
+  p.col_begin.assign(1, 0);
+  p.lcol_begin.assign(1, 0);
+  p.max_graph_arcs = p.max_graph_rows = 0;
+  std::vector<int> in_degree(NS, 0), list;
   const auto columns = [&](const int *of_arc, int a0, int a1, std::vector<int> *begin, std::vector<int> *cols) {
     list.assign(of_arc + a0, of_arc + a1);
-    std::sort(list.begin(), list.end());
-    list.erase(std::unique(list.begin(), list.end()), list.end());
-    cols->insert(cols->end(), list.begin(), list.end());
-    begin->push_back((int)cols->size());
-    return (int)list.size();
+    return append_columns(&list, begin, cols);
   };
   for (int k = 0; k < G; k++) {
     const int a0 = graph_arc_begin[k], a1 = graph_arc_begin[k + 1];
-    num_arcs[k] = a1 - a0;
+    p.num_arcs.push_back(a1 - a0);
     for (int a = a0; a < a1; a++) in_degree[arc_dst[a]]++;
-    max_in_degree[k] = *std::max_element(in_degree.begin() + graph_state_begin[k], in_degree.begin() + graph_state_begin[k + 1]);
-    num_cols[k] = columns(arc_pdf, a0, a1, &col_begin, &col_pdfs);
-    if (arc_label) num_lcols[k] = columns(arc_label, a0, a1, &lcol_begin, &col_labels);
-    max_graph_arcs = std::max(max_graph_arcs, a1 - a0);
-    max_graph_rows = std::max(max_graph_rows, std::max(graph_state_begin[k + 1] - graph_state_begin[k], std::max(num_cols[k], num_lcols[k])));
+    p.max_in_degree.push_back(*std::max_element(in_degree.begin() + graph_state_begin[k], in_degree.begin() + graph_state_begin[k + 1]));
+    p.num_cols.push_back(columns(arc_pdf, a0, a1, &p.col_begin, &p.col_pdfs));
+    p.num_lcols.push_back(arc_label ? columns(arc_label, a0, a1, &p.lcol_begin, &p.col_labels) : 0);
+    p.max_graph_arcs = std::max(p.max_graph_arcs, a1 - a0);
+    p.max_graph_rows = std::max(p.max_graph_rows, std::max(graph_state_begin[k + 1] - graph_state_begin[k], std::max(p.num_cols[k], p.num_lcols[k])));
   }
 
-  // staging: the one wait of this path, for the copies of the assign before last out of the buffer that is now overwritten
-  const int slot = g->assigns & 1;
-  if (g->stage_used[slot]) TDNNF_HIP(hipEventSynchronize(g->stage_event[slot]));
-  char *host = g->stage_host[slot];
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  StagePacker pk;
+  if ((rc = g->stage.begin(&pk))) return rc;
   AlignBuildDev &b = g->build;
-  size_t at = 0;
-  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(g->stage_dev + align_stage(host, &at, static_cast<const int *>(v), n)); };
+  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(g->stage.dev + pk.put(v, n)); };
   b.G = G;
   b.state_begin = raw(graph_state_begin, (size_t)G + 1);
   b.arc_begin = raw(graph_arc_begin, (size_t)G + 1);
-  b.col_begin = raw(col_begin.data(), (size_t)G + 1);
-  b.lcol_begin = raw(lcol_begin.data(), arc_label ? (size_t)G + 1 : 0);
+  b.col_begin = raw(p.col_begin.data(), (size_t)G + 1);
+  b.lcol_begin = raw(p.lcol_begin.data(), arc_label ? (size_t)G + 1 : 0);
   b.src = raw(arc_src, NA);
   b.dst = raw(arc_dst, NA);
   b.pdf = raw(arc_pdf, NA);
   b.lp_bits = raw(arc_logprob, NA);
-  const size_t raw_bytes = at;
+  const size_t raw_bytes = pk.at;
   // the arrays that go to the handle's own device arrays as they are
-  struct Copy {
-    const void *to;
-    size_t from, bytes;
-  } copies[7];
-  int num_copies = 0;
-  const auto direct = [&](const void *to, const void *v, size_t n) {
-    const size_t from = align_stage(host, &at, static_cast<const int *>(v), n);
-    if (n) copies[num_copies++] = Copy{to, from, sizeof(int) * n};
-  };
-  direct(g->dev.init, initial_logprob, NS);
-  direct(g->dev.final, final_logprob, NS);
-  direct(g->num_cols_dev, num_cols.data(), G);
-  direct(g->col_pdfs_dev, col_pdfs.data(), col_pdfs.size());
+  pk.put_to(g->dev.init, initial_logprob, NS);
+  pk.put_to(g->dev.final, final_logprob, NS);
+  pk.put_to(g->num_cols_dev, p.num_cols.data(), G);
+  pk.put_to(g->col_pdfs_dev, p.col_pdfs.data(), p.col_pdfs.size());
   if (arc_label) {
-    direct(g->arc_label_dev, arc_label, NA);
-    direct(g->num_lcols_dev, num_lcols.data(), G);
-    direct(g->col_labels_dev, col_labels.data(), col_labels.size());
+    pk.put_to(g->arc_label_dev, arc_label, NA);
+    pk.put_to(g->num_lcols_dev, p.num_lcols.data(), G);
+    pk.put_to(g->col_labels_dev, p.col_labels.data(), p.col_labels.size());
   }
-  TDNNF_REQUIRE(at <= g->stage_bytes, "%sinternal: the batch needs %zu bytes of staging, the handle has %zu", who, at, g->stage_bytes);
-  TDNNF_HIP(hipMemcpyAsync(g->stage_dev, host, raw_bytes, hipMemcpyHostToDevice, s));
-  for (int i = 0; i < num_copies; i++)
-    TDNNF_HIP(hipMemcpyAsync(const_cast<void *>(copies[i].to), host + copies[i].from, copies[i].bytes, hipMemcpyHostToDevice, s));
-  TDNNF_HIP(hipEventRecord(g->stage_event[slot], s));
-  g->stage_used[slot] = true;
-  if ((rc = align_build_launch(b, max_graph_arcs, max_graph_rows, s))) return rc;
-
-  g->G = G;
-  g->state_begin.assign(graph_state_begin, graph_state_begin + G + 1);
-  g->num_arcs.swap(num_arcs);
-  g->max_in_degree.swap(max_in_degree);
-  g->col_begin.swap(col_begin);
-  g->col_pdfs.swap(col_pdfs);
-  g->lcol_begin.swap(lcol_begin);
-  g->col_labels.swap(col_labels);
-  g->last_stream = s;
-  g->assigns++;
-  return TDNNF_OK;
+  TDNNF_REQUIRE(pk.fits(), "%sinternal: the batch needs %zu bytes of staging, the handle has %zu", who, pk.at, pk.size);
+  return align_commit(g, pk, raw_bytes, nullptr, std::move(p), static_cast<hipStream_t>(stream));
 }
 
 // ---- transcript graphs: a unit set made once, and the assign that compiles a batch of transcripts on the device (align_transcripts.h,
@@ -362,18 +334,18 @@ int tdnnf_unit_set_create(int num_units, int num_pdfs, int context, const int *e
   u->host.take_logprob = take_logprob;
   u->host.skip_logprob = skip_logprob;
   u->arena = nullptr;
-  const auto layout = [&](AlignCarve c) {  // the four tables out of one allocation; with a null base only their size
+  const auto layout = [&](Carve c) {  // the four tables out of one allocation; with a null base only their size
     u->dev.entry_pdf = c.take<int>(n);
     u->dev.loop_pdf = c.take<int>(n);
     u->dev.loop_logprob = c.take<float>(U);
     u->dev.leave_logprob = c.take<float>(U);
     return c.at;
   };
-  if (hipError_t e = hipMalloc(&u->arena, layout(AlignCarve{nullptr, 0}))) {
+  if (hipError_t e = hipMalloc(&u->arena, layout(Carve{nullptr, 0}))) {
     delete u;
     return hip_status(e, "unit_set_create: hipMalloc");
   }
-  layout(AlignCarve{static_cast<char *>(u->arena), 0});
+  layout(Carve{static_cast<char *>(u->arena), 0});
   u->dev.take_logprob = take_logprob;
   u->dev.skip_logprob = skip_logprob;
   u->dev.U = num_units;
@@ -415,44 +387,35 @@ int tdnnf_align_graphs_assign_transcripts(tdnnf_align_graphs *g, const tdnnf_uni
                                           const int *slot_unit, const int *slot_optional, tdnnf_stream stream) {
   const char *who = "align_graphs_assign_transcripts: ";
   TDNNF_REQUIRE(g && units, "%snull graphs or null unit set", who);
-  TDNNF_REQUIRE(g->reserved, "%sthe handle was made by tdnnf_align_graphs_create: only a handle of tdnnf_align_graphs_reserve can be assigned", who);
+  const bool labelled = g->L > 0;  // (a transcript batch brings the labels the handle wants: an arc's is the slot of its destination)
+  int rc;
+  if ((rc = align_assign_handle(who, g, labelled))) return rc;
   TDNNF_REQUIRE(units->host.P == g->P, "%sthe unit set names %d pdfs, the handle was reserved for num_pdfs %d", who, units->host.P, g->P);
   std::string err;
   TDNNF_REQUIRE(transcripts_validate(who, units->host, num_transcripts, slot_begin, slot_unit, slot_optional, &err), "%s", err.c_str());
-  const bool labelled = g->L > 0;
   TranscriptPlan p;
   TDNNF_REQUIRE(transcripts_plan(who, units->host, num_transcripts, slot_begin, slot_unit, slot_optional, labelled, &p, &err), "%s", err.c_str());
   const int G = num_transcripts, NS = p.state_begin[G], NA = p.arc_begin[G], N = slot_begin[G];
   TDNNF_REQUIRE(!labelled || p.max_slots <= g->L, "%sthe longest transcript has %d slots, and a slot is a label: the handle's num_labels = %d is short by %d", who,
                 p.max_slots, g->L, p.max_slots - g->L);
-  TDNNF_REQUIRE(G <= g->cap_graphs, "%s%d graphs exceed the capacity max_graphs = %d by %d", who, G, g->cap_graphs, G - g->cap_graphs);
-  TDNNF_REQUIRE(NS <= g->cap_states, "%s%d states exceed the capacity max_states = %d by %d", who, NS, g->cap_states, NS - g->cap_states);
-  TDNNF_REQUIRE(NA <= g->cap_arcs, "%s%d arcs exceed the capacity max_arcs = %d by %d", who, NA, g->cap_arcs, NA - g->cap_arcs);
-  // the staging's two shapes: on the host the begins, the slots and the column lists; on the device the begins and the slots, behind them
-  // the four arc arrays the kernel writes.  Both fit what tdnnf_align_graphs_reserve sized for 28 bytes an arc (slots < states, 2 <= arcs a graph)
-  const size_t begins = sizeof(int) * ((size_t)G + 1) * (labelled ? 5 : 4), lists = sizeof(int) * (2 * (size_t)G + p.col_pdfs.size() + p.col_labels.size());
-  const size_t raw_bytes = begins + sizeof(int) * (size_t)N;
-  TDNNF_REQUIRE(raw_bytes + lists <= g->stage_bytes && raw_bytes + 4 * sizeof(int) * (size_t)NA <= g->stage_bytes,
-                "%sinternal: the batch needs %zu bytes of staging on the host and %zu on the device, the handle has %zu", who, raw_bytes + lists,
-                raw_bytes + 4 * sizeof(int) * (size_t)NA, g->stage_bytes);
+  if ((rc = align_assign_fits(who, g, G, NS, NA))) return rc;
 
-  // staging: the one wait of this path, for the copies of the assign before last out of the buffer that is now overwritten
-  const int slot = g->assigns & 1;
-  if (g->stage_used[slot]) TDNNF_HIP(hipEventSynchronize(g->stage_event[slot]));
-  char *host = g->stage_host[slot];
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  StagePacker pk;
+  if ((rc = g->stage.begin(&pk))) return rc;
   AlignBuildDev &b = g->build;
   AlignCompileDev c;
-  size_t at = 0;
-  const auto raw = [&](const std::vector<int> &v, size_t n) { return reinterpret_cast<const int *>(g->stage_dev + align_stage(host, &at, v.data(), n)); };
+  const auto raw = [&](const int *v, size_t n) { return reinterpret_cast<const int *>(g->stage.dev + pk.put(v, n)); };
   b.G = G;
-  b.state_begin = c.state_begin = raw(p.state_begin, (size_t)G + 1);
-  b.arc_begin = c.arc_begin = raw(p.arc_begin, (size_t)G + 1);
-  b.col_begin = raw(p.col_begin, (size_t)G + 1);
-  b.lcol_begin = raw(p.lcol_begin, labelled ? (size_t)G + 1 : 0);
-  c.slot_begin = reinterpret_cast<const int *>(g->stage_dev + align_stage(host, &at, slot_begin, (size_t)G + 1));
-  c.slots = raw(p.packed, N);
-  int *arcs = reinterpret_cast<int *>(g->stage_dev + at);  // (device only: the kernel writes them)
+  b.state_begin = c.state_begin = raw(p.state_begin.data(), (size_t)G + 1);
+  b.arc_begin = c.arc_begin = raw(p.arc_begin.data(), (size_t)G + 1);
+  b.col_begin = raw(p.col_begin.data(), (size_t)G + 1);
+  b.lcol_begin = raw(p.lcol_begin.data(), labelled ? (size_t)G + 1 : 0);
+  c.slot_begin = raw(slot_begin, (size_t)G + 1);
+  c.slots = raw(p.packed.data(), N);
+  // the staging's two shapes: on the host the begins, the slots and the column lists; on the device the begins and the slots, behind them
+  // the four arc arrays the kernel writes.  Both fit what tdnnf_align_graphs_reserve sized for 28 bytes an arc (slots < states, 2 <= arcs a graph)
+  const size_t raw_bytes = pk.at, dev_bytes = raw_bytes + 4 * sizeof(int) * (size_t)NA;
+  int *arcs = reinterpret_cast<int *>(g->stage.dev + raw_bytes);  // (device only)
   b.src = c.src = arcs;
   b.dst = c.dst = arcs + NA;
   b.pdf = c.pdf = arcs + 2 * (size_t)NA;
@@ -461,33 +424,15 @@ int tdnnf_align_graphs_assign_transcripts(tdnnf_align_graphs *g, const tdnnf_uni
   c.init = const_cast<float *>(g->dev.init);
   c.final = const_cast<float *>(g->dev.final);
   c.units = units->dev;
-  TDNNF_HIP(hipMemcpyAsync(g->stage_dev, host, at, hipMemcpyHostToDevice, s));
-  const auto direct = [&](const void *to, const std::vector<int> &v) {
-    const size_t from = align_stage(host, &at, v.data(), v.size());
-    return v.empty() ? hipSuccess : hipMemcpyAsync(const_cast<void *>(to), host + from, sizeof(int) * v.size(), hipMemcpyHostToDevice, s);
-  };
-  TDNNF_HIP(direct(g->num_cols_dev, p.num_cols));
-  TDNNF_HIP(direct(g->col_pdfs_dev, p.col_pdfs));
+  pk.put_to(g->num_cols_dev, p.num_cols.data(), p.num_cols.size());
+  pk.put_to(g->col_pdfs_dev, p.col_pdfs.data(), p.col_pdfs.size());
   if (labelled) {
-    TDNNF_HIP(direct(g->num_lcols_dev, p.num_lcols));
-    TDNNF_HIP(direct(g->col_labels_dev, p.col_labels));
+    pk.put_to(g->num_lcols_dev, p.num_lcols.data(), p.num_lcols.size());
+    pk.put_to(g->col_labels_dev, p.col_labels.data(), p.col_labels.size());
   }
-  TDNNF_HIP(hipEventRecord(g->stage_event[slot], s));
-  g->stage_used[slot] = true;
-  int rc;
-  if ((rc = align_compile_launch(c, G, s)) || (rc = align_build_launch(b, p.max_graph_arcs, p.max_graph_rows, s))) return rc;
-
-  g->G = G;
-  g->state_begin.swap(p.state_begin);
-  g->num_arcs.swap(p.num_arcs);
-  g->max_in_degree.swap(p.max_in_degree);
-  g->col_begin.swap(p.col_begin);
-  g->col_pdfs.swap(p.col_pdfs);
-  g->lcol_begin.swap(p.lcol_begin);
-  g->col_labels.swap(p.col_labels);
-  g->last_stream = s;
-  g->assigns++;
-  return TDNNF_OK;
+  TDNNF_REQUIRE(pk.fits() && dev_bytes <= pk.size, "%sinternal: the batch needs %zu bytes of staging on the host and %zu on the device, the handle has %zu", who,
+                pk.at, dev_bytes, pk.size);
+  return align_commit(g, pk, raw_bytes, &c, std::move(p), static_cast<hipStream_t>(stream));
 }
 
 int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *g, int *max_graphs, int *max_states, int *max_arcs, long long *device_bytes, int *device_allocs,
@@ -496,8 +441,8 @@ int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *g, int *max_graphs, in
   if (max_graphs) *max_graphs = g->cap_graphs;
   if (max_states) *max_states = g->cap_states;
   if (max_arcs) *max_arcs = g->cap_arcs;
-  if (device_bytes) *device_bytes = (long long)g->arena_bytes;
-  if (device_allocs) *device_allocs = g->device_allocs;
+  if (device_bytes) *device_bytes = (long long)g->stage.arena_bytes;
+  if (device_allocs) *device_allocs = g->stage.device_allocs;
   if (assigns) *assigns = g->assigns;
   return TDNNF_OK;
 }
@@ -508,7 +453,7 @@ int tdnnf_align_graphs_dump(const tdnnf_align_graphs *g, int table, int which, i
   if (int rc = align_need_batch(g, who)) return rc;
   TDNNF_REQUIRE(table >= 0 && table <= 4 && which >= 0 && which <= (table < 4 ? 2 : 6), "%stable %d, which %d", who, table, which);
   TDNNF_REQUIRE(table != 3 || g->L > 0, "%sthe graphs carry no labels: there is no table 3", who);
-  if (g->reserved) TDNNF_HIP(hipStreamSynchronize(g->last_stream));
+  if (g->reserved) TDNNF_HIP(hipStreamSynchronize(g->stage.last_stream));
   const int NS = g->state_begin[g->G];
   long long NA = 0;
   for (int n : g->num_arcs) NA += n;
@@ -571,11 +516,7 @@ int tdnnf_align_graphs_create_labelled(int num_graphs, int num_pdfs, const int *
 void tdnnf_align_graphs_destroy(tdnnf_align_graphs *g) {
   if (!g) return;
   if (g->reserved) {  // every device array is a piece of the one allocation
-    (void)hipFree(g->arena);
-    for (int i = 0; i < 2; i++) {
-      if (g->stage_host[i]) (void)hipHostFree(g->stage_host[i]);
-      if (g->stage_event[i]) (void)hipEventDestroy(g->stage_event[i]);
-    }
+    g->stage.destroy();
     delete g;
     return;
   }

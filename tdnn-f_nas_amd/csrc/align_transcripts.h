@@ -92,6 +92,16 @@ inline void transcript_graph_size(int context, int n, const int *opt, int *state
   if (max_in_degree) *max_in_degree = deg;
 }
 
+// One graph's column list from `list` (its arcs' pdfs or labels, any order): the ascending distinct values behind cols, the new end behind
+// begin; their number.
+inline int append_columns(std::vector<int> *list, std::vector<int> *begin, std::vector<int> *cols) {
+  std::sort(list->begin(), list->end());
+  list->erase(std::unique(list->begin(), list->end()), list->end());
+  cols->insert(cols->end(), list->begin(), list->end());
+  begin->push_back((int)cols->size());
+  return (int)list->size();
+}
+
 struct TranscriptPlan {  // a validated batch as tdnnf_align_graphs_assign_transcripts stages and records it
   std::vector<int> state_begin, arc_begin;             // [G + 1]
   std::vector<int> num_arcs, max_in_degree;            // [G]
@@ -141,11 +151,7 @@ inline bool transcripts_plan(const char *who, const TranscriptUnits &u, int G, c
         list.push_back(u.loop_pdf[b]);
       }
     }
-    std::sort(list.begin(), list.end());
-    list.erase(std::unique(list.begin(), list.end()), list.end());
-    p->col_pdfs.insert(p->col_pdfs.end(), list.begin(), list.end());
-    p->col_begin.push_back((int)p->col_pdfs.size());
-    p->num_cols.push_back((int)list.size());
+    p->num_cols.push_back(append_columns(&list, &p->col_begin, &p->col_pdfs));
     int rows = std::max(S, (int)list.size());
     if (labelled) {  // an arc's label is the slot of its destination, and every slot has a state
       for (int k = 0; k < n; k++) p->col_labels.push_back(k);

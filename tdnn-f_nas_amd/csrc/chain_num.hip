@@ -208,6 +208,11 @@ void num_wide_posteriors(const tdnnf_supervision *sp, const MatView &y, const Ma
 
 float chain_supervision_weight(const tdnnf_supervision *sp) { return sp->weight; }
 bool chain_supervision_needs_assign(const tdnnf_supervision *sp) { return sp->ts_reserved && sp->ts_assigns == 0; }
+int sup_need_minibatch(const tdnnf_supervision *sp, const char *who) {
+  TDNNF_REQUIRE(!sp->e2e_reserved || sp->e2e_assigns > 0, "%sthe reserved supervision holds no minibatch yet (tdnnf_supervision_assign_e2e gives it one)", who);
+  TDNNF_REQUIRE(!sp->ts_reserved || sp->ts_assigns > 0, "%sthe reserved supervision holds no minibatch yet (tdnnf_supervision_assign gives it one)", who);
+  return TDNNF_OK;
+}
 // (2) numerator recursion; xent_deriv = xent_regularize * gamma_num, xent objective -> workspace.  Does not touch deriv.
 // In two launchable halves: the recursion needs the chain output only (the trainer starts it beside the denominator, under the
 // xent head's forward pass: 1.35 ms of one wave per sequence walking 2 x 500 dependent frames that the step otherwise waited for),
@@ -328,8 +333,7 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision
                                double *results, tdnnf_mat *deriv, tdnnf_mat *xent_deriv, void *ws, size_t ws_bytes,
                                tdnnf_stream stream) {
   TDNNF_REQUIRE(g && sp && mat_ok(y) && mat_ok(deriv) && results, "chain_objf_and_deriv: bad arguments");
-  TDNNF_REQUIRE(!sp->e2e_reserved || sp->e2e_assigns > 0, "chain_objf_and_deriv: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign_e2e gives it one)");
-  TDNNF_REQUIRE(!sp->ts_reserved || sp->ts_assigns > 0, "chain_objf_and_deriv: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign gives it one)");
+  if (int rc = sup_need_minibatch(sp, "chain_objf_and_deriv: ")) return rc;
   const int B = sp->B, T = sp->T;
   TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P && same_dim(y, deriv), "chain_objf_and_deriv: nnet_output must be (B*T) x num_pdfs, t-major");
   TDNNF_REQUIRE(!xent_deriv || (mat_ok(xent_deriv) && same_dim(y, xent_deriv)), "chain_objf_and_deriv: bad xent_deriv");
@@ -346,8 +350,7 @@ int tdnnf_chain_objf_and_deriv(const tdnnf_den_graph *g, const tdnnf_supervision
 int tdnnf_chain_objf(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, const tdnnf_mat *xent_output, float leaky, float l2_regularize,
                      double *results, void *ws, size_t ws_bytes, tdnnf_stream stream) {
   TDNNF_REQUIRE(g && sp && mat_ok(y) && results, "chain_objf: bad arguments");
-  TDNNF_REQUIRE(!sp->e2e_reserved || sp->e2e_assigns > 0, "chain_objf: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign_e2e gives it one)");
-  TDNNF_REQUIRE(!sp->ts_reserved || sp->ts_assigns > 0, "chain_objf: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign gives it one)");
+  if (int rc = sup_need_minibatch(sp, "chain_objf: ")) return rc;
   const int B = sp->B, T = sp->T;
   TDNNF_REQUIRE(y->rows == B * T && y->cols == g->P, "chain_objf: nnet_output must be (B*T) x num_pdfs, t-major");
   TDNNF_REQUIRE(!xent_output || (mat_ok(xent_output) && same_dim(y, xent_output)), "chain_objf: bad xent_output");
@@ -364,8 +367,7 @@ int tdnnf_chain_objf(const tdnnf_den_graph *g, const tdnnf_supervision *sp, cons
 int tdnnf_chain_numerator_part(const tdnnf_den_graph *g, const tdnnf_supervision *sp, const tdnnf_mat *y, int part, double *results, tdnnf_mat *deriv,
                                tdnnf_mat *xent_deriv, void *ws, size_t ws_bytes, tdnnf_stream stream) {
   TDNNF_REQUIRE(g && sp && mat_ok(y) && y->rows == sp->B * sp->T && y->cols == g->P, "chain_numerator_part: bad arguments");
-  TDNNF_REQUIRE(!sp->e2e_reserved || sp->e2e_assigns > 0, "chain_numerator_part: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign_e2e gives it one)");
-  TDNNF_REQUIRE(!sp->ts_reserved || sp->ts_assigns > 0, "chain_numerator_part: the reserved supervision holds no minibatch yet (tdnnf_supervision_assign gives it one)");
+  if (int rc = sup_need_minibatch(sp, "chain_numerator_part: ")) return rc;
   TDNNF_REQUIRE(ws && ws_bytes >= tdnnf_chain_workspace_bytes(g, sp->B, sp->T), "chain_numerator_part: workspace too small");
   TDNNF_REQUIRE(sp->kind == 0 || sp->num_pdfs <= g->P, "chain_numerator_part: the supervision's num_pdfs %d exceeds the denominator graph's %d", sp->num_pdfs, g->P);
   hipStream_t s = (hipStream_t)stream;

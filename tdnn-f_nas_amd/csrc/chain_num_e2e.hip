@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <numeric>
 
 #include "chain_plan.h"
 #include "num_e2e_kernels.h"
@@ -51,6 +52,40 @@ int e2e_posterior_form(const tdnnf_supervision *sp, int blocks, const MatView &y
   if (LDS) TDNNF_HIP(hipFuncSetAttribute((const void *)num_e2e_posterior_kernel<NT, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((num_e2e_posterior_kernel<NT, LDS>), dim3(blocks, sp->B), dim3(NT), lds, s, sp->e2e_graphs->dev, y, xent_out, sp->B, sp->T, sp->weight, sp->e2e_alpha,
                      sp->e2e_beta, num_lp, deriv, xent_deriv, xent_scale, do_xent ? 1 : 0, sp->xent_part, sp->max_states_per_seq);
+  return TDNNF_OK;
+}
+
+// What both assigns of a reserved end-to-end supervision check first, under the call's name `who`: the handle, the arguments (have_arrays:
+// no array the call itself reads is null) and the two capacities beside the graph set's own.
+int e2e_assign_check(const char *who, const tdnnf_supervision *sp, bool have_arrays, int B, int T) {
+  TDNNF_REQUIRE(sp && sp->kind == 1 && sp->e2e_reserved, "%snot a supervision of tdnnf_supervision_reserve_e2e", who);
+  TDNNF_REQUIRE(have_arrays && B > 0 && T > 0, "%sbad arguments", who);
+  std::string err;
+  TDNNF_REQUIRE(within_capacity(who, B, "sequences", sp->e2e_max_sequences, &err) && within_capacity(who, T, "frames", sp->e2e_max_frames, &err), "%s", err.c_str());
+  return TDNNF_OK;
+}
+
+// The rest of both: the recursion's launch form from the minibatch's largest graph, then `assign`, the graph set's assign, and what follows
+// from its return value.  A refusal left the graph set and so the supervision on the previous minibatch; an error of the runtime left the
+// graph set with no batch (assign_stage.h), and the supervision then holds no minibatch either.  The totals are the graph set's.
+template <class Assign>
+int e2e_assign_finish(const char *who, tdnnf_supervision *sp, int B, int T, float weight, int max_states, Assign assign) {
+  AlignFormPlan form;
+  std::string err;
+  TDNNF_REQUIRE(align_form_plan(max_states, sp->num_pdfs, options().align_form, false, kLdsBudget, who, &form, &err), "%s", err.c_str());
+  const tdnnf_align_graphs *g = sp->e2e_graphs;
+  if (int rc = assign()) {
+    if (g->assigns == 0) sp->e2e_assigns = 0;
+    return rc;
+  }
+  sp->B = B;
+  sp->T = T;
+  sp->weight = weight;
+  sp->num_states = g->state_begin[B];
+  sp->num_arcs = std::accumulate(g->num_arcs.begin(), g->num_arcs.end(), 0);
+  sp->max_states_per_seq = sp->max_states_per_frame = max_states;
+  sp->e2e_form = form;
+  sp->e2e_assigns++;
   return TDNNF_OK;
 }
 
@@ -158,66 +193,30 @@ int tdnnf_supervision_assign_e2e(tdnnf_supervision *sp, int B, int T, const int 
                                  const int *arc_dst, const int *arc_pdf, const float *arc_logprob, const float *initial_logprob, const float *final_logprob,
                                  float weight, tdnnf_stream stream) {
   const char *who = "supervision_assign_e2e: ";
-  TDNNF_REQUIRE(sp && sp->kind == 1 && sp->e2e_reserved, "%snot a supervision of tdnnf_supervision_reserve_e2e", who);
-  TDNNF_REQUIRE(B > 0 && T > 0 && seq_state_begin && seq_arc_begin, "%sbad arguments", who);
-  TDNNF_REQUIRE(B <= sp->e2e_max_sequences, "%s%d sequences exceed the capacity max_sequences = %d by %d", who, B, sp->e2e_max_sequences,
-                B - sp->e2e_max_sequences);
-  TDNNF_REQUIRE(T <= sp->e2e_max_frames, "%s%d frames exceed the capacity max_frames = %d by %d", who, T, sp->e2e_max_frames, T - sp->e2e_max_frames);
-  // the recursion's launch form, from this minibatch's largest graph (the graph set's assign refuses an array that is not what it seems)
+  if (int rc = e2e_assign_check(who, sp, seq_state_begin && seq_arc_begin, B, T)) return rc;
+  // this minibatch's largest graph (the graph set's assign refuses an array that is not what it seems)
   int max_states = 0;
   for (int s = 0; s < B; s++) max_states = std::max(max_states, seq_state_begin[s + 1] - seq_state_begin[s]);
-  AlignFormPlan form;
-  std::string err;
-  TDNNF_REQUIRE(align_form_plan(max_states, sp->num_pdfs, options().align_form, false, kLdsBudget, who, &form, &err), "%s", err.c_str());
-  // (validates what tdnnf_align_graphs_create validates and the capacities max_states and max_arcs; a refusal leaves everything as it was)
-  int rc = tdnnf_align_graphs_assign(sp->e2e_graphs, B, seq_state_begin, seq_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob, final_logprob,
-                                     nullptr, stream);
-  if (rc) return rc;
-  sp->B = B;
-  sp->T = T;
-  sp->weight = weight;
-  sp->num_states = seq_state_begin[B];
-  sp->num_arcs = seq_arc_begin[B];
-  sp->max_states_per_seq = sp->max_states_per_frame = max_states;
-  sp->e2e_form = form;
-  sp->e2e_assigns++;
-  return TDNNF_OK;
+  // (the assign validates what tdnnf_align_graphs_create validates and the capacities max_states and max_arcs; a refusal leaves everything as it was)
+  return e2e_assign_finish(who, sp, B, T, weight, max_states, [&] {
+    return tdnnf_align_graphs_assign(sp->e2e_graphs, B, seq_state_begin, seq_arc_begin, arc_src, arc_dst, arc_pdf, arc_logprob, initial_logprob, final_logprob, nullptr, stream);
+  });
 }
 
 int tdnnf_supervision_assign_e2e_transcripts(tdnnf_supervision *sp, const tdnnf_unit_set *units, int B, int T, const int *slot_begin, const int *slot_unit,
                                              const int *slot_optional, float weight, tdnnf_stream stream) {
   const char *who = "supervision_assign_e2e_transcripts: ";
-  TDNNF_REQUIRE(sp && sp->kind == 1 && sp->e2e_reserved, "%snot a supervision of tdnnf_supervision_reserve_e2e", who);
-  TDNNF_REQUIRE(units && B > 0 && T > 0, "%sbad arguments", who);
-  TDNNF_REQUIRE(B <= sp->e2e_max_sequences, "%s%d sequences exceed the capacity max_sequences = %d by %d", who, B, sp->e2e_max_sequences,
-                B - sp->e2e_max_sequences);
-  TDNNF_REQUIRE(T <= sp->e2e_max_frames, "%s%d frames exceed the capacity max_frames = %d by %d", who, T, sp->e2e_max_frames, T - sp->e2e_max_frames);
-  // the recursion's launch form, from this minibatch's largest graph: the closed forms of align_transcripts.h, O(slots)
+  if (int rc = e2e_assign_check(who, sp, units != nullptr, B, T)) return rc;
+  // this minibatch's largest graph: the closed forms of align_transcripts.h, O(slots)
   std::string err;
   TDNNF_REQUIRE(transcripts_validate(who, units->host, B, slot_begin, slot_unit, slot_optional, &err), "%s", err.c_str());
   int max_states = 0;
-  long long num_states = 0, num_arcs = 0;
-  for (int s = 0; s < B; s++) {
-    int S, A;
+  for (int s = 0, S, A; s < B; s++) {
     transcript_graph_size(units->host.context, slot_begin[s + 1] - slot_begin[s], slot_optional + slot_begin[s], &S, &A);
     max_states = std::max(max_states, S);
-    num_states += S;
-    num_arcs += A;
   }
-  AlignFormPlan form;
-  TDNNF_REQUIRE(align_form_plan(max_states, sp->num_pdfs, options().align_form, false, kLdsBudget, who, &form, &err), "%s", err.c_str());
-  // (the capacities max_states and max_arcs and the unit set's num_pdfs; a refusal leaves everything as it was)
-  int rc = tdnnf_align_graphs_assign_transcripts(sp->e2e_graphs, units, B, slot_begin, slot_unit, slot_optional, stream);
-  if (rc) return rc;
-  sp->B = B;
-  sp->T = T;
-  sp->weight = weight;
-  sp->num_states = (int)num_states;
-  sp->num_arcs = (int)num_arcs;
-  sp->max_states_per_seq = sp->max_states_per_frame = max_states;
-  sp->e2e_form = form;
-  sp->e2e_assigns++;
-  return TDNNF_OK;
+  // (the assign checks the capacities max_states and max_arcs and the unit set's num_pdfs; a refusal leaves everything as it was)
+  return e2e_assign_finish(who, sp, B, T, weight, max_states, [&] { return tdnnf_align_graphs_assign_transcripts(sp->e2e_graphs, units, B, slot_begin, slot_unit, slot_optional, stream); });
 }
 
 int tdnnf_supervision_kind(const tdnnf_supervision *sp) {

@@ -15,36 +15,15 @@ namespace tdnnf {
 
 struct SupReserved {
   int max_sequences, max_frames, max_states, max_arcs;
-  void *arena;  // every device array of the supervision, the build's scratch and the device staging
-  size_t arena_bytes;
   SupBuildDev build;
-  char *stage_dev;
-  size_t stage_bytes;
-  char *stage_host[2];  // pinned; staging k uses buffer k & 1 and waits for staging k - 2's copies out of it
-  hipEvent_t stage_event[2];
-  bool stage_used[2];
-  int stagings;  // assigns that reached the staging, the failed ones included: the buffer to use next
-  hipStream_t last_stream;
-  int allocs, allocs_at_reserve;  // device and pinned allocations made for the handle; since the end of reserve
+  AssignStage stage;  // the one allocation (every device array of the supervision, the build's scratch), the staging of the assigns (assign_stage.h)
+  int allocs_at_reserve;  // device and pinned allocations made for the handle by the end of reserve
 };
 
 namespace {
 
-// Hands out pieces of the handle's one allocation, 256 bytes apart at least; with a null base it only counts.
-struct SupCarve {
-  char *base;
-  size_t at;
-  template <class T>
-  T *take(size_t n) {
-    at = (at + 255) & ~(size_t)255;
-    T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += sizeof(T) * std::max<size_t>(n, 1);
-    return p;
-  }
-};
-
 // Every device array of a reserved supervision at the capacities, out of c.  Run once with a null base for the size.
-void sup_reserve_layout(tdnnf_supervision *sp, SupCarve *c) {
+void sup_reserve_layout(tdnnf_supervision *sp, Carve *c) {
   SupReserved *r = sp->ts;
   const size_t Bc = r->max_sequences, Tc = r->max_frames, Sc = r->max_states, Ac = r->max_arcs;
   SupBuildDev &b = r->build;
@@ -74,7 +53,7 @@ void sup_reserve_layout(tdnnf_supervision *sp, SupCarve *c) {
     b.arcpos[t] = c->take<int>(Ac);
   }
   b.out_src = c->take<int>(Ac);
-  r->stage_dev = c->take<char>(r->stage_bytes);
+  r->stage.dev = c->take<char>(r->stage.bytes);
   b.cap_states = r->max_states;
   b.cap_arcs = r->max_arcs;
   b.seq_state_begin = sp->seq_state_begin;
@@ -108,11 +87,7 @@ int sup_build_launch(const SupBuildDev &b, hipStream_t s) {
 void sup_reserved_free(tdnnf_supervision *sp) {
   SupReserved *r = sp->ts;
   if (!r) return;
-  (void)hipFree(r->arena);
-  for (int i = 0; i < 2; i++) {
-    if (r->stage_host[i]) (void)hipHostFree(r->stage_host[i]);
-    if (r->stage_event[i]) (void)hipEventDestroy(r->stage_event[i]);
-  }
+  r->stage.destroy();
   delete r;
   sp->ts = nullptr;
 }
@@ -130,39 +105,25 @@ int tdnnf_supervision_reserve(int max_sequences, int max_frames, int max_states,
   TDNNF_REQUIRE(max_states >= max_sequences, "%smax_states %d is below max_sequences %d: every sequence has a state", who, max_states, max_sequences);
   // (the build's second launch has a wave per (sequence, frame): 64 * sequences * frames threads, below 2^32)
   TDNNF_REQUIRE((long long)max_sequences * ((long long)max_frames + 2) <= 1ll << 25, "%smax_sequences * (max_frames + 2) must not exceed 2^25", who);
-  tdnnf_supervision *sp = new tdnnf_supervision();
-  memset(sp, 0, sizeof(*sp));
+  tdnnf_supervision *sp = new tdnnf_supervision();  // (both zeroed)
   SupReserved *r = new SupReserved();
-  memset(r, 0, sizeof(*r));
   sp->ts = r;
   sp->ts_reserved = true;
   r->max_sequences = max_sequences;
   r->max_frames = max_frames;
   r->max_states = max_states;
   r->max_arcs = max_arcs;
-  r->stage_bytes = sup_stage_bytes(max_sequences, max_frames, max_states, max_arcs);
-  SupCarve size{nullptr, 0};
-  sup_reserve_layout(sp, &size);
-  r->arena_bytes = size.at;
-  hipError_t e = hipMalloc(&r->arena, r->arena_bytes);
-  if (e == hipSuccess) r->allocs++;
-  for (int i = 0; i < 2 && e == hipSuccess; i++)
-    if ((e = hipHostMalloc((void **)&r->stage_host[i], r->stage_bytes, hipHostMallocDefault)) == hipSuccess) {
-      r->allocs++;
-      e = hipEventCreateWithFlags(&r->stage_event[i], hipEventDisableTiming);
-    }
-  if (e != hipSuccess) {
+  if (int rc = r->stage.create("supervision_reserve: allocation", sup_stage_bytes(max_sequences, max_frames, max_states, max_arcs),
+                               [sp](Carve *c) { sup_reserve_layout(sp, c); })) {
     tdnnf_supervision_destroy(sp);
-    return hip_status(e, "supervision_reserve: allocation");
+    return rc;
   }
-  SupCarve carve{static_cast<char *>(r->arena), 0};
-  sup_reserve_layout(sp, &carve);
   // (a created supervision's l2_part starts at zero; every reader writes it first)
-  if ((e = hipMemset(sp->l2_part, 0, sizeof(double) * kFinishL2Parts)) != hipSuccess) {
+  if (hipError_t e = hipMemset(sp->l2_part, 0, sizeof(double) * kFinishL2Parts)) {
     tdnnf_supervision_destroy(sp);
     return hip_status(e, "supervision_reserve: hipMemset");
   }
-  r->allocs_at_reserve = r->allocs;
+  r->allocs_at_reserve = r->stage.device_allocs + r->stage.pinned_allocs;
   *out = sp;
   return TDNNF_OK;
 }
@@ -182,24 +143,13 @@ int tdnnf_supervision_assign(tdnnf_supervision *sp, int B, int T, const int *seq
                 "%s", err.c_str());
   TDNNF_REQUIRE(sup_check_capacity(who, B, T, p, r->max_sequences, r->max_frames, r->max_states, r->max_arcs, &err), "%s", err.c_str());
   sup_widths(B, T, arc_src, &p);
-  const size_t NS = p.num_states, NA = p.num_arcs, nfsb = p.frame_state_begin.size();
-  const size_t need = sizeof(int) * (2 * ((size_t)B + 1) + nfsb + 2 * NS + 4 * NA);
-  TDNNF_REQUIRE(need <= r->stage_bytes, "%sinternal: the minibatch needs %zu bytes of staging, the supervision has %zu", who, need, r->stage_bytes);
+  const size_t NS = p.num_states, NA = p.num_arcs;
 
-  // staging: the one wait of this path, for the copies of the assign before last out of the buffer that is now overwritten
-  const int slot = r->stagings & 1;
-  if (r->stage_used[slot]) TDNNF_HIP(hipEventSynchronize(r->stage_event[slot]));
-  char *host = r->stage_host[slot];
+  StagePacker pk;
+  if (int rc = r->stage.begin(&pk)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  size_t at = 0;
-  const auto stage = [&](const void *v, size_t n) {  // n 4-byte elements; the offset is the same in the device staging
-    const size_t begin = at;
-    if (n) memcpy(host + begin, v, sizeof(int) * n);
-    at += sizeof(int) * n;
-    return begin;
-  };
   SupBuildDev &b = r->build;
-  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(r->stage_dev + stage(v, n)); };
+  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(r->stage.dev + pk.put(v, n)); };
   b.B = B;
   b.T = T;
   b.seq_arc_begin = raw(seq_arc_begin, (size_t)B + 1);
@@ -207,26 +157,19 @@ int tdnnf_supervision_assign(tdnnf_supervision *sp, int B, int T, const int *seq
   b.dst = raw(arc_dst, NA);
   b.pdf = raw(arc_pdf, NA);
   b.lp_bits = raw(arc_logprob, NA);
-  const size_t raw_bytes = at;
+  const size_t raw_bytes = pk.at;
   // the arrays that go to the supervision's own device arrays as they are
-  const struct {
-    void *to;
-    size_t from, bytes;
-  } copies[4] = {{sp->seq_state_begin, stage(seq_state_begin, (size_t)B + 1), sizeof(int) * ((size_t)B + 1)},
-                 {sp->state_time, stage(state_time, NS), sizeof(int) * NS},
-                 {sp->final_logprob, stage(final_logprob, NS), sizeof(float) * NS},
-                 {sp->frame_state_begin, stage(p.frame_state_begin.data(), nfsb), sizeof(int) * nfsb}};
+  pk.put_to(sp->seq_state_begin, seq_state_begin, (size_t)B + 1);
+  pk.put_to(sp->state_time, state_time, NS);
+  pk.put_to(sp->final_logprob, final_logprob, NS);
+  pk.put_to(sp->frame_state_begin, p.frame_state_begin.data(), p.frame_state_begin.size());
+  TDNNF_REQUIRE(pk.fits(), "%sinternal: the minibatch needs %zu bytes of staging, the supervision has %zu", who, pk.at, pk.size);
   // From here on the device tables are being overwritten.  A refusal above left the previous minibatch; an error of the runtime below
-  // (a copy or a launch that fails) leaves NO minibatch: the handle is refused like a fresh one until an assign succeeds.
+  // (a copy or a launch that fails) leaves NO minibatch: the handle is refused like a fresh one until an assign succeeds (assign_stage.h).
   const int assigns_before = sp->ts_assigns;
   sp->ts_assigns = 0;
-  r->stagings++;
-  TDNNF_HIP(hipMemcpyAsync(r->stage_dev, host, raw_bytes, hipMemcpyHostToDevice, s));
-  for (const auto &c : copies)
-    if (c.bytes) TDNNF_HIP(hipMemcpyAsync(c.to, host + c.from, c.bytes, hipMemcpyHostToDevice, s));
-  TDNNF_HIP(hipEventRecord(r->stage_event[slot], s));
-  r->stage_used[slot] = true;
-  if (int rc = sup_build_launch(b, s)) return rc;
+  int rc;
+  if ((rc = r->stage.submit(pk, raw_bytes, s)) || (rc = sup_build_launch(b, s))) return rc;
 
   sp->B = B;
   sp->T = T;
@@ -237,7 +180,6 @@ int tdnnf_supervision_assign(tdnnf_supervision *sp, int B, int T, const int *seq
   sp->max_states_per_frame = p.max_states_per_frame;
   sp->max_arcs_per_frame = p.max_arcs_per_frame;
   sp->wide = p.wide;
-  r->last_stream = s;
   sp->ts_assigns = assigns_before + 1;
   return TDNNF_OK;
 }
@@ -252,8 +194,8 @@ int tdnnf_supervision_capacity(const tdnnf_supervision *sp, int *max_sequences, 
   if (max_states) *max_states = r->max_states;
   if (max_arcs) *max_arcs = r->max_arcs;
   if (assigns) *assigns = sp->ts_assigns;
-  if (allocations_since_reserve) *allocations_since_reserve = r->allocs - r->allocs_at_reserve;
-  if (device_bytes) *device_bytes = (long long)r->arena_bytes;
+  if (allocations_since_reserve) *allocations_since_reserve = r->stage.device_allocs + r->stage.pinned_allocs - r->allocs_at_reserve;
+  if (device_bytes) *device_bytes = (long long)r->stage.arena_bytes;
   return TDNNF_OK;
 }
 
@@ -261,7 +203,7 @@ int tdnnf_supervision_dump(const tdnnf_supervision *sp, const char *table, void 
   const char *who = "supervision_dump: ";
   TDNNF_REQUIRE(sp && table && count, "%snull supervision, table name or count", who);
   TDNNF_REQUIRE(sp->kind == 0, "%san end-to-end supervision has none of these tables (tdnnf_align_graphs_dump shows a graph set's)", who);
-  TDNNF_REQUIRE(!sp->ts_reserved || sp->ts_assigns > 0, "%sthe reserved supervision holds no minibatch yet (tdnnf_supervision_assign gives it one)", who);
+  if (int rc = sup_need_minibatch(sp, who)) return rc;
   const long long NS = sp->num_states, NA = sp->num_arcs, pf = sp->pf_src ? NA : 0;
   const struct {
     const char *name;
@@ -290,7 +232,7 @@ int tdnnf_supervision_dump(const tdnnf_supervision *sp, const char *table, void 
     if (!out) return TDNNF_OK;
     TDNNF_REQUIRE(capacity >= t.n, "%sout holds %lld elements, table %s has %lld", who, capacity, table, t.n);
     TDNNF_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    if (sp->ts && sp->ts->last_stream != static_cast<hipStream_t>(stream)) TDNNF_HIP(hipStreamSynchronize(sp->ts->last_stream));
+    if (sp->ts && sp->ts->stage.last_stream != static_cast<hipStream_t>(stream)) TDNNF_HIP(hipStreamSynchronize(sp->ts->stage.last_stream));
     if (t.n) TDNNF_HIP(hipMemcpy(out, t.data, 4 * (size_t)t.n, hipMemcpyDeviceToHost));
     return TDNNF_OK;
   }

@@ -11,6 +11,8 @@
 #include <string>
 #include <vector>
 
+#include "assign_stage.h"
+
 namespace tdnnf {
 
 inline std::string sup_message(const char *fmt, const char *who, int a = 0, int b = 0, int c = 0) {
@@ -85,23 +87,8 @@ inline bool sup_validate(const char *who, bool have_out, int B, int T, const int
 // The four capacities of a reserved supervision against a validated minibatch; false with *err naming the capacity, its value and the excess.
 inline bool sup_check_capacity(const char *who, int B, int T, const SupPlan &p, int max_sequences, int max_frames, int max_states, int max_arcs,
                                std::string *err) {
-  if (B > max_sequences) {
-    *err = sup_message("%s%d sequences exceed the capacity max_sequences = %d by %d", who, B, max_sequences, B - max_sequences);
-    return false;
-  }
-  if (T > max_frames) {
-    *err = sup_message("%s%d frames exceed the capacity max_frames = %d by %d", who, T, max_frames, T - max_frames);
-    return false;
-  }
-  if (p.num_states > max_states) {
-    *err = sup_message("%s%d states exceed the capacity max_states = %d by %d", who, p.num_states, max_states, p.num_states - max_states);
-    return false;
-  }
-  if (p.num_arcs > max_arcs) {
-    *err = sup_message("%s%d arcs exceed the capacity max_arcs = %d by %d", who, p.num_arcs, max_arcs, p.num_arcs - max_arcs);
-    return false;
-  }
-  return true;
+  return within_capacity(who, B, "sequences", max_sequences, err) && within_capacity(who, T, "frames", max_frames, err) &&
+         within_capacity(who, p.num_states, "states", max_states, err) && within_capacity(who, p.num_arcs, "arcs", max_arcs, err);
 }
 
 // The widths of a minibatch that sup_validate accepted, as tdnnf_supervision_create finds them from its arc tables: the widest frame of any

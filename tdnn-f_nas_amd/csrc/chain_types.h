@@ -29,6 +29,9 @@ struct tdnnf_supervision;
 namespace tdnnf {
 // frees what a reserved time-synchronous supervision holds (tdnnf_supervision_destroy, chain_graph.hip)
 __attribute__((visibility("hidden"))) void sup_reserved_free(tdnnf_supervision *sp);
+// the refusal every entry gives a reserved supervision of either kind that holds no minibatch (none yet, or an assign failed behind its
+// first enqueued copy).  who: the prefix of the message, the call's name (chain_num.hip)
+__attribute__((visibility("hidden"))) int sup_need_minibatch(const tdnnf_supervision *sp, const char *who);
 }
 
 struct tdnnf_den_graph {

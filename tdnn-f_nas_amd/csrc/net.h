@@ -272,6 +272,7 @@ inline int ldpad(int cols) { return (cols + 31) & ~31; }
 inline tdnnf_mat M(float *p, int rows, int cols) { return tdnnf_mat{p, rows, cols, ldpad(cols)}; }
 inline int N_of(const Grid &g, int B) { return g.n * B; }
 // Bump allocator over one device allocation, 256-byte aligned; with base == nullptr it only sizes (take() returns null)
+// (the reserved handles' Carve, assign_stage.h, is the same idea; it pads a zero-length piece to one element, this one must not: the net's layout stays)
 struct Arena {
   size_t off = 0;
   char *base = nullptr;

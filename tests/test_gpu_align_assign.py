@@ -370,3 +370,46 @@ def test_other_refusals(abi, sets):
     refused(abi, lambda: res.assign(broken(final=lambda a: np.full_like(a, NINF))), "align_graphs_assign: graph 1 has no final state")
     assert res.capacity()["assigns"] == 1 and res.G == G
     same_tables(made, res)
+
+
+def test_refusals_take_no_turn_of_the_staging_and_both_assigns_share_it(pkg, abi, sets):
+    """one labelled handle, three rounds of: assign A and a best path, a refused assign, assign_transcripts B and a best path, a refused
+    assign_transcripts, assign A and a best path -- nothing synchronised, nothing read until the end.  Three assigns a round: the two pinned
+    staging buffers change hands with every assign that succeeds, of either kind, and with none that is refused, or a buffer would be
+    written again while its copies are still to run and some output below would be another batch's"""
+    from tests import transcript_graphs_ref as ref
+    P, U = 40, 6
+    A = sets["labels-unit"][0]
+    us = pkg.synth.make_unit_set(U, context=1, seed=5, distinct=False, P=P)
+    units = abi.UnitSet(us["entry_pdf"], us["loop_pdf"], us["loop_logprob"], us["leave_logprob"], us["P"], us["take_logprob"], us["skip_logprob"])
+    transcripts = [(np.asarray([1, 2, 3], np.int32), np.asarray([0, 1, 0], np.int32)), (np.asarray([4, 5], np.int32), np.asarray([1, 0], np.int32))]
+    B = [ref.transcript_graph(us, u, o) for u, o in transcripts]
+    L = max(num_labels(A), num_labels(B))
+    cap = [max(v) for v in zip(totals(A), totals(B))]
+    one_arc_over = [relabelled(in_degrees([cap[2] + 1, 0], P, 1), lambda g: g["pdf"] % L)]
+    assert totals(one_arc_over) == (1, 2, cap[2] + 1) and cap[1] >= 2
+    one_slot_over = [(np.arange(L + 1, dtype=np.int32) % U, np.zeros(L + 1, np.int32))]
+    fa, fb = frames_for(A, 13), [12, 12]
+    (ya, ra), (yb, rb) = nnet_output(A, P, fa, 14), nnet_output(B, P, fb, 15)
+
+    def paths(ag, y, frames, rows):
+        return list(ag.best_path(y, frames, rows, states=True)) + list(ag.best_path_labels(y, frames, rows, states=True))
+
+    want_a = paths(abi.AlignGraphs(A, num_pdfs=P, num_labels=L), ya, fa, ra)
+    want_b = paths(abi.AlignGraphs(B, num_pdfs=P, num_labels=L), yb, fb, rb)
+    res = abi.AlignGraphs.reserve(cap[0], P, cap[1], cap[2], num_labels=L)
+    torch.cuda.synchronize()
+    got = []
+    for _ in range(3):
+        res.assign(A)
+        got.append((want_a, paths(res, ya, fa, ra)))
+        refused(abi, lambda: res.assign(one_arc_over), "align_graphs_assign: ", "max_arcs", "by 1")
+        res.assign_transcripts(units, transcripts)
+        got.append((want_b, paths(res, yb, fb, rb)))
+        refused(abi, lambda: res.assign_transcripts(units, one_slot_over), "align_graphs_assign_transcripts: ", "num_labels = %d" % L, "short by 1")
+        res.assign(A)
+        got.append((want_a, paths(res, ya, fa, ra)))
+    for want, have in got:
+        same_outputs(want, have)
+    assert (want_a[2][:, 1] == 1).all() and (want_b[2][:, 1] == 1).all()  # every utterance has a path: the equal outputs are not all "no path"
+    assert res.capacity()["assigns"] == 9 and res.capacity()["device_allocs"] == 1
