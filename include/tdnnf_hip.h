@@ -622,6 +622,48 @@ int tdnnf_transcript_graph_sizes(const tdnnf_unit_set *, int num_transcripts, co
                                  const int *slot_optional, int *states_out, int *arcs_out);
 int tdnnf_align_graphs_assign_transcripts(tdnnf_align_graphs *, const tdnnf_unit_set *, int num_transcripts, const int *slot_begin,
                                           const int *slot_unit, const int *slot_optional, tdnnf_stream stream);
+/* ALIGNMENT SUPERVISIONS: the next minibatch of a supervision of tdnnf_supervision_reserve compiled on the device from alignments and a
+   frame tolerance -- the supervision regular LF-MMI trains on: an alignment whose unit boundaries may each move by +- tolerance frames.
+   The caller hands over (unit, start frame) pairs and never builds a state or an arc array; the alignment may be this library's
+   (tdnnf_align_graphs_assign_transcripts on a labelled handle, then the run lengths of tdnnf_align_best_path_labels).
+   Sequence s owns the entries [unit_begin[s], unit_begin[s + 1]) of `units` and `starts` (unit_begin[0] = 0): n >= 1 units u_0 .. u_n-1
+   of the unit set (context 0 or 1) that start at the OUTPUT frames b_0 = 0 < b_1 < ... < b_n-1 < T = frames_per_sequence; unit k covers
+   the frames [b_k, b_k+1).  Refused with TDNNF_EINVAL naming the sequence and the unit's position: a sequence without a unit, a unit
+   outside [0, num_units), b_0 != 0, a start that is not behind the one before it, a start >= T; and a negative tolerance.
+   The lattice of one sequence, with tol = tolerance:
+     windows  lo_k = max(b_k - tol, 0), hi_k = min(b_k + tol, T - 1); lo_0 = hi_0 = 0; tightened from the left, lo_k = max(lo_k, lo_k-1 + 1),
+              and from the right against the virtual lo_n = hi_n = T, hi_k = min(hi_k, hi_k+1 - 1): every unit keeps a frame, and
+              lo_k <= b_k <= hi_k, so the alignment itself is always a path.  Unit k may be entered at any frame of [lo_k, hi_k].
+     states   the start, at time 0; E(t, k) for t in [lo_k + 1, hi_k + 1]: unit k was entered at frame t - 1; L(t, k) for t in
+              [lo_k + 2, hi_k+1]: frame t - 1 was a later frame of unit k.  Ordered by time, within one time all E by k, then all L by k.
+     arcs     start -> E(1, 0) with the entry pdf at (-1, u_0).  From X(t, k), X either kind: the enter arc to E(t + 1, k + 1) with the entry
+              pdf at (u_k, u_k+1), if k + 1 < n and lo_k+1 <= t <= hi_k+1; the stay arc to L(t + 1, k) with the loop pdf at
+              (u_k-1 or -1, u_k), if t + 1 <= hi_k+1.  (Context 0 reads both tables at the unit alone.)  Ordered by (source, destination);
+              a state has 0, 1 or 2.  Every arc_logprob is 0.
+     final    0 on the time-T states of unit n - 1, -inf elsewhere.
+   This is Kaldi's supervision FST, which is unweighted: the unit set's loop_logprob, leave_logprob, take_logprob and skip_logprob are NOT
+   used here.  tolerance 0 gives the one path of the alignment (T + 1 states); a tolerance >= T lets every boundary go anywhere.
+   tdnnf_alignment_supervision_sizes is host-only: the states and arcs of every sequence's lattice (either out-pointer may be NULL), for
+   sizing a reserve; it refuses what the assign refuses with the same messages under its own name.
+   tdnnf_supervision_assign_alignments is tdnnf_supervision_assign from alignments: supervisions of tdnnf_supervision_reserve only (an
+   end-to-end or a created supervision is refused, TDNNF_EINVAL).  The host works in O(units + sequences * (frames + 2)): the windows, and
+   from the closed form of a frame (csrc/chain_sup_alignment.h) the begins, frame_state_begin, the counts, the widths and `wide` -- what
+   tdnnf_supervision_assign finds on the lattice's arrays -- then the four capacities, named with their excess as assign names them, all
+   before anything is written: a refused call leaves the previous minibatch.  It stages 12 bytes a unit where assign stages 16 bytes an arc
+   and 8 a state, inside the staging tdnnf_supervision_reserve made, and enqueues on `stream` the copies, ONE kernel that writes state_time,
+   final_logprob and the arcs (csrc/chain_sup_compile_kernels.h) and the two build kernels of tdnnf_supervision_assign, unchanged: the
+   tables are the bytes an assign of the lattice's arrays builds, and the objective's bits with them.  No allocation, no free, no
+   device-wide or stream-wide wait; the one host wait there can be is for the staging copy of the assign before last.  Stream order,
+   tdnnf_supervision_capacity's `assigns` and the failure rule are tdnnf_supervision_assign's (a refusal leaves the previous minibatch, an
+   error of the runtime none); both kinds of assign may alternate on one handle, on the one pair of staging buffers.
+   Not built: alternative unit sequences (pronunciations), frame-subsampling of a frame-rate alignment (the starts are output frames),
+   composition with a normalisation FST (the lattice's paths are not restricted to the denominator graph's), capture into a HIP graph,
+   input that stays on the device (the alignment comes from host arrays). */
+int tdnnf_alignment_supervision_sizes(const tdnnf_unit_set *, int num_sequences, int frames_per_sequence, const int *unit_begin, const int *units,
+                                      const int *starts, int tolerance, int *states_out, int *arcs_out);
+int tdnnf_supervision_assign_alignments(tdnnf_supervision *, const tdnnf_unit_set *, int num_sequences, int frames_per_sequence,
+                                        const int *unit_begin, const int *units, const int *starts, int tolerance, float weight,
+                                        tdnnf_stream stream);
 /* diagnostics (tests): a copy-out of the device arrays of a created or an assigned handle, as ints, after waiting for the stream of the last
    assign.  table 0 by destination, 1 by source, 2 by pdf, 3 by label (labelled handles): which 0 the slots, 1 the heavy-row descriptors,
    2 the arc entries, 4 ints each.  table 4: which 0 the graph descriptors (14 ints a graph), 1 the by-label ranges (4 ints a graph), 2 the

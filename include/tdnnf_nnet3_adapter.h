@@ -454,6 +454,22 @@ inline void SupervisionAssignE2eTranscripts(tdnnf_supervision *sup, const tdnnf_
   Check(tdnnf_supervision_assign_e2e_transcripts(sup, units, num_sequences, frames_per_sequence, slot_begin, slot_unit, slot_optional, weight, stream));
 }
 
+// Alignment supervisions (tdnnf_hip.h, "ALIGNMENT SUPERVISIONS"): SupervisionAssign from alignments, the lattices of regular LF-MMI -- every
+// unit boundary free to move by +-tolerance output frames -- compiled on the device into a supervision of SupervisionReserve.  Sequence s is
+// the entries [unit_begin[s], unit_begin[s + 1]) of units / starts: its units (phones, of the unit set) and the output frames they start
+// at, the first 0 (an alignment at the frame rate is subsampled by the caller).  AlignmentSupervisionSizes: the states and arcs of every
+// sequence's lattice on the host, for the reserve (either out-pointer may be null).  Both throw on a bad alignment, naming the sequence and
+// the unit's position; the assign also on a minibatch beyond a capacity, and the supervision then still holds its previous minibatch.
+inline void AlignmentSupervisionSizes(const tdnnf_unit_set *units, int num_sequences, int frames_per_sequence, const int *unit_begin,
+                                      const int *unit, const int *starts, int tolerance, int *states_out, int *arcs_out) {
+  Check(tdnnf_alignment_supervision_sizes(units, num_sequences, frames_per_sequence, unit_begin, unit, starts, tolerance, states_out, arcs_out));
+}
+inline void SupervisionAssignAlignments(tdnnf_supervision *sup, const tdnnf_unit_set *units, int num_sequences, int frames_per_sequence,
+                                        const int *unit_begin, const int *unit, const int *starts, int tolerance, float weight,
+                                        tdnnf_stream stream) {
+  Check(tdnnf_supervision_assign_alignments(sup, units, num_sequences, frames_per_sequence, unit_begin, unit, starts, tolerance, weight, stream));
+}
+
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance

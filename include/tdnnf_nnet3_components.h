@@ -2096,6 +2096,26 @@ inline void AssignEnd2EndSupervisionFromTranscripts(tdnnf_supervision *supervisi
                                                  slot_unit.data(), slot_optional.data(), weight, Hooks().stream);
 }
 
+// The supervision of regular LF-MMI from ALIGNMENTS (tdnnf_hip.h, "ALIGNMENT SUPERVISIONS"): the lattices in which every unit boundary may
+// move by +-tolerance output frames, compiled on the device into a supervision of ReserveSupervision on the hooks' stream.  Sequence s is the
+// entries [unit_begin[s], unit_begin[s + 1]) of units / starts: its phones and the output frames they start at, the first 0.
+// AlignmentSupervisionSizes: the states and arcs of every sequence's lattice, on the host, for sizing the reserve.
+inline void AlignmentSupervisionSizes(const tdnnf_unit_set *units, int32 frames_per_sequence, const std::vector<int32> &unit_begin,
+                                      const std::vector<int32> &unit, const std::vector<int32> &starts, int32 tolerance, std::vector<int32> *states,
+                                      std::vector<int32> *arcs) {
+  const int32 num_sequences = unit_begin.empty() ? 0 : static_cast<int32>(unit_begin.size()) - 1;
+  states->assign(num_sequences > 0 ? num_sequences : 0, 0);
+  arcs->assign(states->size(), 0);
+  tdnnf_adapter::AlignmentSupervisionSizes(units, num_sequences, frames_per_sequence, unit_begin.data(), unit.data(), starts.data(), tolerance,
+                                           states->data(), arcs->data());
+}
+inline void AssignSupervisionFromAlignments(tdnnf_supervision *supervision, const tdnnf_unit_set *units, int32 frames_per_sequence,
+                                            const std::vector<int32> &unit_begin, const std::vector<int32> &unit, const std::vector<int32> &starts,
+                                            int32 tolerance, float weight) {
+  tdnnf_adapter::SupervisionAssignAlignments(supervision, units, static_cast<int32>(unit_begin.size()) - 1, frames_per_sequence, unit_begin.data(),
+                                             unit.data(), starts.data(), tolerance, weight, Hooks().stream);
+}
+
 // ------------------------------------------------------------------------------------------------ best-path alignment
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames

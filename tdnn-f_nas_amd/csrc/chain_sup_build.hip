@@ -1,12 +1,15 @@
 // chain_sup_build.hip -- the reusable time-synchronous supervision (include/tdnnf_hip.h): tdnnf_supervision_reserve makes every allocation
 // once for four capacities, tdnnf_supervision_assign validates a minibatch on the host (chain_sup_tables.h), stages its raw arrays in pinned
 // memory and enqueues the copies and the device build (chain_sup_build_kernels.h) on the caller's stream -- nothing allocated, nothing freed,
-// no device-wide wait.  tdnnf_supervision_capacity and tdnnf_supervision_dump (created supervisions too) are the diagnostics the tests read.
+// no device-wide wait.  tdnnf_supervision_assign_alignments plans the lattices of a minibatch of alignments on the host (chain_sup_alignment.h),
+// stages units and windows and has the compile kernel (chain_sup_compile.hip) write the raw arrays in front of the same build.
+// tdnnf_supervision_capacity and tdnnf_supervision_dump (created supervisions too) are the diagnostics the tests read.
 // The numerator's host functions (chain_num.hip) see an assigned supervision as they see a created one.
 #include <string.h>
 
 #include <string>
 
+#include "chain_sup_alignment.h"
 #include "chain_sup_build_kernels.h"
 #include "chain_sup_tables.h"
 #include "chain_types.h"
@@ -79,6 +82,31 @@ int sup_build_launch(const SupBuildDev &b, hipStream_t s) {
   TDNNF_LAUNCH_CHECK();
   hipLaunchKernelGGL(sup_build_frames_kernel, dim3(b.B * b.T), dim3(kSupFrameThreads), 0, s, b);
   TDNNF_LAUNCH_CHECK();
+  return TDNNF_OK;
+}
+
+// The second half of an assign, behind every refusal: the copies, the compile launch (compile non-null: an assign from alignments), the
+// build's launches and the record of the minibatch.  From here on the device tables are being overwritten.  A refusal in front of it left
+// the previous minibatch; an error of the runtime in it (a copy or a launch that fails) leaves NO minibatch: the handle is refused like a
+// fresh one until an assign succeeds (assign_stage.h).
+int sup_commit(tdnnf_supervision *sp, const StagePacker &pk, size_t raw_bytes, const SupCompileDev *compile, const SupPlan &p, int B, int T, float weight,
+               hipStream_t s) {
+  SupReserved *r = sp->ts;
+  const int assigns_before = sp->ts_assigns;
+  sp->ts_assigns = 0;
+  int rc;
+  if ((rc = r->stage.submit(pk, raw_bytes, s)) || (compile && (rc = sup_compile_launch(*compile, s))) || (rc = sup_build_launch(r->build, s))) return rc;
+
+  sp->B = B;
+  sp->T = T;
+  sp->weight = weight;
+  sp->num_states = p.num_states;
+  sp->num_arcs = p.num_arcs;
+  sp->max_states_per_seq = p.max_states_per_seq;
+  sp->max_states_per_frame = p.max_states_per_frame;
+  sp->max_arcs_per_frame = p.max_arcs_per_frame;
+  sp->wide = p.wide;
+  sp->ts_assigns = assigns_before + 1;
   return TDNNF_OK;
 }
 
@@ -164,24 +192,68 @@ int tdnnf_supervision_assign(tdnnf_supervision *sp, int B, int T, const int *seq
   pk.put_to(sp->final_logprob, final_logprob, NS);
   pk.put_to(sp->frame_state_begin, p.frame_state_begin.data(), p.frame_state_begin.size());
   TDNNF_REQUIRE(pk.fits(), "%sinternal: the minibatch needs %zu bytes of staging, the supervision has %zu", who, pk.at, pk.size);
-  // From here on the device tables are being overwritten.  A refusal above left the previous minibatch; an error of the runtime below
-  // (a copy or a launch that fails) leaves NO minibatch: the handle is refused like a fresh one until an assign succeeds (assign_stage.h).
-  const int assigns_before = sp->ts_assigns;
-  sp->ts_assigns = 0;
-  int rc;
-  if ((rc = r->stage.submit(pk, raw_bytes, s)) || (rc = sup_build_launch(b, s))) return rc;
+  return sup_commit(sp, pk, raw_bytes, nullptr, p, B, T, weight, s);
+}
 
-  sp->B = B;
-  sp->T = T;
-  sp->weight = weight;
-  sp->num_states = p.num_states;
-  sp->num_arcs = p.num_arcs;
-  sp->max_states_per_seq = p.max_states_per_seq;
-  sp->max_states_per_frame = p.max_states_per_frame;
-  sp->max_arcs_per_frame = p.max_arcs_per_frame;
-  sp->wide = p.wide;
-  sp->ts_assigns = assigns_before + 1;
+int tdnnf_alignment_supervision_sizes(const tdnnf_unit_set *units, int B, int T, const int *unit_begin, const int *unit, const int *starts, int tolerance,
+                                      int *states_out, int *arcs_out) {
+  const char *who = "alignment_supervision_sizes: ";
+  TDNNF_REQUIRE(units, "%snull unit set", who);
+  std::string err;
+  TDNNF_REQUIRE(alignment_sizes(who, units->host, B, T, unit_begin, unit, starts, tolerance, states_out, arcs_out, &err), "%s", err.c_str());
   return TDNNF_OK;
+}
+
+int tdnnf_supervision_assign_alignments(tdnnf_supervision *sp, const tdnnf_unit_set *units, int B, int T, const int *unit_begin, const int *unit,
+                                        const int *starts, int tolerance, float weight, tdnnf_stream stream) {
+  const char *who = "supervision_assign_alignments: ";
+  TDNNF_REQUIRE(sp && units, "%snull supervision or null unit set", who);
+  TDNNF_REQUIRE(sp->kind == 0, "%san end-to-end supervision: tdnnf_supervision_assign_e2e_transcripts assigns those from unit sequences", who);
+  TDNNF_REQUIRE(sp->ts_reserved && sp->ts,
+                "%sthe supervision was made by tdnnf_supervision_create: only a supervision of tdnnf_supervision_reserve can be assigned", who);
+  SupReserved *r = sp->ts;
+  std::string err;
+  TDNNF_REQUIRE(alignments_validate(who, units->host, B, T, unit_begin, unit, starts, tolerance, &err), "%s", err.c_str());
+  AlignmentSupPlan ap;
+  TDNNF_REQUIRE(alignments_plan(who, B, T, unit_begin, starts, tolerance, &ap, &err), "%s", err.c_str());
+  const SupPlan &p = ap.plan;
+  TDNNF_REQUIRE(sup_check_capacity(who, B, T, p, r->max_sequences, r->max_frames, r->max_states, r->max_arcs, &err), "%s", err.c_str());
+  const size_t NA = p.num_arcs, N = unit_begin[B];
+
+  StagePacker pk;
+  if (int rc = r->stage.begin(&pk)) return rc;
+  SupBuildDev &b = r->build;
+  SupCompileDev c;
+  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(r->stage.dev + pk.put(v, n)); };
+  b.B = c.B = B;
+  b.T = c.T = T;
+  c.cap_states = r->max_states;
+  c.cap_arcs = r->max_arcs;
+  b.seq_arc_begin = c.seq_arc_begin = raw(ap.seq_arc_begin.data(), (size_t)B + 1);
+  c.unit_begin = raw(unit_begin, (size_t)B + 1);
+  c.units = raw(unit, N);
+  c.lo = raw(ap.lo.data(), N);
+  c.hi = raw(ap.hi.data(), N);
+  // the staging's two shapes: on the host the begins, three ints a unit, the supervision's begins and frame_state_begin; on the device the
+  // begins and the units, behind them the four arc arrays the kernel writes.  Both fit what tdnnf_supervision_reserve sized for 8 bytes a
+  // state, 16 an arc and 4 a (sequence, frame + 2): units <= sequences * frames, units < states, frames <= arcs of a sequence
+  const size_t raw_bytes = pk.at, dev_bytes = raw_bytes + 4 * sizeof(int) * NA;
+  int *arcs = reinterpret_cast<int *>(r->stage.dev + raw_bytes);  // (device only)
+  b.src = c.src = arcs;
+  b.dst = c.dst = arcs + NA;
+  b.pdf = c.pdf = arcs + 2 * NA;
+  b.lp_bits = c.lp_bits = arcs + 3 * NA;
+  c.seq_state_begin = sp->seq_state_begin;
+  c.frame_state_begin = sp->frame_state_begin;
+  c.state_time = sp->state_time;
+  c.final_logprob = sp->final_logprob;
+  c.frame_arc_begin = b.len[0];
+  c.units_dev = units->dev;
+  pk.put_to(sp->seq_state_begin, ap.seq_state_begin.data(), (size_t)B + 1);
+  pk.put_to(sp->frame_state_begin, p.frame_state_begin.data(), p.frame_state_begin.size());
+  TDNNF_REQUIRE(pk.fits() && dev_bytes <= pk.size, "%sinternal: the minibatch needs %zu bytes of staging on the host and %zu on the device, the supervision has %zu",
+                who, pk.at, dev_bytes, pk.size);
+  return sup_commit(sp, pk, raw_bytes, &c, p, B, T, weight, static_cast<hipStream_t>(stream));
 }
 
 int tdnnf_supervision_capacity(const tdnnf_supervision *sp, int *max_sequences, int *max_frames, int *max_states, int *max_arcs, int *assigns,

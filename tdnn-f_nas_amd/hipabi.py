@@ -239,6 +239,19 @@ def _slots(transcripts):
     return iarr(begin), iarr(cat(0)), iarr(cat(1) != 0)
 
 
+def _alignments(alignments):
+    """A minibatch of alignments -- each a (units, starts) pair of int sequences of one length: the units of a sequence and the output
+    frames they start at -- as the three arrays of the C entries: (unit_begin, units, starts), each an (array, pointer) pair of iarr."""
+    import numpy as np
+    alignments = [(np.asarray(u, dtype=np.int64).reshape(-1), np.asarray(b, dtype=np.int64).reshape(-1)) for u, b in alignments]
+    for s, (u, b) in enumerate(alignments):
+        if len(u) != len(b):
+            raise HipAbiError(f"alignment {s}: {len(u)} units and {len(b)} starts")
+    begin = np.concatenate([[0], np.cumsum([len(u) for u, _ in alignments])])
+    cat = lambda i: np.concatenate([a[i] for a in alignments]) if alignments else np.zeros(0, np.int64)
+    return iarr(begin), iarr(cat(0)), iarr(cat(1))
+
+
 class UnitSet:
     """Device-resident unit set for transcript graphs (tdnnf_unit_set): U units over num_pdfs pdfs, one state per unit with an entry pdf on
     its first frame and a loop pdf on every later one.  entry_pdf / loop_pdf: shape (U,) -- context 0, context-independent -- or (U + 1, U)
@@ -267,6 +280,17 @@ class UnitSet:
         states, arcs = np.zeros(len(begin[0]) - 1, np.int32), np.zeros(len(begin[0]) - 1, np.int32)
         check(load().tdnnf_transcript_graph_sizes(self.h, len(states), begin[1], unit[1], opt[1], states.ctypes.data_as(C.c_void_p),
                                                   arcs.ctypes.data_as(C.c_void_p)))
+        return states, arcs
+
+    def alignment_sizes(self, alignments, frames_per_sequence, tolerance):
+        """tdnnf_alignment_supervision_sizes (host only): (states, arcs), numpy int32 arrays with one entry per alignment -- the lattice
+        of each (units, starts) pair with every boundary free to move by +-tolerance frames; what a Supervision.reserve must cover.
+        Refuses (HipAbiError) what Supervision.assign_alignments refuses."""
+        import numpy as np
+        begin, unit, start = _alignments(alignments)
+        states, arcs = np.zeros(len(begin[0]) - 1, np.int32), np.zeros(len(begin[0]) - 1, np.int32)
+        check(load().tdnnf_alignment_supervision_sizes(self.h, len(states), int(frames_per_sequence), begin[1], unit[1], start[1], int(tolerance),
+                                                       states.ctypes.data_as(C.c_void_p), arcs.ctypes.data_as(C.c_void_p)))
         return states, arcs
 
     def __del__(self):
@@ -376,6 +400,15 @@ class Supervision:
         begin, unit, opt = _slots(transcripts)
         check(load().tdnnf_supervision_assign_e2e_transcripts(self.h, unit_set.h, len(begin[0]) - 1, int(frames_per_sequence), begin[1], unit[1], opt[1],
                                                               float(weight), stream()))
+        self.B, self.T = len(begin[0]) - 1, int(frames_per_sequence)
+
+    def assign_alignments(self, unit_set, alignments, frames_per_sequence, tolerance, weight=1.0):
+        """tdnnf_supervision_assign_alignments on the current stream: the next minibatch of a supervision of reserve, its lattices compiled
+        on the device from one (units, starts) alignment per sequence (UnitSet; starts in output frames, the first 0) with every unit
+        boundary free to move by +-tolerance frames.  A refused minibatch (HipAbiError) leaves the previous one."""
+        begin, unit, start = _alignments(alignments)
+        check(load().tdnnf_supervision_assign_alignments(self.h, unit_set.h, len(begin[0]) - 1, int(frames_per_sequence), begin[1], unit[1], start[1],
+                                                         int(tolerance), float(weight), stream()))
         self.B, self.T = len(begin[0]) - 1, int(frames_per_sequence)
 
     @property

@@ -396,6 +396,24 @@ def _align_stacked(y, frames, graphs, utt_graph, acoustic_scale, labels=False, c
     return [(p, float(res[u, 0]), bool(res[u, 1] == 1.0)) for u, p in enumerate(torch.split(pdfs, frames))]
 
 
+def alignment_from_path(slots_per_frame, transcript):
+    """The segmentation of one utterance from its labelled best path, for Supervision.assign_alignments: slots_per_frame, one int per
+    frame, is the label output of align_labels / AlignGraphs.best_path_labels through a handle whose graphs were compiled from transcripts
+    (AlignGraphs.assign_transcripts: an arc's label is the slot it enters, so a frame's label is the slot it was spent in); transcript the
+    utterance's (units, optional) pair.  Returns (units, starts), int32 arrays with one entry per run of equal labels: the slot's unit and
+    the run's first frame -- an optional slot the path skipped has no run and is dropped.  Pure numpy; ValueError for a path that is not
+    one (no frames, a -1 of an utterance without an accepting path, slots that do not increase or lie outside the transcript)."""
+    slots = np.asarray(slots_per_frame.detach().cpu().numpy() if hasattr(slots_per_frame, "detach") else slots_per_frame, dtype=np.int64).reshape(-1)
+    units = np.asarray(transcript[0], dtype=np.int64).reshape(-1)
+    if len(slots) == 0:
+        raise ValueError("alignment_from_path: no frames")
+    starts = np.concatenate([[0], 1 + np.flatnonzero(slots[1:] != slots[:-1])])
+    runs = slots[starts]
+    if runs.min() < 0 or runs.max() >= len(units) or np.any(runs[1:] <= runs[:-1]):
+        raise ValueError(f"alignment_from_path: the slots of the runs, {runs.tolist()}, are not an increasing walk through {len(units)} slots")
+    return units[runs].astype(np.int32), starts.astype(np.int32)
+
+
 def write_int_vector_archive(path, items):
     """Kaldi binary archive of vector<int32>: per item `key ' ' \\0B \\4 n` then n little-endian int32 (WriteIntegerVector; the intvec
     encoding of include/tdnnf_kaldi_io.h, what the egs reader takes for <AlignmentPdfs>); what ali-to-pdf writes and copy-int-vector

@@ -232,6 +232,65 @@ def make_supervision_lattice(B, T, P, tolerance=2, alternatives=1, mean_dur=3.0,
             "arc_logprob": a_lp, "weight": float(weight)}
 
 
+def supervision_lattice_from_alignments(unit_set, alignments, T, tolerance, weight=1.0):
+    """The tolerance lattices of GIVEN alignments, on the host: what hipabi.Supervision.assign_alignments compiles on the device
+    (include/tdnnf_hip.h, "ALIGNMENT SUPERVISIONS"), as the dict of make_supervision that Supervision.assign takes.  unit_set: the dict of
+    make_unit_set; alignments: one (units, starts) pair per sequence, starts in output frames, the first 0, strictly increasing, below T.
+    make_supervision_lattice's construction with one alternative and its state and arc order, the pdfs from the unit set -- the entry pdf
+    at (unit before or -1, unit) on the frame a unit is entered, its loop pdf on every later one -- and every arc log-prob 0."""
+    ctx, entry, loop = int(unit_set["context"]), np.asarray(unit_set["entry_pdf"]), np.asarray(unit_set["loop_pdf"])
+    state_time, final, a_src, a_dst, a_pdf = [], [], [], [], []
+    seq_state_begin, seq_arc_begin = [0], [0]
+    ns = na = 0
+    for units, starts in alignments:
+        u, b = np.asarray(units, np.int64).reshape(-1), np.asarray(starts, np.int64).reshape(-1)
+        U = len(u)
+        assert U >= 1 and len(b) == U and b[0] == 0 and np.all(np.diff(b) > 0) and b[-1] < T and tolerance >= 0
+        left = np.concatenate([[-1], u[:-1]])
+        e_pdf, l_pdf = (entry[left + 1, u], loop[left + 1, u]) if ctx else (entry[u], loop[u])
+        lo = np.maximum(b - tolerance, 0)
+        hi = np.minimum(b + tolerance, T - 1)
+        lo[0] = hi[0] = 0
+        lo = np.maximum.accumulate(lo - np.arange(U)) + np.arange(U)
+        hi = np.append(hi, T)
+        hi = np.minimum.accumulate((hi - np.arange(U + 1))[::-1])[::-1] + np.arange(U + 1)
+        lo = np.append(lo, T)
+        cE = hi[:U] - lo[:U] + 1
+        cL = hi[1:] - lo[:U] - 1
+        tE, uE = _ranges(lo[:U] + 1, cE)
+        tL, uL = _ranges(lo[:U] + 2, cL)
+        offE = 1 + np.cumsum(cE) - cE
+        offL = 1 + int(cE.sum()) + np.cumsum(cL) - cL
+        idE = offE[uE] + (tE - lo[uE] - 1)
+        idL = offL[uL] + (tL - lo[uL] - 2)
+        t_all, u_all, id_all = np.concatenate([tE, tL]), np.concatenate([uE, uL]), np.concatenate([idE, idL])
+        stay = t_all + 1 <= hi[u_all + 1]
+        enter = (u_all + 1 < U) & (t_all >= lo[np.minimum(u_all + 1, U)]) & (t_all <= hi[u_all + 1])
+        un = u_all[enter] + 1
+        s_loc = np.concatenate([np.zeros(1, np.int64), id_all[stay], id_all[enter]])
+        d_loc = np.concatenate([offE[:1], offL[u_all[stay]] + (t_all[stay] + 1 - lo[u_all[stay]] - 2), offE[un] + (t_all[enter] - lo[un])])
+        p_loc = np.concatenate([e_pdf[:1], l_pdf[u_all[stay]], e_pdf[un]])
+        t_loc = np.concatenate([np.zeros(1, np.int64), tE, tL])
+        f_loc = np.concatenate([np.zeros(1, bool), (tE == T) & (uE == U - 1), (tL == T) & (uL == U - 1)])
+        n_loc = len(t_loc)
+        order = np.argsort(t_loc, kind="stable")  # by time; within a time the entered states by unit, then the looping ones
+        new_id = np.empty(n_loc, np.int64)
+        new_id[order] = np.arange(n_loc)
+        s_loc, d_loc = new_id[s_loc], new_id[d_loc]
+        ao = np.lexsort((d_loc, s_loc))
+        state_time.append(t_loc[order]); final.append(np.where(f_loc[order], 0.0, -np.inf))
+        a_src.append(ns + s_loc[ao]); a_dst.append(ns + d_loc[ao]); a_pdf.append(p_loc[ao])
+        ns += n_loc
+        na += len(ao)
+        seq_state_begin.append(ns)
+        seq_arc_begin.append(na)
+    i32 = lambda x: np.asarray(x, dtype=np.int32)
+    return {"B": len(alignments), "T": int(T), "seq_state_begin": i32(seq_state_begin), "seq_arc_begin": i32(seq_arc_begin),
+            "state_time": i32(np.concatenate(state_time)), "final_logprob": np.concatenate(final).astype(np.float32),
+            "arc_src": i32(np.concatenate(a_src)), "arc_dst": i32(np.concatenate(a_dst)), "arc_pdf": i32(np.concatenate(a_pdf)),
+            "arc_logprob": np.zeros(na, np.float32), "weight": float(weight)}
+
+
 def make_alignment_graph(pdf_sequence, self_loops=True, optional=(), alternatives=None, seed=0, num_pdfs=None, labels=None):
     """Left-to-right transcript graph for best-path alignment: the shape of a compile-train-graphs output reduced to pdf labels.
     Epsilon-free, so a state is "inside a unit": state 0 is the start, unit k is one state, every arc INTO it carries its pdf --

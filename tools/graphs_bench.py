@@ -13,8 +13,11 @@ The clock is the host's around a loop over the cycle that ends in ONE synchronis
 host + assign, assign alone, and tdnnf_align_graphs_assign_transcripts / tdnnf_supervision_assign_e2e_transcripts, alternating.
 --supervision [--tolerance N --alternatives N]: instead, the time-synchronous supervision of regular LF-MMI (see supervision() below):
 tdnnf_supervision_create + tdnnf_chain_objf_and_deriv + tdnnf_supervision_destroy against tdnnf_supervision_assign + the same call.
+--supervision --alignment [--tolerance N]: instead, the same supervision for a caller who starts from alignments (see alignment() below):
+the lattice built on the host + tdnnf_supervision_assign, assign alone, and tdnnf_supervision_assign_alignments, alternating.
 usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts]
-                                              [--supervision [--tolerance N --alternatives N] [--sequences B --frames T]]"""
+                                              [--supervision [--tolerance N --alternatives N] [--sequences B --frames T]]
+                                              [--supervision --alignment [--tolerance N] [--sequences B --frames T]]"""
 import argparse
 import ctypes as C
 import json
@@ -229,6 +232,123 @@ def supervision(args, pkg):
     print(json.dumps(res))
 
 
+def alignment(args, pkg):
+    """--supervision --alignment [--tolerance N, default 5]: what a new minibatch costs per step for a caller who starts from ALIGNMENTS,
+    three ways alternating in one process, a different minibatch every iteration (a cycle of random segmentations generated beforehand),
+    medians of --repeats:
+      host_lattice_assign  (a) the lattice's arrays made on the host (synth.supervision_lattice_from_alignments, numpy array operations),
+                           tdnnf_supervision_assign, tdnnf_chain_objf_and_deriv -- what a caller had to do before
+                           tdnnf_supervision_assign_alignments;
+      assign               (b) assign from arrays made outside the timed region, the call: the assign's own cost, the control;
+      assign_alignments    (c) tdnnf_supervision_assign_alignments, the call.
+    Two shapes: --sequences x --frames (default 128 x 150) at the tolerance with mean duration 6 frames, and one wide shape, 64 x 150 at
+    tolerance 40 with mean duration 3.  Also the host time of the assign_alignments call alone and the device time of what it enqueues.
+    The outputs of the three are compared for equality in the same run.  One JSON line."""
+    abi, synth = pkg.hipabi, pkg.synth
+    lib = abi.load()
+    P, U = args.pdfs, 42
+    us = synth.make_unit_set(U, context=1, seed=1, distinct=False, P=P)
+    units = abi.UnitSet(us["entry_pdf"], us["loop_pdf"], us["loop_logprob"], us["leave_logprob"], P, us["take_logprob"], us["skip_logprob"])
+    dg = abi.DenGraph(synth.make_den_graph(64, P, mean_out_degree=4.0, seed=1))
+    s = abi.stream()
+    res = dict(metric="alignment_supervision_per_minibatch", pdfs=P, cycle=args.cycle, repeats=args.repeats, units=U, context=1)
+
+    def random_alignment(rng, T, mean_dur):
+        d = 1 + np.floor(rng.exponential(mean_dur - 1.0, size=T)).astype(np.int64)
+        b = np.concatenate([[0], np.cumsum(d)])
+        b = b[:int(np.searchsorted(b, T))]
+        return rng.integers(0, U, size=len(b)).astype(np.int32), b.astype(np.int32)
+
+    def pointers(sup):
+        keep = [abi.iarr(sup["seq_state_begin"]), abi.iarr(sup["seq_arc_begin"]), abi.iarr(sup["state_time"]), abi.farr(sup["final_logprob"]),
+                abi.iarr(sup["arc_src"]), abi.iarr(sup["arc_dst"]), abi.iarr(sup["arc_pdf"]), abi.farr(sup["arc_logprob"])]
+        return keep, [k[1] for k in keep]
+
+    def case(name, B, T, tol, mean_dur):
+        rng = np.random.default_rng(1)
+        batches = [[random_alignment(rng, T, mean_dur) for _ in range(B)] for _ in range(args.cycle)]
+        made = [pointers(synth.supervision_lattice_from_alignments(us, b, T, tol)) for b in batches]
+        flat = [abi._alignments(b) for b in batches]
+        NS, NA = max(len(m[0][2][0]) for m in made), max(len(m[0][4][0]) for m in made)
+        reserved = C.c_void_p()
+        abi.check(lib.tdnnf_supervision_reserve(B, T, NS, NA, C.byref(reserved)))
+        y = torch.randn(B * T, P, device="cuda")
+        xo = torch.log_softmax(torch.randn(B * T, P, device="cuda"), dim=1)
+        nb = int(lib.tdnnf_chain_workspace_bytes(dg.h, B, T))
+        ws = abi.workspace(nb)
+        ws.zero_()
+        out = (torch.zeros(8, dtype=torch.float64, device="cuda"), torch.zeros_like(y), torch.zeros_like(y))
+
+        def call():
+            abi.check(lib.tdnnf_chain_objf_and_deriv(dg.h, reserved, abi.pmat(y), abi.pmat(xo), 0.1, 5e-5, 0.1, abi.ptr(out[0]), abi.pmat(out[1]), abi.pmat(out[2]),
+                                                     abi.ptr(ws), nb, s))
+
+        def assign(ptrs):
+            abi.check(lib.tdnnf_supervision_assign(reserved, B, T, *ptrs, 1.0, s))
+
+        def assign_alignments(i):
+            a = flat[i]
+            abi.check(lib.tdnnf_supervision_assign_alignments(reserved, units.h, B, T, a[0][1], a[1][1], a[2][1], tol, 1.0, s))
+
+        fns = dict(host_lattice_assign=lambda i: (assign(pointers(synth.supervision_lattice_from_alignments(us, batches[i], T, tol))[1]), call()),
+                   assign=lambda i: (assign(made[i][1]), call()),
+                   assign_alignments=lambda i: (assign_alignments(i), call()))
+
+        def loop(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(args.cycle):
+                fn(i)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / args.cycle
+
+        ms = {k: [] for k in fns}
+        for r in range(args.repeats + 1):  # the first round warms up
+            for k, fn in fns.items():
+                t = loop(fn)
+                if r:
+                    ms[k].append(t)
+        host_ms, dev_ms = [], []
+        for i in range(args.cycle):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            t0 = time.perf_counter()
+            assign_alignments(i)
+            host_ms.append(1e3 * (time.perf_counter() - t0))
+            e1.record()
+            torch.cuda.synchronize()
+            dev_ms.append(e0.elapsed_time(e1))
+        equal = True
+        for i in range(args.cycle):
+            got = []
+            for fn in fns.values():
+                for t in out:
+                    t.zero_()
+                fn(i)
+                torch.cuda.synchronize()
+                got.append([t.clone() for t in out])
+            equal = equal and all(torch.equal(x.view(torch.uint8), z.view(torch.uint8)) for other in got[1:] for x, z in zip(got[0], other))
+        info = [C.c_int() for _ in range(4)]
+        abi.check(lib.tdnnf_supervision_info(reserved, *[C.byref(x) for x in info]))
+        cap = [C.c_int() for _ in range(6)] + [C.c_longlong()]
+        abi.check(lib.tdnnf_supervision_capacity(reserved, *[C.byref(x) for x in cap]))
+        d = dict(sequences=B, frames=T, tolerance=tol, mean_duration=mean_dur, units=int(max(len(a[1][0]) for a in flat)), states=NS, arcs=NA,
+                 wide=int(info[3].value), max_states_per_frame=int(info[2].value), allocations_since_reserve=int(cap[5].value), outputs_equal=bool(equal),
+                 assign_alignments_host=round(float(np.median(host_ms)), 3), assign_alignments_device=round(float(np.median(dev_ms)), 3))
+        for k, v in ms.items():
+            d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v])
+        d["alignments_over_host_lattice"] = round(d["assign_alignments"]["ms"] / d["host_lattice_assign"]["ms"], 3)
+        d["alignments_over_assign"] = round(d["assign_alignments"]["ms"] / d["assign"]["ms"], 3)
+        lib.tdnnf_supervision_destroy(reserved)
+        res[name] = d
+
+    tol = args.tolerance if args.tolerance > 0 else 5
+    case("regular", args.sequences, args.frames, tol, 6.0)
+    case("wide", 64, 150, 40, 3.0)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -238,6 +358,8 @@ def main():
     ap.add_argument("--transcripts", action="store_true", help="graphs from transcripts: host-built arrays + assign against assign_transcripts")
     ap.add_argument("--supervision", action="store_true", help="time-synchronous supervisions: create + call + destroy against assign + call")
     ap.add_argument("--tolerance", type=int, default=0, help="--supervision: > 0 tolerance lattices (synth.make_supervision_lattice)")
+    ap.add_argument("--alignment", action="store_true",
+                    help="--supervision: from alignments -- host-built lattice + assign against assign_alignments (--tolerance, default 5)")
     ap.add_argument("--alternatives", type=int, default=1)
     ap.add_argument("--sequences", type=int, default=128)
     ap.add_argument("--frames", type=int, default=150)
@@ -245,7 +367,7 @@ def main():
     assert args.cycle >= 8, "different graphs every iteration: a cycle of at least 8 batches"
     pkg = ge.load_package()
     if args.supervision:
-        return supervision(args, pkg)
+        return alignment(args, pkg) if args.alignment else supervision(args, pkg)
     if args.transcripts:
         return transcripts(args, pkg)
     abi, synth = pkg.hipabi, pkg.synth
