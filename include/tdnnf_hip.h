@@ -612,8 +612,9 @@ int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *, int *max_graphs, int
    staging copy of the assign before last.  Stream order, the host-side answers and tdnnf_align_graphs_capacity's `assigns` are
    tdnnf_align_graphs_assign's, and so is the failure rule (a refusal leaves the previous batch, an error of the runtime no batch); both
    kinds of assign may alternate on one handle, on the one pair of staging buffers.
-   Not built: pronunciation alternatives and adjacent optional slots, lexicon and tree handling (the caller maps words to units and
-   (left, unit) to pdfs), right context, units of several states, capture into a HIP graph. */
+   Pronunciation alternatives: "PRONUNCIATION GRAPHS" below.
+   Not built: adjacent optional slots, lexicon and tree handling (the caller maps words to units and (left, unit) to pdfs), right context,
+   units of several states, capture into a HIP graph. */
 typedef struct tdnnf_unit_set tdnnf_unit_set;
 int tdnnf_unit_set_create(int num_units, int num_pdfs, int context, const int *entry_pdf, const int *loop_pdf, const float *loop_logprob,
                           const float *leave_logprob, float take_logprob, float skip_logprob, tdnnf_unit_set **out);
@@ -622,6 +623,62 @@ int tdnnf_transcript_graph_sizes(const tdnnf_unit_set *, int num_transcripts, co
                                  const int *slot_optional, int *states_out, int *arcs_out);
 int tdnnf_align_graphs_assign_transcripts(tdnnf_align_graphs *, const tdnnf_unit_set *, int num_transcripts, const int *slot_begin,
                                           const int *slot_unit, const int *slot_optional, tdnnf_stream stream);
+/* PRONUNCIATION GRAPHS: transcript graphs whose positions (words) have several pronunciations, compiled on the device as the transcript
+   graphs above are, with the unit set (context 0 or 1) as it is.
+   A transcript is n >= 1 POSITIONS; position p has a flag opt_p and A_p >= 1 ALTERNATIVES; alternative (p, a) is L >= 1 units of the unit set
+   and a float alt_logprob.  An ENTRY is one unit of one alternative; a transcript's entries are numbered from 0 in flat order: position,
+   alternative, unit.  The flat arrays of a batch: transcript g owns the positions [pos_begin[g], pos_begin[g + 1]) of pos_optional;
+   position P (counted over the batch) the alternatives [pos_alt_begin[P], pos_alt_begin[P + 1]) of alt_logprob; alternative Q the units
+   [alt_unit_begin[Q], alt_unit_begin[Q + 1]) of alt_units.  All three begin arrays start at 0.
+   The PREDECESSORS of position p: the near ones, the alternatives of p-1 in order (for p = 0 the start); then the far ones, only if
+   opt_p-1, the alternatives of p-2 in order (for p = 1 the start).  The graph:
+     states   0 the start; the entries follow in flat order.  An inner entry (j > 0) has one state; its left unit is the unit before it in
+              its alternative.  A first entry (j = 0) has one state in context 0 and, in context 1, one state per predecessor in their
+              order -- not merged even where two predecessors end in the same unit -- whose left unit is the predecessor's last unit, -1 for
+              the start.  A state's pdfs are entry_pdf and loop_pdf at (left unit, unit).
+     arcs     out of a state of entry (p, a, j) with unit u: a self-loop with the loop pdf and loop_logprob[u];
+              if j + 1 < L one arc to the next entry's state with leave_logprob[u];
+              if j = L - 1, for every alternative a' of p+1 an arc into the state of (p+1, a', 0) that belongs to predecessor (p, a) -- in
+              context 0 its one state -- with leave_logprob[u], then + take_logprob if opt_p+1, then + alt_logprob(p+1, a') if A_p+1 >= 2;
+              if j = L - 1, opt_p+1 and p + 2 < n, for every alternative a'' of p+2 an arc into its far state for (p, a), with
+              leave_logprob[u] + skip_logprob, then + alt_logprob(p+2, a'') if A_p+2 >= 2.
+              The start behaves as the last entry of a position -1 with no leave term: 0.0f + take_logprob or 0.0f into position 0,
+              skip_logprob into position 1 over an optional position 0, then the alternative's term.
+              An arc that enters a state carries that state's entry pdf.  Every weight is a float formed left to right in the order given.
+              Ordered by (source, destination), no pair twice.  The arcs into a state are its loop and the states of its predecessor's last
+              entry, so the in-degree is not bounded: 1 + N where that alternative has one unit and N states.
+     initial  0 at state 0;  final  leave_logprob[u] on the states of the last entries of position n-1 and, if opt_n-1 and n >= 2,
+              leave_logprob[u] + skip_logprob on those of position n-2;  -inf elsewhere.
+     labels   (labelled handles) an arc's label is the entry number of its destination: tdnnf_align_best_path_labels gives per frame the
+              position, the alternative chosen and the unit.  num_labels must cover the most entries of any transcript.
+   A transcript whose every position has one alternative of one unit is the slot transcript above, and its tables are the bytes
+   tdnnf_align_graphs_assign_transcripts builds.  The best path's units and the frames they start at go into
+   tdnnf_supervision_assign_alignments unchanged, so the alignment supervision needs no alternatives.
+   Refused with TDNNF_EINVAL naming the transcript, the position and the alternative: a position without an alternative, an empty alternative,
+   a unit outside [0, num_units), an alt_logprob that is NaN or infinite, two adjacent optional positions, a transcript without a mandatory
+   position; and the capacities and num_labels, in tdnnf_align_graphs_assign's words.  All of it before anything is written: a refusal
+   leaves the previous batch in place.
+   tdnnf_pronunciation_graph_sizes is host-only: the states and arcs of every transcript (either out-pointer may be NULL), for sizing a
+   reserve; it gives the same refusals under its own name.
+   tdnnf_align_graphs_assign_pronunciations is tdnnf_align_graphs_assign_transcripts from these arrays.  The host works in O(entries +
+   first-entry states) (csrc/align_pronunciations.h): the begins, per graph the arcs and the largest in-degree, the column lists, and the
+   first state of every position.  It stages 4 bytes an entry, 12 an alternative and 8 a position inside the staging the reserve made -- a
+   batch within max_states and max_arcs fits, because arcs >= entries + alternatives and states >= entries; a batch that would not is refused
+   by name -- and enqueues ONE kernel (csrc/align_pron_compile_kernels.h) in front of the three unchanged build kernels.  Stream order, the
+   failure rule, `assigns` and the alternation with the other assigns on the one pair of staging buffers are
+   tdnnf_align_graphs_assign_transcripts's; tdnnf_supervision_assign_e2e_pronunciations carries those of
+   tdnnf_supervision_assign_e2e_transcripts.
+   Not built: adjacent optional positions, right context, units of several states, capture into a HIP graph. */
+int tdnnf_pronunciation_graph_sizes(const tdnnf_unit_set *, int num_transcripts, const int *pos_begin, const int *pos_optional,
+                                    const int *pos_alt_begin, const float *alt_logprob, const int *alt_unit_begin, const int *alt_units,
+                                    int *states_out, int *arcs_out);
+int tdnnf_align_graphs_assign_pronunciations(tdnnf_align_graphs *, const tdnnf_unit_set *, int num_transcripts, const int *pos_begin,
+                                             const int *pos_optional, const int *pos_alt_begin, const float *alt_logprob,
+                                             const int *alt_unit_begin, const int *alt_units, tdnnf_stream stream);
+int tdnnf_supervision_assign_e2e_pronunciations(tdnnf_supervision *, const tdnnf_unit_set *, int num_sequences, int frames_per_sequence,
+                                                const int *pos_begin, const int *pos_optional, const int *pos_alt_begin,
+                                                const float *alt_logprob, const int *alt_unit_begin, const int *alt_units, float weight,
+                                                tdnnf_stream stream);
 /* ALIGNMENT SUPERVISIONS: the next minibatch of a supervision of tdnnf_supervision_reserve compiled on the device from alignments and a
    frame tolerance -- the supervision regular LF-MMI trains on: an alignment whose unit boundaries may each move by +- tolerance frames.
    The caller hands over (unit, start frame) pairs and never builds a state or an arc array; the alignment may be this library's

@@ -454,6 +454,31 @@ inline void SupervisionAssignE2eTranscripts(tdnnf_supervision *sup, const tdnnf_
   Check(tdnnf_supervision_assign_e2e_transcripts(sup, units, num_sequences, frames_per_sequence, slot_begin, slot_unit, slot_optional, weight, stream));
 }
 
+// Pronunciation graphs (tdnnf_hip.h, "PRONUNCIATION GRAPHS"): the same from transcripts whose positions (words) have several
+// pronunciations -- the lexicon's alternatives, each a unit sequence with a log-probability.  Transcript g is the positions
+// [pos_begin[g], pos_begin[g + 1]) of pos_optional, position P the alternatives [pos_alt_begin[P], pos_alt_begin[P + 1]) of alt_logprob,
+// alternative Q the units [alt_unit_begin[Q], alt_unit_begin[Q + 1]) of alt_units.  PronunciationGraphSizes (host only) sizes a reserve;
+// either out-pointer may be null.  All three throw on a bad batch, naming the transcript, the position and the alternative, and the two
+// assigns on a batch beyond a capacity; the handle then still holds its previous batch.
+inline void PronunciationGraphSizes(const tdnnf_unit_set *units, int num_transcripts, const int *pos_begin, const int *pos_optional,
+                                    const int *pos_alt_begin, const float *alt_logprob, const int *alt_unit_begin, const int *alt_units,
+                                    int *states_out, int *arcs_out) {
+  Check(tdnnf_pronunciation_graph_sizes(units, num_transcripts, pos_begin, pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units, states_out,
+                                        arcs_out));
+}
+inline void AlignGraphsAssignPronunciations(tdnnf_align_graphs *graphs, const tdnnf_unit_set *units, int num_transcripts, const int *pos_begin,
+                                            const int *pos_optional, const int *pos_alt_begin, const float *alt_logprob, const int *alt_unit_begin,
+                                            const int *alt_units, tdnnf_stream stream) {
+  Check(tdnnf_align_graphs_assign_pronunciations(graphs, units, num_transcripts, pos_begin, pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units,
+                                                 stream));
+}
+inline void SupervisionAssignE2ePronunciations(tdnnf_supervision *sup, const tdnnf_unit_set *units, int num_sequences, int frames_per_sequence,
+                                               const int *pos_begin, const int *pos_optional, const int *pos_alt_begin, const float *alt_logprob,
+                                               const int *alt_unit_begin, const int *alt_units, float weight, tdnnf_stream stream) {
+  Check(tdnnf_supervision_assign_e2e_pronunciations(sup, units, num_sequences, frames_per_sequence, pos_begin, pos_optional, pos_alt_begin, alt_logprob,
+                                                    alt_unit_begin, alt_units, weight, stream));
+}
+
 // Alignment supervisions (tdnnf_hip.h, "ALIGNMENT SUPERVISIONS"): SupervisionAssign from alignments, the lattices of regular LF-MMI -- every
 // unit boundary free to move by +-tolerance output frames -- compiled on the device into a supervision of SupervisionReserve.  Sequence s is
 // the entries [unit_begin[s], unit_begin[s + 1]) of units / starts: its units (phones, of the unit set) and the output frames they start

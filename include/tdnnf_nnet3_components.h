@@ -2096,6 +2096,32 @@ inline void AssignEnd2EndSupervisionFromTranscripts(tdnnf_supervision *supervisi
                                                  slot_unit.data(), slot_optional.data(), weight, Hooks().stream);
 }
 
+// The same from transcripts whose positions (words) have several PRONUNCIATIONS (tdnnf_hip.h, "PRONUNCIATION GRAPHS"), the lexicon's
+// alternatives as one struct of the six flat arrays: transcript g is the positions [pos_begin[g], pos_begin[g + 1]) of pos_optional, position
+// P the alternatives [pos_alt_begin[P], pos_alt_begin[P + 1]) of alt_logprob, alternative Q the units [alt_unit_begin[Q], alt_unit_begin[Q + 1])
+// of alt_units.  PronunciationGraphSizes: the states and arcs of every transcript's graph, on the host, for sizing the reserve.
+struct PronunciationTranscripts {
+  std::vector<int32> pos_begin, pos_optional, pos_alt_begin, alt_unit_begin, alt_units;
+  std::vector<float> alt_logprob;
+  int32 NumTranscripts() const { return pos_begin.empty() ? 0 : static_cast<int32>(pos_begin.size()) - 1; }
+};
+inline void PronunciationGraphSizes(const tdnnf_unit_set *units, const PronunciationTranscripts &t, std::vector<int32> *states, std::vector<int32> *arcs) {
+  states->assign(t.NumTranscripts(), 0);
+  arcs->assign(states->size(), 0);
+  tdnnf_adapter::PronunciationGraphSizes(units, t.NumTranscripts(), t.pos_begin.data(), t.pos_optional.data(), t.pos_alt_begin.data(), t.alt_logprob.data(),
+                                         t.alt_unit_begin.data(), t.alt_units.data(), states->data(), arcs->data());
+}
+inline void AssignAlignGraphsFromPronunciations(tdnnf_align_graphs *graphs, const tdnnf_unit_set *units, const PronunciationTranscripts &t) {
+  tdnnf_adapter::AlignGraphsAssignPronunciations(graphs, units, t.NumTranscripts(), t.pos_begin.data(), t.pos_optional.data(), t.pos_alt_begin.data(),
+                                                 t.alt_logprob.data(), t.alt_unit_begin.data(), t.alt_units.data(), Hooks().stream);
+}
+inline void AssignEnd2EndSupervisionFromPronunciations(tdnnf_supervision *supervision, const tdnnf_unit_set *units, int32 frames_per_sequence,
+                                                       const PronunciationTranscripts &t, float weight) {
+  tdnnf_adapter::SupervisionAssignE2ePronunciations(supervision, units, t.NumTranscripts(), frames_per_sequence, t.pos_begin.data(), t.pos_optional.data(),
+                                                    t.pos_alt_begin.data(), t.alt_logprob.data(), t.alt_unit_begin.data(), t.alt_units.data(), weight,
+                                                    Hooks().stream);
+}
+
 // The supervision of regular LF-MMI from ALIGNMENTS (tdnnf_hip.h, "ALIGNMENT SUPERVISIONS"): the lattices in which every unit boundary may
 // move by +-tolerance output frames, compiled on the device into a supervision of ReserveSupervision on the hooks' stream.  Sequence s is the
 // entries [unit_begin[s], unit_begin[s + 1]) of units / starts: its phones and the output frames they start at, the first 0.

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "align_pronunciations.h"
 #include "align_tables.h"
 #include "align_transcripts.h"
 #include "assign_stage.h"
@@ -78,6 +79,22 @@ struct AlignCompileDev {
   const int *slot_begin;               // [G + 1] (device staging)
   const int *slots;                    // per slot 2 * unit + optional (device staging)
   const int *state_begin, *arc_begin;  // [G + 1] (device staging)
+  int *src, *dst, *pdf, *lp_bits;      // [arcs] device staging: what AlignBuildDev reads
+  int *label;                          // [arcs] the handle's arc labels; null for an unlabelled handle
+  float *init, *final;                 // [states] the handle's
+  AlignUnitDev units;
+};
+
+// ---- the pronunciation compile of a reserved handle (align_pron_compile.hip, align_pron_compile_kernels.h): what its kernel takes by value
+struct AlignPronCompileDev {
+  const int *pos_begin;                // [G + 1] a transcript's positions (all tables: device staging)
+  const int *pos_alt_begin;            // [positions + 1] a position's alternatives
+  const int *pos_info;                 // [positions] 2 * (the position's first state, local to its graph) + optional
+  const int *alt_unit_begin;           // [alternatives + 1] an alternative's entries
+  const int *alt_pos;                  // [alternatives] its position
+  const float *alt_logprob;            // [alternatives]
+  const int *alt_units;                // [entries]
+  const int *state_begin, *arc_begin;  // [G + 1]
   int *src, *dst, *pdf, *lp_bits;      // [arcs] device staging: what AlignBuildDev reads
   int *label;                          // [arcs] the handle's arc labels; null for an unlabelled handle
   float *init, *final;                 // [states] the handle's

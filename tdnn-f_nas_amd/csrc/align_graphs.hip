@@ -3,7 +3,8 @@
 // tdnnf_align_graphs_reserve allocates a handle once for a capacity, tdnnf_align_graphs_assign validates a batch, stages it and enqueues the
 // copies and the device build (align_build.hip) on the caller's stream; tdnnf_align_graphs_assign_transcripts does the same from unit
 // sequences (a tdnnf_unit_set; the host side in align_transcripts.h), with the compile kernel (align_compile.hip) writing the arc arrays in
-// front of the build; tdnnf_align_graphs_dump copies the device arrays of either kind out for tests.  Its readers: align.hip, align_fb.hip, align_sparse.hip, chain_num_e2e.hip.
+// front of the build, and tdnnf_align_graphs_assign_pronunciations from transcripts whose positions have alternative unit sequences
+// (align_pronunciations.h, align_pron_compile.hip); tdnnf_align_graphs_dump copies the device arrays of either kind out for tests.  Its readers: align.hip, align_fb.hip, align_sparse.hip, chain_num_e2e.hip.
 #include <math.h>
 #include <string.h>
 
@@ -193,14 +194,17 @@ int align_assign_fits(const char *who, const tdnnf_align_graphs *g, int G, int N
 int align_build_launch(const AlignBuildDev &b, int max_graph_arcs, int max_graph_rows, hipStream_t s);  // align_build.hip
 int align_compile_launch(const AlignCompileDev &c, int G, hipStream_t s);                                // align_compile.hip
 
-// The end of both assigns: the copies, the transcript compile (c, or null) and the build on s, then the host metadata of the batch (p's,
-// moved out of it).  From the first enqueued copy the device tables are being overwritten: the handle holds no batch until all of it
-// succeeded (assign_stage.h).
-static int align_commit(tdnnf_align_graphs *g, const StagePacker &pk, size_t raw_bytes, const AlignCompileDev *c, TranscriptPlan &&p, hipStream_t s) {
+int align_pron_compile_launch(const AlignPronCompileDev &c, int G, hipStream_t s);                       // align_pron_compile.hip
+
+// The end of every assign: the copies, the compile in front of the build (compile(): the transcript or pronunciation kernel's launch, or
+// nothing) and the build on s, then the host metadata of the batch (p's, moved out of it).  From the first enqueued copy the device tables are
+// being overwritten: the handle holds no batch until all of it succeeded (assign_stage.h).
+template <class Compile>
+static int align_commit(tdnnf_align_graphs *g, const StagePacker &pk, size_t raw_bytes, Compile compile, TranscriptPlan &&p, hipStream_t s) {
   const int assigns_before = g->assigns;
   g->assigns = 0;
   int rc;
-  if ((rc = g->stage.submit(pk, raw_bytes, s)) || (c && (rc = align_compile_launch(*c, g->build.G, s))) ||
+  if ((rc = g->stage.submit(pk, raw_bytes, s)) || (rc = compile()) ||
       (rc = align_build_launch(g->build, p.max_graph_arcs, p.max_graph_rows, s)))
     return rc;
   g->G = g->build.G;
@@ -306,7 +310,7 @@ int tdnnf_align_graphs_assign(tdnnf_align_graphs *g, int num_graphs, const int *
     pk.put_to(g->col_labels_dev, p.col_labels.data(), p.col_labels.size());
   }
   TDNNF_REQUIRE(pk.fits(), "%sinternal: the batch needs %zu bytes of staging, the handle has %zu", who, pk.at, pk.size);
-  return align_commit(g, pk, raw_bytes, nullptr, std::move(p), static_cast<hipStream_t>(stream));
+  return align_commit(g, pk, raw_bytes, [] { return TDNNF_OK; }, std::move(p), static_cast<hipStream_t>(stream));
 }
 
 // ---- transcript graphs: a unit set made once, and the assign that compiles a batch of transcripts on the device (align_transcripts.h,
@@ -432,7 +436,95 @@ int tdnnf_align_graphs_assign_transcripts(tdnnf_align_graphs *g, const tdnnf_uni
   }
   TDNNF_REQUIRE(pk.fits() && dev_bytes <= pk.size, "%sinternal: the batch needs %zu bytes of staging on the host and %zu on the device, the handle has %zu", who,
                 pk.at, dev_bytes, pk.size);
-  return align_commit(g, pk, raw_bytes, &c, std::move(p), static_cast<hipStream_t>(stream));
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  return align_commit(g, pk, raw_bytes, [&] { return align_compile_launch(c, G, s); }, std::move(p), s);
+}
+
+// ---- pronunciation graphs: transcripts whose positions have alternatives (align_pronunciations.h, align_pron_compile.hip)
+
+int tdnnf_pronunciation_graph_sizes(const tdnnf_unit_set *units, int num_transcripts, const int *pos_begin, const int *pos_optional, const int *pos_alt_begin,
+                                    const float *alt_logprob, const int *alt_unit_begin, const int *alt_units, int *states_out, int *arcs_out) {
+  const char *who = "pronunciation_graph_sizes: ";
+  TDNNF_REQUIRE(units, "%snull unit set", who);
+  const PronunciationBatch b = {num_transcripts, pos_begin, pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units};
+  std::string err;
+  TDNNF_REQUIRE(pronunciations_validate(who, units->host, b, &err), "%s", err.c_str());
+  for (int k = 0; k < num_transcripts; k++) {
+    const PronunciationSize z = pronunciation_graph_size(units->host.context, pos_begin[k + 1] - pos_begin[k], pos_optional + pos_begin[k],
+                                                         pos_alt_begin + pos_begin[k], alt_unit_begin);
+    TDNNF_REQUIRE(z.states < 1ll << 31 && z.arcs < 1ll << 31, "%stranscript %d has more than 2^31 states or arcs", who, k);
+    if (states_out) states_out[k] = (int)z.states;
+    if (arcs_out) arcs_out[k] = (int)z.arcs;
+  }
+  return TDNNF_OK;
+}
+
+int tdnnf_align_graphs_assign_pronunciations(tdnnf_align_graphs *g, const tdnnf_unit_set *units, int num_transcripts, const int *pos_begin,
+                                             const int *pos_optional, const int *pos_alt_begin, const float *alt_logprob, const int *alt_unit_begin,
+                                             const int *alt_units, tdnnf_stream stream) {
+  const char *who = "align_graphs_assign_pronunciations: ";
+  TDNNF_REQUIRE(g && units, "%snull graphs or null unit set", who);
+  const bool labelled = g->L > 0;  // (the batch brings the labels the handle wants: an arc's is the entry of its destination)
+  int rc;
+  if ((rc = align_assign_handle(who, g, labelled))) return rc;
+  TDNNF_REQUIRE(units->host.P == g->P, "%sthe unit set names %d pdfs, the handle was reserved for num_pdfs %d", who, units->host.P, g->P);
+  const PronunciationBatch batch = {num_transcripts, pos_begin, pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units};
+  std::string err;
+  TDNNF_REQUIRE(pronunciations_validate(who, units->host, batch, &err), "%s", err.c_str());
+  PronunciationPlan p;
+  TDNNF_REQUIRE(pronunciations_plan(who, units->host, batch, labelled, &p, &err), "%s", err.c_str());
+  const int G = num_transcripts, NS = p.state_begin[G], NA = p.arc_begin[G];
+  const int NP = pos_begin[G], NQ = pos_alt_begin[NP], NE = alt_unit_begin[NQ];
+  TDNNF_REQUIRE(!labelled || p.max_entries <= g->L,
+                "%sthe largest transcript has %d entries (units of its alternatives), and an entry is a label: the handle's num_labels = %d is short by %d", who,
+                p.max_entries, g->L, p.max_entries - g->L);
+  if ((rc = align_assign_fits(who, g, G, NS, NA))) return rc;
+
+  StagePacker pk;
+  if ((rc = g->stage.begin(&pk))) return rc;
+  AlignBuildDev &b = g->build;
+  AlignPronCompileDev c;
+  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(g->stage.dev + pk.put(v, n)); };
+  b.G = G;
+  b.state_begin = c.state_begin = raw(p.state_begin.data(), (size_t)G + 1);
+  b.arc_begin = c.arc_begin = raw(p.arc_begin.data(), (size_t)G + 1);
+  b.col_begin = raw(p.col_begin.data(), (size_t)G + 1);
+  b.lcol_begin = raw(p.lcol_begin.data(), labelled ? (size_t)G + 1 : 0);
+  c.pos_begin = raw(pos_begin, (size_t)G + 1);
+  c.pos_alt_begin = raw(pos_alt_begin, (size_t)NP + 1);
+  c.pos_info = raw(p.pos_info.data(), NP);
+  c.alt_unit_begin = raw(alt_unit_begin, (size_t)NQ + 1);
+  c.alt_pos = raw(p.alt_pos.data(), NQ);
+  c.alt_logprob = reinterpret_cast<const float *>(raw(alt_logprob, NQ));
+  c.alt_units = raw(alt_units, NE);
+  // The staging's two shapes, as the transcript assign's: on the host the tables above and the column lists; on the device the tables, behind
+  // them the four arc arrays the kernel writes.  Both fit what tdnnf_align_graphs_reserve sized (28 bytes an arc, 8 a state, 24 a graph and
+  // 16): the tables are at most pronunciations_raw_ints = 5 G + 7 + 2 positions + 3 alternatives + entries ints with positions <=
+  // alternatives <= entries; every entry has a state beside the start (states >= G + entries), every entry has its loop and every first
+  // entry's state an arc that enters it (arcs >= entries + alternatives).  So 3 arcs + 2 states + G >= 5 entries + 3 alternatives + 3 G
+  // covers the tables behind the begins on the device, where 4 ints an arc follow; on the host the column lists are at most arcs + entries
+  // ints and the four arc arrays are absent.  The check below refuses by name what this does not cover.
+  const size_t raw_bytes = pk.at, dev_bytes = raw_bytes + 4 * sizeof(int) * (size_t)NA;
+  int *arcs = reinterpret_cast<int *>(g->stage.dev + raw_bytes);  // (device only)
+  b.src = c.src = arcs;
+  b.dst = c.dst = arcs + NA;
+  b.pdf = c.pdf = arcs + 2 * (size_t)NA;
+  b.lp_bits = c.lp_bits = arcs + 3 * (size_t)NA;
+  c.label = labelled ? const_cast<int *>(g->arc_label_dev) : nullptr;
+  c.init = const_cast<float *>(g->dev.init);
+  c.final = const_cast<float *>(g->dev.final);
+  c.units = units->dev;
+  pk.put_to(g->num_cols_dev, p.num_cols.data(), p.num_cols.size());
+  pk.put_to(g->col_pdfs_dev, p.col_pdfs.data(), p.col_pdfs.size());
+  if (labelled) {
+    pk.put_to(g->num_lcols_dev, p.num_lcols.data(), p.num_lcols.size());
+    pk.put_to(g->col_labels_dev, p.col_labels.data(), p.col_labels.size());
+  }
+  TDNNF_REQUIRE(pk.fits() && dev_bytes <= pk.size,
+                "%sthe batch needs %zu bytes of staging on the host and %zu on the device, the handle's staging for max_states = %d and max_arcs = %d has %zu", who, pk.at,
+                dev_bytes, g->cap_states, g->cap_arcs, pk.size);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  return align_commit(g, pk, raw_bytes, [&] { return align_pron_compile_launch(c, G, s); }, std::move(p), s);
 }
 
 int tdnnf_align_graphs_capacity(const tdnnf_align_graphs *g, int *max_graphs, int *max_states, int *max_arcs, long long *device_bytes, int *device_allocs,

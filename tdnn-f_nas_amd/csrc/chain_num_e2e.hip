@@ -219,6 +219,26 @@ int tdnnf_supervision_assign_e2e_transcripts(tdnnf_supervision *sp, const tdnnf_
   return e2e_assign_finish(who, sp, B, T, weight, max_states, [&] { return tdnnf_align_graphs_assign_transcripts(sp->e2e_graphs, units, B, slot_begin, slot_unit, slot_optional, stream); });
 }
 
+int tdnnf_supervision_assign_e2e_pronunciations(tdnnf_supervision *sp, const tdnnf_unit_set *units, int B, int T, const int *pos_begin, const int *pos_optional,
+                                                const int *pos_alt_begin, const float *alt_logprob, const int *alt_unit_begin, const int *alt_units, float weight,
+                                                tdnnf_stream stream) {
+  const char *who = "supervision_assign_e2e_pronunciations: ";
+  if (int rc = e2e_assign_check(who, sp, units != nullptr, B, T)) return rc;
+  // this minibatch's largest graph: the closed forms of align_pronunciations.h
+  const PronunciationBatch batch = {B, pos_begin, pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units};
+  std::string err;
+  TDNNF_REQUIRE(pronunciations_validate(who, units->host, batch, &err), "%s", err.c_str());
+  long long max_states = 0;
+  for (int s = 0; s < B; s++)
+    max_states = std::max(max_states, pronunciation_graph_size(units->host.context, pos_begin[s + 1] - pos_begin[s], pos_optional + pos_begin[s],
+                                                               pos_alt_begin + pos_begin[s], alt_unit_begin).states);
+  TDNNF_REQUIRE(max_states < 1ll << 31, "%sa transcript has more than 2^31 states", who);
+  // (the assign checks the capacities max_states and max_arcs and the unit set's num_pdfs; a refusal leaves everything as it was)
+  return e2e_assign_finish(who, sp, B, T, weight, (int)max_states, [&] {
+    return tdnnf_align_graphs_assign_pronunciations(sp->e2e_graphs, units, B, pos_begin, pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units, stream);
+  });
+}
+
 int tdnnf_supervision_kind(const tdnnf_supervision *sp) {
   if (!sp) {
     set_error("supervision_kind: null supervision");

@@ -239,6 +239,29 @@ def _slots(transcripts):
     return iarr(begin), iarr(cat(0)), iarr(cat(1) != 0)
 
 
+def _pronunciations(transcripts):
+    """A batch of transcripts with pronunciation alternatives -- each (positions, optional[, alt_logprob]): positions[p] a list of unit
+    sequences, optional[p] a flag, alt_logprob[p] a list of floats (default 0) -- as the six arrays of the C entries: (pos_begin,
+    pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units), each an (array, pointer) pair of iarr / farr."""
+    pos_begin, pos_optional, pos_alt_begin, alt_logprob, alt_unit_begin, alt_units = [0], [], [0], [], [0], []
+    for g, t in enumerate(transcripts):
+        positions, optional = t[0], t[1]
+        logprob = t[2] if len(t) > 2 and t[2] is not None else [[0.0] * len(pos) for pos in positions]
+        if len(positions) != len(optional) or len(logprob) != len(positions):
+            raise HipAbiError(f"transcript {g}: {len(positions)} positions, {len(optional)} optional flags and {len(logprob)} rows of alt_logprob")
+        for p, (pos, row) in enumerate(zip(positions, logprob)):
+            if len(pos) != len(row):
+                raise HipAbiError(f"transcript {g} position {p}: {len(pos)} alternatives and {len(row)} alt_logprob")
+            for alt, lp in zip(pos, row):
+                alt_units.extend(int(u) for u in alt)
+                alt_unit_begin.append(len(alt_units))
+                alt_logprob.append(float(lp))
+            pos_alt_begin.append(len(alt_logprob))
+            pos_optional.append(1 if optional[p] else 0)
+        pos_begin.append(len(pos_optional))
+    return iarr(pos_begin), iarr(pos_optional), iarr(pos_alt_begin), farr(alt_logprob), iarr(alt_unit_begin), iarr(alt_units)
+
+
 def _alignments(alignments):
     """A minibatch of alignments -- each a (units, starts) pair of int sequences of one length: the units of a sequence and the output
     frames they start at -- as the three arrays of the C entries: (unit_begin, units, starts), each an (array, pointer) pair of iarr."""
@@ -280,6 +303,17 @@ class UnitSet:
         states, arcs = np.zeros(len(begin[0]) - 1, np.int32), np.zeros(len(begin[0]) - 1, np.int32)
         check(load().tdnnf_transcript_graph_sizes(self.h, len(states), begin[1], unit[1], opt[1], states.ctypes.data_as(C.c_void_p),
                                                   arcs.ctypes.data_as(C.c_void_p)))
+        return states, arcs
+
+    def pronunciation_sizes(self, transcripts):
+        """tdnnf_pronunciation_graph_sizes (host only): (states, arcs), numpy int32 arrays with one entry per transcript with pronunciation
+        alternatives ((positions, optional[, alt_logprob])) -- what a reserve must cover.  Refuses (HipAbiError) what assign_pronunciations
+        refuses."""
+        import numpy as np
+        k = _pronunciations(transcripts)
+        states, arcs = np.zeros(len(k[0][0]) - 1, np.int32), np.zeros(len(k[0][0]) - 1, np.int32)
+        check(load().tdnnf_pronunciation_graph_sizes(self.h, len(states), *[x[1] for x in k], states.ctypes.data_as(C.c_void_p),
+                                                     arcs.ctypes.data_as(C.c_void_p)))
         return states, arcs
 
     def alignment_sizes(self, alignments, frames_per_sequence, tolerance):
@@ -401,6 +435,15 @@ class Supervision:
         check(load().tdnnf_supervision_assign_e2e_transcripts(self.h, unit_set.h, len(begin[0]) - 1, int(frames_per_sequence), begin[1], unit[1], opt[1],
                                                               float(weight), stream()))
         self.B, self.T = len(begin[0]) - 1, int(frames_per_sequence)
+
+    def assign_pronunciations(self, unit_set, transcripts, frames_per_sequence, weight=1.0):
+        """tdnnf_supervision_assign_e2e_pronunciations on the current stream: assign with the graphs compiled on the device from one
+        (positions, optional[, alt_logprob]) transcript per sequence, positions[p] the list of unit sequences that pronounce position p
+        (UnitSet).  A refused minibatch (HipAbiError) leaves the previous one."""
+        k = _pronunciations(transcripts)
+        check(load().tdnnf_supervision_assign_e2e_pronunciations(self.h, unit_set.h, len(k[0][0]) - 1, int(frames_per_sequence), *[x[1] for x in k],
+                                                                 float(weight), stream()))
+        self.B, self.T = len(k[0][0]) - 1, int(frames_per_sequence)
 
     def assign_alignments(self, unit_set, alignments, frames_per_sequence, tolerance, weight=1.0):
         """tdnnf_supervision_assign_alignments on the current stream: the next minibatch of a supervision of reserve, its lattices compiled
@@ -542,6 +585,22 @@ class AlignGraphs:
         on = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
         check(load().tdnnf_align_graphs_assign_transcripts(self.h, unit_set.h, len(begin[0]) - 1, begin[1], unit[1], opt[1], on))
         states, arcs = unit_set.sizes(transcripts)
+        self.G, self._keep = len(states), []
+        self.num_states = [int(s) for s in states]
+        self.arc_begin = np.concatenate([[0], np.cumsum(arcs)]).astype(np.int64)
+
+    def assign_pronunciations(self, unit_set, transcripts, stream=None):
+        """tdnnf_align_graphs_assign_pronunciations: the handle's next batch compiled on the device from transcripts with pronunciation
+        alternatives -- each (positions, optional[, alt_logprob]), positions[p] a list of unit sequences (UnitSet) -- in stream order as
+        assign; on a labelled handle an arc's label is the entry it enters, the entries numbered in flat order (position, alternative,
+        unit).  G, num_states and arc_begin follow the new batch.  A refused batch (HipAbiError) leaves the handle and this object on the
+        previous one."""
+        import numpy as np
+        import torch
+        k = _pronunciations(transcripts)
+        on = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+        check(load().tdnnf_align_graphs_assign_pronunciations(self.h, unit_set.h, len(k[0][0]) - 1, *[x[1] for x in k], on))
+        states, arcs = unit_set.pronunciation_sizes(transcripts)
         self.G, self._keep = len(states), []
         self.num_states = [int(s) for s in states]
         self.arc_begin = np.concatenate([[0], np.cumsum(arcs)]).astype(np.int64)

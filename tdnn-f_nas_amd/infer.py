@@ -414,6 +414,40 @@ def alignment_from_path(slots_per_frame, transcript):
     return units[runs].astype(np.int32), starts.astype(np.int32)
 
 
+def alignment_from_pronunciation_path(entries_per_frame, transcript):
+    """alignment_from_path for a transcript with pronunciation alternatives: entries_per_frame, one int per frame, is the label output of
+    AlignGraphs.best_path_labels through a handle assigned with assign_pronunciations (an arc's label is the entry it enters, the entries
+    numbered in flat order: position, alternative, unit); transcript the utterance's (positions, optional[, alt_logprob]).  Returns (units,
+    starts, chosen): int32 arrays with one entry per run of equal labels -- the entry's unit and the run's first frame, ready for
+    Supervision.assign_alignments -- and chosen[p], the alternative the path took at position p, -1 for a skipped optional position.
+    Pure numpy; ValueError for a path that is not one: no frames, a -1 of an utterance without an accepting path, an entry outside the
+    transcript, an alternative entered elsewhere than at its first unit or left before its last, positions that do not increase or that
+    skip a mandatory one."""
+    entries = np.asarray(entries_per_frame.detach().cpu().numpy() if hasattr(entries_per_frame, "detach") else entries_per_frame, dtype=np.int64).reshape(-1)
+    positions, optional = transcript[0], transcript[1]
+    of_entry = [(p, a, j, int(u), len(alt)) for p, pos in enumerate(positions) for a, alt in enumerate(pos) for j, u in enumerate(alt)]
+    if len(entries) == 0:
+        raise ValueError("alignment_from_pronunciation_path: no frames")
+    starts = np.concatenate([[0], 1 + np.flatnonzero(entries[1:] != entries[:-1])])
+    runs = entries[starts]
+    if runs.min() < 0 or runs.max() >= len(of_entry):
+        raise ValueError(f"alignment_from_pronunciation_path: the entries of the runs, {runs.tolist()}, are not all among the transcript's {len(of_entry)}")
+    chosen = np.full(len(positions), -1, np.int32)
+    before = None  # the entry of the run before
+    for e in runs:
+        p, a, j, _, _ = of_entry[e]
+        inside = before is not None and before[:2] == (p, a) and before[2] + 1 == j
+        enters = j == 0 and (before is None or (before[2] + 1 == before[4] and before[0] < p))
+        if not (inside or enters):
+            raise ValueError(f"alignment_from_pronunciation_path: the entries of the runs, {runs.tolist()}, are not a walk through the transcript "
+                             f"(at entry {int(e)}: position {p}, alternative {a}, unit {j})")
+        chosen[p] = a
+        before = of_entry[e]
+    if before[2] + 1 != before[4] or any(chosen[p] < 0 and not optional[p] for p in range(len(positions))):
+        raise ValueError(f"alignment_from_pronunciation_path: the path ends inside an alternative or skips a mandatory position (chosen {chosen.tolist()})")
+    return np.asarray([of_entry[e][3] for e in runs], np.int32), starts.astype(np.int32), chosen
+
+
 def write_int_vector_archive(path, items):
     """Kaldi binary archive of vector<int32>: per item `key ' ' \\0B \\4 n` then n little-endian int32 (WriteIntegerVector; the intvec
     encoding of include/tdnnf_kaldi_io.h, what the egs reader takes for <AlignmentPdfs>); what ali-to-pdf writes and copy-int-vector

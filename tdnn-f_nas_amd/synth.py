@@ -455,3 +455,26 @@ def make_transcripts(B, U, slots=(1, 8), optional_rate=0.3, seed=0):
             opt[0] = 0
         out.append((units, opt))
     return out
+
+
+def make_pronunciation_transcripts(B, U, positions=(1, 6), alternatives=(1, 3), units=(1, 3), optional_rate=0.3, seed=0):
+    """B transcripts with pronunciation alternatives for hipabi.UnitSet: each (positions, optional, alt_logprob) -- lo .. hi positions,
+    positions[p] a list of lo .. hi alternatives, each an int32 array of lo .. hi units at random from U; optional[p] as make_transcripts
+    draws it (never two adjacent, one position mandatory at least); alt_logprob[p] one multiple of 1/8 in [-2, 0] per alternative, so that
+    sums of a few weights are exact in float32."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(B):
+        n = int(rng.integers(positions[0], positions[1] + 1))
+        pos, logprob = [], []
+        for _ in range(n):
+            A = int(rng.integers(alternatives[0], alternatives[1] + 1))
+            pos.append([rng.integers(0, U, size=int(rng.integers(units[0], units[1] + 1))).astype(np.int32) for _ in range(A)])
+            logprob.append((-rng.integers(0, 17, size=A) / 8.0).astype(np.float32))
+        opt = np.zeros(n, np.int32)
+        for k in range(n):
+            opt[k] = int(rng.random() < optional_rate and not (k and opt[k - 1]))
+        if opt.all():  # (n = 1)
+            opt[0] = 0
+        out.append((pos, opt, logprob))
+    return out

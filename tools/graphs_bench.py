@@ -11,11 +11,13 @@ The clock is the host's around a loop over the cycle that ends in ONE synchronis
 --repeats.  After the timing every batch of the cycle runs once either way and the outputs are compared for equality.  One JSON line.
 --transcripts: instead, the cost of a new batch for a caller who starts from transcripts (see transcripts() below): arc arrays built on the
 host + assign, assign alone, and tdnnf_align_graphs_assign_transcripts / tdnnf_supervision_assign_e2e_transcripts, alternating.
+--pronunciations: instead, the same for transcripts with pronunciation alternatives (see pronunciations() below): statement-style arc arrays
+built on the host + assign, assign alone, and tdnnf_align_graphs_assign_pronunciations, alternating.
 --supervision [--tolerance N --alternatives N]: instead, the time-synchronous supervision of regular LF-MMI (see supervision() below):
 tdnnf_supervision_create + tdnnf_chain_objf_and_deriv + tdnnf_supervision_destroy against tdnnf_supervision_assign + the same call.
 --supervision --alignment [--tolerance N]: instead, the same supervision for a caller who starts from alignments (see alignment() below):
 the lattice built on the host + tdnnf_supervision_assign, assign alone, and tdnnf_supervision_assign_alignments, alternating.
-usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts]
+usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts] [--pronunciations]
                                               [--supervision [--tolerance N --alternatives N] [--sequences B --frames T]]
                                               [--supervision --alignment [--tolerance N] [--sequences B --frames T]]"""
 import argparse
@@ -125,6 +127,94 @@ def transcripts(args, pkg):
                                                          abi.ptr(ws), nb, s)),
          list(out))
     lib.tdnnf_supervision_destroy(sup)
+    print(json.dumps(res))
+
+
+def pronunciations(args, pkg):
+    """--pronunciations: what a new batch of graph tables costs when the caller starts from transcripts with PRONUNCIATION ALTERNATIVES,
+    three ways, alternating in one process, a different batch every iteration, medians of --repeats; the clock stops behind one synchronise
+    after the cycle's assigns (no alignment call: the tables are the product):
+      host_graphs_assign     (a) the arc arrays made on the host as the numpy statement makes them (tests/pronunciation_graphs_ref.py
+                             pronunciation_graph: a Python walk over states and arcs, then stacked), tdnnf_align_graphs_assign -- the
+                             only route before tdnnf_align_graphs_assign_pronunciations;
+      assign                 (b) assign from arrays made outside the timed region: the assign's own cost, the control;
+      assign_pronunciations  (c) tdnnf_align_graphs_assign_pronunciations from the six flat arrays.
+    Two shapes, context 1, 42 units, alternatives of 3 units, 1 or 2 a position (mean 1.5): 128 transcripts of 11 to 13 positions, and
+    64 of 39 to 41.  Also the bytes each route stages on the host, and the host time of the assign_pronunciations call alone.  After the
+    timing the device tables of (b) and (c) are compared for equality on every batch of the cycle.  One JSON line."""
+    from tests import pronunciation_graphs_ref as ref
+    abi, synth = pkg.hipabi, pkg.synth
+    lib = abi.load()
+    P, U = args.pdfs, 42
+    us = synth.make_unit_set(U, context=1, seed=1, distinct=False, P=P)
+    units = abi.UnitSet(us["entry_pdf"], us["loop_pdf"], us["loop_logprob"], us["leave_logprob"], P, us["take_logprob"], us["skip_logprob"])
+    res = dict(metric="pronunciations_per_batch", pdfs=P, cycle=args.cycle, repeats=args.repeats, units=U, context=1)
+    s = abi.stream()
+    keys = ("S", "P", "src", "dst", "pdf", "logprob", "init", "final")
+
+    def host_graphs(batch):
+        return abi.Supervision._stack_e2e([{k: g[k] for k in keys} for g in (ref.pronunciation_graph(us, t) for t in batch)])[1]
+
+    def case(name, B, positions):
+        batches = [synth.make_pronunciation_transcripts(B, U, positions=positions, alternatives=(1, 2), units=(3, 3), optional_rate=0.15, seed=100 + c)
+                   for c in range(args.cycle)]
+        flat = [abi._pronunciations(b) for b in batches]
+        stacked = [host_graphs(b) for b in batches]
+        NS, NA = int(max(k[0][0][-1] for k in stacked)), int(max(k[1][0][-1] for k in stacked))
+        graphs = abi.AlignGraphs.reserve(B, P, NS, NA)
+
+        def assign(k):
+            abi.check(lib.tdnnf_align_graphs_assign(graphs.h, B, *[x[1] for x in k], None, s))
+
+        def assign_pronunciations(i):
+            abi.check(lib.tdnnf_align_graphs_assign_pronunciations(graphs.h, units.h, B, *[x[1] for x in flat[i]], s))
+
+        fns = dict(host_graphs_assign=lambda i: assign(host_graphs(batches[i])), assign=lambda i: assign(stacked[i]), assign_pronunciations=assign_pronunciations)
+
+        def loop(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(args.cycle):
+                fn(i)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / args.cycle
+
+        ms = {k: [] for k in fns}
+        for r in range(args.repeats + 1):  # the first round warms up
+            for k, fn in fns.items():
+                t = loop(fn)
+                if r:
+                    ms[k].append(t)
+        host_ms = []
+        for i in range(args.cycle):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            assign_pronunciations(i)
+            host_ms.append(1e3 * (time.perf_counter() - t0))
+        equal = True
+        for i in range(args.cycle):
+            tables = []
+            for k in ("assign", "assign_pronunciations"):
+                fns[k](i)
+                graphs.G = B
+                tables.append(graphs.tables())
+            flatten = lambda t: [v for x in t.values() for v in (x.values() if isinstance(x, dict) else [x])]
+            equal = equal and all(np.array_equal(x, z) for x, z in zip(flatten(tables[0]), flatten(tables[1])))
+        # what the two routes stage on the host per batch (the largest of the cycle): assign 28 bytes an arc, 8 a state and the begins;
+        # assign_pronunciations the six flat arrays, two ints a position and one an alternative more, and the begins
+        entries = max(len(f[5][0]) for f in flat)
+        staged = max(4 * (5 * (B + 1) + 2 * len(f[1][0]) + 1 + 3 * len(f[3][0]) + 1 + len(f[5][0])) for f in flat)
+        d = dict(transcripts=B, positions=list(positions), entries=entries, states=NS, arcs=NA, tables_equal=bool(equal),
+                 staged_bytes_assign=4 * (4 * (B + 1) + 4 * NA + 2 * NS), staged_bytes_assign_pronunciations=staged,
+                 assign_pronunciations_host=round(float(np.median(host_ms)), 3))
+        for k, v in ms.items():
+            d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v])
+        d["pronunciations_over_host_graphs"] = round(d["assign_pronunciations"]["ms"] / d["host_graphs_assign"]["ms"], 4)
+        d["pronunciations_over_assign"] = round(d["assign_pronunciations"]["ms"] / d["assign"]["ms"], 3)
+        res[name] = d
+
+    case("128x12", 128, (11, 13))
+    case("64x40", 64, (39, 41))
     print(json.dumps(res))
 
 
@@ -356,6 +446,8 @@ def main():
     ap.add_argument("--pdfs", type=int, default=6034)
     ap.add_argument("--only", choices=["forced", "free", "numerator"])
     ap.add_argument("--transcripts", action="store_true", help="graphs from transcripts: host-built arrays + assign against assign_transcripts")
+    ap.add_argument("--pronunciations", action="store_true",
+                    help="graphs from transcripts with pronunciation alternatives: host-built arrays + assign against assign_pronunciations")
     ap.add_argument("--supervision", action="store_true", help="time-synchronous supervisions: create + call + destroy against assign + call")
     ap.add_argument("--tolerance", type=int, default=0, help="--supervision: > 0 tolerance lattices (synth.make_supervision_lattice)")
     ap.add_argument("--alignment", action="store_true",
@@ -370,6 +462,8 @@ def main():
         return alignment(args, pkg) if args.alignment else supervision(args, pkg)
     if args.transcripts:
         return transcripts(args, pkg)
+    if args.pronunciations:
+        return pronunciations(args, pkg)
     abi, synth = pkg.hipabi, pkg.synth
     lib = abi.load()
     P = args.pdfs
