@@ -721,6 +721,47 @@ int tdnnf_alignment_supervision_sizes(const tdnnf_unit_set *, int num_sequences,
 int tdnnf_supervision_assign_alignments(tdnnf_supervision *, const tdnnf_unit_set *, int num_sequences, int frames_per_sequence,
                                         const int *unit_begin, const int *units, const int *starts, int tolerance, float weight,
                                         tdnnf_stream stream);
+/* ALIGNMENT CHUNKS: the supervision of a fixed-length chunk cut out of an utterance, compiled on the device from the alignment of the
+   WHOLE utterance -- what regular LF-MMI trains on (chunks of 150 output frames in the recipes).  A chunk may begin and end in the middle of
+   a unit, and boundaries that lie outside it may still be moved into it by the tolerance; Kaldi's SupervisionSplitter::GetFrameRange,
+   before its determinisation.
+   Sequence s is given by the alignment of its utterance -- the entries [unit_begin[s], unit_begin[s + 1]) of `units` and `starts`, exactly
+   what "ALIGNMENT SUPERVISIONS" takes with T replaced by utt_frames[s]: n >= 1 units, b_0 = 0 < b_1 < ... < utt_frames[s] -- and by
+   chunk_begin[s] = o with 0 <= o and o + T <= utt_frames[s], T = frames_per_sequence common to the minibatch.  Two chunks of one utterance
+   are two sequences that repeat its alignment.  Refused with TDNNF_EINVAL naming the sequence: everything "ALIGNMENT SUPERVISIONS"
+   refuses, utt_frames[s] < 1, chunk_begin[s] < 0, chunk_begin[s] + T > utt_frames[s].
+   Let U be the utterance's lattice as defined above: the windows from `tolerance`, tightened over the whole utterance, states E(t, k) and
+   L(t, k).  The chunk's lattice:
+     states   a new start at time 0, then every state of U with time t in [o + 1, o + T], in U's order (time, then all E by unit, then all L
+              by unit), re-timed to t - o.
+     arcs     every arc of U between two kept states, unchanged; and out of the start one arc to every kept state of time o + 1, in state
+              order, with the pdf that all arcs into that state carry in U: for E(o + 1, k) the entry pdf at (u_k-1 or -1, u_k), for
+              L(o + 1, k) the loop pdf at (u_k-1 or -1, u_k).  (Context 0 reads both tables at the unit alone.)  For o = 0 this is the one arc
+              into E(1, 0).  Every arc_logprob is 0; ordered by (source, destination).
+     final    0 on every state of time o + T, -inf elsewhere; for o + T = utt_frames[s] these are the states of unit n - 1 only.
+   o = 0 and T = utt_frames[s] give U itself, and the bytes tdnnf_supervision_assign_alignments builds.  The accepting paths of a chunk are
+   exactly the restrictions to [o, o + T) of U's accepting paths (every state of U lies on one, so nothing has to be trimmed).
+   tdnnf_alignment_chunk_supervision_sizes is host-only: the states and arcs of every chunk's lattice (either out-pointer may be NULL), for
+   sizing a reserve; it refuses what the assign refuses with the same messages under its own name.
+   tdnnf_supervision_assign_alignment_chunks is tdnnf_supervision_assign_alignments from chunks: supervisions of tdnnf_supervision_reserve
+   only.  The host works in O(units of the utterances + sequences * (frames + 2)): the utterance's windows, the frames o + 1 .. o + T from the
+   same closed form (csrc/chain_sup_alignment.h), and from them the begins, frame_state_begin, the counts, the widths and `wide`; then the
+   four capacities, named with their excess as assign names them.  It stages, per sequence, only the units the chunk's frames can name and
+   their neighbours (12 bytes each) and 16 bytes of scalars.  The reserve's sizes stay as they are, and short chunks can need more staging
+   than it made for 8 bytes a state and 16 an arc (a one-frame chunk has 2 states, 1 arc and up to 3 staged units): such a minibatch is
+   refused, TDNNF_EINVAL naming the shortfall in bytes.  All of it before anything is written: a refused call leaves the previous
+   minibatch.  Then the copies, the ONE compile kernel of tdnnf_supervision_assign_alignments (csrc/chain_sup_compile_kernels.h: a whole
+   alignment is its chunk o = 0) and the two unchanged build kernels on `stream`.  No allocation, no free, no device-wide or stream-wide
+   wait; stream order, tdnnf_supervision_capacity's `assigns` and the failure rule are tdnnf_supervision_assign's (a refusal leaves the
+   previous minibatch, an error of the runtime none), and all three kinds of assign may alternate on one handle.
+   Not built: frame-subsampling of a frame-rate alignment, chunks shorter than T at an utterance's end, sharing one utterance's units
+   between sequences, determinisation, composition with a normalisation FST, capture into a HIP graph. */
+int tdnnf_alignment_chunk_supervision_sizes(const tdnnf_unit_set *, int num_sequences, int frames_per_sequence, const int *unit_begin,
+                                            const int *units, const int *starts, const int *utt_frames, const int *chunk_begin, int tolerance,
+                                            int *states_out, int *arcs_out);
+int tdnnf_supervision_assign_alignment_chunks(tdnnf_supervision *, const tdnnf_unit_set *, int num_sequences, int frames_per_sequence,
+                                              const int *unit_begin, const int *units, const int *starts, const int *utt_frames,
+                                              const int *chunk_begin, int tolerance, float weight, tdnnf_stream stream);
 /* diagnostics (tests): a copy-out of the device arrays of a created or an assigned handle, as ints, after waiting for the stream of the last
    assign.  table 0 by destination, 1 by source, 2 by pdf, 3 by label (labelled handles): which 0 the slots, 1 the heavy-row descriptors,
    2 the arc entries, 4 ints each.  table 4: which 0 the graph descriptors (14 ints a graph), 1 the by-label ranges (4 ints a graph), 2 the

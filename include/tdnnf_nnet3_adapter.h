@@ -495,6 +495,26 @@ inline void SupervisionAssignAlignments(tdnnf_supervision *sup, const tdnnf_unit
   Check(tdnnf_supervision_assign_alignments(sup, units, num_sequences, frames_per_sequence, unit_begin, unit, starts, tolerance, weight, stream));
 }
 
+// Alignment chunks (tdnnf_hip.h, "ALIGNMENT CHUNKS"): the supervisions of fixed-length chunks, what nnet3-chain-get-egs cuts out of an
+// utterance's supervision (SupervisionSplitter::GetFrameRange, before its determinisation), compiled on the device from the alignment of the
+// WHOLE utterance.  Sequence s is the output frames [chunk_begin[s], chunk_begin[s] + frames_per_sequence) of an utterance of utt_frames[s]
+// output frames, whose units and starts are the entries [unit_begin[s], unit_begin[s + 1]) of units / starts; two chunks of one utterance
+// repeat its alignment.  AlignmentChunkSupervisionSizes: the states and arcs of every chunk's lattice on the host, for the reserve (either
+// out-pointer may be null).  Both throw on a bad alignment or chunk, naming the sequence; the assign also on a minibatch beyond a capacity
+// or beyond the reserve's staging (many very short chunks: reserve more states), and the supervision then still holds its previous minibatch.
+inline void AlignmentChunkSupervisionSizes(const tdnnf_unit_set *units, int num_sequences, int frames_per_sequence, const int *unit_begin,
+                                           const int *unit, const int *starts, const int *utt_frames, const int *chunk_begin, int tolerance,
+                                           int *states_out, int *arcs_out) {
+  Check(tdnnf_alignment_chunk_supervision_sizes(units, num_sequences, frames_per_sequence, unit_begin, unit, starts, utt_frames, chunk_begin, tolerance,
+                                                states_out, arcs_out));
+}
+inline void SupervisionAssignAlignmentChunks(tdnnf_supervision *sup, const tdnnf_unit_set *units, int num_sequences, int frames_per_sequence,
+                                             const int *unit_begin, const int *unit, const int *starts, const int *utt_frames,
+                                             const int *chunk_begin, int tolerance, float weight, tdnnf_stream stream) {
+  Check(tdnnf_supervision_assign_alignment_chunks(sup, units, num_sequences, frames_per_sequence, unit_begin, unit, starts, utt_frames, chunk_begin,
+                                                  tolerance, weight, stream));
+}
+
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance

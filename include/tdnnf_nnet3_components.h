@@ -2142,6 +2142,32 @@ inline void AssignSupervisionFromAlignments(tdnnf_supervision *supervision, cons
                                              unit.data(), starts.data(), tolerance, weight, Hooks().stream);
 }
 
+// The same supervision for CHUNKS of utterances (tdnnf_hip.h, "ALIGNMENT CHUNKS"): sequence s is the output frames
+// [chunk_begin[s], chunk_begin[s] + frames_per_sequence) of an utterance of utt_frames[s] output frames, and the entries
+// [unit_begin[s], unit_begin[s + 1]) of units / starts are the alignment of that WHOLE utterance (two chunks of one utterance repeat it).
+// AlignmentChunkSupervisionSizes: the states and arcs of every chunk's lattice, on the host, for sizing the reserve.
+inline void AlignmentChunkSupervisionSizes(const tdnnf_unit_set *units, int32 frames_per_sequence, const std::vector<int32> &unit_begin,
+                                           const std::vector<int32> &unit, const std::vector<int32> &starts, const std::vector<int32> &utt_frames,
+                                           const std::vector<int32> &chunk_begin, int32 tolerance, std::vector<int32> *states,
+                                           std::vector<int32> *arcs) {
+  const int32 num_sequences = unit_begin.empty() ? 0 : static_cast<int32>(unit_begin.size()) - 1;
+  states->assign(num_sequences > 0 ? num_sequences : 0, 0);
+  arcs->assign(states->size(), 0);
+  if (utt_frames.size() != states->size() || chunk_begin.size() != states->size())
+    throw std::runtime_error("tdnnf: AlignmentChunkSupervisionSizes: utt_frames and chunk_begin must have one entry a sequence");
+  tdnnf_adapter::AlignmentChunkSupervisionSizes(units, num_sequences, frames_per_sequence, unit_begin.data(), unit.data(), starts.data(), utt_frames.data(),
+                                                chunk_begin.data(), tolerance, states->data(), arcs->data());
+}
+inline void AssignSupervisionFromAlignmentChunks(tdnnf_supervision *supervision, const tdnnf_unit_set *units, int32 frames_per_sequence,
+                                                 const std::vector<int32> &unit_begin, const std::vector<int32> &unit, const std::vector<int32> &starts,
+                                                 const std::vector<int32> &utt_frames, const std::vector<int32> &chunk_begin, int32 tolerance,
+                                                 float weight) {
+  if (utt_frames.size() + 1 != unit_begin.size() || chunk_begin.size() + 1 != unit_begin.size())
+    throw std::runtime_error("tdnnf: AssignSupervisionFromAlignmentChunks: utt_frames and chunk_begin must have one entry a sequence");
+  tdnnf_adapter::SupervisionAssignAlignmentChunks(supervision, units, static_cast<int32>(unit_begin.size()) - 1, frames_per_sequence, unit_begin.data(),
+                                                  unit.data(), starts.data(), utt_frames.data(), chunk_begin.data(), tolerance, weight, Hooks().stream);
+}
+
 // ------------------------------------------------------------------------------------------------ best-path alignment
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames

@@ -2,7 +2,8 @@
 // once for four capacities, tdnnf_supervision_assign validates a minibatch on the host (chain_sup_tables.h), stages its raw arrays in pinned
 // memory and enqueues the copies and the device build (chain_sup_build_kernels.h) on the caller's stream -- nothing allocated, nothing freed,
 // no device-wide wait.  tdnnf_supervision_assign_alignments plans the lattices of a minibatch of alignments on the host (chain_sup_alignment.h),
-// stages units and windows and has the compile kernel (chain_sup_compile.hip) write the raw arrays in front of the same build.
+// stages units and windows and has the compile kernel (chain_sup_compile.hip) write the raw arrays in front of the same build;
+// tdnnf_supervision_assign_alignment_chunks does so for chunks of whole-utterance alignments, staging the slice of units each chunk needs.
 // tdnnf_supervision_capacity and tdnnf_supervision_dump (created supervisions too) are the diagnostics the tests read.
 // The numerator's host functions (chain_num.hip) see an assigned supervision as they see a created one.
 #include <string.h>
@@ -230,10 +231,11 @@ int tdnnf_supervision_assign_alignments(tdnnf_supervision *sp, const tdnnf_unit_
   c.cap_states = r->max_states;
   c.cap_arcs = r->max_arcs;
   b.seq_arc_begin = c.seq_arc_begin = raw(ap.seq_arc_begin.data(), (size_t)B + 1);
-  c.unit_begin = raw(unit_begin, (size_t)B + 1);
+  c.slice_begin = raw(unit_begin, (size_t)B + 1);  // (a whole alignment's slice is all its units)
   c.units = raw(unit, N);
   c.lo = raw(ap.lo.data(), N);
   c.hi = raw(ap.hi.data(), N);
+  c.chunk = nullptr;
   // the staging's two shapes: on the host the begins, three ints a unit, the supervision's begins and frame_state_begin; on the device the
   // begins and the units, behind them the four arc arrays the kernel writes.  Both fit what tdnnf_supervision_reserve sized for 8 bytes a
   // state, 16 an arc and 4 a (sequence, frame + 2): units <= sequences * frames, units < states, frames <= arcs of a sequence
@@ -253,6 +255,69 @@ int tdnnf_supervision_assign_alignments(tdnnf_supervision *sp, const tdnnf_unit_
   pk.put_to(sp->frame_state_begin, p.frame_state_begin.data(), p.frame_state_begin.size());
   TDNNF_REQUIRE(pk.fits() && dev_bytes <= pk.size, "%sinternal: the minibatch needs %zu bytes of staging on the host and %zu on the device, the supervision has %zu",
                 who, pk.at, dev_bytes, pk.size);
+  return sup_commit(sp, pk, raw_bytes, &c, p, B, T, weight, static_cast<hipStream_t>(stream));
+}
+
+int tdnnf_alignment_chunk_supervision_sizes(const tdnnf_unit_set *units, int B, int T, const int *unit_begin, const int *unit, const int *starts,
+                                            const int *utt_frames, const int *chunk_begin, int tolerance, int *states_out, int *arcs_out) {
+  const char *who = "alignment_chunk_supervision_sizes: ";
+  TDNNF_REQUIRE(units, "%snull unit set", who);
+  std::string err;
+  TDNNF_REQUIRE(alignment_sizes(who, units->host, B, T, unit_begin, unit, starts, tolerance, states_out, arcs_out, &err, true, utt_frames, chunk_begin), "%s",
+                err.c_str());
+  return TDNNF_OK;
+}
+
+int tdnnf_supervision_assign_alignment_chunks(tdnnf_supervision *sp, const tdnnf_unit_set *units, int B, int T, const int *unit_begin, const int *unit,
+                                              const int *starts, const int *utt_frames, const int *chunk_begin, int tolerance, float weight,
+                                              tdnnf_stream stream) {
+  const char *who = "supervision_assign_alignment_chunks: ";
+  TDNNF_REQUIRE(sp && units, "%snull supervision or null unit set", who);
+  TDNNF_REQUIRE(sp->kind == 0, "%san end-to-end supervision: tdnnf_supervision_assign_e2e_transcripts assigns those from unit sequences", who);
+  TDNNF_REQUIRE(sp->ts_reserved && sp->ts,
+                "%sthe supervision was made by tdnnf_supervision_create: only a supervision of tdnnf_supervision_reserve can be assigned", who);
+  SupReserved *r = sp->ts;
+  std::string err;
+  TDNNF_REQUIRE(alignments_validate(who, units->host, B, T, unit_begin, unit, starts, tolerance, &err, true, utt_frames, chunk_begin), "%s", err.c_str());
+  AlignmentSupPlan ap;
+  TDNNF_REQUIRE(alignment_chunks_plan(who, B, T, unit_begin, unit, starts, utt_frames, chunk_begin, tolerance, &ap, &err), "%s", err.c_str());
+  const SupPlan &p = ap.plan;
+  TDNNF_REQUIRE(sup_check_capacity(who, B, T, p, r->max_sequences, r->max_frames, r->max_states, r->max_arcs, &err), "%s", err.c_str());
+  // short chunks may need more staging than the reserve sized (chain_sup_alignment.h)
+  TDNNF_REQUIRE(alignment_chunks_fit_staging(who, B, ap, r->stage.bytes, &err), "%s", err.c_str());
+  const size_t NA = p.num_arcs, N = ap.lo.size(), raw_ints = alignment_chunks_raw_ints(B, ap);
+
+  StagePacker pk;
+  if (int rc = r->stage.begin(&pk)) return rc;
+  SupBuildDev &b = r->build;
+  SupCompileDev c;
+  const auto raw = [&](const void *v, size_t n) { return reinterpret_cast<const int *>(r->stage.dev + pk.put(v, n)); };
+  b.B = c.B = B;
+  b.T = c.T = T;
+  c.cap_states = r->max_states;
+  c.cap_arcs = r->max_arcs;
+  b.seq_arc_begin = c.seq_arc_begin = raw(ap.seq_arc_begin.data(), (size_t)B + 1);
+  c.slice_begin = raw(ap.slice_begin.data(), (size_t)B + 1);
+  c.units = raw(ap.units.data(), N);
+  c.lo = raw(ap.lo.data(), N);
+  c.hi = raw(ap.hi.data(), N);
+  c.chunk = raw(ap.chunk.data(), 4 * (size_t)B);
+  const size_t raw_bytes = pk.at;
+  int *arcs = reinterpret_cast<int *>(r->stage.dev + raw_bytes);  // (device only)
+  b.src = c.src = arcs;
+  b.dst = c.dst = arcs + NA;
+  b.pdf = c.pdf = arcs + 2 * NA;
+  b.lp_bits = c.lp_bits = arcs + 3 * NA;
+  c.seq_state_begin = sp->seq_state_begin;
+  c.frame_state_begin = sp->frame_state_begin;
+  c.state_time = sp->state_time;
+  c.final_logprob = sp->final_logprob;
+  c.frame_arc_begin = b.len[0];
+  c.units_dev = units->dev;
+  pk.put_to(sp->seq_state_begin, ap.seq_state_begin.data(), (size_t)B + 1);
+  pk.put_to(sp->frame_state_begin, p.frame_state_begin.data(), p.frame_state_begin.size());
+  TDNNF_REQUIRE(pk.fits() && raw_bytes == sizeof(int) * raw_ints, "%sinternal: the minibatch needs %zu bytes of staging on the host, the supervision has %zu", who,
+                pk.at, pk.size);
   return sup_commit(sp, pk, raw_bytes, &c, p, B, T, weight, static_cast<hipStream_t>(stream));
 }
 

@@ -275,6 +275,15 @@ def _alignments(alignments):
     return iarr(begin), iarr(cat(0)), iarr(cat(1))
 
 
+def _chunks(num_sequences, utt_frames, chunk_begins):
+    """(utt_frames, chunk_begin) of a minibatch of chunks as (array, pointer) pairs of iarr: one int a sequence each."""
+    import numpy as np
+    frames, first = np.asarray(utt_frames, dtype=np.int64).reshape(-1), np.asarray(chunk_begins, dtype=np.int64).reshape(-1)
+    if len(frames) != num_sequences or len(first) != num_sequences:
+        raise HipAbiError(f"{num_sequences} alignments, {len(frames)} utt_frames and {len(first)} chunk_begins")
+    return iarr(frames), iarr(first)
+
+
 class UnitSet:
     """Device-resident unit set for transcript graphs (tdnnf_unit_set): U units over num_pdfs pdfs, one state per unit with an entry pdf on
     its first frame and a loop pdf on every later one.  entry_pdf / loop_pdf: shape (U,) -- context 0, context-independent -- or (U + 1, U)
@@ -325,6 +334,19 @@ class UnitSet:
         states, arcs = np.zeros(len(begin[0]) - 1, np.int32), np.zeros(len(begin[0]) - 1, np.int32)
         check(load().tdnnf_alignment_supervision_sizes(self.h, len(states), int(frames_per_sequence), begin[1], unit[1], start[1], int(tolerance),
                                                        states.ctypes.data_as(C.c_void_p), arcs.ctypes.data_as(C.c_void_p)))
+        return states, arcs
+
+    def alignment_chunk_sizes(self, alignments, utt_frames, chunk_begins, frames_per_sequence, tolerance):
+        """tdnnf_alignment_chunk_supervision_sizes (host only): (states, arcs), numpy int32 arrays with one entry per chunk -- the lattice
+        of the frames [chunk_begins[s], chunk_begins[s] + frames_per_sequence) of the utterance of utt_frames[s] frames whose whole
+        alignment is alignments[s]; what a Supervision.reserve must cover.  Refuses (HipAbiError) what
+        Supervision.assign_alignment_chunks refuses."""
+        import numpy as np
+        begin, unit, start = _alignments(alignments)
+        frames, first = _chunks(len(begin[0]) - 1, utt_frames, chunk_begins)
+        states, arcs = np.zeros(len(begin[0]) - 1, np.int32), np.zeros(len(begin[0]) - 1, np.int32)
+        check(load().tdnnf_alignment_chunk_supervision_sizes(self.h, len(states), int(frames_per_sequence), begin[1], unit[1], start[1], frames[1], first[1],
+                                                             int(tolerance), states.ctypes.data_as(C.c_void_p), arcs.ctypes.data_as(C.c_void_p)))
         return states, arcs
 
     def __del__(self):
@@ -452,6 +474,18 @@ class Supervision:
         begin, unit, start = _alignments(alignments)
         check(load().tdnnf_supervision_assign_alignments(self.h, unit_set.h, len(begin[0]) - 1, int(frames_per_sequence), begin[1], unit[1], start[1],
                                                          int(tolerance), float(weight), stream()))
+        self.B, self.T = len(begin[0]) - 1, int(frames_per_sequence)
+
+    def assign_alignment_chunks(self, unit_set, alignments, utt_frames, chunk_begins, frames_per_sequence, tolerance, weight=1.0):
+        """tdnnf_supervision_assign_alignment_chunks on the current stream: the next minibatch of a supervision of reserve, sequence s
+        the frames [chunk_begins[s], chunk_begins[s] + frames_per_sequence) of an utterance of utt_frames[s] output frames, its lattice
+        compiled on the device from the (units, starts) alignment of the WHOLE utterance, alignments[s], with every unit boundary free to
+        move by +-tolerance frames (infer.chunk_begins spreads chunks over an utterance; two chunks of one utterance repeat its
+        alignment).  A refused minibatch (HipAbiError) leaves the previous one."""
+        begin, unit, start = _alignments(alignments)
+        frames, first = _chunks(len(begin[0]) - 1, utt_frames, chunk_begins)
+        check(load().tdnnf_supervision_assign_alignment_chunks(self.h, unit_set.h, len(begin[0]) - 1, int(frames_per_sequence), begin[1], unit[1], start[1],
+                                                               frames[1], first[1], int(tolerance), float(weight), stream()))
         self.B, self.T = len(begin[0]) - 1, int(frames_per_sequence)
 
     @property

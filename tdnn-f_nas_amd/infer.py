@@ -414,6 +414,19 @@ def alignment_from_path(slots_per_frame, transcript):
     return units[runs].astype(np.int32), starts.astype(np.int32)
 
 
+def chunk_begins(utt_frames, T):
+    """The first frames of the chunks of T output frames that cover an utterance of utt_frames, for Supervision.assign_alignment_chunks:
+    none for an utterance shorter than T; else n = ceil(utt_frames / T) chunks spread evenly, round(i * (utt_frames - T) / (n - 1)) --
+    the first at 0, the last ending with the utterance, neighbours overlapping where T does not divide utt_frames -- or [0] for n = 1."""
+    utt_frames, T = int(utt_frames), int(T)
+    if T < 1:
+        raise ValueError(f"chunk_begins: chunks of {T} frames")
+    if utt_frames < T:
+        return []
+    n = -(-utt_frames // T)
+    return [0] if n == 1 else [int(round(i * (utt_frames - T) / (n - 1))) for i in range(n)]
+
+
 def alignment_from_pronunciation_path(entries_per_frame, transcript):
     """alignment_from_path for a transcript with pronunciation alternatives: entries_per_frame, one int per frame, is the label output of
     AlignGraphs.best_path_labels through a handle assigned with assign_pronunciations (an arc's label is the entry it enters, the entries

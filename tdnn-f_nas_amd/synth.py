@@ -291,6 +291,43 @@ def supervision_lattice_from_alignments(unit_set, alignments, T, tolerance, weig
             "arc_logprob": np.zeros(na, np.float32), "weight": float(weight)}
 
 
+def supervision_lattice_from_alignment_chunks(unit_set, alignments, utt_frames, chunk_begins, T, tolerance, weight=1.0):
+    """The tolerance lattices of chunks of GIVEN whole-utterance alignments, on the host: what hipabi.Supervision.assign_alignment_chunks
+    compiles on the device (include/tdnnf_hip.h, "ALIGNMENT CHUNKS"), as the dict of make_supervision that Supervision.assign takes.
+    Sequence s is the frames [chunk_begins[s], chunk_begins[s] + T) of an utterance of utt_frames[s] frames with the alignment
+    alignments[s].  The route a caller without the device compile takes: the utterance's lattice from
+    supervision_lattice_from_alignments, cut to the states of the chunk's times behind a new start, which enters every state of the
+    first time with the pdf of the arcs into it; every state of the last time is final."""
+    state_time, final, a_src, a_dst, a_pdf = [], [], [], [], []
+    seq_state_begin, seq_arc_begin = [0], [0]
+    ns = na = 0
+    for al, Tu, o in zip(alignments, utt_frames, chunk_begins):
+        Tu, o = int(Tu), int(o)
+        assert 0 <= o and o + T <= Tu and T >= 1
+        utt = supervision_lattice_from_alignments(unit_set, [al], Tu, tolerance)
+        t, src, dst, pdf = (utt[k].astype(np.int64) for k in ("state_time", "arc_src", "arc_dst", "arc_pdf"))
+        keep = (t > o) & (t <= o + T)
+        new_id = np.cumsum(keep)  # (the new start is 0)
+        pdf_in = np.zeros(len(t), np.int64)
+        pdf_in[dst] = pdf  # (all arcs into a state carry one pdf)
+        first = np.flatnonzero(t == o + 1)
+        inner = keep[src] & keep[dst]
+        state_time.append(np.concatenate([[0], t[keep] - o]))
+        final.append(np.where(state_time[-1] == T, 0.0, -np.inf))
+        a_src.append(ns + np.concatenate([np.zeros(len(first), np.int64), new_id[src[inner]]]))
+        a_dst.append(ns + np.concatenate([new_id[first], new_id[dst[inner]]]))
+        a_pdf.append(np.concatenate([pdf_in[first], pdf[inner]]))
+        ns += len(state_time[-1])
+        na += len(first) + int(inner.sum())
+        seq_state_begin.append(ns)
+        seq_arc_begin.append(na)
+    i32 = lambda x: np.asarray(x, dtype=np.int32)
+    return {"B": len(alignments), "T": int(T), "seq_state_begin": i32(seq_state_begin), "seq_arc_begin": i32(seq_arc_begin),
+            "state_time": i32(np.concatenate(state_time)), "final_logprob": np.concatenate(final).astype(np.float32),
+            "arc_src": i32(np.concatenate(a_src)), "arc_dst": i32(np.concatenate(a_dst)), "arc_pdf": i32(np.concatenate(a_pdf)),
+            "arc_logprob": np.zeros(na, np.float32), "weight": float(weight)}
+
+
 def make_alignment_graph(pdf_sequence, self_loops=True, optional=(), alternatives=None, seed=0, num_pdfs=None, labels=None):
     """Left-to-right transcript graph for best-path alignment: the shape of a compile-train-graphs output reduced to pdf labels.
     Epsilon-free, so a state is "inside a unit": state 0 is the start, unit k is one state, every arc INTO it carries its pdf --

@@ -17,9 +17,12 @@ built on the host + assign, assign alone, and tdnnf_align_graphs_assign_pronunci
 tdnnf_supervision_create + tdnnf_chain_objf_and_deriv + tdnnf_supervision_destroy against tdnnf_supervision_assign + the same call.
 --supervision --alignment [--tolerance N]: instead, the same supervision for a caller who starts from alignments (see alignment() below):
 the lattice built on the host + tdnnf_supervision_assign, assign alone, and tdnnf_supervision_assign_alignments, alternating.
+--supervision --alignment --chunks [--utt-frames N]: the same three routes for chunks of --frames frames cut at random begins out of
+utterances of --utt-frames (default 1000): the utterance's lattice built and cut on the host + assign, assign alone, and
+tdnnf_supervision_assign_alignment_chunks.
 usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts] [--pronunciations]
                                               [--supervision [--tolerance N --alternatives N] [--sequences B --frames T]]
-                                              [--supervision --alignment [--tolerance N] [--sequences B --frames T]]"""
+                                              [--supervision --alignment [--chunks [--utt-frames N]] [--tolerance N] [--sequences B --frames T]]"""
 import argparse
 import ctypes as C
 import json
@@ -333,7 +336,10 @@ def alignment(args, pkg):
       assign_alignments    (c) tdnnf_supervision_assign_alignments, the call.
     Two shapes: --sequences x --frames (default 128 x 150) at the tolerance with mean duration 6 frames, and one wide shape, 64 x 150 at
     tolerance 40 with mean duration 3.  Also the host time of the assign_alignments call alone and the device time of what it enqueues.
-    The outputs of the three are compared for equality in the same run.  One JSON line."""
+    The outputs of the three are compared for equality in the same run.  One JSON line.
+    --chunks: every sequence is a chunk of --frames frames at a random begin of an utterance of --utt-frames frames with an alignment of
+    its own; (a) builds the utterance's lattice and cuts it (synth.supervision_lattice_from_alignment_chunks), (c) is
+    tdnnf_supervision_assign_alignment_chunks; the keys of the JSON line keep their names."""
     abi, synth = pkg.hipabi, pkg.synth
     lib = abi.load()
     P, U = args.pdfs, 42
@@ -341,7 +347,10 @@ def alignment(args, pkg):
     units = abi.UnitSet(us["entry_pdf"], us["loop_pdf"], us["loop_logprob"], us["leave_logprob"], P, us["take_logprob"], us["skip_logprob"])
     dg = abi.DenGraph(synth.make_den_graph(64, P, mean_out_degree=4.0, seed=1))
     s = abi.stream()
-    res = dict(metric="alignment_supervision_per_minibatch", pdfs=P, cycle=args.cycle, repeats=args.repeats, units=U, context=1)
+    res = dict(metric="alignment_chunk_supervision_per_minibatch" if args.chunks else "alignment_supervision_per_minibatch", pdfs=P, cycle=args.cycle,
+               repeats=args.repeats, units=U, context=1)
+    if args.chunks:
+        res["utt_frames"] = args.utt_frames
 
     def random_alignment(rng, T, mean_dur):
         d = 1 + np.floor(rng.exponential(mean_dur - 1.0, size=T)).astype(np.int64)
@@ -356,8 +365,17 @@ def alignment(args, pkg):
 
     def case(name, B, T, tol, mean_dur):
         rng = np.random.default_rng(1)
-        batches = [[random_alignment(rng, T, mean_dur) for _ in range(B)] for _ in range(args.cycle)]
-        made = [pointers(synth.supervision_lattice_from_alignments(us, b, T, tol)) for b in batches]
+        Tu = args.utt_frames if args.chunks else T  # (without --chunks a sequence is its utterance)
+        assert Tu >= T, "--utt-frames below --frames"
+        batches = [[random_alignment(rng, Tu, mean_dur) for _ in range(B)] for _ in range(args.cycle)]
+        begins = [abi._chunks(B, [Tu] * B, rng.integers(0, Tu - T + 1, size=B)) for _ in range(args.cycle)]
+
+        def host_lattice(i):
+            if args.chunks:
+                return synth.supervision_lattice_from_alignment_chunks(us, batches[i], begins[i][0][0], begins[i][1][0], T, tol)
+            return synth.supervision_lattice_from_alignments(us, batches[i], T, tol)
+
+        made = [pointers(host_lattice(i)) for i in range(args.cycle)]
         flat = [abi._alignments(b) for b in batches]
         NS, NA = max(len(m[0][2][0]) for m in made), max(len(m[0][4][0]) for m in made)
         reserved = C.c_void_p()
@@ -378,9 +396,13 @@ def alignment(args, pkg):
 
         def assign_alignments(i):
             a = flat[i]
-            abi.check(lib.tdnnf_supervision_assign_alignments(reserved, units.h, B, T, a[0][1], a[1][1], a[2][1], tol, 1.0, s))
+            if args.chunks:
+                abi.check(lib.tdnnf_supervision_assign_alignment_chunks(reserved, units.h, B, T, a[0][1], a[1][1], a[2][1], begins[i][0][1], begins[i][1][1], tol,
+                                                                        1.0, s))
+            else:
+                abi.check(lib.tdnnf_supervision_assign_alignments(reserved, units.h, B, T, a[0][1], a[1][1], a[2][1], tol, 1.0, s))
 
-        fns = dict(host_lattice_assign=lambda i: (assign(pointers(synth.supervision_lattice_from_alignments(us, batches[i], T, tol))[1]), call()),
+        fns = dict(host_lattice_assign=lambda i: (assign(pointers(host_lattice(i))[1]), call()),
                    assign=lambda i: (assign(made[i][1]), call()),
                    assign_alignments=lambda i: (assign_alignments(i), call()))
 
@@ -452,6 +474,9 @@ def main():
     ap.add_argument("--tolerance", type=int, default=0, help="--supervision: > 0 tolerance lattices (synth.make_supervision_lattice)")
     ap.add_argument("--alignment", action="store_true",
                     help="--supervision: from alignments -- host-built lattice + assign against assign_alignments (--tolerance, default 5)")
+    ap.add_argument("--chunks", action="store_true",
+                    help="--supervision --alignment: chunks of --frames frames out of utterances of --utt-frames, assign_alignment_chunks")
+    ap.add_argument("--utt-frames", type=int, default=1000)
     ap.add_argument("--alternatives", type=int, default=1)
     ap.add_argument("--sequences", type=int, default=128)
     ap.add_argument("--frames", type=int, default=150)
