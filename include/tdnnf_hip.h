@@ -1379,6 +1379,48 @@ int tdnnf_infer_counts(const tdnnf_infer *, int *fused_layers, int *fallback_pas
    lda, tdnn1, every layer's .linear and .affine, prefinal-l, the head's affine and linear, the output. */
 int tdnnf_infer_gemm_counts(const tdnnf_infer *, long long *plane_gemms, long long *f32_gemms);
 
+/* CHUNK INPUTS: the input of tdnnf_net_forward_backward for a minibatch of chunks, gathered on the device from whole utterances -- the
+   features of the chunks whose supervisions "ALIGNMENT CHUNKS" compiles, so that a training pass over aligned utterances needs no archive
+   and no host-built array of features.
+   Utterances u = 0..U-1 have frames[u] input frames; their features are stacked row-wise in one device matrix exactly as
+   tdnnf_infer_compute takes them, their i-vectors the same way: R_u rows each, one every ivector_period input frames, or
+   ivector_period <= 0 for one per utterance (R_u = 1; ivector_rows_host is then not read).  fsf = frame_subsampling,
+   O_u = (frames[u] + fsf - 1) / fsf.  Sequence b of a minibatch of B is the output frames [begin_b, begin_b + T) of utterance seq_utt[b],
+   T = frames_per_sequence; first_t and num_t are what tdnnf_net_input_frames reports.
+     feats_out     (num_t * B) x feat_dim, t-major: row (t - first_t) * B + b, t = first_t .. first_t + num_t - 1, is feature row
+                   clamp(begin_b * fsf + t - frame_shift, 0, frames[u] - 1) of utterance u.  frame_shift has the sign of tdnnf_egs_merge
+                   (example times += frame_shift); clamping is nnet3's edge padding, as in "inference".
+     ivectors_out  B x ivector_dim: row b is i-vector row min(((begin_b + T / 2) * fsf) / ivector_period, R_u - 1) of utterance u, or row 0
+                   for ivector_period <= 0 (integer divisions: the rule of tdnnf_infer_plan with k F / fsf -> begin_b, n_k -> T).  With
+                   ivector_dim == 0 (ivectors NULL or of no columns) no i-vector argument is read or written.
+   Refused with TDNNF_EINVAL, by name, before any device call and leaving the handle as it was: begin_b < 0, begin_b + T > O_u, seq_utt[b]
+   outside [0, U) (each naming the sequence); frames[u] < 1, R_u < 1 where i-vectors are used (naming the utterance);
+   |frame_shift| >= fsf; feats, ivectors, feats_out or ivectors_out of another shape than the above; more sequences than max_sequences
+   (named with the excess, as the assigns name a capacity).
+   tdnnf_chunk_input_create makes every allocation: the device table and two pinned staging buffers that take turns (the ring of the
+   reserved-handle assigns: turn k waits only for the copies of turn k - 2).  tdnnf_chunk_input_plan is host only, no device, no handle: the
+   table of a minibatch, 4 ints a sequence -- the first stacked feature row of its utterance, the utterance's frames[u], the window start
+   begin_b * fsf - frame_shift, the stacked i-vector row (0 when ivector_period > 0 comes without ivector_rows_host: no i-vectors) -- after
+   the same checks.  tdnnf_chunk_input_gather validates, stages those 16 bytes a sequence and enqueues one copy and ONE kernel on `stream`
+   (csrc/chunk_input_kernels.h: a grid-stride copy through the table, consecutive lanes on consecutive columns of one output row; 16-byte
+   loads and stores where feat_dim, ivector_dim, every stride and every base pointer allow, else a float at a time; the i-vector rows in
+   the same launch).  No allocation, no free, no stream or device synchronise; work enqueued on `stream` before a gather still reads the
+   outputs of the previous one if they are other buffers.  It takes first_t / num_t / frame_subsampling as integers, not a net.
+   tdnnf_chunk_input_info: allocations made since create (0), successful gathers, and the form of the last (4: 16-byte, 1: scalar, 0: none
+   yet); any out-pointer may be NULL.
+   Not built: 16-bit stored features, chunks shorter than T at an utterance's end, frame-rate (not output-rate) alignments, device-side
+   validation, capture into a HIP graph. */
+typedef struct tdnnf_chunk_input tdnnf_chunk_input;
+int tdnnf_chunk_input_create(int max_sequences, tdnnf_chunk_input **out);
+void tdnnf_chunk_input_destroy(tdnnf_chunk_input *);
+int tdnnf_chunk_input_plan(int frame_subsampling, int frames_per_sequence, int num_sequences, const int *seq_utt_host, const int *chunk_begin_host,
+                           int frame_shift, int num_utts, const int *frames_host, const int *ivector_rows_host, int ivector_period, int *table_out);
+int tdnnf_chunk_input_gather(tdnnf_chunk_input *, int first_t, int num_t, int frame_subsampling, int frames_per_sequence, int num_sequences,
+                             const int *seq_utt_host, const int *chunk_begin_host, int frame_shift, int num_utts, const int *frames_host,
+                             const tdnnf_mat *feats, const int *ivector_rows_host, const tdnnf_mat *ivectors, int ivector_period, tdnnf_mat *feats_out,
+                             tdnnf_mat *ivectors_out, tdnnf_stream stream);
+int tdnnf_chunk_input_info(const tdnnf_chunk_input *, int *max_sequences, long long *allocations, long long *gathers, int *last_form);
+
 /* ======================================================================== inference (forward only, streaming)
  * The same output for streams whose features arrive a few frames at a time: nnet3's looped computation
  * (DecodableNnetLoopedOnline, UPSTREAM, not shipped) restated.  Same models, outputs and BatchNorm as "inference" above, and the

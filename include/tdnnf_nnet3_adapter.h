@@ -515,6 +515,31 @@ inline void SupervisionAssignAlignmentChunks(tdnnf_supervision *sup, const tdnnf
                                                   tolerance, weight, stream));
 }
 
+// Chunk inputs (tdnnf_hip.h, "CHUNK INPUTS"): the features and i-vectors of the same chunks, what nnet3-chain-get-egs cuts out of an
+// utterance's feature matrix and nnet3-chain-merge-egs interleaves, gathered on the device from the utterances' matrices stacked row-wise
+// (as the inference calls take them).  A handle is created once for the largest minibatch; release with tdnnf_chunk_input_destroy.
+// Sequence b is the output frames [chunk_begin[b], chunk_begin[b] + frames_per_sequence) of utterance seq_utt[b]; first_t / num_t: the
+// net's input window (tdnnf_net_input_frames).  feats_out: (num_t * num_sequences) x feat_dim, t-major; ivectors / ivectors_out may be
+// null for a model without i-vectors (ivector_rows is then not read).  Throws on a bad chunk, naming the sequence, on matrices of another
+// shape and on a minibatch beyond the capacity -- before anything is enqueued, the outputs as they were.
+inline tdnnf_chunk_input *ChunkInputCreate(int max_sequences) {
+  tdnnf_chunk_input *input = nullptr;
+  Check(tdnnf_chunk_input_create(max_sequences, &input));
+  return input;
+}
+template <class CuMat>
+inline void ChunkInputGather(tdnnf_chunk_input *input, int first_t, int num_t, int frame_subsampling, int frames_per_sequence, int num_sequences,
+                             const int *seq_utt, const int *chunk_begin, int frame_shift, int num_utts, const int *frames, const CuMat &feats,
+                             const int *ivector_rows, const CuMat *ivectors, int ivector_period, CuMat *feats_out, CuMat *ivectors_out,
+                             tdnnf_stream stream) {
+  if (!feats_out) TDNNF_ADAPTER_FAIL("tdnnf: ChunkInputGather needs feats_out");
+  tdnnf_mat vf = View(feats), vo = View(*feats_out), vi, vio;
+  if (ivectors) vi = View(*ivectors);
+  if (ivectors_out) vio = View(*ivectors_out);
+  Check(tdnnf_chunk_input_gather(input, first_t, num_t, frame_subsampling, frames_per_sequence, num_sequences, seq_utt, chunk_begin, frame_shift, num_utts,
+                                 frames, &vf, ivector_rows, ivectors ? &vi : nullptr, ivector_period, &vo, ivectors_out ? &vio : nullptr, stream));
+}
+
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance

@@ -2168,6 +2168,24 @@ inline void AssignSupervisionFromAlignmentChunks(tdnnf_supervision *supervision,
                                                   unit.data(), starts.data(), utt_frames.data(), chunk_begin.data(), tolerance, weight, Hooks().stream);
 }
 
+// The INPUT of the same chunks (tdnnf_hip.h, "CHUNK INPUTS"): their features, t-major as the net takes them, and one i-vector a sequence,
+// gathered on the hooks' stream from the utterances' matrices stacked row-wise on the device.  Sequence b is the output frames
+// [chunk_begin[b], chunk_begin[b] + frames_per_sequence) of utterance seq_utt[b]; frames: the input frames of every utterance;
+// first_t / num_t: the net's input window.  ivectors / ivectors_out null: a model without i-vectors (ivector_rows is not read).
+// NewChunkInput: the handle, once for the largest minibatch; release with tdnnf_chunk_input_destroy.
+inline tdnnf_chunk_input *NewChunkInput(int32 max_sequences) { return tdnnf_adapter::ChunkInputCreate(max_sequences); }
+inline void GatherChunkInput(tdnnf_chunk_input *input, int32 first_t, int32 num_t, int32 frame_subsampling, int32 frames_per_sequence,
+                             const std::vector<int32> &seq_utt, const std::vector<int32> &chunk_begin, int32 frame_shift,
+                             const std::vector<int32> &frames, const CuMatrixBase &feats, const std::vector<int32> &ivector_rows,
+                             const CuMatrixBase *ivectors, int32 ivector_period, CuMatrixBase *feats_out, CuMatrixBase *ivectors_out) {
+  if (chunk_begin.size() != seq_utt.size()) throw std::runtime_error("tdnnf: GatherChunkInput: seq_utt and chunk_begin must have one entry a sequence");
+  if (ivectors && ivector_period > 0 && ivector_rows.size() != frames.size())
+    throw std::runtime_error("tdnnf: GatherChunkInput: frames and ivector_rows must have one entry an utterance");
+  tdnnf_adapter::ChunkInputGather(input, first_t, num_t, frame_subsampling, frames_per_sequence, static_cast<int32>(seq_utt.size()), seq_utt.data(),
+                                  chunk_begin.data(), frame_shift, static_cast<int32>(frames.size()), frames.data(), feats,
+                                  ivector_rows.empty() ? nullptr : ivector_rows.data(), ivectors, ivector_period, feats_out, ivectors_out, Hooks().stream);
+}
+
 // ------------------------------------------------------------------------------------------------ best-path alignment
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames

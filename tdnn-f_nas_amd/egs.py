@@ -1,6 +1,8 @@
 """ctypes plumbing of the egs reader / writer / merge in csrc/egs_io.hip (include/tdnnf_hip.h, "egs" section): chain
 example archives in Kaldi's binary format (restated, see the header of egs_io.hip) to and from numpy, and the merge of
-single-sequence examples into the minibatch the trainer takes.  Host only, no GPU needed."""
+single-sequence examples into the minibatch the trainer takes.  Host only, no GPU needed -- but for the minibatch generators, which
+hand device objects to the trainer: from an archive (minibatches), or straight from aligned utterances with the features gathered and
+the supervisions compiled on the device (minibatches_from_utterances; write_chunk_egs is its host route into an archive)."""
 import ctypes as C
 
 import numpy as np
@@ -146,17 +148,28 @@ class ReusedSupervision:
     def __init__(self):
         self.sup, self.caps, self.reserves = None, (0, 0, 0, 0), 0
 
-    def assign(self, s):
-        """The handle holding supervision dict `s`; valid until the next assign."""
-        need = (int(s["B"]), int(s["T"]), len(s["state_time"]), len(s["arc_src"]))
+    def _room_for(self, need):
+        """a handle of at least `need` = (sequences, frames, states, arcs): the one there is, or a new one with HEADROOM"""
         if self.sup is None or any(n > c for n, c in zip(need, self.caps)):
             room = (need[0], need[1], int(need[2] * self.HEADROOM) + 1, int(need[3] * self.HEADROOM) + 1)
             self.caps = tuple(max(c, r) for c, r in zip(self.caps, room))
             self.sup = None  # (the old handle goes first: its memory is free for the new one)
             self.sup = hipabi.Supervision.reserve(*self.caps)
             self.reserves += 1
-        self.sup.assign(s)
         self.sup.reserves = self.reserves
+
+    def assign(self, s):
+        """The handle holding supervision dict `s`; valid until the next assign."""
+        self._room_for((int(s["B"]), int(s["T"]), len(s["state_time"]), len(s["arc_src"])))
+        self.sup.assign(s)
+        return self.sup
+
+    def assign_alignment_chunks(self, unit_set, alignments, utt_frames, chunk_begins, frames_per_sequence, tolerance, weight=1.0):
+        """The handle holding the chunks' supervisions, compiled on the device (hipabi.Supervision.assign_alignment_chunks); it is sized
+        with UnitSet.alignment_chunk_sizes, host arithmetic.  Valid until the next assign."""
+        states, arcs = unit_set.alignment_chunk_sizes(alignments, utt_frames, chunk_begins, frames_per_sequence, tolerance)
+        self._room_for((len(states), int(frames_per_sequence), int(states.sum()), int(arcs.sum())))
+        self.sup.assign_alignment_chunks(unit_set, alignments, utt_frames, chunk_begins, frames_per_sequence, tolerance, weight)
         return self.sup
 
 
@@ -272,3 +285,95 @@ def minibatches_by_width(path, nets, frame_shift=0, reuse=False):
             bins[T] = []
             yield (net, torch.from_numpy(f).cuda(), torch.from_numpy(iv).cuda() if iv is not None else None,
                    reused[id(net)].assign(sup) if reuse else hipabi.Supervision(sup))
+
+
+def utterance_chunks(out_frames, frames_per_sequence):
+    """Every chunk of frames_per_sequence output frames of utterances of out_frames[u] output frames, as (utterance, begin) in utterance
+    order: the begins of infer.chunk_begins; an utterance shorter than a chunk contributes none."""
+    from . import infer
+    return [(u, o) for u, n in enumerate(out_frames) for o in infer.chunk_begins(n, frames_per_sequence)]
+
+
+def chunk_minibatches(chunks, num_sequences, seed=0, discard_partial=True):
+    """One epoch's minibatches of `chunks`: permuted with numpy.random.default_rng(seed), taken num_sequences at a time; what is left
+    over is dropped, or with discard_partial false refused (ValueError).  Host arithmetic: a list of lists of chunks."""
+    order = np.random.default_rng(seed).permutation(len(chunks))
+    full = len(chunks) - len(chunks) % num_sequences
+    if full < len(chunks) and not discard_partial:
+        raise ValueError("the last %d chunks do not fill a minibatch of %d" % (len(chunks) - full, num_sequences))
+    return [[chunks[i] for i in order[k:k + num_sequences]] for k in range(0, full, num_sequences)]
+
+
+def _stack_utterances(utterances, feat_dim, ivector_dim, ivector_period):
+    """(feats, ivectors or None, frames, ivector_rows) on the device: the utterances' rows stacked as AcousticModel.compute stacks them"""
+    import torch
+    feats, ivs = [], []
+    for f, iv in utterances:
+        feats.append(torch.as_tensor(f, dtype=torch.float32).cuda().reshape(-1, feat_dim))
+        if ivector_dim > 0:
+            iv = torch.as_tensor(iv, dtype=torch.float32).cuda().reshape(-1, ivector_dim)
+            ivs.append(iv if ivector_period > 0 else iv[:1])
+    return (torch.cat(feats).contiguous(), torch.cat(ivs).contiguous() if ivs else None, [int(f.shape[0]) for f in feats],
+            [int(iv.shape[0]) for iv in ivs] if ivs else None)
+
+
+def minibatches_from_utterances(utterances, alignments, net, unit_set, tolerance, frame_shift=0, ivector_period=10, seed=0, weight=1.0,
+                                discard_partial=True):
+    """One epoch of training minibatches straight from aligned utterances -- no archive, no host-built array of features.  utterances: the
+    list of (feats T_u x feat_dim, ivectors R_u x ivector_dim) that AcousticModel.compute takes (numpy or torch; stacked on the device
+    once); alignments[u]: the (units, starts) of utterance u over its O_u = ceil(T_u / fsf) output frames (infer.alignment_from_path);
+    unit_set: a hipabi.UnitSet.  The chunks of net.cfg.frames_per_chunk / fsf output frames of every utterance (utterance_chunks) are
+    permuted with seed and taken net.cfg.num_sequences at a time (chunk_minibatches).  Yields (feats, ivectors, supervision) as
+    minibatches(..., reuse=True) does: the features and i-vectors gathered on the device (hipabi.ChunkInput: include/tdnnf_hip.h, "CHUNK
+    INPUTS"; frame_shift and ivector_period as there), the supervision ONE reserved handle compiled on the device by
+    assign_alignment_chunks (ReusedSupervision: sized with UnitSet.alignment_chunk_sizes plus headroom, reserved again, larger, when a
+    minibatch exceeds it) whose .chunks lists the minibatch's (utterance, begin).  All three are valid until the next item is requested:
+    work enqueued on the current stream before that still sees them."""
+    import torch
+    cfg = net.cfg
+    fsf, B = int(cfg.frame_subsampling), int(cfg.num_sequences)
+    T = int(cfg.frames_per_chunk) // fsf
+    if len(alignments) != len(utterances):
+        raise ValueError("%d utterances and %d alignments" % (len(utterances), len(alignments)))
+    feats, ivs, frames, iv_rows = _stack_utterances(utterances, int(cfg.feat_dim), int(cfg.ivector_dim), ivector_period)
+    out_frames = [(t + fsf - 1) // fsf for t in frames]
+    batches = chunk_minibatches(utterance_chunks(out_frames, T), B, seed, discard_partial)
+    if not batches:
+        return
+    gatherer, reused = hipabi.ChunkInput(B), ReusedSupervision()
+    out = (torch.empty(net.num_t_in * B, feats.shape[1], dtype=torch.float32, device=feats.device),
+           torch.empty(B, ivs.shape[1], dtype=torch.float32, device=feats.device) if ivs is not None else None)
+    for chunks in batches:
+        utt, begins = [u for u, _ in chunks], [o for _, o in chunks]
+        f, iv = gatherer.gather(net, T, utt, begins, frames, feats, iv_rows, ivs, ivector_period, frame_shift, out=out)
+        sup = reused.assign_alignment_chunks(unit_set, [alignments[u] for u in utt], [out_frames[u] for u in utt], begins, T, tolerance, weight)
+        sup.chunks = list(chunks)
+        yield f, iv, sup
+
+
+def write_chunk_egs(path, utterances, alignments, net, unit_set, tolerance, chunks, margin=None, compress=False, ivector_period=10, weight=1.0):
+    """The host route to the same chunks: one single-sequence example per (utterance, begin) of `chunks` into the archive `path` (Writer),
+    for Kaldi's tools or for minibatches(path, net, frame_shift=s).  utterances, alignments as minibatches_from_utterances takes them, on
+    the host; unit_set: the unit set DICT (synth.make_unit_set), since the supervision is the host lattice
+    synth.supervision_lattice_from_alignment_chunks through sequence_of.  An example's input rows cover the times
+    net.first_t - margin .. net.first_t + net.num_t_in - 1 + margin relative to begin * fsf, clamped to the utterance (nnet3's edge
+    padding); margin defaults to fsf - 1, so that every legal frame shift can be merged.  Its i-vector is the row of "CHUNK INPUTS".
+    Keys are utt<u>-<begin>.  Returns the number of examples written."""
+    from . import synth
+    cfg = net.cfg
+    fsf = int(cfg.frame_subsampling)
+    T = int(cfg.frames_per_chunk) // fsf
+    margin = fsf - 1 if margin is None else int(margin)
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    with Writer(path) as w:
+        for u, o in chunks:
+            f = host(utterances[u][0]).astype(np.float32, copy=False).reshape(-1, int(cfg.feat_dim))
+            out_frames = (len(f) + fsf - 1) // fsf
+            times = np.clip(o * fsf + np.arange(net.first_t - margin, net.first_t + net.num_t_in + margin), 0, len(f) - 1)
+            iv = None
+            if cfg.ivector_dim > 0:
+                rows = host(utterances[u][1]).astype(np.float32, copy=False).reshape(-1, int(cfg.ivector_dim))
+                iv = rows[min(((o + T // 2) * fsf) // ivector_period, len(rows) - 1) if ivector_period > 0 else 0]
+            sup = synth.supervision_lattice_from_alignment_chunks(unit_set, [alignments[u]], [out_frames], [o], T, tolerance, weight=weight)
+            w.write("utt%d-%d" % (u, o), f[times], net.first_t - margin, sequence_of(sup, 0), int(cfg.num_pdfs), ivector=iv, compress=compress, t_step=fsf)
+    return len(chunks)

@@ -900,3 +900,80 @@ class AlignGraphs:
         if getattr(self, "h", None) and _lib is not None:
             _lib.tdnnf_align_graphs_destroy(self.h)
             self.h = None
+
+
+def _sequence_chunks(seq_utt, chunk_begins):
+    """(seq_utt, chunk_begin) of a minibatch of chunks as (array, pointer) pairs of iarr: one int a sequence each."""
+    import numpy as np
+    utt, first = np.asarray(seq_utt, dtype=np.int64).reshape(-1), np.asarray(chunk_begins, dtype=np.int64).reshape(-1)
+    if len(utt) != len(first):
+        raise HipAbiError(f"{len(utt)} seq_utt and {len(first)} chunk_begins")
+    return iarr(utt), iarr(first)
+
+
+class ChunkInput:
+    """The net's input for minibatches of chunks, gathered on the device from whole utterances (tdnnf_chunk_input; include/tdnnf_hip.h,
+    "CHUNK INPUTS"): one handle for up to max_sequences sequences, allocated once; every gather stages 16 bytes a sequence and enqueues a
+    copy and one kernel on the current stream."""
+
+    def __init__(self, max_sequences):
+        self.h = C.c_void_p()
+        self.max_sequences = int(max_sequences)
+        check(load().tdnnf_chunk_input_create(self.max_sequences, C.byref(self.h)))
+
+    @staticmethod
+    def _shape(net_or_shape):
+        """(first_t, num_t, frame_subsampling) of a ChainNet, or the triple itself"""
+        if hasattr(net_or_shape, "num_t_in"):
+            return int(net_or_shape.first_t), int(net_or_shape.num_t_in), int(net_or_shape.cfg.frame_subsampling)
+        first_t, num_t, fsf = net_or_shape
+        return int(first_t), int(num_t), int(fsf)
+
+    @staticmethod
+    def plan(frame_subsampling, frames_per_sequence, seq_utt, chunk_begins, frames, ivector_rows=None, ivector_period=10, frame_shift=0):
+        """tdnnf_chunk_input_plan (host only, no device, no handle): the table of a minibatch, numpy int32 (sequences, 4) -- the first stacked
+        feature row of the sequence's utterance, the utterance's frames, the window start begin * fsf - frame_shift, the stacked i-vector
+        row (ivector_rows None with ivector_period > 0: no i-vectors, 0).  Refuses (HipAbiError) what gather refuses of these arguments."""
+        import numpy as np
+        utt, first = _sequence_chunks(seq_utt, chunk_begins)
+        fr = iarr(frames)
+        ivr = iarr(ivector_rows) if ivector_rows is not None else (None, None)
+        table = np.zeros((max(len(utt[0]), 1), 4), np.int32)
+        check(load().tdnnf_chunk_input_plan(int(frame_subsampling), int(frames_per_sequence), len(utt[0]), utt[1], first[1], int(frame_shift), len(fr[0]),
+                                            fr[1], ivr[1], int(ivector_period), table.ctypes.data_as(C.c_void_p)))
+        return table[:len(utt[0])]
+
+    def gather(self, net_or_shape, frames_per_sequence, seq_utt, chunk_begins, frames, feats, ivector_rows, ivectors, ivector_period, frame_shift=0,
+               out=None):
+        """tdnnf_chunk_input_gather on the current stream.  net_or_shape: a ChainNet or (first_t, num_t, frame_subsampling); sequence b is the
+        output frames [chunk_begins[b], chunk_begins[b] + frames_per_sequence) of utterance seq_utt[b]; frames: the input frames of every
+        utterance; feats / ivectors: the utterances' rows stacked, CUDA tensors (ivectors None or of no columns: none; ivector_rows may be
+        None for ivector_period <= 0).  out: (feats_out, ivectors_out) to write into, default new tensors.  Returns (feats_out
+        [num_t * sequences, feat_dim] t-major, ivectors_out [sequences, ivector_dim] or None) as ChainNet.forward_backward takes them."""
+        import torch
+        first_t, num_t, fsf = self._shape(net_or_shape)
+        utt, first = _sequence_chunks(seq_utt, chunk_begins)
+        B = len(utt[0])
+        fr = iarr(frames)
+        use_iv = ivectors is not None and ivectors.shape[1] > 0
+        ivr = iarr(ivector_rows) if ivector_rows is not None else (None, None)
+        if out is None:
+            out = (torch.empty(num_t * B, feats.shape[1], dtype=torch.float32, device=feats.device),
+                   torch.empty(B, ivectors.shape[1], dtype=torch.float32, device=feats.device) if use_iv else None)
+        feats_out, ivectors_out = out
+        check(load().tdnnf_chunk_input_gather(self.h, first_t, num_t, fsf, int(frames_per_sequence), B, utt[1], first[1], int(frame_shift), len(fr[0]), fr[1],
+                                              pmat(feats), ivr[1], pmat(ivectors) if use_iv else None, int(ivector_period), pmat(feats_out),
+                                              pmat(ivectors_out) if use_iv else None, stream()))
+        return feats_out, (ivectors_out if use_iv else None)
+
+    def info(self):
+        """{max_sequences, allocations, gathers, last_form} (tdnnf_chunk_input_info): device and pinned allocations since create, successful
+        gathers, the last one's form -- 4: 16-byte loads and stores, 1: a float at a time, 0: none yet."""
+        a, b, c, d = C.c_int(), C.c_longlong(), C.c_longlong(), C.c_int()
+        check(load().tdnnf_chunk_input_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(max_sequences=a.value, allocations=b.value, gathers=c.value, last_form=d.value)
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.tdnnf_chunk_input_destroy(self.h)
+            self.h = None

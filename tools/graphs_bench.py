@@ -20,7 +20,10 @@ the lattice built on the host + tdnnf_supervision_assign, assign alone, and tdnn
 --supervision --alignment --chunks [--utt-frames N]: the same three routes for chunks of --frames frames cut at random begins out of
 utterances of --utt-frames (default 1000): the utterance's lattice built and cut on the host + assign, assign alone, and
 tdnnf_supervision_assign_alignment_chunks.
+--features [--sequences B --frames T --utt-frames N]: instead, the INPUT of a minibatch of chunks (see features() below): the t-major
+features and the i-vectors sliced out of host copies with numpy and uploaded, against tdnnf_chunk_input_gather from the device copies.
 usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts] [--pronunciations]
+                                              [--features [--sequences B --frames T --utt-frames N]]
                                               [--supervision [--tolerance N --alternatives N] [--sequences B --frames T]]
                                               [--supervision --alignment [--chunks [--utt-frames N]] [--tolerance N] [--sequences B --frames T]]"""
 import argparse
@@ -461,6 +464,85 @@ def alignment(args, pkg):
     print(json.dumps(res))
 
 
+def features(args, pkg):
+    """--features: what the INPUT of a minibatch of chunks costs when the utterances' features are already on the device (as
+    AcousticModel.compute took them for the alignment pass), two ways, alternating in one process, other chunks every iteration, medians
+    of --repeats:
+      host_slice_upload  the t-major matrix sliced out of host copies with numpy (one fancy index through the clamped row numbers) and
+                         uploaded, the i-vector rows alike -- what a caller had to do before tdnnf_chunk_input_gather;
+      gather             hipabi.ChunkInput.gather into the same output buffers.
+    --sequences x --frames output frames and 64 x --frames, feat_dim 40, ivector_dim 100, the input window of the default model graph at
+    that chunk width (a net of small dimensions is made for tdnnf_net_input_frames alone); --utt-frames output frames an utterance.  The
+    outputs of the two are compared for equality in the same run.  bytes: what the host route uploads per minibatch (the gather reads and
+    writes as many on the device) and what the gather stages."""
+    abi, fsf, D, Di, period = pkg.hipabi, 3, 40, 100, 10
+    net = pkg.trainer.ChainNet(pkg.trainer.make_config(frames_per_chunk=args.frames * fsf, num_sequences=1, bottleneck=16, feat_dim=D, ivector_dim=Di, num_pdfs=64,
+                                                       hidden_dim=64, small_dim=32))
+    shape = (net.first_t, net.num_t_in, fsf)
+    net.close()
+    rng = np.random.default_rng(0)
+    U, T = 64, args.frames
+    frames = rng.integers(args.utt_frames * fsf - 2 * fsf, args.utt_frames * fsf + 1, size=U)
+    rows = (frames + period - 1) // period
+    F, IV = rng.standard_normal((int(frames.sum()), D)).astype(np.float32), rng.standard_normal((int(rows.sum()), Di)).astype(np.float32)
+    feat0, iv0 = np.concatenate([[0], np.cumsum(frames)[:-1]]), np.concatenate([[0], np.cumsum(rows)[:-1]])
+    F_dev, IV_dev = torch.from_numpy(F).cuda(), torch.from_numpy(IV).cuda()
+    res = dict(metric="chunk_features_per_minibatch", cycle=args.cycle, repeats=args.repeats, feat_dim=D, ivector_dim=Di, first_t=shape[0], num_t=shape[1],
+               frame_subsampling=fsf, utterances=U, utt_frames=args.utt_frames)
+
+    def case(name, B):
+        batches = []
+        for c in range(args.cycle):
+            utt = rng.integers(0, U, size=B)
+            batches.append((utt, rng.integers(0, (frames[utt] + fsf - 1) // fsf - T + 1), int(rng.integers(-(fsf - 1), fsf))))
+        h = abi.ChunkInput(B)
+        out = {k: (torch.zeros(shape[1] * B, D, device="cuda"), torch.zeros(B, Di, device="cuda")) for k in ("host_slice_upload", "gather")}
+        times = np.arange(shape[0], shape[0] + shape[1])
+
+        def host_route(i, o=out["host_slice_upload"]):
+            utt, begins, shift = batches[i]
+            t = np.clip(begins[None, :] * fsf + times[:, None] - shift, 0, frames[utt][None, :] - 1) + feat0[utt][None, :]
+            o[0].copy_(torch.from_numpy(F[t.reshape(-1)]), non_blocking=False)
+            o[1].copy_(torch.from_numpy(IV[iv0[utt] + np.minimum(((begins + T // 2) * fsf) // period, rows[utt] - 1)]), non_blocking=False)
+
+        def gather(i, o=out["gather"]):
+            utt, begins, shift = batches[i]
+            h.gather(shape, T, utt, begins, frames, F_dev, rows, IV_dev, period, frame_shift=shift, out=o)
+
+        fns = dict(host_slice_upload=host_route, gather=gather)
+
+        def loop(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(args.cycle):
+                fn(i)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / args.cycle
+
+        ms = {k: [] for k in fns}
+        for r in range(args.repeats + 1):  # the first round warms up
+            for k, fn in fns.items():
+                t = loop(fn)
+                if r:
+                    ms[k].append(t)
+        equal = True
+        for i in range(args.cycle):
+            host_route(i), gather(i)
+            torch.cuda.synchronize()
+            equal = equal and all(torch.equal(x.view(torch.int32), z.view(torch.int32)) for x, z in zip(out["host_slice_upload"], out["gather"]))
+        info = h.info()
+        d = dict(sequences=B, frames=T, outputs_equal=bool(equal), last_form=info["last_form"], allocations=info["allocations"],
+                 bytes_uploaded_host_route=4 * (shape[1] * B * D + B * Di), bytes_staged_gather=16 * B)
+        for k, v in ms.items():
+            d[k] = dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v])
+        d["gather_over_host"] = round(d["gather"]["ms"] / d["host_slice_upload"]["ms"], 3)
+        res[name] = d
+
+    case("regular", args.sequences)
+    case("half", 64)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -477,12 +559,16 @@ def main():
     ap.add_argument("--chunks", action="store_true",
                     help="--supervision --alignment: chunks of --frames frames out of utterances of --utt-frames, assign_alignment_chunks")
     ap.add_argument("--utt-frames", type=int, default=1000)
+    ap.add_argument("--features", action="store_true",
+                    help="the input of a minibatch of chunks: numpy slicing of host copies + upload against tdnnf_chunk_input_gather (--sequences, --frames, --utt-frames)")
     ap.add_argument("--alternatives", type=int, default=1)
     ap.add_argument("--sequences", type=int, default=128)
     ap.add_argument("--frames", type=int, default=150)
     args = ap.parse_args()
     assert args.cycle >= 8, "different graphs every iteration: a cycle of at least 8 batches"
     pkg = ge.load_package()
+    if args.features:
+        return features(args, pkg)
     if args.supervision:
         return alignment(args, pkg) if args.alignment else supervision(args, pkg)
     if args.transcripts:
