@@ -1408,8 +1408,9 @@ int tdnnf_infer_gemm_counts(const tdnnf_infer *, long long *plane_gemms, long lo
    outputs of the previous one if they are other buffers.  It takes first_t / num_t / frame_subsampling as integers, not a net.
    tdnnf_chunk_input_info: allocations made since create (0), successful gathers, and the form of the last (4: 16-byte, 1: scalar, 0: none
    yet); any out-pointer may be NULL.
-   Not built: 16-bit stored features, chunks shorter than T at an utterance's end, frame-rate (not output-rate) alignments, device-side
-   validation, capture into a HIP graph. */
+   Stored (8- and 16-bit) features: "FEATURE STORES" below, tdnnf_chunk_input_gather_stored.
+   Not built: chunks shorter than T at an utterance's end, frame-rate (not output-rate) alignments, device-side validation, capture into
+   a HIP graph. */
 typedef struct tdnnf_chunk_input tdnnf_chunk_input;
 int tdnnf_chunk_input_create(int max_sequences, tdnnf_chunk_input **out);
 void tdnnf_chunk_input_destroy(tdnnf_chunk_input *);
@@ -1420,6 +1421,82 @@ int tdnnf_chunk_input_gather(tdnnf_chunk_input *, int first_t, int num_t, int fr
                              const tdnnf_mat *feats, const int *ivector_rows_host, const tdnnf_mat *ivectors, int ivector_period, tdnnf_mat *feats_out,
                              tdnnf_mat *ivectors_out, tdnnf_stream stream);
 int tdnnf_chunk_input_info(const tdnnf_chunk_input *, int *max_sequences, long long *allocations, long long *gathers, int *last_form);
+
+/* FEATURE STORES: the utterances' features kept on the device as Kaldi stores them, CompressedMatrix codes, and decoded where they are
+   read -- in the gather of a chunk minibatch and in an expand for the whole-utterance passes.  A resident training set then costs what its
+   archive does: 1 byte a value ("CM", what copy-feats --compress=true writes, and "CM3") or 2 ("CM2", what the recipes' egs hold), not 4.
+   VALUE OF A CODE, float32, one rounding an operation, in this order, never contracted into an FMA (csrc/feature_code_value.h, which the egs
+   reader's read_general_matrix uses too: the two agree bit for bit).  k16 = 1.0f / 65535.0f; (min, range) the matrix's global header:
+     format 2 "CM2", code w (uint16):  min + range * k16 * w
+     format 3 "CM3", code b (uint8):   min + range * (1.0f / 255.0f) * b
+     format 1 "CM",  code b (uint8) of column j with percentiles h0..h3 (uint16), p_i = min + range * k16 * h_i:
+                     b <= 64: p0 + (p1 - p0) * b * (1.0f / 64.0f);  b <= 192: p1 + (p2 - p1) * (b - 64) * (1.0f / 128.0f);
+                     else: p2 + (p3 - p2) * (b - 192) * (1.0f / 63.0f)
+   A STORE holds one format (1, 2 or 3) and one feat_dim, and up to max_utterances utterances of max_frames frames in all (< 2^31), all
+   fixed at create, which makes every allocation.  BYTE LAYOUT, w = 2 bytes a code in format 2, else 1: utterance u's codes are row-major
+   (Kaldi's format 1 is column-major: transposed on the host at append, so that lanes on consecutive columns read consecutive bytes) at
+   byte offset[u] of the code buffer, offset[0] = 0, offset[u + 1] = offset[u] + round_up(frames[u] * feat_dim * w, 16): every utterance
+   begins at a 16-byte boundary; offsets are 64-bit.  Beside the codes an utterance takes a 32-byte table entry (offset, frames, header row,
+   min, range) and, in format 1, its p0..p3 as four floats a column, computed on the host by the expression above.  So
+     device_bytes = sum_u round_up(frames[u] * feat_dim * w, 16) + U * (32 + (format == 1 ? 16 * feat_dim : 0)),
+   which tdnnf_feature_store_layout computes on the host (no device, no handle; offsets_out: num_utts + 1 entries, or NULL) and
+   tdnnf_feature_store_info reports of a store; reserved_bytes is the arena create allocated for the capacities.
+   APPEND takes payloads in Kaldi's order, exactly as an archive holds them behind the token (format 1: percentiles cols x 4 uint16, codes
+   cols x rows bytes column-major; format 2: rows x cols uint16; format 3: rows x cols bytes), validates, packs and copies them behind the
+   store's last utterance; or (append_float) compresses float matrices -- rows_host[i] rows each, feat_dim columns, stacked contiguously
+   -- on the host by write_matrix's rule, bit for bit: [min, max] of the matrix, max = min + 1 where not max > min, code
+   (uint16) min(65535, max(0, (x - min) / range * 65535 + 0.499)) in format 2, the same with 255 and uint8 in format 3; format 1 from floats
+   is refused by name (Kaldi's percentile selection is not built).  An append is a load-time call: it waits for its copies, makes no device
+   or pinned allocation, and writes only bytes no earlier call reads.  Utterances are numbered in append order.
+   Refused with TDNNF_EINVAL, by name, before any device call and leaving the store as it was: more utterances or frames than reserved
+   (naming the excess, as the assigns name a capacity), cols != feat_dim, rows < 1, a non-finite min or range (of a payload, or of a float
+   matrix), a payload of another format than the store's.
+   USE.  tdnnf_feature_store_expand writes the decoded rows of the listed utterances, stacked in list order, any order, repeats allowed:
+   the matrix tdnnf_infer_compute and tdnnf_chunk_input_gather take.  It stages 8 bytes a list entry through the store's own ring (two
+   pinned buffers of 8 KB that take turns, whatever the capacities) and enqueues one copy and one kernel a piece of 1024 entries.
+   tdnnf_chunk_input_gather_stored is tdnnf_chunk_input_gather, "CHUNK INPUTS" word for word, with "feature row r of utterance u" read as
+   the decoded row r of the store's utterance u: seq_utt indexes the store, frames[u] is the store's, ivector_rows_host has one entry an
+   utterance of the store; the clamp, the frame shift, the i-vector row and the refusals are the same (named chunk_input_gather_stored);
+   i-vectors stay float.  It stages the same 16 bytes a sequence through the chunk-input handle's ring -- the table's first entry the
+   utterance's index -- and enqueues one copy and ONE kernel; the per-utterance facts come from the table the store built at append.
+   Neither call allocates, frees or synchronises a stream or the device; work enqueued on `stream` before it still reads the outputs of
+   the previous call if they are other buffers.  Kernels (csrc/feature_store_kernels.h): the grid-stride walk of chunk_input_gather_kernel;
+   form 4, where feat_dim is a multiple of 4 and the outputs' (and i-vectors') strides and base pointers allow 16 bytes: a lane takes 4
+   columns, its codes in one 4- or 8-byte load, one 16-byte store; else form 1, a code at a time.
+   tdnnf_feature_store_info: the store's format, feat_dim, utterances, frames, device_bytes (the closed form), reserved_bytes, device and
+   pinned allocations since create (0), successful gathers and expands, the form of the last of either (4, 1; 0: none yet); any
+   out-pointer may be NULL.  tdnnf_chunk_input_info keeps counting the float gathers alone.  tdnnf_feature_store_frames: frames[first ..
+   first + count) of the store.
+   Host only, no device, no handle, the functions the appends use (csrc/feature_store_plan.h): tdnnf_feature_store_layout (above);
+   tdnnf_feature_store_pack: one payload's header floats (format 1: 4 * feat_dim, p0..p3 a column; else header_out is not written and may
+   be NULL) and its rows * feat_dim codes row-major, after the payload's checks; tdnnf_feature_store_compress: (min, range) and the codes
+   of a float matrix in format 2 or 3.
+   Not built: format-1 compression of float input, removing or replacing utterances, mixed formats in one store, compressed i-vectors,
+   decoding inside tdnnf_infer_compute's own gather (an expand costs one float copy of a batch), streaming input from a store, device-side
+   validation, capture into a HIP graph. */
+typedef struct tdnnf_feature_store tdnnf_feature_store;
+typedef struct {
+  int format; /* 1 "CM", 2 "CM2", 3 "CM3" */
+  float min_value, range;
+  int rows, cols;
+  const void *percentiles; /* format 1: cols x 4 uint16; else not read */
+  const void *codes;
+} tdnnf_feature_payload;
+int tdnnf_feature_store_create(int format, int feat_dim, int max_utterances, long long max_frames, tdnnf_feature_store **out);
+void tdnnf_feature_store_destroy(tdnnf_feature_store *);
+int tdnnf_feature_store_layout(int format, int feat_dim, int num_utts, const int *frames_host, long long *offsets_out, long long *device_bytes_out);
+int tdnnf_feature_store_pack(int feat_dim, const tdnnf_feature_payload *item, float *header_out, void *codes_out);
+int tdnnf_feature_store_compress(int format, int rows, int cols, const float *matrix_host, float *min_out, float *range_out, void *codes_out);
+int tdnnf_feature_store_append(tdnnf_feature_store *, int num_items, const tdnnf_feature_payload *items);
+int tdnnf_feature_store_append_float(tdnnf_feature_store *, int num_items, const int *rows_host, const float *matrices_host);
+int tdnnf_feature_store_expand(tdnnf_feature_store *, int num_utts, const int *utt_host, tdnnf_mat *out, tdnnf_stream stream);
+int tdnnf_chunk_input_gather_stored(tdnnf_chunk_input *, int first_t, int num_t, int frame_subsampling, int frames_per_sequence, int num_sequences,
+                                    const int *seq_utt_host, const int *chunk_begin_host, int frame_shift, tdnnf_feature_store *store,
+                                    const int *ivector_rows_host, const tdnnf_mat *ivectors, int ivector_period, tdnnf_mat *feats_out,
+                                    tdnnf_mat *ivectors_out, tdnnf_stream stream);
+int tdnnf_feature_store_info(const tdnnf_feature_store *, int *format, int *feat_dim, int *utterances, long long *frames, long long *device_bytes,
+                             long long *reserved_bytes, long long *allocations, long long *gathers, long long *expands, int *last_form);
+int tdnnf_feature_store_frames(const tdnnf_feature_store *, int first, int count, int *frames_out);
 
 /* ======================================================================== inference (forward only, streaming)
  * The same output for streams whose features arrive a few frames at a time: nnet3's looped computation

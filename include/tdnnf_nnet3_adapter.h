@@ -540,6 +540,41 @@ inline void ChunkInputGather(tdnnf_chunk_input *input, int first_t, int num_t, i
                                  frames, &vf, ivector_rows, ivectors ? &vi : nullptr, ivector_period, &vo, ivectors_out ? &vio : nullptr, stream));
 }
 
+// Feature stores (tdnnf_hip.h, "FEATURE STORES"): the utterances' features kept on the device as the CompressedMatrix codes a Kaldi data
+// directory holds (CM, what copy-feats --compress=true writes; CM2; CM3) and decoded where they are read, so that a resident training set
+// costs what its archive does.  A store is created once for one format (1, 2, 3), one feat_dim and its capacities; release with
+// tdnnf_feature_store_destroy.  FeatureStoreAppend takes payloads exactly as CompressedMatrix holds them behind its token (global header
+// min / range / rows / cols, format 1: per-column percentiles and column-major bytes) and waits for its copies; utterances are numbered in
+// append order.  FeatureStoreExpand writes the decoded rows of the listed utterances stacked in list order -- what InferCompute and
+// ChunkInputGather take.  ChunkInputGatherStored is ChunkInputGather with the features decoded out of the store: seq_utt indexes the
+// store, the frames are the store's; ivector_rows has one entry an utterance of the store, i-vectors stay float.  All throw on what the
+// C entries refuse, by name, the store and the outputs as they were.
+inline tdnnf_feature_store *FeatureStoreCreate(int format, int feat_dim, int max_utterances, long long max_frames) {
+  tdnnf_feature_store *store = nullptr;
+  Check(tdnnf_feature_store_create(format, feat_dim, max_utterances, max_frames, &store));
+  return store;
+}
+inline void FeatureStoreAppend(tdnnf_feature_store *store, int num_items, const tdnnf_feature_payload *items) {
+  Check(tdnnf_feature_store_append(store, num_items, items));
+}
+template <class CuMat>
+inline void FeatureStoreExpand(tdnnf_feature_store *store, int num_utts, const int *utts, CuMat *out, tdnnf_stream stream) {
+  if (!out) TDNNF_ADAPTER_FAIL("tdnnf: FeatureStoreExpand needs out");
+  tdnnf_mat vo = View(*out);
+  Check(tdnnf_feature_store_expand(store, num_utts, utts, &vo, stream));
+}
+template <class CuMat>
+inline void ChunkInputGatherStored(tdnnf_chunk_input *input, int first_t, int num_t, int frame_subsampling, int frames_per_sequence, int num_sequences,
+                                   const int *seq_utt, const int *chunk_begin, int frame_shift, tdnnf_feature_store *store, const int *ivector_rows,
+                                   const CuMat *ivectors, int ivector_period, CuMat *feats_out, CuMat *ivectors_out, tdnnf_stream stream) {
+  if (!feats_out) TDNNF_ADAPTER_FAIL("tdnnf: ChunkInputGatherStored needs feats_out");
+  tdnnf_mat vo = View(*feats_out), vi, vio;
+  if (ivectors) vi = View(*ivectors);
+  if (ivectors_out) vio = View(*ivectors_out);
+  Check(tdnnf_chunk_input_gather_stored(input, first_t, num_t, frame_subsampling, frames_per_sequence, num_sequences, seq_utt, chunk_begin, frame_shift, store,
+                                        ivector_rows, ivectors ? &vi : nullptr, ivector_period, &vo, ivectors_out ? &vio : nullptr, stream));
+}
+
 // Best-path alignment (tdnnf_hip.h, "best-path alignment"; what nnet3-align-compiled | ali-to-pdf prints, or the free best path through the
 // denominator graph): frame t of utterance u is row utt_row_begin[u] + t * row_stride of nnet_output.  The index arrays are host memory;
 // pdf_out_dev: sum(utt_frames) ints, state_out_dev (may be null): sum(utt_frames) + num_utts ints, results_dev: 2 doubles per utterance

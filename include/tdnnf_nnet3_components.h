@@ -2186,6 +2186,31 @@ inline void GatherChunkInput(tdnnf_chunk_input *input, int32 first_t, int32 num_
                                   ivector_rows.empty() ? nullptr : ivector_rows.data(), ivectors, ivector_period, feats_out, ivectors_out, Hooks().stream);
 }
 
+// The same with the utterances' features held compressed on the device (tdnnf_hip.h, "FEATURE STORES"): a store of one CompressedMatrix
+// format (1 CM, 2 CM2, 3 CM3) and one feat_dim, created once for its capacities (release with tdnnf_feature_store_destroy), filled with
+// payloads exactly as CompressedMatrix holds them -- utterances are numbered in append order --, and decoded where it is read, on the
+// hooks' stream: ExpandFeatureStore writes the listed utterances' rows stacked (what the inference calls and GatherChunkInput take),
+// GatherStoredChunkInput is GatherChunkInput with seq_utt indexing the store and the frames the store's.
+inline tdnnf_feature_store *NewFeatureStore(int32 format, int32 feat_dim, int32 max_utterances, long long max_frames) {
+  return tdnnf_adapter::FeatureStoreCreate(format, feat_dim, max_utterances, max_frames);
+}
+inline void AppendFeatureStore(tdnnf_feature_store *store, const std::vector<tdnnf_feature_payload> &items) {
+  tdnnf_adapter::FeatureStoreAppend(store, static_cast<int32>(items.size()), items.data());
+}
+inline void ExpandFeatureStore(tdnnf_feature_store *store, const std::vector<int32> &utts, CuMatrixBase *out) {
+  tdnnf_adapter::FeatureStoreExpand(store, static_cast<int32>(utts.size()), utts.data(), out, Hooks().stream);
+}
+inline void GatherStoredChunkInput(tdnnf_chunk_input *input, int32 first_t, int32 num_t, int32 frame_subsampling, int32 frames_per_sequence,
+                                   const std::vector<int32> &seq_utt, const std::vector<int32> &chunk_begin, int32 frame_shift, tdnnf_feature_store *store,
+                                   const std::vector<int32> &ivector_rows, const CuMatrixBase *ivectors, int32 ivector_period, CuMatrixBase *feats_out,
+                                   CuMatrixBase *ivectors_out) {
+  if (chunk_begin.size() != seq_utt.size())
+    throw std::runtime_error("tdnnf: GatherStoredChunkInput: seq_utt and chunk_begin must have one entry a sequence");
+  tdnnf_adapter::ChunkInputGatherStored(input, first_t, num_t, frame_subsampling, frames_per_sequence, static_cast<int32>(seq_utt.size()), seq_utt.data(),
+                                        chunk_begin.data(), frame_shift, store, ivector_rows.empty() ? nullptr : ivector_rows.data(), ivectors,
+                                        ivector_period, feats_out, ivectors_out, Hooks().stream);
+}
+
 // ------------------------------------------------------------------------------------------------ best-path alignment
 // What nnet3-align-compiled | ali-to-pdf prints for the utterances whose output rows lie stacked in nnet_output (utterance u: rows
 // utt_row_begin[u] .. + utt_frames[u]), or the free best path through the denominator graph: pdf-ids into pdf_out_dev (sum of utt_frames

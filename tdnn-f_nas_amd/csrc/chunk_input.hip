@@ -6,18 +6,10 @@
 // turn before last.
 #include <string>
 
-#include "assign_stage.h"
+#include "chunk_input_handle.h"
 #include "chunk_input_kernels.h"
 
 using namespace tdnnf;
-
-struct tdnnf_chunk_input {
-  int max_sequences;
-  AssignStage stage;  // the device table is the whole of its allocation
-  int allocs_at_create;
-  long long gathers;
-  int last_form;  // of the last gather: 4 the 16-byte form, 1 the scalar form, 0 before the first
-};
 
 extern "C" {
 

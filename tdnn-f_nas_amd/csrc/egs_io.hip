@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.h"
+#include "feature_code_value.h"
 #include "tdnnf_hip.h"
 
 namespace {
@@ -146,7 +147,8 @@ void read_general_matrix(In &in, Io *io) {
     io->rows = rows;
     io->cols = cols;
     io->data.resize((size_t)rows * cols);
-    auto u16 = [&](uint16_t v) { return min_value + range * (1.0f / 65535.0f) * v; };
+    // (the value of every code: feature_code_value.h, shared with the feature stores)
+    auto u16 = [&](uint16_t v) { return tdnnf::code16_value(min_value, range, v); };
     if (format == 1) {
       std::vector<uint16_t> hdr((size_t)cols * 4);
       in.raw(hdr.data(), hdr.size() * 2);
@@ -155,12 +157,7 @@ void read_general_matrix(In &in, Io *io) {
       for (int j = 0; j < cols; j++) {
         const float p0 = u16(hdr[4 * j]), p25 = u16(hdr[4 * j + 1]), p75 = u16(hdr[4 * j + 2]), p100 = u16(hdr[4 * j + 3]);
         for (int i = 0; i < rows; i++) {
-          const uint8_t b = bytes[(size_t)j * rows + i];
-          float v;
-          if (b <= 64) v = p0 + (p25 - p0) * b * (1.0f / 64.0f);
-          else if (b <= 192) v = p25 + (p75 - p25) * (b - 64) * (1.0f / 128.0f);
-          else v = p75 + (p100 - p75) * (b - 192) * (1.0f / 63.0f);
-          io->data[(size_t)i * cols + j] = v;
+          io->data[(size_t)i * cols + j] = tdnnf::percentile_code_value(p0, p25, p75, p100, bytes[(size_t)j * rows + i]);
         }
       }
     } else if (format == 2) {
@@ -170,7 +167,7 @@ void read_general_matrix(In &in, Io *io) {
     } else {
       std::vector<uint8_t> b((size_t)rows * cols);
       in.raw(b.data(), b.size());
-      for (size_t i = 0; i < b.size(); i++) io->data[i] = min_value + range * (1.0f / 255.0f) * b[i];
+      for (size_t i = 0; i < b.size(); i++) io->data[i] = tdnnf::code8_value(min_value, range, b[i]);
     }
     return;
   }
@@ -420,13 +417,8 @@ void write_matrix(OutS &o, const float *data, int rows, int cols, int compress) 
     return;
   }
   // kTwoByteAuto: 16 bits over [min, max] of the matrix (what nnet3-chain-get-egs --compress=true writes for features)
-  float mn = std::numeric_limits<float>::infinity(), mx = -mn;
-  for (size_t i = 0; i < (size_t)rows * cols; i++) {
-    mn = std::min(mn, data[i]);
-    mx = std::max(mx, data[i]);
-  }
-  if (!(mx > mn)) mx = mn + 1.0f;
-  const float range = mx - mn;
+  float mn, range;
+  tdnnf::code_range(data, (size_t)rows * cols, &mn, &range);
   o.token("CM2");
   o.raw(&mn, 4);
   o.raw(&range, 4);
@@ -434,10 +426,7 @@ void write_matrix(OutS &o, const float *data, int rows, int cols, int compress) 
   o.raw(&r, 4);
   o.raw(&c, 4);
   std::vector<uint16_t> w((size_t)rows * cols);
-  for (size_t i = 0; i < w.size(); i++) {
-    const float f = (data[i] - mn) / range;
-    w[i] = (uint16_t)std::min(65535.0f, std::max(0.0f, f * 65535.0f + 0.499f));
-  }
+  for (size_t i = 0; i < w.size(); i++) w[i] = (uint16_t)tdnnf::value_code(data[i], mn, range, 65535.0f);
   o.raw(w.data(), w.size() * 2);
 }
 

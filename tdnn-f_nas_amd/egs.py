@@ -2,7 +2,8 @@
 example archives in Kaldi's binary format (restated, see the header of egs_io.hip) to and from numpy, and the merge of
 single-sequence examples into the minibatch the trainer takes.  Host only, no GPU needed -- but for the minibatch generators, which
 hand device objects to the trainer: from an archive (minibatches), or straight from aligned utterances with the features gathered and
-the supervisions compiled on the device (minibatches_from_utterances; write_chunk_egs is its host route into an archive)."""
+the supervisions compiled on the device (minibatches_from_utterances; write_chunk_egs is its host route into an archive), or with the
+features held as Kaldi's compressed codes (minibatches_from_store; read_feature_archive / write_feature_archive: feature archives)."""
 import ctypes as C
 
 import numpy as np
@@ -349,6 +350,126 @@ def minibatches_from_utterances(utterances, alignments, net, unit_set, tolerance
         sup = reused.assign_alignment_chunks(unit_set, [alignments[u] for u in utt], [out_frames[u] for u in utt], begins, T, tolerance, weight)
         sup.chunks = list(chunks)
         yield f, iv, sup
+
+
+def minibatches_from_store(store, ivectors, alignments, net, unit_set, tolerance, frame_shift=0, ivector_period=10, seed=0, weight=1.0, discard_partial=True):
+    """minibatches_from_utterances with the features taken from a hipabi.FeatureStore (include/tdnnf_hip.h, "FEATURE STORES"): the
+    utterances are the store's, in append order, their features decoded inside the gather (ChunkInput.gather_stored) -- no float copy of
+    them exists.  ivectors[u]: the i-vector rows R_u x ivector_dim of utterance u (numpy or torch; stacked on the device once, float), not
+    read by a net without i-vectors; alignments[u] as there.  The same chunk order for a seed, the same reserved supervision and the same
+    validity rule: what it yields is, minibatch for minibatch, what minibatches_from_utterances yields for store.expand's features."""
+    import torch
+    cfg = net.cfg
+    fsf, B = int(cfg.frame_subsampling), int(cfg.num_sequences)
+    T = int(cfg.frames_per_chunk) // fsf
+    frames = list(store.frames)
+    if len(alignments) != len(frames):
+        raise ValueError("%d utterances and %d alignments" % (len(frames), len(alignments)))
+    if store.feat_dim != int(cfg.feat_dim):
+        raise ValueError("a store of feat_dim %d for a net of feat_dim %d" % (store.feat_dim, int(cfg.feat_dim)))
+    ivs = iv_rows = None
+    if cfg.ivector_dim > 0:
+        if len(ivectors) != len(frames):
+            raise ValueError("%d utterances and %d i-vector matrices" % (len(frames), len(ivectors)))
+        rows = [torch.as_tensor(iv, dtype=torch.float32).cuda().reshape(-1, int(cfg.ivector_dim)) for iv in ivectors]
+        rows = [iv if ivector_period > 0 else iv[:1] for iv in rows]
+        ivs, iv_rows = torch.cat(rows).contiguous(), [int(iv.shape[0]) for iv in rows]
+    out_frames = [(t + fsf - 1) // fsf for t in frames]
+    batches = chunk_minibatches(utterance_chunks(out_frames, T), B, seed, discard_partial)
+    if not batches:
+        return
+    gatherer, reused = hipabi.ChunkInput(B), ReusedSupervision()
+    out = (torch.empty(net.num_t_in * B, store.feat_dim, dtype=torch.float32, device="cuda"),
+           torch.empty(B, ivs.shape[1], dtype=torch.float32, device="cuda") if ivs is not None else None)
+    for chunks in batches:
+        utt, begins = [u for u, _ in chunks], [o for _, o in chunks]
+        f, iv = gatherer.gather_stored(net, T, utt, begins, store, iv_rows, ivs, ivector_period, frame_shift, out=out)
+        sup = reused.assign_alignment_chunks(unit_set, [alignments[u] for u in utt], [out_frames[u] for u in utt], begins, T, tolerance, weight)
+        sup.chunks = list(chunks)
+        yield f, iv, sup
+
+
+_MATRIX_TOKENS = {b"CM": 1, b"CM2": 2, b"CM3": 3}
+
+
+def read_feature_archive(path):
+    """Iterates over a Kaldi binary archive of matrices (what copy-feats writes to ark:path; per entry `key ' ' \\0B` then a GeneralMatrix)
+    and yields (key, item).  A CompressedMatrix (token CM, CM2 or CM3) comes as the item dict hipabi.FeatureStore.append takes, its codes
+    UNTOUCHED, in Kaldi's order: {"format": 1 | 2 | 3, "min", "range" (numpy float32), "rows", "cols", "codes": uint8 [cols, rows]
+    (format 1, column-major), uint16 [rows, cols] (2) or uint8 [rows, cols] (3), and for format 1 "percentiles": uint16 [cols, 4]}.  A full
+    matrix (FM, DM) comes as a float32 array.  Host only."""
+    with open(path, "rb") as f:
+        data = f.read()
+    at = 0
+
+    def take(n, what):
+        nonlocal at
+        if at + n > len(data):
+            raise ValueError("%s: unexpected end of file in %s" % (path, what))
+        at += n
+        return data[at - n:at]
+
+    def token():
+        end = data.find(b" ", at)
+        if end < 0:
+            raise ValueError("%s: unexpected end of file in a token" % path)
+        return take(end + 1 - at, "a token")[:-1]
+
+    def i32():
+        if take(1, "an integer") != b"\x04":
+            raise ValueError("%s: expected a 4-byte integer" % path)
+        return int(np.frombuffer(take(4, "an integer"), "<i4")[0])
+
+    while at < len(data):
+        key = token().decode()
+        if take(2, "the binary mark") != b"\0B":
+            raise ValueError("%s: entry %s is not in binary mode" % (path, key))
+        tok = token()
+        if tok in _MATRIX_TOKENS:
+            fmt = _MATRIX_TOKENS[tok]
+            mn, rg = np.frombuffer(take(8, "a matrix header"), "<f4")
+            rows, cols = (int(x) for x in np.frombuffer(take(8, "a matrix header"), "<i4"))
+            if rows < 0 or cols < 0:
+                raise ValueError("%s: entry %s has a compressed matrix of %d x %d" % (path, key, rows, cols))
+            item = dict(format=fmt, min=np.float32(mn), range=np.float32(rg), rows=rows, cols=cols)
+            if fmt == 1:
+                item["percentiles"] = np.frombuffer(take(8 * cols, "the percentiles"), "<u2").reshape(cols, 4).copy()
+                item["codes"] = np.frombuffer(take(rows * cols, "the codes"), np.uint8).reshape(cols, rows).copy()
+            elif fmt == 2:
+                item["codes"] = np.frombuffer(take(2 * rows * cols, "the codes"), "<u2").reshape(rows, cols).copy()
+            else:
+                item["codes"] = np.frombuffer(take(rows * cols, "the codes"), np.uint8).reshape(rows, cols).copy()
+            yield key, item
+        elif tok in (b"FM", b"DM"):
+            rows, cols = i32(), i32()
+            if rows < 0 or cols < 0:
+                raise ValueError("%s: entry %s has a matrix of %d x %d" % (path, key, rows, cols))
+            width, kind = (4, "<f4") if tok == b"FM" else (8, "<f8")
+            yield key, np.frombuffer(take(width * rows * cols, "a matrix"), kind).reshape(rows, cols).astype(np.float32)
+        else:
+            raise ValueError("%s: entry %s holds %r, not a matrix (FM, DM, CM, CM2, CM3)" % (path, key, tok))
+
+
+def write_feature_archive(path, items):
+    """The inverse for compressed items: (key, item dict as read_feature_archive yields it) back into Kaldi's bytes -- reading an archive
+    of compressed matrices and writing it gives the file again.  Float matrices go through infer.write_matrix_archive."""
+    tokens = {v: k for k, v in _MATRIX_TOKENS.items()}
+    with open(path, "wb") as f:
+        for key, item in items:
+            fmt, rows, cols = int(item["format"]), int(item["rows"]), int(item["cols"])
+            if fmt not in tokens or not key or " " in key:
+                raise ValueError("%s: entry %r of format %r: a key without spaces and format 1, 2 or 3 are needed" % (path, key, fmt))
+            codes = np.ascontiguousarray(item["codes"], dtype="<u2" if fmt == 2 else np.uint8)
+            if rows < 0 or cols < 0 or codes.size != rows * cols:
+                raise ValueError("%s: entry %s is %d x %d with %d codes" % (path, key, rows, cols, codes.size))
+            f.write(key.encode() + b" \0B" + tokens[fmt] + b" ")
+            f.write(np.asarray([item["min"], item["range"]], "<f4").tobytes() + np.asarray([rows, cols], "<i4").tobytes())
+            if fmt == 1:
+                pct = np.ascontiguousarray(item["percentiles"], dtype="<u2")
+                if pct.size != 4 * cols:
+                    raise ValueError("%s: entry %s has %d columns and %d percentiles" % (path, key, cols, pct.size))
+                f.write(pct.tobytes())
+            f.write(codes.tobytes())
 
 
 def write_chunk_egs(path, utterances, alignments, net, unit_set, tolerance, chunks, margin=None, compress=False, ivector_period=10, weight=1.0):

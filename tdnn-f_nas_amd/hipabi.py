@@ -966,6 +966,26 @@ class ChunkInput:
                                               pmat(ivectors_out) if use_iv else None, stream()))
         return feats_out, (ivectors_out if use_iv else None)
 
+    def gather_stored(self, net_or_shape, frames_per_sequence, seq_utt, chunk_begins, store, ivector_rows, ivectors, ivector_period, frame_shift=0,
+                      out=None):
+        """tdnnf_chunk_input_gather_stored on the current stream: gather with the features decoded out of `store` (a FeatureStore; include/
+        tdnnf_hip.h, "FEATURE STORES").  seq_utt indexes the store's utterances, whose frames are the store's; ivector_rows / ivectors:
+        one entry / the rows of every utterance of the store, float, as gather takes them.  Counted in store.info(), not in info()."""
+        import torch
+        first_t, num_t, fsf = self._shape(net_or_shape)
+        utt, first = _sequence_chunks(seq_utt, chunk_begins)
+        B = len(utt[0])
+        use_iv = ivectors is not None and ivectors.shape[1] > 0
+        ivr = iarr(ivector_rows) if ivector_rows is not None else (None, None)
+        if out is None:
+            out = (torch.empty(num_t * B, store.feat_dim, dtype=torch.float32, device="cuda"),
+                   torch.empty(B, ivectors.shape[1], dtype=torch.float32, device="cuda") if use_iv else None)
+        feats_out, ivectors_out = out
+        check(load().tdnnf_chunk_input_gather_stored(self.h, first_t, num_t, fsf, int(frames_per_sequence), B, utt[1], first[1], int(frame_shift), store.h,
+                                                     ivr[1], pmat(ivectors) if use_iv else None, int(ivector_period), pmat(feats_out),
+                                                     pmat(ivectors_out) if use_iv else None, stream()))
+        return feats_out, (ivectors_out if use_iv else None)
+
     def info(self):
         """{max_sequences, allocations, gathers, last_form} (tdnnf_chunk_input_info): device and pinned allocations since create, successful
         gathers, the last one's form -- 4: 16-byte loads and stores, 1: a float at a time, 0: none yet."""
@@ -976,4 +996,138 @@ class ChunkInput:
     def __del__(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.tdnnf_chunk_input_destroy(self.h)
+            self.h = None
+
+
+class FeaturePayload(C.Structure):
+    """tdnnf_feature_payload: one CompressedMatrix in Kaldi's order, as an archive holds it"""
+    _fields_ = [("format", C.c_int), ("min_value", C.c_float), ("range", C.c_float), ("rows", C.c_int), ("cols", C.c_int), ("percentiles", C.c_void_p),
+                ("codes", C.c_void_p)]
+
+
+FEATURE_TOKENS = {1: "CM", 2: "CM2", 3: "CM3"}
+
+
+def _payload(item, format=None):
+    """(FeaturePayload, the arrays it points into) of an item dict {"min", "range", "rows", "cols", "codes"[, "percentiles"][, "format"]}:
+    codes uint8 [cols, rows] (format 1, column-major as Kaldi holds them), uint16 [rows, cols] (2) or uint8 [rows, cols] (3); percentiles
+    uint16 [cols, 4].  The format is the item's own where it names one, else `format`."""
+    import numpy as np
+    fmt = int(item.get("format", format if format is not None else 0))
+    rows, cols = int(item["rows"]), int(item["cols"])
+    codes = np.ascontiguousarray(item["codes"], dtype=np.uint16 if fmt == 2 else np.uint8)
+    if codes.size != rows * cols:
+        raise HipAbiError(f"an item of {rows} x {cols} with {codes.size} codes")
+    pct = None
+    if fmt == 1:
+        pct = np.ascontiguousarray(item.get("percentiles"), dtype=np.uint16)
+        if pct.size != 4 * cols:
+            raise HipAbiError(f"an item of {cols} columns with {pct.size} percentiles")
+    p = FeaturePayload(fmt, float(item["min"]), float(item["range"]), rows, cols, pct.ctypes.data if pct is not None else None, codes.ctypes.data)
+    return p, (codes, pct)
+
+
+class FeatureStore:
+    """Utterances' features kept on the device as Kaldi's CompressedMatrix codes (tdnnf_feature_store; include/tdnnf_hip.h, "FEATURE
+    STORES"): one format (1 "CM", 2 "CM2", 3 "CM3") and one feat_dim, capacities fixed and everything allocated at create.  Utterances are
+    numbered in append order; ChunkInput.gather_stored and expand decode them on the device, bit for bit egs.Reader's values."""
+
+    def __init__(self, format, feat_dim, max_utterances, max_frames):
+        self.h = C.c_void_p()
+        self.format, self.feat_dim = int(format), int(feat_dim)
+        self.frames = []  # of every utterance, in append order: the library's (tdnnf_feature_store_frames), read back behind every append
+        check(load().tdnnf_feature_store_create(self.format, self.feat_dim, int(max_utterances), int(max_frames), C.byref(self.h)))
+
+    def _read_frames(self):
+        import numpy as np
+        n = self.info()["utterances"]
+        frames = np.zeros(max(n, 1), np.int32)
+        check(load().tdnnf_feature_store_frames(self.h, 0, n, frames.ctypes.data_as(C.c_void_p)))
+        self.frames = [int(f) for f in frames[:n]]
+
+    def append(self, items):
+        """tdnnf_feature_store_append: item dicts {"min", "range", "rows", "cols", "codes"[, "percentiles"]} in Kaldi's order, as
+        egs.read_feature_archive yields them.  Waits for its copies; a refusal (HipAbiError) leaves the store as it was."""
+        payloads = [_payload(item, self.format) for item in items]
+        arr = (FeaturePayload * max(len(payloads), 1))(*[p for p, _ in payloads])
+        check(load().tdnnf_feature_store_append(self.h, len(payloads), arr))
+        self._read_frames()
+
+    def append_float(self, matrices):
+        """tdnnf_feature_store_append_float: float matrices [frames, feat_dim] (numpy or torch) compressed on the host by the egs writer's
+        rule into the store's format (2 or 3; format 1 is refused)."""
+        import numpy as np
+        ms = [np.ascontiguousarray(m.detach().cpu().numpy() if hasattr(m, "detach") else m, dtype=np.float32) for m in matrices]
+        for i, m in enumerate(ms):
+            if m.ndim != 2 or (m.shape[1] != self.feat_dim and m.shape[0] > 0):
+                raise HipAbiError(f"feature_store_append_float: item {i} has shape {m.shape}, feat_dim is {self.feat_dim}")
+        rows = iarr([m.shape[0] for m in ms])
+        stacked = farr(np.concatenate([m.reshape(-1, self.feat_dim) for m in ms]) if ms else np.zeros((0, self.feat_dim), np.float32))
+        check(load().tdnnf_feature_store_append_float(self.h, len(ms), rows[1], stacked[1]))
+        self._read_frames()
+
+    def expand(self, utts, out=None):
+        """tdnnf_feature_store_expand on the current stream: the decoded rows of the listed utterances stacked in list order (any order,
+        repeats allowed), a float32 CUDA tensor [sum of their frames, feat_dim] -- out, or a new one."""
+        import torch
+        u = iarr(utts)
+        if out is None:
+            rows = sum(self.frames[i] for i in u[0] if 0 <= i < len(self.frames))
+            out = torch.empty(rows, self.feat_dim, dtype=torch.float32, device="cuda")
+        check(load().tdnnf_feature_store_expand(self.h, len(u[0]), u[1], pmat(out), stream()))
+        return out
+
+    def utterances(self, utts, ivectors):
+        """The [(feats, ivectors)] list AcousticModel.compute / align / posteriors* take, for the listed utterances: the features are views
+        of ONE expand, ivectors[k] goes with utts[k]."""
+        import torch
+        utts = [int(u) for u in utts]
+        if len(ivectors) != len(utts):
+            raise HipAbiError(f"{len(utts)} utterances and {len(ivectors)} i-vector matrices")
+        feats = torch.split(self.expand(utts), [self.frames[u] for u in utts]) if utts else []
+        return list(zip(feats, ivectors))
+
+    def info(self):
+        """{format, feat_dim, utterances, frames, device_bytes, reserved_bytes, allocations, gathers, expands, last_form}
+        (tdnnf_feature_store_info): device_bytes is the closed form of the header (layout), reserved_bytes the arena of the capacities,
+        allocations those since create, last_form 4 (a lane decodes 4 columns: 16-byte stores), 1 (a code at a time) or 0 (none yet)."""
+        v = [C.c_int(), C.c_int(), C.c_int(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_int()]
+        check(load().tdnnf_feature_store_info(self.h, *[C.byref(x) for x in v]))
+        keys = ("format", "feat_dim", "utterances", "frames", "device_bytes", "reserved_bytes", "allocations", "gathers", "expands", "last_form")
+        return {k: x.value for k, x in zip(keys, v)}
+
+    @staticmethod
+    def layout(format, feat_dim, frames):
+        """tdnnf_feature_store_layout (host only): (code offsets numpy int64 [utterances + 1], device_bytes) of utterances of these frames."""
+        import numpy as np
+        fr = iarr(frames)
+        offsets, total = np.zeros(len(fr[0]) + 1, np.int64), C.c_longlong()
+        check(load().tdnnf_feature_store_layout(int(format), int(feat_dim), len(fr[0]), fr[1], offsets.ctypes.data_as(C.c_void_p), C.byref(total)))
+        return offsets, total.value
+
+    @staticmethod
+    def pack(format, feat_dim, item):
+        """Host only, what an append copies to the device.  item a dict: tdnnf_feature_store_pack -- {"min", "range", "header": float32
+        [feat_dim, 4] p0..p3 a column (format 1) or None, "codes": row-major [rows, feat_dim] uint8 or uint16}.  item a float matrix:
+        tdnnf_feature_store_compress in `format` -- the same dict with the matrix's (min, range) and codes."""
+        import numpy as np
+        if isinstance(item, dict):
+            p, keep = _payload(item, format)
+            if p.format != int(format):
+                raise HipAbiError(f"feature_store_pack: item 0 is a payload of format {p.format}, not of format {int(format)}")
+            header = np.zeros((int(feat_dim), 4), np.float32) if p.format == 1 else None
+            codes = np.zeros((max(p.rows, 0), int(feat_dim)), np.uint16 if p.format == 2 else np.uint8)
+            check(load().tdnnf_feature_store_pack(int(feat_dim), C.byref(p), header.ctypes.data_as(C.c_void_p) if header is not None else None,
+                                                  codes.ctypes.data_as(C.c_void_p)))
+            return dict(min=np.float32(p.min_value), range=np.float32(p.range), header=header, codes=codes)
+        m = np.ascontiguousarray(item, dtype=np.float32)
+        codes = np.zeros(m.shape, np.uint16 if int(format) == 2 else np.uint8)
+        mn, rg = C.c_float(), C.c_float()
+        check(load().tdnnf_feature_store_compress(int(format), m.shape[0], m.shape[1] if m.ndim == 2 else 0, m.ctypes.data_as(C.c_void_p), C.byref(mn), C.byref(rg),
+                                                  codes.ctypes.data_as(C.c_void_p)))
+        return dict(min=np.float32(mn.value), range=np.float32(rg.value), header=None, codes=codes)
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.tdnnf_feature_store_destroy(self.h)
             self.h = None

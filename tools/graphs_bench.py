@@ -22,8 +22,10 @@ utterances of --utt-frames (default 1000): the utterance's lattice built and cut
 tdnnf_supervision_assign_alignment_chunks.
 --features [--sequences B --frames T --utt-frames N]: instead, the INPUT of a minibatch of chunks (see features() below): the t-major
 features and the i-vectors sliced out of host copies with numpy and uploaded, against tdnnf_chunk_input_gather from the device copies.
+--features --stored 1|2|3: the utterances' features held as Kaldi's compressed codes in a feature store of that format (see stored_features()
+below): the float gather against tdnnf_chunk_input_gather_stored, a device copy of a batch of utterances against tdnnf_feature_store_expand.
 usage (GPU box): python tools/graphs_bench.py [--repeats R] [--cycle N] [--pdfs P] [--only forced|free|numerator] [--transcripts] [--pronunciations]
-                                              [--features [--sequences B --frames T --utt-frames N]]
+                                              [--features [--stored 1|2|3] [--sequences B --frames T --utt-frames N]]
                                               [--supervision [--tolerance N --alternatives N] [--sequences B --frames T]]
                                               [--supervision --alignment [--chunks [--utt-frames N]] [--tolerance N] [--sequences B --frames T]]"""
 import argparse
@@ -543,6 +545,109 @@ def features(args, pkg):
     print(json.dumps(res))
 
 
+def stored_features(args, pkg):
+    """--features --stored FORMAT: the same minibatches with the utterances' features held in a hipabi.FeatureStore of format 1 (CM), 2
+    (CM2) or 3 (CM3) (include/tdnnf_hip.h, "FEATURE STORES") instead of a float matrix, alternating in one process, medians of --repeats:
+      gather / gather_stored   ChunkInput.gather from the float copy against ChunkInput.gather_stored from the store, into the same kind of
+                               output buffers; the float copy IS the store's expand, so the outputs are compared for equality;
+      copy / expand            a batch of --expand-utts utterances: torch.index_select of their rows out of the float copy (one device
+                               kernel through a row list made beforehand) against FeatureStore.expand.
+    Wall-clock per call including the enqueue, not the kernels alone.  device_bytes: what the utterances take each way."""
+    abi, fsf, D, Di, period, fmt = pkg.hipabi, 3, 40, 100, 10, args.stored
+    net = pkg.trainer.ChainNet(pkg.trainer.make_config(frames_per_chunk=args.frames * fsf, num_sequences=1, bottleneck=16, feat_dim=D, ivector_dim=Di, num_pdfs=64,
+                                                       hidden_dim=64, small_dim=32))
+    shape = (net.first_t, net.num_t_in, fsf)
+    net.close()
+    rng = np.random.default_rng(0)
+    U, T = 64, args.frames
+    frames = rng.integers(args.utt_frames * fsf - 2 * fsf, args.utt_frames * fsf + 1, size=U)
+    rows = (frames + period - 1) // period
+    store = abi.FeatureStore(fmt, D, U, int(frames.sum()))
+    for f in frames:  # codes and headers drawn directly: any codes cost the same
+        f = int(f)
+        item = dict(format=fmt, min=np.float32(-3.0), range=np.float32(9.0), rows=f, cols=D)
+        if fmt == 1:
+            item["percentiles"] = np.sort(rng.integers(0, 65536, size=(D, 4)), axis=1).astype(np.uint16)
+            item["codes"] = rng.integers(0, 256, size=(D, f)).astype(np.uint8)
+        else:
+            item["codes"] = rng.integers(0, 65536 if fmt == 2 else 256, size=(f, D)).astype(np.uint16 if fmt == 2 else np.uint8)
+        store.append([item])
+    F_dev = store.expand(np.arange(U))
+    IV_dev = torch.from_numpy(rng.standard_normal((int(rows.sum()), Di)).astype(np.float32)).cuda()
+    feat0 = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    res = dict(metric="stored_chunk_features_per_minibatch", format=fmt, cycle=args.cycle, repeats=args.repeats, feat_dim=D, ivector_dim=Di, first_t=shape[0],
+               num_t=shape[1], frame_subsampling=fsf, utterances=U, utt_frames=args.utt_frames, device_bytes_float=4 * int(frames.sum()) * D,
+               device_bytes_stored=store.info()["device_bytes"], reserved_bytes_stored=store.info()["reserved_bytes"])
+
+    def timed(fns):
+        def loop(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(args.cycle):
+                fn(i)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / args.cycle
+        ms = {k: [] for k in fns}
+        for r in range(args.repeats + 1):  # the first round warms up
+            for k, fn in fns.items():
+                t = loop(fn)
+                if r:
+                    ms[k].append(t)
+        return {k: dict(ms=round(float(np.median(v)), 3), ms_all=[round(x, 3) for x in v]) for k, v in ms.items()}
+
+    def case(name, B):
+        batches = []
+        for c in range(args.cycle):
+            utt = rng.integers(0, U, size=B)
+            batches.append((utt, rng.integers(0, (frames[utt] + fsf - 1) // fsf - T + 1), int(rng.integers(-(fsf - 1), fsf))))
+        h = abi.ChunkInput(B)
+        out = {k: (torch.zeros(shape[1] * B, D, device="cuda"), torch.zeros(B, Di, device="cuda")) for k in ("gather", "gather_stored")}
+
+        def gather(i, o=out["gather"]):
+            utt, begins, shift = batches[i]
+            h.gather(shape, T, utt, begins, frames, F_dev, rows, IV_dev, period, frame_shift=shift, out=o)
+
+        def gather_stored(i, o=out["gather_stored"]):
+            utt, begins, shift = batches[i]
+            h.gather_stored(shape, T, utt, begins, store, rows, IV_dev, period, frame_shift=shift, out=o)
+
+        d = dict(sequences=B, frames=T, **timed(dict(gather=gather, gather_stored=gather_stored)))
+        equal = True
+        for i in range(args.cycle):
+            gather(i), gather_stored(i)
+            torch.cuda.synchronize()
+            equal = equal and all(torch.equal(x.view(torch.int32), z.view(torch.int32)) for x, z in zip(out["gather"], out["gather_stored"]))
+        d.update(outputs_equal=bool(equal), last_form=store.info()["last_form"], stored_over_float=round(d["gather_stored"]["ms"] / d["gather"]["ms"], 3))
+        res[name] = d
+
+    case("regular", args.sequences)
+    case("half", 64)
+    # the expand of a batch of utterances against a device copy of the same float rows
+    n = min(args.expand_utts, U)
+    lists = [rng.permutation(U)[:n] for _ in range(args.cycle)]
+    row_lists = [torch.from_numpy(np.concatenate([np.arange(feat0[u], feat0[u] + frames[u]) for u in l])).cuda() for l in lists]
+    most = max(len(r) for r in row_lists)
+    bufs = {k: torch.zeros(most, D, device="cuda") for k in ("copy", "expand")}
+
+    def copy(i):
+        torch.index_select(F_dev, 0, row_lists[i], out=bufs["copy"][:len(row_lists[i])])
+
+    def expand(i):
+        store.expand(lists[i], out=bufs["expand"][:len(row_lists[i])])
+
+    d = dict(utterances=n, rows=int(np.mean([len(r) for r in row_lists])), **timed(dict(copy=copy, expand=expand)))
+    equal = True
+    for i in range(args.cycle):
+        copy(i), expand(i)
+        torch.cuda.synchronize()
+        k = len(row_lists[i])
+        equal = equal and torch.equal(bufs["copy"][:k].view(torch.int32), bufs["expand"][:k].view(torch.int32))
+    d.update(outputs_equal=bool(equal), last_form=store.info()["last_form"], expand_over_copy=round(d["expand"]["ms"] / d["copy"]["ms"], 3))
+    res["expand"] = d
+    res["allocations"] = store.info()["allocations"]
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -561,6 +666,9 @@ def main():
     ap.add_argument("--utt-frames", type=int, default=1000)
     ap.add_argument("--features", action="store_true",
                     help="the input of a minibatch of chunks: numpy slicing of host copies + upload against tdnnf_chunk_input_gather (--sequences, --frames, --utt-frames)")
+    ap.add_argument("--stored", type=int, default=0, choices=[0, 1, 2, 3],
+                    help="--features: the features held in a FeatureStore of this format (1 CM, 2 CM2, 3 CM3): float gather against gather_stored, copy against expand")
+    ap.add_argument("--expand-utts", type=int, default=16, help="--features --stored: utterances in an expand")
     ap.add_argument("--alternatives", type=int, default=1)
     ap.add_argument("--sequences", type=int, default=128)
     ap.add_argument("--frames", type=int, default=150)
@@ -568,7 +676,7 @@ def main():
     assert args.cycle >= 8, "different graphs every iteration: a cycle of at least 8 batches"
     pkg = ge.load_package()
     if args.features:
-        return features(args, pkg)
+        return stored_features(args, pkg) if args.stored else features(args, pkg)
     if args.supervision:
         return alignment(args, pkg) if args.alignment else supervision(args, pkg)
     if args.transcripts:
